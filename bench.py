@@ -218,6 +218,31 @@ def warm_device(pkg, nbytes, dev, launches=400):
         torch.cuda.synchronize()
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: under 64 MB in all, .npy headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, n_envs, budget=DUMP_BUDGET_BYTES):
+    """Write the per-env output tensors `arrays` (name -> tensor with n_envs rows) as float32 DIR/<name>.npy, plus
+    DIR/env_index.npy (float64): the env rows written.  All rows if they fit in `budget` bytes, else a fixed sample
+    (RandomState(DUMP_SAMPLE_SEED), sorted) of as many envs as fit -- the same rows on every run of the same shape.
+    Returns {"dir", "files", "envs", "of"}."""
+    import numpy as np
+    import torch
+    per_env = 8 + sum(4 * t[0].numel() for t in arrays.values())
+    k = max(1, min(n_envs, budget // per_env))
+    idx = np.arange(n_envs) if k == n_envs else np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n_envs, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for name, t in arrays.items():
+        rows = t if k == n_envs else t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), rows.to(torch.float32).cpu().numpy())
+        files.append(name + ".npy")
+    np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    files.append("env_index.npy")
+    return {"dir": os.path.abspath(out_dir), "files": files, "envs": int(k), "of": int(n_envs)}
+
+
 # ------------------------------------------------------------------------------------------------
 # self-launch: `python bench.py --gpus N` from a plain shell
 # ------------------------------------------------------------------------------------------------
@@ -305,7 +330,14 @@ def parse_args(argv=None):
                          "Default, whatever --steps is: enough rows for 320 MiB (80 rows at 1M envs), more than the "
                          "256 MiB Infinity Cache holds, so every step's row comes from HBM; c2: the 256 rows of SURVEY "
                          "8(d) C2.  32 rows of 1M envs are 134 MB, stay in the cache and flatter the step kernel.")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's obs, reward, done -- and the "
+                         "foveal streams where the step has them) as float32 DIR/<name>.npy, at most 64 MB in all: every "
+                         "env, or a fixed seeded sample of envs (DIR/env_index.npy) when they do not fit")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def default_action_rows(workload, N):
@@ -530,6 +562,17 @@ def main():
     else:  # episodes restart: nobody is past the step limit, and everybody moved
         assert 1 <= int(env.step_count.min().item()) and int(env.step_count.max().item()) <= env.step_limit
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before the event replays below move the state
+        outs = {"obs": env.obs}
+        if hier:
+            outs["obs_local"] = env.obs_local
+        outs.update(reward=env.reward, done=env.done)
+        if args.workload in ("v1", "v5"):
+            outs.update(foveal_reward=env.foveal_reward, foveal_done=env.foveal_done)
+        dumped = dump_outputs(args.dump_outputs, outs, N)
+
     v5_events = None
     if hier and rank == 0:
         # replay the timed steps from the snapshot (same actions, goals and epochs => the same trajectory) and count
@@ -672,6 +715,8 @@ def main():
             out["config"]["local_done_rate"] = v5_events["local_dones"] / float(N * args.steps)
         if v4_events is not None:
             out["config"]["v4_events_in_timed_steps"] = v4_events
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only
             out["cpu_baseline"] = (cpu_baseline_foveal(args.workload, args.cpu_baseline_seconds) if foveal
                                    else cpu_baseline(args.workload, G, layout, args.cpu_baseline_seconds))

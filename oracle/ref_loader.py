@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE ONLY (oracle/): loads the upstream reference's env classes.
 
 Build-container only.  /root/reference does not exist on the GPU box, so nothing in
-tests/, bench.py or __graft_entry__ imports this module at run time; its single use is
-`oracle/gen_golden.py`, which writes the committed fixtures under tests/golden/.
+tests/, bench.py or __graft_entry__ loads the reference at run time (tests/test_golden_provenance.py
+only asks `available()`); its single use is `oracle/gen_golden.py`, which writes the committed
+fixtures under tests/golden/.
 
 Why a loader is needed: every reference env file starts with
 `import gym` / `import cv2` (gym_lmaze/envs/lmaze_env.py:1-6) and neither is installed

@@ -1,6 +1,7 @@
-"""CPU, build container only (skipped where /root/reference is absent, e.g. on the GPU box): the committed fixtures
-are what the committed generator emits -- byte for byte, whichever generators run before -- so a recording can
-always be traced to oracle/gen_golden.py running the reference's own reset()/step()."""
+"""CPU: the committed fixtures are what the committed generator emits -- byte for byte, whichever generators run
+before -- so a recording can always be traced to oracle/gen_golden.py running the reference's own reset()/step().
+Regenerating needs the reference tree (oracle/ref_loader.py: LMAZE_REFERENCE_ROOT), so that test is skipped where the
+tree is absent, e.g. on the GPU box; that every fixture has a generator is checked everywhere."""
 import filecmp
 import os
 import subprocess
@@ -8,11 +9,12 @@ import sys
 
 import pytest
 
+import ref_loader
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/gym_lmaze/envs"),
-                                reason="the reference tree only exists in the build container")
+needs_reference = pytest.mark.skipif(not ref_loader.available(), reason="the reference tree is not present here")
 
 
 def _generate(out_dir, *which):
@@ -22,6 +24,7 @@ def _generate(out_dir, *which):
     return sorted(f for f in os.listdir(str(out_dir)) if f.endswith(".npz"))
 
 
+@needs_reference
 def test_v5_and_v6_recordings_do_not_depend_on_generator_order(tmp_path):
     """Round 1's v5_seed0 only came out as committed when `gen_golden.py v5` ran alone (the layout cache consumed
     draws from the freshly seeded global streams).  Alone, and after another generator has filled that cache: the

@@ -138,3 +138,33 @@ def test_torchrun_entry_still_works():
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["collective_backend"] == "rccl" and "external" in d["config"]["launcher"]
+
+
+@pytest.mark.parametrize("flags", [
+    ("--steps", "6", "--warmup", "2", "--no-cpu-baseline"),                                   # the metric's config: sampled
+    ("--workload", "c2", "--one-launch", "--auto-reset", "--steps", "16", "--warmup", "4", "--no-cpu-baseline"),
+    ("--workload", "v5", "--envs", "65536", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"),
+])
+def test_dump_outputs_are_the_same_on_every_run(flags, tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 .npy, at most 64 MB, and -- same arguments, same
+    inputs -- the same bytes from two runs (autotune and placement trials pick a policy, never a result)."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out_dir = tmp_path / ("run%d" % k)
+        d = _run(*flags, "--dump-outputs", str(out_dir))
+        assert d["steps"] == int(flags[flags.index("--steps") + 1]) and d["ms_per_step"] > 0
+        info = d["dumped_outputs"]
+        assert info["of"] == d["config"]["envs_per_gpu"] and 0 < info["envs"] <= info["of"]
+        assert sum(os.path.getsize(str(out_dir / f)) for f in info["files"]) <= 64 * 10 ** 6
+        runs.append((out_dir, info))
+    (a, info), (b, _) = runs
+    names = {"obs", "reward", "done", "env_index"} | ({"obs_local", "foveal_reward", "foveal_done"} if "v5" in flags else set())
+    assert set(f[:-4] for f in info["files"]) == names
+    for f in info["files"]:
+        x, y = np.load(str(a / f)), np.load(str(b / f))
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == info["envs"], f
+        assert x.tobytes() == y.tobytes(), f
+    done, reward = np.load(str(a / "done.npy")), np.load(str(a / "reward.npy"))
+    assert set(np.unique(done)) <= {0.0, 1.0} and np.isfinite(reward).all()
+    assert np.load(str(a / "obs.npy")).any()            # the planes were rendered
