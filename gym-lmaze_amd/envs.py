@@ -30,8 +30,65 @@ def _f32_bits(x):
     return int(np.float32(x).view(np.uint32))
 
 
-class _LmazeBase(Env):
+class _DropIn(Env):
+    """What the drop-in classes of both engines share: the host mirror of the state block, the single-env step
+    through page-locked staging, and the conversion of float32 rewards to the reference's Python floats."""
     metadata = {'render.modes': ['human']}
+
+    @property
+    def core(self):
+        """The batched engine (LmazeVecEnv / LmazeFovealVecEnv): state tensors, obs buffer, set_state()."""
+        return self._core
+
+    def _sync_host(self):
+        if self._stage is not None:
+            self._host = self._core.host_state(raw=self._stage.fetch(state=self._core._state)["state"].copy())
+        else:
+            self._host = self._core.host_state()
+        return self._host
+
+    def _scalar(self, key, idx=None):
+        h = self._host if self._host is not None else self._sync_host()
+        v = h[key][0]
+        return v if idx is None else v[idx]
+
+    def _step_single(self, action, local=False):
+        """N = 1: upload the action, step, render xE, and bring the observation(s) + scalars back with one sync.
+        Returns ({"obs": view, "loc": view (v5/v6, local=True)} -- page-locked mirrors, none in compact mode --,
+        host scalars)."""
+        core, stage = self._core, self._stage
+        expanded = self.obs_mode == "expanded"
+
+        def body(act_dev):
+            core.step(act_dev)
+            want = {"state": core._state}
+            if expanded:
+                want["obs"] = core.expanded()[0]
+                if local:
+                    want["loc"] = core.expanded_local()[0]
+            return want
+
+        got = stage.step(("step", expanded, local), action, body)    # one hipGraph launch + one sync
+        self._host = core.host_state(raw=got["state"].copy())
+        return got, self._host
+
+    def _reward_to_python(self, r32):
+        """float32 from the device -> the double the reference would have returned."""
+        table = getattr(self, "_reward_table", None)
+        if table is None:
+            table = {_f32_bits(v): float(v) for v in (self.negativeNominal, self.positiveNominal, self.positiveFull,
+                                                      -0.0, 0.0)}
+            self._reward_table = table
+        return table.get(int(np.float32(r32).view(np.uint32)), float(r32))
+
+    def rendering(self, msg):
+        self.VISUALIZE = msg
+
+    def writing(self, msg):
+        self.SAVEFRAME = msg
+
+
+class _LmazeBase(_DropIn):
     _variant = "v0"
 
     # ------------------------------------------------------------------ construction
@@ -93,43 +150,6 @@ class _LmazeBase(Env):
     def gridsize(self, value):
         pass  # derived; accepted so reference-style attribute overrides do not fail
 
-    # ------------------------------------------------------------------ host mirror (single env)
-    def _sync_host(self):
-        if self._stage is not None:
-            self._host = self._core.host_state(raw=self._stage.fetch(state=self._core._state)["state"].copy())
-        else:
-            self._host = self._core.host_state()
-        return self._host
-
-    def _step_single(self, action):
-        """N = 1: upload the action, step, render xE, and bring observation + scalars back with one sync.
-        Returns (page-locked view of the (C,GE,GE) observation or None in compact mode, host scalars)."""
-        core, stage = self._core, self._stage
-        expanded = self.obs_mode == "expanded"
-
-        def body(act_dev):
-            core.step(act_dev)
-            return {"obs": core.expanded()[0], "state": core._state} if expanded else {"state": core._state}
-
-        got = stage.step(("step", expanded), action, body)       # one hipGraph launch + one sync
-        self._host = core.host_state(raw=got["state"].copy())
-        return got.get("obs"), self._host
-
-    def _scalar(self, key, idx=None):
-        h = self._host if self._host is not None else self._sync_host()
-        v = h[key][0]
-        return v if idx is None else v[idx]
-
-    def _reward_to_python(self, r32):
-        """float32 from the device -> the double the reference would have returned."""
-        table = getattr(self, "_reward_table", None)
-        if table is None:
-            table = {_f32_bits(v): float(v) for v in (self.negativeNominal, self.positiveNominal,
-                                                      self.positiveFull, -0.0, 0.0)}
-            table[_f32_bits(-0.0)] = -0.0
-            self._reward_table = table
-        return table.get(int(np.float32(r32).view(np.uint32)), float(r32))
-
     ball_x0 = property(lambda s: int(s._scalar("ball_xy", 0)), lambda s, v: s._poke_ball(x=v))
     ball_y0 = property(lambda s: int(s._scalar("ball_xy", 1)), lambda s, v: s._poke_ball(y=v))
     goal_x = property(lambda s: int(s._scalar("goal_xy", 0)), lambda s, v: s._poke_goal(x=v))
@@ -172,21 +192,10 @@ class _LmazeBase(Env):
             return full
         return self._stage.fetch(obs=full[0])["obs"].copy()  # a fresh array per call, like lmaze_env.py:217
 
-    @property
-    def core(self):
-        """The batched engine (LmazeVecEnv): state tensors, obs buffer, set_state()."""
-        return self._core
-
     # ------------------------------------------------------------------ reference extras
     def render(self, mode='human', close=False):
         # lmaze_env.py:55-59 only flips the flag; the cv2 window itself is out of scope
         self.VISUALIZE = (mode == 'human')
-
-    def rendering(self, msg):
-        self.VISUALIZE = msg
-
-    def writing(self, msg):
-        self.SAVEFRAME = msg
 
 
 class LmazeEnv(_LmazeBase):
@@ -259,8 +268,8 @@ class LmazeEnv(_LmazeBase):
         core = self._core
         if self._single:
             a = int(msg)                                     # lmaze_env.py:148
-            view, h = self._step_single(a if -2 ** 31 <= a < 2 ** 31 else _NOOP_ACTION)
-            obs = view.copy() if view is not None else core.obs      # a fresh array per call (lmaze_env.py:217)
+            got, h = self._step_single(a if -2 ** 31 <= a < 2 ** 31 else _NOOP_ACTION)
+            obs = got["obs"].copy() if "obs" in got else core.obs    # a fresh array per call (lmaze_env.py:217)
             return obs, self._reward_to_python(h["reward"][0]), bool(h["done"][0]), a
         core.step(msg)
         self._host = None
@@ -389,8 +398,8 @@ class LmazeEnv_v3(_LmazeBase):
     def step(self, goal):
         core = self._core
         if self._single:
-            view, h = self._step_single(_decode_v3_action(goal))
-            obs = self._single_obs(view) if view is not None else core.obs
+            got, h = self._step_single(_decode_v3_action(goal))
+            obs = self._single_obs(got["obs"]) if "obs" in got else core.obs
             return obs, self._reward_to_python(h["reward"][0]), bool(h["done"][0]), goal
         core.step(goal)   # batched: int32 ids, 0..3 move, anything else is the no-op
         self._host = None

@@ -20,16 +20,12 @@ import numpy as np
 
 from . import layouts as L
 from ._staging import HostStaging
-from .compat import Box, Discrete, Env
+from .compat import Box, Discrete
+from .envs import _DropIn
 from .foveal_env import LmazeFovealVecEnv
 
 
-def _f32_bits(x):
-    return int(np.float32(x).view(np.uint32))
-
-
-class _FovealBase(Env):
-    metadata = {'render.modes': ['human']}
+class _FovealBase(_DropIn):
     _variant = "v2"
 
     def _setup(self, num_envs, device, obs_mode, seed):
@@ -43,36 +39,6 @@ class _FovealBase(Env):
         self._stage = HostStaging(self._core.device) if self._single else None
         self._host = None
 
-    @property
-    def core(self):
-        return self._core
-
-    def _sync(self):
-        if self._stage is not None:
-            self._host = self._core.host_state(raw=self._stage.fetch(state=self._core._state)["state"].copy())
-        else:
-            self._host = self._core.host_state()
-        return self._host
-
-    def _step_single(self, action, local=False):
-        """N = 1: upload the action, step, render x7, and bring the observation(s) + scalars back with one
-        sync.  Returns ({"obs": view, "loc": view (v5/v6)}, host scalars); views are page-locked mirrors."""
-        core, stage = self._core, self._stage
-        expanded = self.obs_mode == "expanded"
-
-        def body(act_dev):
-            core.step(act_dev)
-            want = {"state": core._state}
-            if expanded:
-                want["obs"] = core.expanded()[0]
-                if local:
-                    want["loc"] = core.expanded_local()[0]
-            return want
-
-        got = stage.step(("step", expanded, local), action, body)    # one hipGraph launch + one sync
-        self._host = core.host_state(raw=got["state"].copy())
-        return got, self._host
-
     def _reused(self, arr):
         """the reference's one shared output buffer (v2:66,123,223; v4:66,163,270)"""
         if getattr(self, "retStateExpanded", None) is None or self.retStateExpanded.shape != arr.shape:
@@ -80,24 +46,12 @@ class _FovealBase(Env):
         np.copyto(self.retStateExpanded, arr)
         return self.retStateExpanded
 
-    def _h(self, key):
-        return (self._host if self._host is not None else self._sync())[key][0]
-
-    def _reward_py(self, r32):
-        table = getattr(self, "_rtab", None)
-        if table is None:
-            table = {_f32_bits(v): float(v) for v in (self.negativeNominal, self.positiveNominal, self.positiveFull)}
-            table[_f32_bits(-0.0)] = -0.0
-            table[_f32_bits(0.0)] = 0.0
-            self._rtab = table
-        return table.get(int(np.float32(r32).view(np.uint32)), float(r32))
-
-    ball_x0 = property(lambda s: int(s._h("ball_xy")[0]))
-    ball_y0 = property(lambda s: int(s._h("ball_xy")[1]))
-    goal_x = property(lambda s: int(s._h("goal_xy")[0]))
-    goal_y = property(lambda s: int(s._h("goal_xy")[1]))
-    stepCount = property(lambda s: int(s._h("step_count")) if s._single else s._core.step_count)
-    originalReward = property(lambda s: s._reward_py(s._h("reward")) if s._single else s._core.reward)
+    ball_x0 = property(lambda s: int(s._scalar("ball_xy")[0]))
+    ball_y0 = property(lambda s: int(s._scalar("ball_xy")[1]))
+    goal_x = property(lambda s: int(s._scalar("goal_xy")[0]))
+    goal_y = property(lambda s: int(s._scalar("goal_xy")[1]))
+    stepCount = property(lambda s: int(s._scalar("step_count")) if s._single else s._core.step_count)
+    originalReward = property(lambda s: s._reward_to_python(s._scalar("reward")) if s._single else s._core.reward)
 
     def _obs_np(self, reuse):
         """single env, expanded mode: numpy (C,35,35); `reuse` = the reference's one shared buffer"""
@@ -107,12 +61,6 @@ class _FovealBase(Env):
     def render(self, mode='human', close=False):
         if mode == 'human':
             self.VISUALIZE = True
-
-    def rendering(self, msg):
-        self.VISUALIZE = msg
-
-    def writing(self, msg):
-        self.SAVEFRAME = msg
 
     def setevaldir(self, msg):
         self.dirhead = msg
@@ -141,10 +89,10 @@ class LmazeEnv_v1(_FovealBase):
         self.reset()                                         # v1:57
         print("init-end")
 
-    f_goal_x = property(lambda s: int(s._h("fgoal_xy")[0]))
-    f_goal_y = property(lambda s: int(s._h("fgoal_xy")[1]))
-    fovealStepCount = property(lambda s: int(s._h("foveal_step_count")) if s._single else s._core.foveal_step_count)
-    fovealReward = property(lambda s: s._reward_py(s._h("foveal_reward")) if s._single else s._core.foveal_reward)
+    f_goal_x = property(lambda s: int(s._scalar("fgoal_xy")[0]))
+    f_goal_y = property(lambda s: int(s._scalar("fgoal_xy")[1]))
+    fovealStepCount = property(lambda s: int(s._scalar("foveal_step_count")) if s._single else s._core.foveal_step_count)
+    fovealReward = property(lambda s: s._reward_to_python(s._scalar("foveal_reward")) if s._single else s._core.foveal_reward)
 
     def _out(self):
         if self.obs_mode == "compact":
@@ -172,7 +120,7 @@ class LmazeEnv_v1(_FovealBase):
             a = next((k for k in range(4) if msg == k), -1)  # v1:126-133 compares, never casts
             got, h = self._step_single(a)
             obs = got["obs"].copy() if "obs" in got else core.obs    # a fresh array per call (v1:258)
-            return (obs, self._reward_py(h["reward"][0]), self._reward_py(h["foveal_reward"][0]),
+            return (obs, self._reward_to_python(h["reward"][0]), self._reward_to_python(h["foveal_reward"][0]),
                     bool(h["foveal_done"][0]), bool(h["done"][0]), msg)
         core.step(msg)
         self._host = None
@@ -221,7 +169,7 @@ class LmazeEnv_v1(_FovealBase):
 
     def isFovealEpisodeFinished(self):                       # v1:308-324
         if self._single:
-            return bool(self._h("foveal_done"))
+            return bool(self._scalar("foveal_done"))
         return self._core.foveal_done
 
 
@@ -315,7 +263,7 @@ class _TeleportBase(_FovealBase):
             self._fgoal = (bx + g // 5 - 2, by + g % 5 - 2)  # v2:151-152
             got, h = self._step_single(g)
             obs = self._reused(got["obs"]) if "obs" in got else core.obs
-            return obs, self._reward_py(h["reward"][0]), bool(h["done"][0]), g
+            return obs, self._reward_to_python(h["reward"][0]), bool(h["done"][0]), g
         core.step(goal)
         self._host = None
         return self._out(), core.reward, core.done, goal
@@ -391,27 +339,27 @@ class LmazeEnv_v5(_TeleportBase):
         self.reset()                                         # v5:80
 
     # reference attribute names (v5:62-78)
-    f_goal_x0 = property(lambda s: int(s._h("fgoal_xy")[0]))
-    f_goal_y0 = property(lambda s: int(s._h("fgoal_xy")[1]))
-    ball_x1 = property(lambda s: int(s._h("ball1_xy")[0]))
-    ball_y1 = property(lambda s: int(s._h("ball1_xy")[1]))
-    fovea_x0 = property(lambda s: int(s._h("fovea_xy")[0]))
-    fovea_y0 = property(lambda s: int(s._h("fovea_xy")[1]))
-    fovea_x1 = property(lambda s: int(s._h("fovea_xy")[2]))
-    fovea_y1 = property(lambda s: int(s._h("fovea_xy")[3]))
-    fovealStepCount = property(lambda s: int(s._h("foveal_step_count")) if s._single else s._core.foveal_step_count,
+    f_goal_x0 = property(lambda s: int(s._scalar("fgoal_xy")[0]))
+    f_goal_y0 = property(lambda s: int(s._scalar("fgoal_xy")[1]))
+    ball_x1 = property(lambda s: int(s._scalar("ball1_xy")[0]))
+    ball_y1 = property(lambda s: int(s._scalar("ball1_xy")[1]))
+    fovea_x0 = property(lambda s: int(s._scalar("fovea_xy")[0]))
+    fovea_y0 = property(lambda s: int(s._scalar("fovea_xy")[1]))
+    fovea_x1 = property(lambda s: int(s._scalar("fovea_xy")[2]))
+    fovea_y1 = property(lambda s: int(s._scalar("fovea_xy")[3]))
+    fovealStepCount = property(lambda s: int(s._scalar("foveal_step_count")) if s._single else s._core.foveal_step_count,
                                lambda s, v: None)
-    globalReward = property(lambda s: s._reward_py(s._h("reward")) if s._single else s._core.reward)
-    originalReward = property(lambda s: s._reward_py(s._h("foveal_reward")) if s._single else s._core.foveal_reward)
-    globalDone = property(lambda s: bool(s._h("done")) if s._single else s._core.done)
-    localDone = property(lambda s: bool(s._h("foveal_done")) if s._single else s._core.foveal_done, lambda s, v: None)
+    globalReward = property(lambda s: s._reward_to_python(s._scalar("reward")) if s._single else s._core.reward)
+    originalReward = property(lambda s: s._reward_to_python(s._scalar("foveal_reward")) if s._single else s._core.foveal_reward)
+    globalDone = property(lambda s: bool(s._scalar("done")) if s._single else s._core.done)
+    localDone = property(lambda s: bool(s._scalar("foveal_done")) if s._single else s._core.foveal_done, lambda s, v: None)
 
     @property
     def fovealGoal(self):
         """float32 (1,5,5) one-hot plane (v5:166-169)."""
         if self._single:
             p = np.zeros((1, 5, 5), np.float32)
-            p.reshape(-1)[int(self._h("foveal_goal"))] = 1.0
+            p.reshape(-1)[int(self._scalar("foveal_goal"))] = 1.0
             return p
         return self._core.obs_local[:, 3:4]
 
@@ -464,7 +412,7 @@ class LmazeEnv_v5(_TeleportBase):
                         raise IndexError("index %d is out of bounds for axis with size 5 (lmaze_env_v5.py:364-365)" % idx)
             fov = got["obs"].copy() if "obs" in got else core.obs            # fresh arrays, v5:308,359
             loc = got["loc"].copy() if "loc" in got else core.obs_local
-            return (fov, loc, self._reward_py(h["reward"][0]), self._reward_py(h["foveal_reward"][0]),
+            return (fov, loc, self._reward_to_python(h["reward"][0]), self._reward_to_python(h["foveal_reward"][0]),
                     bool(h["done"][0]), bool(h["foveal_done"][0]), self.fovealGoal, a)
         core.step(goal)
         self._host = None
