@@ -50,23 +50,28 @@ __device__ __forceinline__ void store16(int4* p, const int4& v) {
 // reaches the goal (about every second wave of a random rollout).  One lane per env, so the atomicity itself is unused.
 __device__ __forceinline__ void count_goal(int32_t* p) { __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// One env's inputs, loaded into registers BEFORE the workgroup's LDS set-up and first barrier so
-// that the two global round trips (layout, state) overlap instead of chaining: at launch-bound
-// batch sizes (65 536 x 8x8) the kernel is nothing but that latency chain.
-struct EnvIn {
+// This launch's planes go beyond the caches (n envs of `cells` int32 cells each).
+__host__ __device__ inline bool beyond_caches(int64_t n, int cells) { return (size_t)n * cells * 4 > kNonTemporalObsBytes; }
+
+// One env's register state: the reference's per-env fields, this step's action and the done byte.  The done byte is
+// the flag on entry as loaded (load_env) until env_advance replaces it with the step's own flag (0 / 1).
+struct EnvState {
     int2 b, g;
-    int act, sc, was_done;
+    int act, sc, done;
     float r;
 };
 
+// One env's inputs, loaded into registers BEFORE the workgroup's LDS set-up and first barrier so
+// that the two global round trips (layout, state) overlap instead of chaining: at launch-bound
+// batch sizes (65 536 x 8x8) the kernel is nothing but that latency chain.
 template <int VARIANT, bool DO_STEP>
-__device__ __forceinline__ EnvIn load_env(const StepArgs& a, int64_t e) {
+__device__ __forceinline__ EnvState load_env(const StepArgs& a, int64_t e) {
     constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
-    EnvIn in;
+    EnvState in;
     in.b = a.ball[e];
     in.g = make_int2(-1, -1);
     if (V3) in.g = a.goal[e];
-    in.act = 0; in.sc = 0; in.was_done = 0; in.r = 0.0f;
+    in.act = 0; in.sc = 0; in.done = 0; in.r = 0.0f;
     if (DO_STEP) {
         in.act = a.action[e];
         in.sc = a.step_count[e];
@@ -74,54 +79,88 @@ __device__ __forceinline__ EnvIn load_env(const StepArgs& a, int64_t e) {
         // branch-free (a load under a branch is waited for where the branch ends, in front of whatever else is in flight):
         // without the fused reset the lane reads byte 0 of the layout instead -- one cached address, no traffic
         const uint8_t* dp = a.auto_reset ? a.done + e : a.layout;
-        // ... and the byte is kept as loaded: every use is `a.auto_reset && in.was_done`.  A select here is a USE of the
+        // ... and the byte is kept as loaded: every use is `a.auto_reset && in.done`.  A select here is a USE of the
         // loaded value inside the caller's `if (tid < nb)`: the wave then waits for its state loads before the set-up's
         // layout loads are even issued -- two global round trips in series at the head of every workgroup.
-        in.was_done = *dp;
+        in.done = *dp;
     }
     return in;
+}
+
+// reference reset() of one env (v0:64-110): the placement's cells (< 0: leave unchanged) and zeroed counters
+template <int VARIANT>
+__device__ __forceinline__ void env_reset(int ball_cell, int goal_cell, int G, EnvState& s) {
+    if (ball_cell >= 0) s.b = make_int2(ball_cell / G, ball_cell % G);
+    if (VARIANT == LMAZE_VARIANT_V3 && goal_cell >= 0) s.g = make_int2(goal_cell / G, goal_cell % G);
+    s.sc = 0;      // v0:110
+    s.r = -0.0f;   // v0:109
+}
+
+// the ball kept on the grid, as env_advance does first (the observe-only launches)
+__device__ __forceinline__ void clamp_ball(EnvState& s, int G) { s.b = make_int2(clampi(s.b.x, 0, G - 1), clampi(s.b.y, 0, G - 1)); }
+
+// reference step() of one env (v0:146-249, v3:220-402) on its register state; returns v0's goal hit (v0:195).
+// cell_at(tx, ty) = the layout character of the target cell, from wherever the kernel keeps the layout.
+template <int VARIANT, class CellAt>
+__device__ __forceinline__ bool env_advance(const StepArgs& a, int G, CellAt cell_at, EnvState& s) {
+    int bx = clampi(s.b.x, 0, G - 1), by = clampi(s.b.y, 0, G - 1);
+    s.sc += 1;  // v0:151, v3:225
+    int ox, oy;
+    decode_action(s.act, ox, oy);
+    const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
+    float r;
+    bool dn;
+    const bool hit = transition_rule<VARIANT>(a, cell_at(tx, ty), ox, oy, tx, ty, s.sc, s.r, s.g.x, s.g.y, bx, by, r, dn);
+    s.b = make_int2(bx, by);
+    s.r = r;
+    s.done = dn ? 1 : 0;
+    return hit;
+}
+
+// the per-env state a step kernel writes back
+__device__ __forceinline__ void store_state(const StepArgs& a, int64_t e, const EnvState& s) {
+    a.ball[e] = s.b;
+    a.step_count[e] = s.sc;
+    a.reward[e] = s.r;
+    a.done[e] = s.done;
+}
+
+// cells of the planes' ball and goal bits; -8 = no goal (v0, or a v3 goal off the grid)
+__device__ __forceinline__ int ball_cell_of(const int2& b, int G) { return b.x * G + b.y; }
+template <int VARIANT>
+__device__ __forceinline__ int goal_cell_of(const int2& g, int G) {
+    return (VARIANT == LMAZE_VARIANT_V3 && g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) ? g.x * G + g.y : -8;
+}
+
+// The reset epoch of a step launch, read at kernel start (a uniform load in front of every store: one scalar load):
+// fetched where a done env draws its placement it was a global round trip inside phase 1 for every wave with a done
+// env -- 90.0 instead of 83.4 us per step at 1M x 11x11 once the epoch lives on the device (captured rollouts)
+__device__ __forceinline__ uint64_t step_epoch(const StepArgs& a, bool autoreset) {
+    const uint64_t epoch = autoreset ? launch_epoch(a.epoch, a.epoch_in) : 0;
+    if (autoreset) pass_epoch_on(a.epoch_in, a.epoch_out);
+    return epoch;
 }
 
 // one env of phase 1 (layout in LDS); returns the env's ball (and goal) cell index for phase 2
 // `place(draw, ball_cell, goal_cell)` = the fused reset's placement over the accepted cells (a list in LDS or bit masks)
 template <int VARIANT, bool DO_STEP, class Place>
-__device__ __forceinline__ void env_phase1(const StepArgs& a, const uint8_t* lay, int G, int64_t e, EnvIn in,
+__device__ __forceinline__ void env_phase1(const StepArgs& a, const uint8_t* lay, int G, int64_t e, EnvState s,
                                            Place place, uint64_t epoch, int& ball_cell, int& goal_cell) {
-    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
-    int2 b = in.b, g = in.g;
     if (DO_STEP) {
-        int sc_in = in.sc;
-        float r_in = in.r;
-        if (a.auto_reset && in.was_done) {  // reference reset(): placement + zeroed counters
+        if (a.auto_reset && s.done) {
             int bc, gc;
             place(env_draw(a.seed, epoch, a.env_base + e), bc, gc);
-            if (bc >= 0) b = make_int2(bc / G, bc % G);
-            if (V3 && gc >= 0) {
-                g = make_int2(gc / G, gc % G);
-                a.goal_rw[e] = g;
-            }
-            sc_in = 0;      // v0:110
-            r_in = -0.0f;   // v0:109
+            env_reset<VARIANT>(bc, gc, G, s);
+            if (VARIANT == LMAZE_VARIANT_V3 && gc >= 0) a.goal_rw[e] = s.g;
         }
-        int bx = clampi(b.x, 0, G - 1), by = clampi(b.y, 0, G - 1);
-        const int sc = sc_in + 1;  // v0:151, v3:225
-        int ox, oy;
-        decode_action(in.act, ox, oy);
-        const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-        float r;
-        bool dn;
-        if (transition_rule<VARIANT>(a, lay[tx * G + ty], ox, oy, tx, ty, sc, r_in, g.x, g.y, bx, by, r, dn) && a.goal_count)
+        if (env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) && a.goal_count)
             count_goal(a.goal_count + e);
-        a.ball[e] = make_int2(bx, by);
-        a.step_count[e] = sc;
-        a.reward[e] = r;
-        a.done[e] = dn ? 1 : 0;
-        b = make_int2(bx, by);
+        store_state(a, e, s);
     } else {
-        b = make_int2(clampi(b.x, 0, G - 1), clampi(b.y, 0, G - 1));
+        clamp_ball(s, G);
     }
-    ball_cell = b.x * G + b.y;
-    goal_cell = (V3 && g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) ? g.x * G + g.y : -8;
+    ball_cell = ball_cell_of(s.b, G);
+    goal_cell = goal_cell_of<VARIANT>(s.g, G);
 }
 
 // ------------------------------------------------------------------------------------
@@ -173,13 +212,11 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_kernel(const StepArgs
     int nb = (int)min((int64_t)EPB, a.n - blockbase);  // envs of the current chunk
     const bool masked = !DO_STEP && a.mask != nullptr;
     const bool autoreset = DO_STEP && a.auto_reset;
-    // the reset epoch, read HERE (a uniform load in front of every store: one scalar load): fetched where a done env
-    // draws its placement it was a global round trip inside phase 1 for every wave with a done env -- 90.0 instead of
-    // 83.4 us per step at 1M x 11x11 once the epoch lives on the device (captured rollouts)
+    // step_epoch() written out: through the helper this kernel's set-up compiles to other branches and waits
     const uint64_t epoch = autoreset ? launch_epoch(a.epoch, a.epoch_in) : 0;
     if (autoreset) pass_epoch_on(a.epoch_in, a.epoch_out);
 
-    EnvIn in{};
+    EnvState in{};
     if (tid < nb) in = load_env<VARIANT, DO_STEP>(a, blockbase + tid);
     // Streaming regime without the fused reset: the state loads are waited for BEFORE the set-up's layout loads go out.
     // That is a second round trip in series at the head of every workgroup, and it is faster: 1M x 11x11 at the default
@@ -201,6 +238,8 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_kernel(const StepArgs
     // 86 us when the rows are cache-resident anyway).
     // The same for the per-env state, which is only cached if nothing else ran since the previous step: with a
     // 512-MB copy between two steps (a stand-in for a policy network) the step took 131 us instead of 83.
+    // Written out here and in step_shared_u8_kernel, not as a shared helper: through one, this kernel's set-up compiled
+    // to other branches and waited for one more load (vmcnt(0) instead of vmcnt(1)) before its first chunk.
     int warmed = 0;
     if (DO_STEP && NT) {
         warmed = warm_lines(a.action, a.n * 4, 256) + warm_lines(a.ball, a.n * 8, 256) +
@@ -265,7 +304,7 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_kernel(const StepArgs
     const int64_t next = chunk + gridDim.x;
     const bool has_next = next < nchunks;                         // uniform over the workgroup
     uint32_t* mk = marks + buf * NPL * NGW;
-    EnvIn in_next{};
+    EnvState in_next{};
     int nb_next = 0;
     if (has_next) {                                               // issued now, consumed one chunk later
         nb_next = (int)min((int64_t)EPB, a.n - next * EPB);
@@ -412,18 +451,14 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_perenv_kernel(const StepArgs
     const int R = nb * CELLS;  // layout bytes read == obs dwords written by this workgroup
     const bool autoreset = DO_STEP && a.auto_reset;
     const bool masked = !DO_STEP && a.mask != nullptr;
-    // the reset epoch, read HERE (a uniform load in front of every store: one scalar load): fetched where a done env
-    // draws its placement it was a global round trip inside phase 1 for every wave with a done env -- 90.0 instead of
-    // 83.4 us per step at 1M x 11x11 once the epoch lives on the device (captured rollouts)
-    const uint64_t epoch = autoreset ? launch_epoch(a.epoch, a.epoch_in) : 0;
-    if (autoreset) pass_epoch_on(a.epoch_in, a.epoch_out);
+    const uint64_t epoch = step_epoch(a, autoreset);
 
-    EnvIn in{};  // this lane's env, loaded while the layouts are still on their way
-    if (tid < nb) in = load_env<VARIANT, DO_STEP>(a, blockbase + tid);
+    EnvState s{};  // this lane's env, loaded while the layouts are still on their way
+    if (tid < nb) s = load_env<VARIANT, DO_STEP>(a, blockbase + tid);
     if (tid <= EPB) {
         int f = 0;
         if (tid < nb) {
-            if (autoreset) f = in.was_done != 0;
+            if (autoreset) f = s.done != 0;
             if (masked) f = a.mask[blockbase + tid] != 0;
         }
         flag[tid] = f;
@@ -452,47 +487,27 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_perenv_kernel(const StepArgs
         int bcell = -8, gcell = -8;
         if (tid < nb) {
             const int64_t e = blockbase + tid;
-            int2 b = in.b, g = in.g;
             if (DO_STEP) {
-                int sc_in = in.sc;
-                float r_in = in.r;
                 if (autoreset && flag[tid]) {
-                    const int bc = newball[tid], gc = newgoal[tid];
-                    if (bc >= 0) b = make_int2(bc / G, bc % G);
-                    if (V3 && gc >= 0) {
-                        g = make_int2(gc / G, gc % G);
-                        a.goal_rw[e] = g;
-                    }
-                    sc_in = 0;
-                    r_in = -0.0f;
+                    const int gc = newgoal[tid];
+                    env_reset<VARIANT>(newball[tid], gc, G, s);
+                    if (V3 && gc >= 0) a.goal_rw[e] = s.g;
                 }
-                int bx = clampi(b.x, 0, G - 1), by = clampi(b.y, 0, G - 1);
-                const int sc = sc_in + 1;
-                int ox, oy;
-                decode_action(in.act, ox, oy);
-                const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-                float r;
-                bool dn;
-                if (transition_rule<VARIANT>(a, tile[tid * CELLS + tx * G + ty], ox, oy, tx, ty, sc, r_in, g.x, g.y, bx, by,
-                                             r, dn) && a.goal_count)
+                if (env_advance<VARIANT>(a, G, [&](int tx, int ty) { return tile[tid * CELLS + tx * G + ty]; }, s) && a.goal_count)
                     count_goal(a.goal_count + e);
-                a.ball[e] = make_int2(bx, by);
-                a.step_count[e] = sc;
-                a.reward[e] = r;
-                a.done[e] = dn ? 1 : 0;
-                b = make_int2(bx, by);
+                store_state(a, e, s);
             } else {
-                b = make_int2(clampi(b.x, 0, G - 1), clampi(b.y, 0, G - 1));
+                clamp_ball(s, G);
             }
-            bcell = b.x * G + b.y;
-            if (V3 && g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) gcell = g.x * G + g.y;
+            bcell = ball_cell_of(s.b, G);
+            gcell = goal_cell_of<VARIANT>(s.g, G);
         }
         ballcell[tid] = bcell;
         if (V3) goalcell[tid] = gcell;
     }
     if (a.obs == nullptr) return;
     // large batches: non-temporal stores, as in the other kernels (1M x 11x11 per-env layouts, 8-KiB tiles: 121 -> 102 us)
-    const bool stream = (size_t)a.n * CELLS * 4 > kNonTemporalObsBytes;   // uniform
+    const bool stream = beyond_caches(a.n, CELLS);   // uniform
     __syncthreads();
 
     int32_t* obs = a.obs + (size_t)blockbase * CELLS;
@@ -549,6 +564,9 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_perenv_kernel(const StepArgs
 // the transition is fetched with v_readlane; every quantity of the transition is
 // wave-uniform, lane 0 stores it; the lane's 4 cells per register become one 16-byte store,
 // so every wave store instruction writes 1 KiB contiguous.  Waves never wait for each other.
+// The one kernel that spells out the transition (env_reset, env_advance, store_state, the cell helpers, step_epoch)
+// itself: through the shared helpers -- any subset of them -- its registers were allocated differently, 71 instead of
+// 69 VGPRs at G = 32 (v0) and 83 instead of 79 (v3, one wave per SIMD fewer).  A change of the rule lands here too.
 // ------------------------------------------------------------------------------------
 template <int G, int VARIANT, bool DO_STEP, bool NT>
 __global__ __launch_bounds__(LMAZE_BLOCK) void step_perenv_wave_kernel(const StepArgs a) {
@@ -560,9 +578,7 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_perenv_wave_kernel(const Ste
     const int64_t wave = (int64_t)blockIdx.x * (LMAZE_BLOCK / 64) + (threadIdx.x >> 6);
     const bool autoreset = DO_STEP && a.auto_reset;
     const bool masked = !DO_STEP && a.mask != nullptr;
-    // the reset epoch, read HERE (a uniform load in front of every store: one scalar load): fetched where a done env
-    // draws its placement it was a global round trip inside phase 1 for every wave with a done env -- 90.0 instead of
-    // 83.4 us per step at 1M x 11x11 once the epoch lives on the device (captured rollouts)
+    // the reset epoch at kernel start, as step_epoch()
     const uint64_t epoch = autoreset ? launch_epoch(a.epoch, a.epoch_in) : 0;
     if (autoreset) pass_epoch_on(a.epoch_in, a.epoch_out);
 
@@ -664,76 +680,40 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_wave8_kernel(const St
     if (base >= a.n) return;
     const int nb = (int)min((int64_t)EPW, a.n - base);
     const bool autoreset = DO_STEP && a.auto_reset;
-    // the reset epoch, read HERE (a uniform load in front of every store: one scalar load): fetched where a done env
-    // draws its placement it was a global round trip inside phase 1 for every wave with a done env -- 90.0 instead of
-    // 83.4 us per step at 1M x 11x11 once the epoch lives on the device (captured rollouts)
-    const uint64_t epoch = autoreset ? launch_epoch(a.epoch, a.epoch_in) : 0;
-    if (autoreset) pass_epoch_on(a.epoch_in, a.epoch_out);
+    const uint64_t epoch = step_epoch(a, autoreset);
     const bool live = lane < nb;
     const int myc = a.layout[lane];                                   // cell `lane` of the layout; issued first
-    EnvIn in{};
-    in.b = make_int2(1, 1); in.g = make_int2(-1, -1);
-    if (live) in = load_env<VARIANT, DO_STEP>(a, base + lane);
+    EnvState s{};
+    s.b = make_int2(1, 1); s.g = make_int2(-1, -1);
+    if (live) s = load_env<VARIANT, DO_STEP>(a, base + lane);
     const int mypat = cell_bits<VARIANT>((uint8_t)myc);
     const int p4 = (lane & 15) << 2;                                  // first cell of this lane's stores
     const int4 pat4 = make_int4(__shfl(mypat, p4, 64), __shfl(mypat, p4 + 1, 64), __shfl(mypat, p4 + 2, 64),
                                 __shfl(mypat, p4 + 3, 64));
     int4* obs4 = reinterpret_cast<int4*>(a.obs + (size_t)base * CELLS);
-    int2 b = in.b, g = in.g;
     if (DO_STEP) {
-        int sc_in = in.sc;
-        float r_in = in.r;
-        if (autoreset) {   // reference reset(): placement over the accepted cells, ranked row-major (lmaze_common.h place_from_list)
-            const unsigned long long ok = __ballot(interior(lane, G) && spawn_ok<VARIANT>((uint8_t)myc));
-            if (in.was_done) {
-                const uint4 d = env_draw(a.seed, epoch, a.env_base + base + lane);
-                const int count = __popcll(ok);
-                if (V3) {
-                    int kg = -1;
-                    if (count > 0) {
-                        kg = (int)__umulhi(d.x, (uint32_t)count);
-                        const int gc = kth_set_bit(ok, kg);
-                        g = make_int2(gc / G, gc % G);
-                        if (live) a.goal_rw[base + lane] = g;
-                    }
-                    if (count > 1) {
-                        int kb = (int)__umulhi(d.y, (uint32_t)(count - 1));
-                        kb += (kb >= kg);
-                        const int bc = kth_set_bit(ok, kb);
-                        b = make_int2(bc / G, bc % G);
-                    }
-                } else if (count > 0) {
-                    const int bc = kth_set_bit(ok, (int)__umulhi(d.y, (uint32_t)count));
-                    b = make_int2(bc / G, bc % G);
-                }
-                sc_in = 0;      // v0:110
-                r_in = -0.0f;   // v0:109
+        if (autoreset) {   // placement over the accepted cells of the wave's 64, one ballot
+            const unsigned long long ok[1] = {__ballot(interior(lane, G) && spawn_ok<VARIANT>((uint8_t)myc))};
+            if (s.done) {
+                int bc, gc;
+                place_from_masks<VARIANT, 1>(ok, __popcll(ok[0]), env_draw(a.seed, epoch, a.env_base + base + lane), bc, gc);
+                env_reset<VARIANT>(bc, gc, G, s);
+                if (V3 && gc >= 0 && live) a.goal_rw[base + lane] = s.g;
             }
         }
-        int bx = clampi(b.x, 0, G - 1), by = clampi(b.y, 0, G - 1);
-        const int sc = sc_in + 1;  // v0:151, v3:225
-        int ox, oy;
-        decode_action(in.act, ox, oy);
-        const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-        const uint8_t c = (uint8_t)__shfl(myc, tx * G + ty, 64);      // v0:172, v3:251 -- every lane takes part
-        float r;
-        bool dn;
-        const bool hit = transition_rule<VARIANT>(a, c, ox, oy, tx, ty, sc, r_in, g.x, g.y, bx, by, r, dn);
+        // v0:172, v3:251 -- every lane takes part in the __shfl
+        const bool hit = env_advance<VARIANT>(a, G, [&](int tx, int ty) { return (uint8_t)__shfl(myc, tx * G + ty, 64); }, s);
         if (live) {
             const int64_t e = base + lane;
             if (hit && a.goal_count) count_goal(a.goal_count + e);
-            a.ball[e] = make_int2(bx, by);
-            a.step_count[e] = sc;
-            a.reward[e] = r;
-            a.done[e] = dn ? 1 : 0;
+            store_state(a, e, s);
         }
-        b = make_int2(bx, by);
     } else {
-        b = make_int2(clampi(b.x, 0, G - 1), clampi(b.y, 0, G - 1));
+        clamp_ball(s, G);
     }
     if (a.obs == nullptr) return;
-    const int ball_cell = b.x * G + b.y;
-    const int goal_cell = (V3 && g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) ? g.x * G + g.y : -8;
+    const int ball_cell = ball_cell_of(s.b, G);
+    const int goal_cell = goal_cell_of<VARIANT>(s.g, G);
 #pragma unroll
     for (int k = 0; k < EPW / 4; ++k) {
         const int le = (lane >> 4) + 4 * k;                           // env of store k
@@ -778,11 +758,11 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_u8_kernel(const StepA
     int nb = (int)min((int64_t)EPB, a.n - blockbase);
     const bool masked = !DO_STEP && a.mask != nullptr;
     const bool autoreset = DO_STEP && a.auto_reset;
-    const uint64_t epoch = autoreset ? launch_epoch(a.epoch, a.epoch_in) : 0;
-    if (autoreset) pass_epoch_on(a.epoch_in, a.epoch_out);
-    EnvIn in{};
+    const uint64_t epoch = step_epoch(a, autoreset);
+    EnvState in{};
     if (tid < nb) in = load_env<VARIANT, DO_STEP>(a, blockbase + tid);
     // large batches: the first 256 workgroups touch every line of this step's per-env inputs once, as step_shared_kernel does
+    // (the same block, written out in both kernels: see there)
     int warmed = 0;
     if (DO_STEP && (a.launch_hint & 0x100)) {
         warmed = warm_lines(a.action, a.n * 4, 256) + warm_lines(a.ball, a.n * 8, 256) + warm_lines(a.step_count, a.n * 4, 256);
@@ -816,7 +796,7 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_u8_kernel(const StepA
   for (;;) {
     const int64_t next = chunk + gridDim.x;
     const bool has_next = next < nchunks;                               // uniform over the workgroup
-    EnvIn in_next{};
+    EnvState in_next{};
     int nb_next = 0;
     if (has_next) {
         nb_next = (int)min((int64_t)EPB, a.n - next * EPB);
@@ -903,6 +883,44 @@ struct RolloutArgs {
     int32_t T;
 };
 
+// The rollout kernels' registers, loaded once: the env's state with the action row of step 0 in act (a lane without
+// an env holds a neutral one)
+template <int VARIANT>
+__device__ __forceinline__ EnvState rollout_load(const StepArgs& a, const RolloutArgs& ro, int64_t e, bool live) {
+    EnvState s;
+    s.b = make_int2(1, 1); s.g = make_int2(-1, -1);
+    s.act = -1; s.sc = 0; s.done = 0; s.r = 0.0f;
+    if (live) {
+        s.b = a.ball[e];
+        if (VARIANT == LMAZE_VARIANT_V3) s.g = a.goal[e];
+        s.sc = a.step_count[e];
+        if (VARIANT != LMAZE_VARIANT_V3) s.r = a.reward[e];
+        if (a.auto_reset) s.done = a.done[e];
+        s.act = ro.actions[e];
+    }
+    return s;
+}
+
+// step t's reward / done rows, for the caller who asked for the trajectory
+__device__ __forceinline__ void rollout_record(const RolloutArgs& ro, int64_t n, int t, int64_t e, const EnvState& s) {
+    if (ro.reward_t) ro.reward_t[(size_t)t * n + e] = s.r;
+    if (ro.done_t) ro.done_t[(size_t)t * n + e] = s.done;
+}
+
+// the state goes back once, at the end of the rollout: v3's goal only when the fused reset can have moved it
+template <int VARIANT>
+__device__ __forceinline__ void rollout_store(const StepArgs& a, const RolloutArgs& ro, int64_t e, bool live, const EnvState& s,
+                                              int hits) {
+    if (live && ro.T > 0) {
+        a.ball[e] = s.b;
+        if (VARIANT == LMAZE_VARIANT_V3 && a.auto_reset) a.goal_rw[e] = s.g;
+        a.step_count[e] = s.sc;
+        a.reward[e] = s.r;
+        a.done[e] = s.done;
+        if (hits && a.goal_count) a.goal_count[e] += hits;
+    }
+}
+
 template <int VARIANT, int EPW>
 __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_wave8_kernel(const StepArgs a, const RolloutArgs ro) {
     constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
@@ -915,68 +933,28 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_wave8_kernel(const
     const bool live = lane < nb;
     const int64_t e = base + lane;
     const int myc = a.layout[lane];
-    int2 b = make_int2(1, 1), g = make_int2(-1, -1);
-    int sc = 0, was_done = 0, hits = 0, act_next = -1;
-    float r = 0.0f;
-    if (live) {
-        b = a.ball[e];
-        if (V3) g = a.goal[e];
-        sc = a.step_count[e];
-        if (!V3) r = a.reward[e];
-        if (autoreset) was_done = a.done[e];
-        act_next = ro.actions[e];
-    }
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);
+    int hits = 0, act_next = s.act;
     const int mypat = cell_bits<VARIANT>((uint8_t)myc);
     const int p4 = (lane & 15) << 2;
     const int4 pat4 = make_int4(__shfl(mypat, p4, 64), __shfl(mypat, p4 + 1, 64), __shfl(mypat, p4 + 2, 64),
                                 __shfl(mypat, p4 + 3, 64));
-    const unsigned long long ok = __ballot(interior(lane, G) && spawn_ok<VARIANT>((uint8_t)myc));
+    const unsigned long long ok[1] = {__ballot(interior(lane, G) && spawn_ok<VARIANT>((uint8_t)myc))};
     int4* obs4 = a.obs ? reinterpret_cast<int4*>(a.obs + (size_t)base * CELLS) : nullptr;
-    bool dn = false;
     for (int t = 0; t < ro.T; ++t) {
-        const int act = act_next;
+        s.act = act_next;
         if (t + 1 < ro.T && live) act_next = ro.actions[(size_t)(t + 1) * a.n + e];      // next step's row, in flight over this step
-        float r_in = r;
-        if (autoreset && was_done) {   // reference reset(): as step_shared_wave8_kernel, with this step's epoch
-            const uint4 d = env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e);
-            const int count = __popcll(ok);
-            if (V3) {
-                int kg = -1;
-                if (count > 0) {
-                    kg = (int)__umulhi(d.x, (uint32_t)count);
-                    const int gc = kth_set_bit(ok, kg);
-                    g = make_int2(gc / G, gc % G);
-                }
-                if (count > 1) {
-                    int kb = (int)__umulhi(d.y, (uint32_t)(count - 1));
-                    kb += (kb >= kg);
-                    const int bc = kth_set_bit(ok, kb);
-                    b = make_int2(bc / G, bc % G);
-                }
-            } else if (count > 0) {
-                const int bc = kth_set_bit(ok, (int)__umulhi(d.y, (uint32_t)count));
-                b = make_int2(bc / G, bc % G);
-            }
-            sc = 0;         // v0:110
-            r_in = -0.0f;   // v0:109
+        if (autoreset && s.done) {   // as step_shared_wave8_kernel, with this step's epoch
+            int bc, gc;
+            place_from_masks<VARIANT, 1>(ok, __popcll(ok[0]), env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
+            env_reset<VARIANT>(bc, gc, G, s);
         }
-        int bx = clampi(b.x, 0, G - 1), by = clampi(b.y, 0, G - 1);
-        sc += 1;            // v0:151, v3:225
-        int ox, oy;
-        decode_action(act, ox, oy);
-        const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-        const uint8_t c = (uint8_t)__shfl(myc, tx * G + ty, 64);      // v0:172, v3:251 -- every lane takes part
-        const bool hit = transition_rule<VARIANT>(a, c, ox, oy, tx, ty, sc, r_in, g.x, g.y, bx, by, r, dn);
-        hits += hit ? 1 : 0;
-        b = make_int2(bx, by);
-        was_done = dn ? 1 : 0;
-        if (live) {
-            if (ro.reward_t) ro.reward_t[(size_t)t * a.n + e] = r;
-            if (ro.done_t) ro.done_t[(size_t)t * a.n + e] = dn ? 1 : 0;
-        }
+        // every lane takes part in the __shfl
+        hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return (uint8_t)__shfl(myc, tx * G + ty, 64); }, s) ? 1 : 0;
+        if (live) rollout_record(ro, a.n, t, e, s);
         if (obs4) {
-            const int ball_cell = b.x * G + b.y;
-            const int goal_cell = (V3 && g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) ? g.x * G + g.y : -8;
+            const int ball_cell = ball_cell_of(s.b, G);
+            const int goal_cell = goal_cell_of<VARIANT>(s.g, G);
 #pragma unroll
             for (int k = 0; k < EPW / 4; ++k) {
                 const int le = (lane >> 4) + 4 * k;
@@ -989,13 +967,38 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_wave8_kernel(const
             }
         }
     }
-    if (live && ro.T > 0) {
-        a.ball[e] = b;
-        if (V3 && autoreset) a.goal_rw[e] = g;
-        a.step_count[e] = sc;
-        a.reward[e] = r;
-        a.done[e] = dn ? 1 : 0;
-        if (hits && a.goal_count) a.goal_count[e] += hits;
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+}
+
+// One step's planes of a rollout workgroup (R dwords): dword f of the range = cell f % CELLS of env f / CELLS, a lane
+// walking its 16-byte stores 1024 dwords apart, then the ragged tail (nb*G*G not a multiple of 4).  bits(le, c) = the
+// ball-free plane bits of cell c of env le.
+template <int VARIANT, class Bits>
+__device__ __forceinline__ void rollout_render(int32_t* obs, int R, int CELLS, const int* ballflat, const int* goalflat, Bits bits) {
+    const int tid = threadIdx.x, nq = R >> 2;
+    auto value = [&](int le, int c) {
+        int v = bits(le, c);
+        v |= (ballflat[le] == c) ? LMAZE_OBS_BALL : 0;
+        if (VARIANT == LMAZE_VARIANT_V3) v |= (goalflat[le] == c) ? LMAZE_OBS_GOAL : 0;
+        return v;
+    };
+    int le = (tid << 2) / CELLS, c = (tid << 2) - le * CELLS;
+    const int dle = (LMAZE_BLOCK << 2) / CELLS, dc = (LMAZE_BLOCK << 2) - dle * CELLS;
+    for (int q = tid; q < nq; q += LMAZE_BLOCK) {
+        int vals[4], l2 = le, c2 = c;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            vals[j] = value(l2, c2);
+            if (++c2 == CELLS) { c2 = 0; ++l2; }
+        }
+        reinterpret_cast<int4*>(obs)[q] = make_int4(vals[0], vals[1], vals[2], vals[3]);
+        le += dle; c += dc;
+        if (c >= CELLS) { c -= CELLS; ++le; }
+    }
+    const int f = (nq << 2) + tid;
+    if (f < R) {
+        const int l2 = f / CELLS;
+        obs[f] = value(l2, f - l2 * CELLS);
     }
 }
 
@@ -1023,17 +1026,8 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_kernel(const StepA
     const int nb = (int)min((int64_t)EPB, a.n - blockbase);
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
-    int2 b = make_int2(1, 1), g = make_int2(-1, -1);
-    int sc = 0, was_done = 0, hits = 0, act_next = -1;
-    float r = 0.0f;
-    if (live) {                                                               // in flight over the set-up
-        b = a.ball[e];
-        if (V3) g = a.goal[e];
-        sc = a.step_count[e];
-        if (!V3) r = a.reward[e];
-        if (autoreset) was_done = a.done[e];
-        act_next = ro.actions[e];
-    }
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
+    int hits = 0, act_next = s.act;
     for (int i = tid; i < CELLS; i += LMAZE_BLOCK) {
         const uint8_t c = a.layout[i];
         lay[i] = c;
@@ -1047,71 +1041,26 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_kernel(const StepA
     const int spawn_count = autoreset ? spawn_count_s : 0;
 
     int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
-    const int R = nb * CELLS, nq = R >> 2;
-    bool dn = false;
     for (int t = 0; t < ro.T; ++t) {
         if (live) {
-            const int act = act_next;
+            s.act = act_next;
             if (t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];       // next step's row, in flight over this step
-            float r_in = r;
-            if (autoreset && was_done) {                                              // reference reset(), as env_phase1
+            if (autoreset && s.done) {                                                // as env_phase1
                 int bc, gc;
                 place_from_list<VARIANT>(spawn, spawn_count, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
-                if (bc >= 0) b = make_int2(bc / G, bc % G);
-                if (V3 && gc >= 0) g = make_int2(gc / G, gc % G);
-                sc = 0;         // v0:110
-                r_in = -0.0f;   // v0:109
+                env_reset<VARIANT>(bc, gc, G, s);
             }
-            int bx = clampi(b.x, 0, G - 1), by = clampi(b.y, 0, G - 1);
-            sc += 1;            // v0:151, v3:225
-            int ox, oy;
-            decode_action(act, ox, oy);
-            const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-            hits += transition_rule<VARIANT>(a, lay[tx * G + ty], ox, oy, tx, ty, sc, r_in, g.x, g.y, bx, by, r, dn) ? 1 : 0;
-            b = make_int2(bx, by);
-            was_done = dn ? 1 : 0;
-            if (ro.reward_t) ro.reward_t[(size_t)t * a.n + e] = r;
-            if (ro.done_t) ro.done_t[(size_t)t * a.n + e] = dn ? 1 : 0;
-            ballflat[tid] = b.x * G + b.y;
-            if (V3) goalflat[tid] = (g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) ? g.x * G + g.y : -8;
+            hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
+            rollout_record(ro, a.n, t, e, s);
+            ballflat[tid] = ball_cell_of(s.b, G);
+            if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
         }
         if (obs == nullptr) continue;                                                 // uniform
         __syncthreads();
-        // dword f of the workgroup's range = cell f % CELLS of env f / CELLS; a lane walks its stores 1024 dwords apart
-        int le = (tid << 2) / CELLS, c = (tid << 2) - le * CELLS;
-        const int dle = (LMAZE_BLOCK << 2) / CELLS, dc = (LMAZE_BLOCK << 2) - dle * CELLS;
-        for (int q = tid; q < nq; q += LMAZE_BLOCK) {
-            int vals[4], l2 = le, c2 = c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int v = pat[c2];
-                v |= (ballflat[l2] == c2) ? LMAZE_OBS_BALL : 0;
-                if (V3) v |= (goalflat[l2] == c2) ? LMAZE_OBS_GOAL : 0;
-                vals[j] = v;
-                if (++c2 == CELLS) { c2 = 0; ++l2; }
-            }
-            reinterpret_cast<int4*>(obs)[q] = make_int4(vals[0], vals[1], vals[2], vals[3]);
-            le += dle; c += dc;
-            if (c >= CELLS) { c -= CELLS; ++le; }
-        }
-        const int f = (nq << 2) + tid;                                                // ragged tail: nb*G*G not a multiple of 4
-        if (f < R) {
-            const int l2 = f / CELLS, c2 = f - l2 * CELLS;
-            int v = pat[c2];
-            v |= (ballflat[l2] == c2) ? LMAZE_OBS_BALL : 0;
-            if (V3) v |= (goalflat[l2] == c2) ? LMAZE_OBS_GOAL : 0;
-            obs[f] = v;
-        }
+        rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat, [&](int, int c) { return pat[c]; });
         __syncthreads();                                                              // ballflat / goalflat are rewritten by the next step
     }
-    if (live && ro.T > 0) {
-        a.ball[e] = b;
-        if (V3 && autoreset) a.goal_rw[e] = g;
-        a.step_count[e] = sc;
-        a.reward[e] = r;
-        a.done[e] = dn ? 1 : 0;
-        if (hits && a.goal_count) a.goal_count[e] += hits;
-    }
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
 }
 
 // The same for per-env layouts: the workgroup's EPB layouts (EPB * G * G bytes) are copied to LDS once and serve the
@@ -1132,17 +1081,8 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_perenv_kernel(const StepA
     const int nb = (int)min((int64_t)EPB, a.n - blockbase);
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
-    int2 b = make_int2(1, 1), g = make_int2(-1, -1);
-    int sc = 0, was_done = 0, hits = 0, act_next = -1;
-    float r = 0.0f;
-    if (live) {
-        b = a.ball[e];
-        if (V3) g = a.goal[e];
-        sc = a.step_count[e];
-        if (!V3) r = a.reward[e];
-        if (autoreset) was_done = a.done[e];
-        act_next = ro.actions[e];
-    }
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);
+    int hits = 0, act_next = s.act;
     {   // EPB is a multiple of 4: the workgroup's layouts start on a dword and are whole dwords
         const uint32_t* src = reinterpret_cast<const uint32_t*>(a.layout + (size_t)blockbase * CELLS);
         uint32_t* dst = reinterpret_cast<uint32_t*>(lays);
@@ -1153,78 +1093,33 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_perenv_kernel(const StepA
     __syncthreads();
 
     int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
-    const int R = nb * CELLS, nq = R >> 2;
-    bool dn = false;
     for (int t = 0; t < ro.T; ++t) {
         if (tid < 64) {                                                               // wave 0, every lane: the ballots below
-            const int act = act_next;
+            s.act = act_next;
             if (live && t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];
-            float r_in = r;
             // reference reset() of the done envs, one whole-wave placement each on the env's own layout
-            unsigned long long todo = __ballot(live && autoreset && was_done);
+            unsigned long long todo = __ballot(live && autoreset && s.done);
             while (todo) {
                 const int j = __ffsll((long long)todo) - 1;
                 todo &= todo - 1ull;
                 int bc, gc;
                 wave_place<VARIANT>(lays + j * CELLS, G, CELLS, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + blockbase + j), tid, bc, gc);
-                if (tid == j) {
-                    if (bc >= 0) b = make_int2(bc / G, bc % G);
-                    if (V3 && gc >= 0) g = make_int2(gc / G, gc % G);
-                    sc = 0;         // v0:110
-                    r_in = -0.0f;   // v0:109
-                }
+                if (tid == j) env_reset<VARIANT>(bc, gc, G, s);
             }
             if (live) {
-                int bx = clampi(b.x, 0, G - 1), by = clampi(b.y, 0, G - 1);
-                sc += 1;            // v0:151, v3:225
-                int ox, oy;
-                decode_action(act, ox, oy);
-                const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-                hits += transition_rule<VARIANT>(a, lays[tid * CELLS + tx * G + ty], ox, oy, tx, ty, sc, r_in, g.x, g.y, bx, by, r, dn) ? 1 : 0;
-                b = make_int2(bx, by);
-                was_done = dn ? 1 : 0;
-                if (ro.reward_t) ro.reward_t[(size_t)t * a.n + e] = r;
-                if (ro.done_t) ro.done_t[(size_t)t * a.n + e] = dn ? 1 : 0;
-                ballflat[tid] = b.x * G + b.y;
-                if (V3) goalflat[tid] = (g.x >= 0 && g.x < G && g.y >= 0 && g.y < G) ? g.x * G + g.y : -8;
+                hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lays[tid * CELLS + tx * G + ty]; }, s) ? 1 : 0;
+                rollout_record(ro, a.n, t, e, s);
+                ballflat[tid] = ball_cell_of(s.b, G);
+                if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
             }
         }
         if (obs == nullptr) continue;                                                 // uniform
         __syncthreads();
-        int le = (tid << 2) / CELLS, c = (tid << 2) - le * CELLS;
-        const int dle = (LMAZE_BLOCK << 2) / CELLS, dc = (LMAZE_BLOCK << 2) - dle * CELLS;
-        for (int q = tid; q < nq; q += LMAZE_BLOCK) {
-            int vals[4], l2 = le, c2 = c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int v = cell_bits<VARIANT>(lays[l2 * CELLS + c2]);
-                v |= (ballflat[l2] == c2) ? LMAZE_OBS_BALL : 0;
-                if (V3) v |= (goalflat[l2] == c2) ? LMAZE_OBS_GOAL : 0;
-                vals[j] = v;
-                if (++c2 == CELLS) { c2 = 0; ++l2; }
-            }
-            reinterpret_cast<int4*>(obs)[q] = make_int4(vals[0], vals[1], vals[2], vals[3]);
-            le += dle; c += dc;
-            if (c >= CELLS) { c -= CELLS; ++le; }
-        }
-        const int f = (nq << 2) + tid;                                                // ragged tail
-        if (f < R) {
-            const int l2 = f / CELLS, c2 = f - l2 * CELLS;
-            int v = cell_bits<VARIANT>(lays[l2 * CELLS + c2]);
-            v |= (ballflat[l2] == c2) ? LMAZE_OBS_BALL : 0;
-            if (V3) v |= (goalflat[l2] == c2) ? LMAZE_OBS_GOAL : 0;
-            obs[f] = v;
-        }
+        rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat,
+                                [&](int le, int c) { return cell_bits<VARIANT>(lays[le * CELLS + c]); });
         __syncthreads();
     }
-    if (live && ro.T > 0) {
-        a.ball[e] = b;
-        if (V3 && autoreset) a.goal_rw[e] = g;
-        a.step_count[e] = sc;
-        a.reward[e] = r;
-        a.done[e] = dn ? 1 : 0;
-        if (hits && a.goal_count) a.goal_count[e] += hits;
-    }
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1308,7 +1203,7 @@ template <int GT, int VARIANT, bool DO_STEP, int EPB>
 static hipError_t launch_shared(const StepArgs& a, hipStream_t s) {
     const int64_t blocks = (a.n + EPB - 1) / EPB;
     size_t lds = shared_lds_bytes(a.grid, GT != 0, EPB, VARIANT == LMAZE_VARIANT_V3);
-    const bool nt = a.obs != nullptr && (size_t)a.n * a.grid * a.grid * 4 > kNonTemporalObsBytes;
+    const bool nt = a.obs != nullptr && beyond_caches(a.n, a.grid * a.grid);
     // default (workgroups per CU, chunks per workgroup) of the streaming regime: the generated table (round 2 kept them
     // in a hand-edited if-chain here, retuned four times in its last hour; LAB_NOTES.md has that history)
     int def_cu = 3, def_m = 2;
@@ -1352,7 +1247,7 @@ static hipError_t launch_perenv_wave(const StepArgs& a, hipStream_t s) {
     b.envs_per_block = 1;
     const int64_t per_block = (int64_t)b.envs_per_block * (LMAZE_BLOCK / 64);
     const int64_t blocks = (a.n + per_block - 1) / per_block;
-    const bool nt = a.obs != nullptr && (size_t)a.n * G * G * 4 > kNonTemporalObsBytes;
+    const bool nt = a.obs != nullptr && beyond_caches(a.n, G * G);
     if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
     if (a.info) {
         char name[96];
@@ -1411,7 +1306,7 @@ static hipError_t launch_one(const StepArgs& a, int layout_mode, hipStream_t s) 
     if (layout_mode != LMAZE_LAYOUT_SHARED) return launch_perenv<GT, VARIANT, DO_STEP>(a, s);
     if constexpr (GT == 8) {
         // small batches (the planes stay on-die): the wave-autonomous kernel, no LDS, no barrier
-        const bool small = a.obs == nullptr || (size_t)a.n * 64 * 4 <= kNonTemporalObsBytes;
+        const bool small = a.obs == nullptr || !beyond_caches(a.n, 64);
         if (small && a.mask == nullptr && (a.launch_hint & 0x100) == 0) {
             // envs per wave: launch_hint bits 4-7 = 1: 64, 2: 32, 3: 16 (0 = default)
             // Defaults, measured at 65 536 envs under hipGraph (us per step, two boxes): 64 envs per wave x 4 waves per
@@ -1450,7 +1345,7 @@ static hipError_t launch_one(const StepArgs& a, int layout_mode, hipStream_t s) 
         // with the fused reset (after its set-up lost the compacted spawn list and the early wait) 32 envs uncapped 78.8-83.5
         // on two boxes, 64 envs at (3, 2) 81 / 95-97, at (3, 1) 81-84.
         int sel = (a.launch_hint >> 10) & 3;
-        const bool streaming = a.obs != nullptr && (size_t)a.n * GT * GT * 4 > kNonTemporalObsBytes;
+        const bool streaming = a.obs != nullptr && beyond_caches(a.n, GT * GT);
         // 12x12 (1M envs, 643 MB): 16 envs (9 KiB) per workgroup, uncapped 97.1-97.4 us, (5, 2) 96.0, against 104-105 for 64
         // envs at (2, 1) and 111-119 for nearly everything else; with the fused reset 103-104 against 109.  (3: 16 envs.)
         if (sel == 0) {
@@ -1467,7 +1362,7 @@ static hipError_t launch_one(const StepArgs& a, int layout_mode, hipStream_t s) 
         // policy of 32 envs but (2, 2) (132.5); 512K x 18x18 v3: 16 envs at (4, 1) or (3, 2) 104.3-104.5 against 109.5
         // for 32 at (2, 1) -- but 118-134 one step to either side, so there it stays a tuner candidate.
         int sel = (a.launch_hint >> 10) & 3;
-        const bool streaming = a.obs != nullptr && (size_t)a.n * GT * GT * 4 > kNonTemporalObsBytes;
+        const bool streaming = a.obs != nullptr && beyond_caches(a.n, GT * GT);
         if (sel == 0) sel = ((GT == 14 || VARIANT == LMAZE_VARIANT_V3) && streaming) ? 2 : 1;
         if (((a.launch_hint >> 10) & 3) == 0 && streaming) sel = table_sel<VARIANT>(a, sel);   // v3 18x18 since its render went to bit strings: 16 envs at 4-5 per CU 109 us (with the fused reset 5-8 per CU 103-107) against 112-120
         if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 16>(a, s);
@@ -1477,7 +1372,7 @@ static hipError_t launch_one(const StepArgs& a, int layout_mode, hipStream_t s) 
         // step: 4 envs at (5, 1) 84.0 / 337 and at (4, 1) 85.0 / 323 against 96 / 363 for 8 envs at (2, 1); with the fused
         // reset 4 envs at (5, 1) 88.6 / 342, at (6, 1) 81.8 / 313, against 102 / 403.
         int sel = (a.launch_hint >> 10) & 3;
-        const bool streaming = a.obs != nullptr && (size_t)a.n * GT * GT * 4 > kNonTemporalObsBytes;
+        const bool streaming = a.obs != nullptr && beyond_caches(a.n, GT * GT);
         if (sel == 0) sel = streaming ? table_sel<VARIANT>(a, 2) : 1;
         if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 4>(a, s);
         return launch_shared<GT, VARIANT, DO_STEP, 8>(a, s);
@@ -1487,7 +1382,7 @@ static hipError_t launch_one(const StepArgs& a, int layout_mode, hipStream_t s) 
         int sel = (a.launch_hint >> 10) & 3;
         if (sel == 0) {
             sel = a.grid >= 15 ? 3 : (a.grid >= 5 ? 2 : 1);
-            if (a.obs != nullptr && (size_t)a.n * a.grid * a.grid * 4 > kNonTemporalObsBytes && a.grid >= 5) sel = table_sel<VARIANT>(a, sel);
+            if (a.obs != nullptr && beyond_caches(a.n, a.grid * a.grid) && a.grid >= 5) sel = table_sel<VARIANT>(a, sel);
         }
         if (sel == 3) return launch_shared<GT, VARIANT, DO_STEP, 16>(a, s);
         if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 64>(a, s);
@@ -1564,7 +1459,7 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
                           uint8_t* done_t, hipStream_t s) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
     const bool on_die8 = layout_mode == LMAZE_LAYOUT_SHARED && a0.grid == 8 &&
-                         (a0.obs == nullptr || (size_t)a0.n * 64 * 4 <= kNonTemporalObsBytes) && (a0.launch_hint & 0x100) == 0;
+                         (a0.obs == nullptr || !beyond_caches(a0.n, 64)) && (a0.launch_hint & 0x100) == 0;
     if (on_die8) {
         RolloutArgs ro{actions, reward_t, done_t, T};
         const int epw = 64, wpb = a0.n >= 65536 ? 4 : 1;
@@ -1597,7 +1492,7 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         // 512K x 18x18: 64: 89.2, 16: 98.4, 8: 74.2, 4: 76.2; 256K x 32x32 (no size fits): 146 / 140 / 133.7 / 141.6
         // (profiles/r03/rollout_envs_per_workgroup.txt).  launch_hint bits 12-14 = k > 0 ask for 4 << (k - 1) envs.
         // (Only beyond the Infinity Cache: 262 144 x 11x11, 127 MB of planes, runs 9.9 us per step at 64 envs and 12.9 at 16.)
-        if ((size_t)a0.n * a0.grid * a0.grid * 4 > kNonTemporalObsBytes) {
+        if (beyond_caches(a0.n, a0.grid * a0.grid)) {
             int fit = 64;
             while (fit > 8 && (size_t)fit * a0.grid * a0.grid * 4 > 12288) fit >>= 1;
             if (fit < a.envs_per_block) a.envs_per_block = fit;
@@ -1630,7 +1525,7 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         const int cells = a0.grid * a0.grid;
         int epb = a0.n >= 65536 ? 64 : (a0.n >= 16384 ? 32 : 16);
         while (epb > 4 && (size_t)epb * cells > (size_t)32 << 10) epb >>= 1;         // at most 32 KiB of layouts per workgroup
-        if ((size_t)a0.n * cells * 4 > kNonTemporalObsBytes)                         // beyond the caches: planes that fit the L2s, as above
+        if (beyond_caches(a0.n, cells))                                              // planes that fit the L2s, as above
             while (epb > 8 && (size_t)epb * cells * 4 > 12288) epb >>= 1;
         if ((a0.launch_hint >> 12) & 7) epb = 4 << (((a0.launch_hint >> 12) & 7) - 1);
         if (epb > 64) epb = 64;                                                      // every env's lane sits in wave 0
