@@ -32,7 +32,7 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_v5_planner_step", "lmaze_v5_hier_step", "lmaze_v6_safe_foveal_goal", "lmaze_expand_planes",
            "lmaze_foveal_visit_bytes", "lmaze_foveal_materialise_visit", "lmaze_foveal_load_visit",
            "lmaze_describe_step", "lmaze_describe_foveal_step", "lmaze_rollout",
-           "lmaze_step_u8", "lmaze_observe_u8")
+           "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout")
 
 
 class LmazeParams(C.Structure):
@@ -148,6 +148,10 @@ def _load():
     lib.lmaze_describe_step.argtypes = [P, i64, i32, i32, C.c_char_p, i32]
     lib.lmaze_describe_foveal_step.restype = C.c_int
     lib.lmaze_describe_foveal_step.argtypes = [FP, i64, i32, C.c_char_p, i32]
+    lib.lmaze_foveal_rollout.restype = C.c_int
+    lib.lmaze_foveal_rollout.argtypes = [FP, vp, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp]
+    lib.lmaze_describe_foveal_rollout.restype = C.c_int
+    lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -183,6 +187,15 @@ def describe_step(params, n, auto_reset=False, with_obs=True):
 def describe_foveal_step(params, n, auto_reset=False):
     buf = C.create_string_buffer(256)
     check("lmaze_describe_foveal_step", lib.lmaze_describe_foveal_step(C.byref(params), int(n), 1 if auto_reset else 0, buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+def describe_foveal_rollout(params, n, T, auto_reset=False, two_level=False):
+    """The kernel / grid / launch policy lmaze_foveal_rollout would queue for n envs and T steps."""
+    buf = C.create_string_buffer(256)
+    check("lmaze_describe_foveal_rollout", lib.lmaze_describe_foveal_rollout(C.byref(params), int(n), int(T),
+                                                                             1 if auto_reset else 0, 1 if two_level else 0,
+                                                                             buf, 256))
     return buf.value.decode("ascii", "replace")
 
 

@@ -56,6 +56,17 @@ struct FovealArgs {
     LaunchInfo* info;       // host pointer; non-null: describe the launch instead of queueing it (lmaze_describe_foveal_step)
 };
 
+// The one-launch rollout (foveal_rollout_kernel, lmaze_foveal_rollout): T steps of one chunk of envs before the next
+// chunk; step t reads action row t (and planner-goal row t) of the int32[T,N] tensors in FovealArgs and draws its
+// resets with epoch + t.  Row t of the trajectory outputs (nullable) gets every env's reward / done after step t.
+struct FovealRoll {
+    int32_t T;
+    float* reward_t;        // [T,N] reward
+    uint8_t* done_t;        // [T,N] done
+    float* freward_t;       // [T,N] foveal_reward (v1, v5/v6)
+    uint8_t* fdone_t;       // [T,N] foveal_done (v1, v5/v6)
+};
+
 struct EnvRec {           // one env after its transition (registers only; phase 1 turns it into plane masks)
     int16_t cx, cy;       // centre of the current window (ball after the move)
     int16_t px, py;       // centre of the "previous" window
@@ -207,823 +218,29 @@ __device__ __forceinline__ uint32_t visit_add(uint32_t bits, int E) { return lma
 #else
 #define LMAZE_FOVEAL_ATTR
 #endif
+// The step kernels and the rollout kernel share one body, lmaze_foveal_body.h, included into each (a kernel of its own
+// rather than a __device__ function: through a function the existing step kernels compiled to other code -- their kernel
+// argument loads lost their no-clobber marks, and v5's two-level step went from 127 to 129 VGPRs, one wave per SIMD less).
+// ROLL = false: one step over one chunk per workgroup round, as ever; everything the rollout adds is dead code.
 template <int VARIANT, int MODE, int EPB, int GT, bool AR>
 __global__ __launch_bounds__(LMAZE_BLOCK) LMAZE_FOVEAL_ATTR void foveal_kernel(const FovealArgs a) {
-    constexpr bool V1 = VARIANT == LMAZE_VARIANT_V1, V5 = VARIANT == LMAZE_VARIANT_V5;
-    constexpr bool V4 = VARIANT == LMAZE_VARIANT_V4 || V5;   // "has a visit map"
-    constexpr int C = V1 ? 4 : (V4 ? 7 : 5);
-    // reset placement: row reads in flight per pass (mask_counts).  The two-level variants sit at the 128-VGPR step
-    // (4 waves per SIMD) and any unrolling there costs a wave; v2/v4 have the room
-    constexpr int PLACE_U = V5 ? 1 : 4;
-    constexpr int PERENV = C * W25;  // floats of observation per env
-    const int G = GT ? GT : a.p.grid, CELLS = G * G, L = V1 ? 1 : a.p.n_layouts;
+    constexpr bool ROLL = false;
+    const FovealRoll ro{};
+#define LMAZE_FOVEAL_BODY_SITE
+#include "lmaze_foveal_body.h"
+#undef LMAZE_FOVEAL_BODY_SITE
+}
 
-    // LDS: per-env plane masks and window centres, the two 5x5 samples of the visit map (v4-v6), one
-    // 64-bit row mask per layout row for each static plane, and the layout characters for the transition
-    extern __shared__ int4 lds4[];
-    // the 0/1 planes as bit strings, bit f = float f of the workgroup's contiguous output range (the float visit
-    // planes of v4-v6 are zero bits there and come from vwin): a 16-byte store is one nibble of the string
-    uint32_t* obits = reinterpret_cast<uint32_t*>(lds4);                   // [EPB*PERENV bits]  obs
-    uint32_t* lbits = obits + EPB * 8;                                     // [EPB*100 bits]     obs_local (v5/v6)
-    int16_t* cen = reinterpret_cast<int16_t*>(lbits + EPB * 4);            // [EPB][4]  cx, cy, px, py
-    int32_t* flags = reinterpret_cast<int32_t*>(cen + EPB * 4);            // [EPB]     bit0 skip, bit1 visit update, bit2 fresh episode, bit3 not stepped
-    int16_t* rcen = reinterpret_cast<int16_t*>(flags + EPB);               // [EPB][2]  ball a fused reset placed (visit map re-init)
-    float* vwin = reinterpret_cast<float*>(rcen + EPB * 2);                // [EPB][2][25] visit-map samples (v4-v6)
-    int32_t* clk = reinterpret_cast<int32_t*>(vwin + (V4 ? EPB * 2 * W25 : 0));   // [EPB] visit clock on entry (v4-v6)
-    int32_t* dlist = clk + (V4 ? EPB : 0);                                 // [EPB] envs whose whole map is rewritten this call
-    uint64_t* rowfree = reinterpret_cast<uint64_t*>(dlist + (V4 ? EPB : 0));   // [L*G] free = B|S|X
-    uint64_t* rowgoal = rowfree + L * G;                                   // [L*G] interior, not 'W', not 'S' (v2:279)
-    uint64_t* rowball = rowgoal + L * G;                                   // [L*G] interior, not 'W', not 'X' (v2:292)
-    uint64_t* rowwall = rowball + L * G;                                   // [G] v1: 'W'
-    uint64_t* rowx = rowwall + G;                                          // [G] v1: 'X'
-    uint8_t* lays = reinterpret_cast<uint8_t*>(rowx + G);                  // [L*CELLS]
-    static_assert(PERENV <= 8 * 32 - 32 && 4 * W25 <= 4 * 32 - 4, "bit strings fit the 32 B / 16 B per env reserved for them");
-    __shared__ int any_skip, ndense;
-
-    const int tid = threadIdx.x;
-    // A workgroup takes chunks of EPB envs grid-stride (chunk = blockIdx.x, + gridDim.x, ...; one chunk each unless the
-    // launcher asked for more): the set-up below -- row masks of all L layouts -- is paid once per workgroup while the
-    // private range it streams at any moment stays one small chunk (lmaze_step.hip step_shared_kernel does the same)
-    const int64_t nchunks = (a.n + EPB - 1) / EPB;
-    int64_t chunk = blockIdx.x;
-    int64_t blockbase = chunk * EPB;
-    int nb = (int)min((int64_t)EPB, a.n - blockbase);
-    if (tid == 0) { any_skip = 0; ndense = 0; }
-    for (int i = tid; i < EPB * 12; i += LMAZE_BLOCK) obits[i] = 0u;       // obits and lbits
-    if (V4) for (int i = tid; i < EPB * 2 * W25; i += LMAZE_BLOCK) vwin[i] = 0.0f;   // window cells outside the array read 0
-    // the reset epoch, read in front of every store (one uniform scalar load; lmaze_step.hip step_shared_kernel)
-    const uint64_t epoch = launch_epoch(a.epoch, a.epoch_in);
-    if (MODE == FM_STEP && AR) pass_epoch_on(a.epoch_in, a.epoch_out);
-    // large batches: the first 256 workgroups touch every 64-byte line of this step's action array at kernel
-    // start, one burst of reads, so that the per-workgroup loads later in the launch hit the memory-side cache
-    // instead of turning the saturated write stream around (lmaze_step.hip, step_shared_kernel)
-    int warmed = 0;
-    if (MODE == FM_STEP && a.nt) {
-        warmed = warm_lines(a.action, a.n * 4, 256);
-        // v1, v2: the per-env state as well (v2 -3 %).  v4 since its visit map is window-only (round 3: 334-338 us against
-        // 341-377 without, three interleaved passes); v5/v6: no gain (418-443 against 425-465) -- experiment switch only
-        if (!V5 || LMAZE_WARM_V4(a)) {
-            warmed += warm_lines(a.b.ball_xy, a.n * 8, 256) + warm_lines(a.b.step_count, a.n * 4, 256);
-            if (V1) warmed += warm_lines(a.b.fgoal_xy, a.n * 8, 256) + warm_lines(a.b.foveal_step_count, a.n * 4, 256);
-            else warmed += warm_lines(a.b.goal_xy, a.n * 8, 256) + warm_lines(a.b.layout_id, a.n * 4, 256);
-            if (V4) warmed += warm_lines(a.b.visit_clock, a.n * 4, 256);
-            if (V5) warmed += warm_lines(a.b.fgoal_xy, a.n * 8, 256) + warm_lines(a.b.foveal_step_count, a.n * 4, 256) +
-                              warm_lines(a.b.fovea_xy, a.n * 16, 256) + warm_lines(a.b.ball1_xy, a.n * 8, 256) +
-                              warm_lines(a.b.last_xy, a.n * 8, 256) + warm_lines(a.b.foveal_goal, a.n * 4, 256) +
-                              warm_lines(a.goal2, a.n * 4, 256);
-        }
-    }
-    if (LMAZE_XP(a, 1)) {
-        // experiment: no set-up
-    } else if (GT != 0) {
-        // Row masks by ballot, straight from global memory: a wave-iteration covers RPW whole layout rows (their
-        // characters are RPW*G contiguous bytes, one per lane), four ballots give the rows' masks, and every load of
-        // the workgroup -- these and the copy of the characters the transition looks cells up in -- is in flight
-        // before the first is used.  One barrier.  (Round 1 copied the characters to LDS byte by byte, barrier, then
-        // 90 lanes walked 18 LDS bytes each, twice: 58 of the 520 us of a v5 launch.)
-        constexpr int GG = GT ? GT : 1, RPW = 64 / GG, UNR = 8;
-        const int wave = tid >> 6, lane = tid & 63, rows = L * G;
-        const int rsub = lane / GG, y = lane - rsub * GG;
-        const bool dwords = ((reinterpret_cast<uintptr_t>(a.layouts) | (uintptr_t)(L * CELLS)) & 3) == 0;
-        uint32_t cw[2] = {0u, 0u};
-        if (dwords) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) cw[j] = reinterpret_cast<const uint32_t*>(a.layouts)[tid + j * LMAZE_BLOCK];
-        }
-        for (int r00 = 0; r00 < rows; r00 += UNR * 4 * RPW) {
-            uint8_t cc[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int row = r00 + (u * 4 + wave) * RPW + rsub;
-                cc[u] = (rsub < RPW && row < rows) ? a.layouts[(size_t)row * G + y] : (uint8_t)0;
-            }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int row = r00 + (u * 4 + wave) * RPW + rsub;
-                const bool in = rsub < RPW && row < rows;
-                const uint8_t c = cc[u];
-                const unsigned long long bf = __ballot(in && (c == 'B' || c == 'S' || c == 'X'));   // v1:78, v2:94
-                const unsigned long long bw = __ballot(in && c == 'W');                              // v1:70
-                const unsigned long long bx = __ballot(in && c == 'X');                              // v1:74
-                const unsigned long long bs = __ballot(in && c == 'S');
-                if (in && y == 0) {
-                    const int sh = rsub * GG;
-                    const uint64_t keep = GG == 64 ? ~0ull : ((1ull << GG) - 1ull);
-                    const uint64_t fr = (bf >> sh) & keep, wl = (bw >> sh) & keep, xx = (bx >> sh) & keep, ss = (bs >> sh) & keep;
-                    rowfree[row] = fr;
-                    if (V1) { rowwall[row] = wl; rowx[row] = xx; }
-                    if (!V1 && (MODE == FM_RESET || (MODE == FM_STEP && AR))) {
-                        const int x = row % G;
-                        const uint64_t interior = (x >= 1 && x <= G - 2) ? (((1ull << (G - 2)) - 1ull) << 1) : 0ull;
-                        rowgoal[row] = fr & ~ss & interior;      // B or X
-                        rowball[row] = fr & ~xx & interior;      // B or S
-                    }
-                }
-            }
-        }
-        if (dwords) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) reinterpret_cast<uint32_t*>(lays)[tid + j * LMAZE_BLOCK] = cw[j];
-            for (int i = tid + 2 * LMAZE_BLOCK; i < (L * CELLS) >> 2; i += LMAZE_BLOCK)     // more than 2 KiB of layouts
-                reinterpret_cast<uint32_t*>(lays)[i] = reinterpret_cast<const uint32_t*>(a.layouts)[i];
-        } else {
-            for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
-        }
-    } else {
-    for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
-    __syncthreads();
-    for (int i = tid; i < L * G; i += LMAZE_BLOCK) {
-        uint64_t fr = 0, wl = 0, xx = 0;
-        for (int y = 0; y < G; ++y) {
-            const uint8_t c = lays[i * G + y];
-            fr |= (uint64_t)(c == 'B' || c == 'S' || c == 'X') << y;       // v1:78, v2:94
-            wl |= (uint64_t)(c == 'W') << y;                                // v1:70
-            xx |= (uint64_t)(c == 'X') << y;                                // v1:74
-        }
-        rowfree[i] = fr;
-        if (V1) { rowwall[i] = wl; rowx[i] = xx; }
-        if (!V1 && (MODE == FM_RESET || (MODE == FM_STEP && AR))) {
-            uint64_t ss = 0;
-            for (int y = 0; y < G; ++y) ss |= (uint64_t)(lays[i * G + y] == 'S') << y;
-            const int x = i % G;
-            const uint64_t interior = (x >= 1 && x <= G - 2) ? (((1ull << (G - 2)) - 1ull) << 1) : 0ull;
-            rowgoal[i] = fr & ~ss & interior;      // B or X
-            rowball[i] = fr & ~xx & interior;      // B or S
-        }
-    }
-    }
-    __syncthreads();
-
-  for (;;) {
-    // ---------------- phase 1: one lane per env ----------------
-    for (int le = tid; le < (LMAZE_XP(a, 8) ? 0 : nb); le += LMAZE_BLOCK) {
-        const int64_t e = blockbase + le;
-        EnvRec r;
-        r.skip = 0; r.flat = -1; r.action = -1; r.lid = 0; r.gx = r.gy = -9;
-        r.b0x = r.b0y = r.b1x = r.b1y = r.f1x = r.f1y = 0; r.upd = 0; r.pad = 0;
-        bool fresh = false, nostep = false;   // fused reset: new episode this call / its step was refused
-        bool last_is_cur = true;              // v5/v6: the window shown as "previous" from now on is this call's current one
-        int rx = 0, ry = 0;                   // ball the fused reset placed
-        int bx = a.b.ball_xy[2 * e], by = a.b.ball_xy[2 * e + 1];
-        // every per-env input of a step is requested HERE, before anything is branched on: a load that sits behind a branch
-        // on another loaded value (the done flag of the fused reset, localDone of the two-level step) is a second global
-        // round trip in series -- v4's fused reset cost +58...95 us per launch that way (round 3, tools/_ar_study)
-        const int act_in = (MODE == FM_STEP) ? a.action[e] : 0;
-        const int sc_ld = (MODE == FM_STEP) ? a.b.step_count[e] : 0;
-        const int done_in = (MODE == FM_STEP && AR) ? a.b.done[e] : 0;
-        const int goal2_in = (MODE == FM_STEP && AR && V5) ? a.goal2[e] : 0;
-        const int vword = (V4 && !(V5 && MODE == FM_PLANNER)) ? a.b.visit_clock[e] : 0;
-        const int vclock = vword & 0xff;
-        r.px = (int16_t)bx; r.py = (int16_t)by;
-        if (MODE != FM_STEP && a.mask && !a.mask[e]) r.skip = 1;
-        if (V1) {
-            int fgx = a.b.fgoal_xy[2 * e], fgy = a.b.fgoal_xy[2 * e + 1];
-            r.action = 1;  // local view unless this is a reset
-            if (MODE == FM_STEP) {
-                int sc_in = sc_ld;
-                if (AR && done_in) {                         // fused reset(): v1:82-93
-                    for (int c = 0; c < CELLS; ++c)
-                        if (lays[c] == 'S') { bx = c / G; by = c % G; break; }
-                    sc_in = 0;
-                }
-                const int act = act_in;
-                const int sc = sc_in + 1;                              // v1:117
-                const int fsc = a.b.foveal_step_count[e] + 1;          // v1:118
-                float fr = -0.0f, rw = -0.0f;                          // v1:120-121
-                bool local_done = false;                               // v1:123
-                int ox, oy;
-                decode_action(act, ox, oy);                            // v1:125-133
-                const int tx = clampi(bx + ox, 0, G - 1), ty = clampi(by + oy, 0, G - 1);
-                const uint8_t c = lays[tx * G + ty];
-                if (c == 'W') {                                        // v1:135-138
-                    rw = a.p.reward_wall; fr = a.p.reward_wall;
-                } else if (c == 'B') {                                 // v1:140-163
-                    bx = tx; by = ty;
-                    rw = a.p.reward_move; fr = a.p.reward_move;
-                    if (bx < fgx - 1 || bx > fgx + 2 || by < fgy - 1 || by > fgy + 2) {
-                        local_done = true; fr = a.p.reward_wall;
-                    } else if (by == fgy && bx == fgx) {
-                        local_done = true; fr = a.p.reward_goal;
-                    }
-                } else if (c == 'X') {                                 // v1:165-183
-                    bx = tx; by = ty;
-                    rw = a.p.reward_goal;
-                    if (by == fgy && bx == fgx) { local_done = true; fr = a.p.reward_goal; }
-                    else fr = a.p.reward_move;
-                }
-                const bool done = (rw == a.p.reward_goal) || (sc == a.p.step_limit);                         // v1:294-304
-                const bool fdone = local_done || fr == a.p.reward_goal || fsc == a.p.foveal_step_limit || done;  // v1:308-324
-                a.b.ball_xy[2 * e] = bx; a.b.ball_xy[2 * e + 1] = by;
-                a.b.step_count[e] = sc; a.b.foveal_step_count[e] = fsc;
-                a.b.reward[e] = rw; a.b.foveal_reward[e] = fr;
-                a.b.done[e] = done ? 1 : 0; a.b.foveal_done[e] = fdone ? 1 : 0;
-            } else if (MODE == FM_RESET && !r.skip) {
-                if (a.place) {                                         // v1:82-84: ball = first 'S'
-                    for (int c = 0; c < CELLS; ++c)
-                        if (lays[c] == 'S') { bx = c / G; by = c % G; break; }
-                    a.b.ball_xy[2 * e] = bx; a.b.ball_xy[2 * e + 1] = by;
-                }
-                a.b.reward[e] = -0.0f; a.b.foveal_reward[e] = -0.0f;   // v1:90-91
-                a.b.step_count[e] = 0;                                 // v1:93 (fovealStepCount kept, v1:94)
-                a.b.done[e] = 0; a.b.foveal_done[e] = 0;
-                r.action = 0;                                          // v1:100 getGlobalView
-            } else if (MODE == FM_SETGOAL && !r.skip) {                // v1:104-110
-                fgx = bx + a.action[2 * e] - 2;
-                fgy = by + a.action[2 * e + 1] - 2;
-                a.b.fgoal_xy[2 * e] = fgx; a.b.fgoal_xy[2 * e + 1] = fgy;
-                a.b.foveal_step_count[e] = 0;
-            }
-            int flat = fgx * G + fgy;                                  // v1:244-245, numpy negative-index wrap
-            if (flat < 0) flat += CELLS;
-            r.flat = (flat >= 0 && flat < CELLS) ? flat : -1;
-        } else if (V5) {
-            int lid = clampi(a.b.layout_id[e], 0, L - 1);
-            int gx = a.b.goal_xy[2 * e], gy = a.b.goal_xy[2 * e + 1];
-            int fg = a.b.foveal_goal[e];
-            int f0x = a.b.fovea_xy[4 * e], f0y = a.b.fovea_xy[4 * e + 1];
-            int f1x = a.b.fovea_xy[4 * e + 2], f1y = a.b.fovea_xy[4 * e + 3];
-            int b1x = a.b.ball1_xy[2 * e], b1y = a.b.ball1_xy[2 * e + 1];
-            int lx = a.b.last_xy[2 * e], ly = a.b.last_xy[2 * e + 1];
-            if (MODE == FM_STEP) {                                     // v5:187-292
-                const int act = act_in;
-                int fgx = a.b.fgoal_xy[2 * e], fgy = a.b.fgoal_xy[2 * e + 1];
-                int fsc = a.b.foveal_step_count[e];
-                int sc_in = sc_ld;
-                bool ld = a.b.foveal_done[e] != 0, gd = a.b.done[e] != 0;   // both persist across step() calls
-                if (AR) {
-                    // the two-level loop around step() (lmaze_v5_hier_step): reset() for an env that enters with
-                    // globalDone, plannerStep(goal) for one that enters with localDone or was just reset
-                    const bool plan = ld || gd;
-                    bool planned = false;
-                    if (gd) {                                          // reset(): v5:104-150, as FM_RESET below
-                        const uint4 d = env_draw(a.seed, epoch, a.env_base + e);
-                        lid = (int)__umulhi(d.z, (uint32_t)L);         // v5:105 setGrid first
-                        int goal_cell, ball_cell;
-                        place_goal_ball<PLACE_U>(rowgoal + lid * G, rowball + lid * G, G, d, goal_cell, ball_cell);
-                        if (goal_cell >= 0) { gx = goal_cell / G; gy = goal_cell % G; }
-                        if (ball_cell >= 0) { bx = ball_cell / G; by = ball_cell % G; }
-                        a.b.layout_id[e] = lid;
-                        a.b.goal_xy[2 * e] = gx; a.b.goal_xy[2 * e + 1] = gy;
-                        fsc = 0; sc_in = 0; gd = false; ld = false;    // v5:109-112
-                        fg = 12;                                       // v5:127-128
-                        f0x = f1x = b1x = lx = fgx = bx; f0y = f1y = b1y = ly = fgy = by;   // v5:136-143
-                        fresh = true;
-                    }
-                    if (plan) {                                        // plannerStep(goal): v5:158-182, as FM_PLANNER below
-                        const int g = goal2_in;
-                        if (g >= 0 && g < W25) {
-                            fg = g;
-                            sc_in = 0;                                 // v5:160
-                            ld = false;                                // v5:162
-                            fgx = bx + g / FOV - 2; fgy = by + g % FOV - 2;   // v5:172-173
-                            if (fsc > 0) { f1x = f0x; f1y = f0y; }     // v5:175-177
-                            fsc += 1;                                  // v5:179
-                            planned = true;
-                        }
-                    }
-                    if (fresh || planned) {
-                        a.b.foveal_goal[e] = fg;
-                        a.b.fgoal_xy[2 * e] = fgx; a.b.fgoal_xy[2 * e + 1] = fgy;
-                        a.b.fovea_xy[4 * e + 2] = f1x; a.b.fovea_xy[4 * e + 3] = f1y;
-                        a.b.foveal_step_count[e] = fsc;
-                    }
-                }
-                const uint8_t* lay = lays + lid * CELLS;
-                b1x = bx; b1y = by;                                    // v5:193-194
-                float lr = -0.0f, gr;                                  // v5:196
-                const int sc = sc_in + 1;                              // v5:197
-                const int dx = (act == 0) - (act == 1), dy = (act == 2) - (act == 3);   // v5:205-217
-                const int nx = bx + dx, ny = by + dy;
-                const bool nin = nx >= 0 && ny >= 0 && nx < G && ny < G;
-                const uint8_t c = nin ? lay[nx * G + ny] : (uint8_t)'W';
-                if (c == 'W') {                                        // v5:232-233
-                    lr = a.p.reward_wall;
-                } else if (nx == fgx && ny == fgy) {                   // v5:235-239
-                    lr = a.p.reward_goal; bx = nx; by = ny; ld = true;
-                } else if (c == 'B' || c == 'S' || c == 'X') {         // v5:241-248
-                    if (nx < f1x - 3 || nx > f1x + 2 || ny < f1y - 3 || ny > f1y + 2) ld = true;
-                    lr = a.p.reward_move; bx = nx; by = ny;
-                }
-                if (nx == gx && ny == gy) { gr = a.p.reward_goal; gd = true; }   // v5:254-262
-                else if (nx == fgx && ny == fgy) gr = a.p.reward_move;
-                else gr = a.p.reward_wall;
-                f0x = bx; f0y = by;                                    // v5:264-265
-                if (sc >= a.p.step_limit) ld = true;                   // v5:267
-                if (fsc >= a.p.foveal_step_limit) { gd = true; ld = true; }   // v5:269-271
-                if (fsc == 0) { lx = f0x; ly = f0y; }                  // v5:322-323
-                r.px = (int16_t)lx; r.py = (int16_t)ly;                // window the foveal obs shows as "previous"
-                r.upd = ld ? 1 : 0;                                    // v5:313-318
-                if (ld) { lx = f0x; ly = f0y; }                        // v5:344-346 (after the render)
-                last_is_cur = lx == f0x && ly == f0y;
-                a.b.ball_xy[2 * e] = bx; a.b.ball_xy[2 * e + 1] = by;
-                a.b.ball1_xy[2 * e] = b1x; a.b.ball1_xy[2 * e + 1] = b1y;
-                a.b.fovea_xy[4 * e] = f0x; a.b.fovea_xy[4 * e + 1] = f0y;
-                a.b.last_xy[2 * e] = lx; a.b.last_xy[2 * e + 1] = ly;
-                a.b.step_count[e] = sc;
-                a.b.reward[e] = gr; a.b.foveal_reward[e] = lr;
-                a.b.done[e] = gd ? 1 : 0; a.b.foveal_done[e] = ld ? 1 : 0;
-            } else if (MODE == FM_PLANNER && !r.skip) {                // v5:158-182
-                const int g = a.action[e];
-                if (g < 0 || g >= W25) {
-                    r.skip = 1;                                        // the reference raises half-way (v5:169)
-                } else {
-                    fg = g;
-                    a.b.step_count[e] = 0;                             // v5:160
-                    a.b.reward[e] = -0.0f;                             // v5:161
-                    a.b.foveal_done[e] = 0;                            // v5:162
-                    a.b.foveal_goal[e] = g;
-                    a.b.fgoal_xy[2 * e] = bx + g / FOV - 2;            // v5:172-173
-                    a.b.fgoal_xy[2 * e + 1] = by + g % FOV - 2;
-                    const int fsc = a.b.foveal_step_count[e];
-                    if (fsc > 0) {                                     // v5:175-177
-                        f1x = f0x; f1y = f0y;
-                        a.b.fovea_xy[4 * e + 2] = f1x; a.b.fovea_xy[4 * e + 3] = f1y;
-                    }
-                    a.b.foveal_step_count[e] = fsc + 1;                // v5:179
-                }
-            } else if (MODE == FM_RESET && !r.skip) {                  // v5:104-150
-                if (a.place) {
-                    const uint4 d = env_draw(a.seed, a.epoch, a.env_base + e);
-                    lid = (int)__umulhi(d.z, (uint32_t)L);             // v5:105 setGrid first
-                    a.b.layout_id[e] = lid;
-                    int goal_cell, ball_cell;
-                    place_goal_ball<PLACE_U>(rowgoal + lid * G, rowball + lid * G, G, d, goal_cell, ball_cell);
-                    if (goal_cell >= 0) {
-                        gx = goal_cell / G; gy = goal_cell % G;
-                        a.b.goal_xy[2 * e] = gx; a.b.goal_xy[2 * e + 1] = gy;
-                    }
-                    if (ball_cell >= 0) {
-                        bx = ball_cell / G; by = ball_cell % G;
-                        a.b.ball_xy[2 * e] = bx; a.b.ball_xy[2 * e + 1] = by;
-                    }
-                }
-                a.b.foveal_reward[e] = -0.0f; a.b.reward[e] = -0.0f;   // v5:107-108
-                a.b.foveal_step_count[e] = 0; a.b.step_count[e] = 0;   // v5:109-110
-                a.b.done[e] = 0; a.b.foveal_done[e] = 0;               // v5:111-112
-                fg = 12;                                               // v5:127-128
-                a.b.foveal_goal[e] = fg;
-                f0x = f1x = b1x = lx = bx; f0y = f1y = b1y = ly = by;  // v5:136-143
-                a.b.fovea_xy[4 * e] = bx; a.b.fovea_xy[4 * e + 1] = by;
-                a.b.fovea_xy[4 * e + 2] = bx; a.b.fovea_xy[4 * e + 3] = by;
-                a.b.fgoal_xy[2 * e] = bx; a.b.fgoal_xy[2 * e + 1] = by;
-                a.b.ball1_xy[2 * e] = bx; a.b.ball1_xy[2 * e + 1] = by;
-                a.b.last_xy[2 * e] = bx; a.b.last_xy[2 * e + 1] = by;
-                r.px = (int16_t)bx; r.py = (int16_t)by;
-            }
-            r.lid = (int16_t)lid;
-            r.gx = (int16_t)gx; r.gy = (int16_t)gy;
-            r.action = (int16_t)fg;
-            r.b0x = (int16_t)bx; r.b0y = (int16_t)by; r.b1x = (int16_t)b1x; r.b1y = (int16_t)b1y;
-            r.f1x = (int16_t)f1x; r.f1y = (int16_t)f1y;
-            bx = f0x; by = f0y;                                        // the window centre is fovea_0
-        } else {
-            int lid = a.b.layout_id[e];
-            int gx = a.b.goal_xy[2 * e], gy = a.b.goal_xy[2 * e + 1];
-            int sc_in = 0;
-            const bool fused = MODE == FM_STEP && AR && done_in != 0;
-            if ((MODE == FM_RESET && !r.skip) || fused) {              // reset(): v2:80-123, v4:95-163
-                if (a.place || fused) {
-                    const uint4 d = env_draw(a.seed, epoch, a.env_base + e);
-                    const int lid_new = (int)__umulhi(d.z, (uint32_t)L);
-                    if (V4) lid = lid_new;                             // v4:97 setGrid first
-                    lid = clampi(lid, 0, L - 1);
-                    int goal_cell, ball_cell;
-                    place_goal_ball<PLACE_U>(rowgoal + lid * G, rowball + lid * G, G, d, goal_cell, ball_cell);
-                    if (goal_cell >= 0) {
-                        gx = goal_cell / G; gy = goal_cell % G;
-                        a.b.goal_xy[2 * e] = gx; a.b.goal_xy[2 * e + 1] = gy;
-                    }
-                    if (ball_cell >= 0) {
-                        bx = ball_cell / G; by = ball_cell % G;
-                        a.b.ball_xy[2 * e] = bx; a.b.ball_xy[2 * e + 1] = by;
-                    }
-                    lid = lid_new;                                     // v2:92 setGrid last
-                    a.b.layout_id[e] = lid;
-                }
-                a.b.reward[e] = -0.0f;                                 // v2:84
-                a.b.step_count[e] = 0;                                 // v2:86
-                a.b.done[e] = 0;
-                r.px = (int16_t)bx; r.py = (int16_t)by;                // v2:109: previous = current
-                fresh = true;
-                rx = bx; ry = by;
-            } else if (MODE == FM_STEP) {
-                sc_in = sc_ld;
-            }
-            if (MODE == FM_STEP) {
-                const int act = act_in;
-                if (act < 0 || act >= W25) {
-                    if (fresh) nostep = true;                          // reset, then the reference's step() raises
-                    else r.skip = 1;                                   // the reference raises before touching anything
-                } else {
-                    lid = clampi(lid, 0, L - 1);
-                    const uint8_t* lay = lays + lid * CELLS;
-                    float rw = -0.0f;                                  // v2:146
-                    const int sc = sc_in + 1;                          // v2:147
-                    const int fx = bx + act / FOV - 2, fy = by + act % FOV - 2;   // v2:151-152
-                    if (fx < G - 2 && fx > 1 && fy < G - 2 && fy > 1) {           // v2:157-159
-                        bx = fx; by = fy;
-                    } else {                                           // v2:160-169
-                        if (fx >= G - 2) bx = G - 3;
-                        if (fx <= 1) bx = 2;
-                        if (fy >= G - 2) by = G - 3;
-                        if (fy <= 1) by = 2;
-                    }
-                    const bool fin = fx >= 0 && fy >= 0 && fx < G && fy < G;
-                    const uint8_t c = fin ? lay[fx * G + fy] : (uint8_t)'W';
-                    if (fx == gx && fy == gy) rw = a.p.reward_goal;    // v2:175-180
-                    else if (c == 'W') rw = a.p.reward_wall;
-                    else if (c == 'B' || c == 'S') rw = a.p.reward_move;
-                    a.b.ball_xy[2 * e] = bx; a.b.ball_xy[2 * e + 1] = by;
-                    a.b.step_count[e] = sc;
-                    a.b.reward[e] = rw;
-                    a.b.done[e] = (rw == a.p.reward_goal || sc > a.p.step_limit) ? 1 : 0;   // v2:222
-                    r.action = (int16_t)act;
-                }
-            }
-            r.lid = (int16_t)clampi(lid, 0, L - 1);
-            r.gx = (int16_t)gx; r.gy = (int16_t)gy;
-        }
-        r.cx = (int16_t)bx; r.cy = (int16_t)by;
-        // the observation as 25-bit planes (the float visit planes are sampled in phase 3)
-        uint32_t m[8];
-        if (V1) {
-            m[0] = 1u << 12;                                                               // ball, v1:216
-            m[1] = window_bits(rowwall, G, r.cx, r.cy);
-            m[2] = r.action ? (r.flat >= 0 ? onehot_bits(r.flat / G, r.flat % G, r.cx, r.cy) : 0u)   // v1:244-245
-                            : window_bits(rowx, G, r.cx, r.cy);
-            m[3] = window_bits(rowfree, G, r.cx, r.cy);
-        } else {
-            constexpr int PER = VARIANT == LMAZE_VARIANT_V2 ? 2 : 3;
-            const uint64_t* rows = rowfree + r.lid * G;
-            m[0] = window_bits(rows, G, r.cx, r.cy);                                       // v2:94
-            m[1] = onehot_bits(r.gx, r.gy, r.cx, r.cy);                                    // v2:95
-            m[PER] = (r.action >= 0 && r.action < W25) ? (1u << r.action) : 0u;            // v2:135-136, v5:166-169
-            m[PER + 1] = window_bits(rows, G, r.px, r.py);
-            m[PER + 2] = onehot_bits(r.gx, r.gy, r.px, r.py);
-            if (V5) {                                                                      // v5:356-380
-                uint32_t lm[4];
-                lm[0] = m[0];
-                const int i0 = wrap5(r.b0x - r.f1x + 2), j0 = wrap5(r.b0y - r.f1y + 2);
-                const int i1 = wrap5(r.b1x - r.f1x + 2), j1 = wrap5(r.b1y - r.f1y + 2);
-                lm[1] = (i0 >= 0 && j0 >= 0) ? (1u << (FOV * i0 + j0)) : 0u;
-                lm[2] = (i1 >= 0 && j1 >= 0) ? (1u << (FOV * i1 + j1)) : 0u;
-                lm[3] = m[PER];
-                if (MODE != FM_RESET && !r.skip)
-                    for (int ch = 0; ch < 4; ++ch) put_bits(lbits, le * (4 * W25) + ch * W25, lm[ch]);
-            }
-        }
-        if (!r.skip) {
-#pragma unroll
-            for (int ch = 0; ch < C; ++ch)
-                if (!(V4 && (ch == 2 || ch == 6))) put_bits(obits, le * PERENV + ch * W25, m[ch]);
-        }
-        cen[le * 4 + 0] = r.cx; cen[le * 4 + 1] = r.cy; cen[le * 4 + 2] = r.px; cen[le * 4 + 3] = r.py;
-        int fl = (r.skip ? 1 : 0) | (r.upd ? 2 : 0) | (fresh ? 4 : 0) | (nostep ? 8 : 0);
-        if (V4 && !(V5 && MODE == FM_PLANNER) && !r.skip) {
-            // What this call does to the env's visit map, in clock terms (phase 2 carries it out on the cells):
-            //   zero    reset(): the map restarts from zeros, clock 0 (v4:112, v5:130)
-            //   renorm  the clock is about to leave the exponent range: rewrite the map in true values, clock VISIT_BIAS
-            //   pre     fused reset of v4: the reset's own (0 + window) / 2 at the placed ball (v4:116-119)
-            //   add     this call's (map + window) / 2 at the window centre: v4 every step and every reset
-            //           (v4:211-214), v5/v6 only on localDone (v5:313-318) and never at reset (v5:130)
-            const bool zero = MODE == FM_RESET || (MODE == FM_STEP && AR && fresh);
-            const bool renorm = !zero && vclock >= VISIT_RENORM;
-            const bool pre = !V5 && MODE == FM_STEP && AR && fresh;
-            const bool add = !(V5 && MODE == FM_RESET) && !nostep && !(V5 && MODE == FM_STEP && !r.upd);
-            // the "previous window" record behind the tiles: it must hold the window the NEXT call shows as previous, in
-            // true values -- this call's current window (cw0: v4 always; v5/v6 when retStatelast moved, v5:322-346), or
-            // the previous one as this call left it (cw1: the map or the episode changed under it)
-            const bool cw0 = V5 && (MODE == FM_RESET || last_is_cur);
-            const bool cw1 = V5 && !cw0 && (fresh || add);
-            // v5/v6: does the env's record hold the window this call shows as "previous"?  (a freshly loaded state does not)
-            const bool hit = V5 && !zero && (vword >> 8) == (visit_tag(r.px, r.py) >> 8);
-            fl |= (zero ? 16 : 0) | (renorm ? 32 : 0) | (pre ? 64 : 0) | (add ? 128 : 0) | (cw0 ? 256 : 0) | (cw1 ? 512 : 0) | (hit ? 1024 : 0);
-            int c1 = (zero ? 0 : (renorm ? VISIT_BIAS : vclock)) + (pre ? 1 : 0) + (add ? 1 : 0);
-            // the record's tag: the centre it will hold after this call (cw0 / cw1), else as it was
-            if (V5) c1 |= cw0 ? visit_tag(r.cx, r.cy) : (cw1 ? visit_tag(r.px, r.py) : (vword & ~0xff));
-            if (c1 != vword) a.b.visit_clock[e] = c1;
-            if (zero || renorm) dlist[atomicAdd(&ndense, 1)] = le;
-        }
-        if (V4) clk[le] = vclock;
-        flags[le] = fl;
-        rcen[le * 2] = (int16_t)rx; rcen[le * 2 + 1] = (int16_t)ry;
-        if (r.skip) any_skip = 1;
-    }
-    __syncthreads();
-    const bool some_skipped = any_skip != 0;
-
-    // ---------------- phase 2 (v4-v6): the visit maps, v4:116-119 / v4:211-214 / v5:313-318 ----------------
-    // Clock-relative tiles (include/lmaze.h "The visit map"): the whole-plane halving already happened in phase 1 (the
-    // env's clock moved); what is left is the 5x5 window.  The few envs whose whole map is rewritten (reset: zeros; clock at
-    // VISIT_RENORM: true values) are streamed tile by tile; everybody else goes through the window pass below, one lane per
-    // window row.  (Tried and dropped this round, LAB_NOTES.md R3.1 / R3.5: one lane per TILE row -- the bookkeeping made the
-    // phase issue-bound --, whole tiles staged in LDS by LDS-DMA -- 640 B of LDS per env --, one wave instruction per env, and
-    // a software-pipelined chunk loop that issues the next chunk's phase 1 and tile loads before this chunk's stores --
-    // 45 registers of loads held across the store phase: 171-214 VGPRs, 2-3 waves per SIMD, 357 / 552 us against 296 / 422.)
-    if (V4 && !(V5 && MODE == FM_PLANNER) && !LMAZE_XP(a, 32)) {
-        const int TB = visit_tiles(G), TILES = TB * TB;
-        uint32_t* vis = reinterpret_cast<uint32_t*>(a.b.visit) + (size_t)blockbase * TILES * (VT * VT);
-        uint32_t* rec = reinterpret_cast<uint32_t*>(a.b.visit) + (size_t)a.n * TILES * (VT * VT) + (size_t)blockbase * VPC;
-        // One tile row of an env whose WHOLE map is rewritten this call: zeros (reset) or true values (clock at
-        // VISIT_RENORM) first, then the fused reset's own window at the placed ball (`pre`, v4:116-119), then `add`.
-        auto tile_row_whole = [&](uint32_t (&s)[4], int x, int y0, int le, int fl) {
-            const int E0 = clk[le];
-            const bool zero = fl & 16, renorm = fl & 32, pre = fl & 64, add = fl & 128;
-            const int cx = cen[le * 4], cy = cen[le * 4 + 1], px = cen[le * 4 + 2], py = cen[le * 4 + 3];
-            const int E1 = zero ? 0 : (renorm ? VISIT_BIAS : E0);
-            const int dx = x - cx + 2, ex = x - px + 2;
-#pragma unroll 1
-            for (int k = 0; k < 4; ++k) {
-                const int y = y0 + k;
-                const bool cell_ok = x < G && y < G;      // tiles are padded up to a multiple of 4: those cells stay 0
-                uint32_t b = s[k];
-                if (zero) b = 0u;
-                else if (renorm) b = visit_true(b, E0);
-                int E = E1;
-                if (pre) {
-                    const int qx = x - rcen[le * 2] + 2, qy = y - rcen[le * 2 + 1] + 2;
-                    if (cell_ok && (unsigned)qx <= 4u && (unsigned)qy <= 4u) b = visit_add(b, E);
-                    ++E;
-                }
-                const int dy = y - cy + 2, ey = y - py + 2;
-                const bool in = cell_ok && (unsigned)dx <= 4u && (unsigned)dy <= 4u;
-                if (add) {
-                    if (in) b = visit_add(b, E);
-                    ++E;
-                }
-                s[k] = b;
-                if (in) vwin[le * 2 * W25 + dx * FOV + dy] = __uint_as_float(visit_true(b, E));
-                if (cell_ok && (unsigned)ex <= 4u && (unsigned)ey <= 4u)
-                    vwin[le * 2 * W25 + W25 + ex * FOV + ey] = __uint_as_float(visit_true(b, E));
-            }
-        };
-        // ---- whole maps first: envs that were reset (zeros, nothing loaded) or whose clock reached VISIT_RENORM
-        {
-            const int nd = ndense, per = TILES * VT;
-            for (int j = tid; j < nd * per; j += LMAZE_BLOCK) {
-                const int d = j / per, r = j - d * per;
-                const int le = dlist[d], fl = flags[le];
-                const int tile = r >> 2, row = r & 3;
-                const int tx = tile / TB, ty = tile - tx * TB;
-                uint32_t* p = vis + (le * TILES + tile) * (VT * VT) + row * VT;
-                uint32_t sv[4] = {0u, 0u, 0u, 0u};
-                if (!(fl & 16)) {
-                    const uint4 t4 = *reinterpret_cast<const uint4*>(p);
-                    sv[0] = t4.x; sv[1] = t4.y; sv[2] = t4.z; sv[3] = t4.w;
-                }
-                tile_row_whole(sv, tx * VT + row, ty * VT, le, fl & 0xff);
-                *reinterpret_cast<uint4*>(p) = make_uint4(sv[0], sv[1], sv[2], sv[3]);
-            }
-        }
-        // ---- the windows: ONE LANE PER WINDOW ROW.  Item = (env, window 0: current / 1: "previous", row 0..4): the row's
-        // five cells lie in two horizontally adjacent tiles, on one tile row each -- two 16-byte loads, eight words, the
-        // five wanted ones start at word y0 & 3 --, or, v5/v6, in the env's "previous window" record (20 contiguous
-        // bytes) when that window lies elsewhere.  Every load of the chunk is in flight before the first is used, and
-        // nothing is stored before every lane has its loads (the barrier): a cell both windows show is loaded by two
-        // lanes and each works out the same new value for it.  Cells of the current window take (v + 1) / 2 when the map
-        // updates this call and the two 16-byte pieces go back re-encoded under the new clock (into lines the loads have
-        // just brought into L2); the TRUE values both windows show -- the previous one sampled live from the updated
-        // map, Appendix B-7 -- are left in vwin for phase 3.
-        {
-            // SUB envs at a time (one barrier each): the loads of a pass are held in registers, 9 per row
-            constexpr int IPE = 2 * FOV, SUB = EPB < LMAZE_WIN_SUB ? EPB : LMAZE_WIN_SUB, NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
-          for (int sb = 0; sb < nb; sb += SUB) {
-            const int items = LMAZE_XP(a, 256) ? 0 : min(SUB, nb - sb) * IPE;
-            uint4 va[NIT], vb[NIT];
-            int meta[NIT];    // -1 nothing; else global word offset of piece A (tiles) or of the row (record) | 1 << 28 record | 1 << 29 piece A outside | 1 << 30 piece B outside
-#pragma unroll
-            for (int u = 0; u < NIT; ++u) {
-                const int i = tid + u * LMAZE_BLOCK;
-                meta[u] = -1;
-                va[u] = make_uint4(0u, 0u, 0u, 0u);
-                vb[u] = make_uint4(0u, 0u, 0u, 0u);
-                if (i >= items) continue;
-                const int le = sb + i / IPE, r = i % IPE;
-                const int w = r >= FOV ? 1 : 0, row = r - w * FOV;
-                const int fl = flags[le];
-                if (fl & (1 | 16 | 32)) continue;                           // untouched, or rewritten whole above
-                const int cx = cen[le * 4], cy = cen[le * 4 + 1];
-                const int wx = cen[le * 4 + 2 * w], wy = cen[le * 4 + 2 * w + 1];
-                const int x = wx - 2 + row, y0 = wy - 2;
-                if ((unsigned)x >= (unsigned)G) continue;                   // outside the array: stays 0
-                // v5/v6: the record serves the previous window unless this call's update reaches into this row
-                const bool touched = (fl & 128) && (unsigned)(x - cx + 2) <= 4u && (unsigned)(wy - cy + 4) <= 8u;
-                if (V5 && w == 1 && (fl & 1024) && !touched) {
-                    const int o = le * VPC + row * FOV;
-                    struct __attribute__((packed, aligned(4))) Q4 { uint32_t v[4]; };
-                    const Q4 q = *reinterpret_cast<const Q4*>(rec + o);
-                    va[u] = make_uint4(q.v[0], q.v[1], q.v[2], q.v[3]);
-                    vb[u].x = rec[o + 4];
-                    meta[u] = o | (1 << 28);
-                } else {
-                    const int ty0 = y0 >> 2;                                // floor: -1 when the window pokes out on the left
-                    const int o = (le * TILES + (x >> 2) * TB + ty0) * (VT * VT) + (x & 3) * VT;
-                    const bool a_out = ty0 < 0, b_out = ty0 + 1 >= TB;
-                    if (!a_out) va[u] = *reinterpret_cast<const uint4*>(vis + o);
-                    if (!b_out) vb[u] = *reinterpret_cast<const uint4*>(vis + o + VT * VT);
-                    meta[u] = (o & 0x0fffffff) | (a_out ? 1 << 29 : 0) | (b_out ? 1 << 30 : 0);
-                }
-            }
-            __syncthreads();       // every load of this chunk's envs has returned before any of their cells is stored
-#pragma unroll
-            for (int u = 0; u < NIT; ++u) {
-                if (meta[u] < 0) continue;
-                const int i = tid + u * LMAZE_BLOCK;
-                const int le = sb + i / IPE, r = i % IPE;
-                const int w = r >= FOV ? 1 : 0, row = r - w * FOV;
-                const int fl = flags[le], E0 = clk[le];
-                const bool add = fl & 128, from_rec = (meta[u] >> 28) & 1;
-                const int cx = cen[le * 4], cy = cen[le * 4 + 1];
-                const int x = cen[le * 4 + 2 * w] - 2 + row, y0 = cen[le * 4 + 2 * w + 1] - 2;
-                const int sh = from_rec ? 0 : (y0 & 3);
-                // the eight words rotated so that the row's cells are c[0..4]
-                uint32_t c[8] = {va[u].x, va[u].y, va[u].z, va[u].w, vb[u].x, vb[u].y, vb[u].z, vb[u].w};
-                if (sh & 1) {
-#pragma unroll
-                    for (int k = 0; k < 7; ++k) c[k] = c[k + 1];
-                }
-                if (sh & 2) {
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) c[k] = c[k + 2];
-                }
-                const bool rowc = (unsigned)(x - cx + 2) <= 4u;
-                bool changed = false;
-                float* out = vwin + le * 2 * W25 + w * W25 + row * FOV;
-                const bool rec_out = V5 && (fl & (w == 0 ? 256 : 512));     // v5/v6: the record takes the window the NEXT call shows as previous
-                // One cell: its true value under the clock this call ends with (a record holds true values, i.e. values stored
-                // under clock VISIT_BIAS, and serves a row only when this call's update does not reach into it; a cell outside
-                // the current window only takes the whole-plane halving of this call's update, if there is one).  `slow`: decode
-                // by lmaze_visit_true (values that decayed below 2^-126) instead of the exponent subtraction.
-                auto one_cell = [&](uint32_t& cj, int j, bool slow) -> bool {
-                    const int y = y0 + j;
-                    if ((unsigned)y >= (unsigned)G) return false;           // outside the array: stays 0
-                    const bool in_cur = !from_rec && rowc && (unsigned)(y - cy + 2) <= 4u;
-                    const int E = in_cur ? E0 : (from_rec ? VISIT_BIAS : E0) + (add ? 1 : 0);
-                    const int n = E - VISIT_BIAS, f = (int)(cj >> 23);
-                    const bool fast = cj == 0u || (f >= 1 && f - n >= 1);
-                    uint32_t t = slow ? visit_true(cj, E) : (cj == 0u ? 0u : (uint32_t)((int)cj - n * (1 << 23)));
-                    if (in_cur && add) {
-                        const float nv = (__uint_as_float(t) + 1.0f) * 0.5f;    // v4:214; see lmaze_visit_add
-                        t = __float_as_uint(nv);
-                        if (fast || slow) cj = lmaze_visit_store(nv, E0 + 1);
-                        changed = true;
-                    }
-                    out[j] = __uint_as_float(t);
-                    if (rec_out) rec[le * VPC + row * FOV + j] = t;
-                    return !fast;
-                };
-                uint32_t redo = 0u;
-#pragma unroll
-                for (int j = 0; j < FOV; ++j) redo |= one_cell(c[j], j, false) ? 1u << j : 0u;
-#pragma unroll 1
-                for (; redo; redo &= redo - 1u) {                           // rare: cells below 2^-126
-                    const int j = __ffs((int)redo) - 1;
-                    uint32_t cj = j == 0 ? c[0] : (j == 1 ? c[1] : (j == 2 ? c[2] : (j == 3 ? c[3] : c[4])));
-                    one_cell(cj, j, true);
-                    c[0] = j == 0 ? cj : c[0]; c[1] = j == 1 ? cj : c[1]; c[2] = j == 2 ? cj : c[2];
-                    c[3] = j == 3 ? cj : c[3]; c[4] = j == 4 ? cj : c[4];
-                }
-                if (w == 0 && changed) {
-                    // the updated words back where they came from: word k of the row sits at c[k - sh] for k >= sh
-                    uint32_t d[8] = {va[u].x, va[u].y, va[u].z, va[u].w, vb[u].x, vb[u].y, vb[u].z, vb[u].w};
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-#pragma unroll
-                        for (int j = 0; j < FOV; ++j)
-                            if (k - j >= 0 && k - j <= 3 && sh == k - j) d[k] = c[j];
-                    }
-                    const int o = meta[u] & 0x0fffffff;
-                    if (!((meta[u] >> 29) & 1)) *reinterpret_cast<uint4*>(vis + o) = make_uint4(d[0], d[1], d[2], d[3]);
-                    if (!((meta[u] >> 30) & 1)) *reinterpret_cast<uint4*>(vis + o + VT * VT) = make_uint4(d[4], d[5], d[6], d[7]);
-                }
-            }
-            if (V5) {
-                // rows of a new record that lie outside the array hold zeros
-                for (int i = tid; i < items; i += LMAZE_BLOCK) {
-                    const int le = sb + i / IPE, r = i % IPE;
-                    const int w = r >= FOV ? 1 : 0, row = r - w * FOV;
-                    const int fl = flags[le];
-                    if ((fl & (1 | 16 | 32)) || !(fl & (w == 0 ? 256 : 512))) continue;
-                    const int x = cen[le * 4 + 2 * w] - 2 + row, y0 = cen[le * 4 + 2 * w + 1] - 2;
-                    for (int j = 0; j < FOV; ++j)
-                        if ((unsigned)x >= (unsigned)G || (unsigned)(y0 + j) >= (unsigned)G) rec[le * VPC + row * FOV + j] = 0u;
-                }
-            }
-          }
-        }
-        __syncthreads();
-        if (V5) {
-            // whole-map envs (reset / renormalised this call): their window values are in vwin now
-            const int nd = ndense;
-            for (int j = tid; j < nd * W25; j += LMAZE_BLOCK) {
-                const int le = dlist[j / W25], k = j % W25, fl = flags[le];
-                if (!(fl & (256 | 512))) continue;
-                const int wsel = (fl & 256) ? 0 : 1;
-                rec[le * VPC + k] = __float_as_uint(vwin[le * 2 * W25 + wsel * W25 + k]);
-            }
-        }
-    }
-
-    // ---------------- phase 3: render float[nb*C*25], contiguous, 16-byte stores ----------------
-    // float `rem` of env le's observation: a bit of the string, or -- visit planes 2 and 6 of v4-v6, sampled live at
-    // the current / "previous" window -- one of the env's 2 x 25 samples
-    auto element = [&](int le, int rem) -> float {
-        if (V4 && rem >= 2 * W25 && rem < 3 * W25) return vwin[le * 2 * W25 + rem - 2 * W25];
-        if (V4 && rem >= 6 * W25) return vwin[le * 2 * W25 + rem - 5 * W25];
-        const int f = le * PERENV + rem;
-        return ((obits[f >> 5] >> (f & 31)) & 1u) ? 1.0f : 0.0f;
-    };
-    float* obs = a.b.obs + (size_t)blockbase * PERENV;
-    const int R = (V5 && MODE == FM_PLANNER) ? 0 : nb * PERENV;   // plannerStep returns only the local observation
-    const int nq = some_skipped ? 0 : (R >> 2);
-    if (LMAZE_XP(a, 16) && !V4 && EPB == 128) {
-        // experiment: the 4-KiB pieces of 8 consecutive workgroups interleaved (piece k*8 + w of the group's 1024
-        // envs), content from this workgroup's own bit string (garbage addresses-wise)
-        const int w = blockIdx.x & 7;
-        float* gbase = a.b.obs + (size_t)(blockIdx.x >> 3) * 1024 * PERENV;
-        const int npieces = 1024 * PERENV / 1024;
-        for (int k = 0; k * 8 + w < npieces; ++k) {
-            float v[4];
-            nibble_floats(obits, (k * 256 + tid) % (EPB * PERENV / 4), v);
-            typedef float v4f __attribute__((ext_vector_type(4)));
-            v4f t = {v[0], v[1], v[2], v[3]};
-            v4f* dst = reinterpret_cast<v4f*>(gbase) + (size_t)(k * 8 + w) * 256 + tid;
-            if (a.nt) stream_store16(dst, t); else *dst = t;
-        }
-    }
-    const int nq_run = (LMAZE_XP(a, 4) || (LMAZE_XP(a, 16) && !V4 && EPB == 128)) ? 0 : nq;
-    for (int q = tid; q < nq_run; q += LMAZE_BLOCK) {
-        const int f = q << 2;
-        int le = f / PERENV;
-        int rem = f - le * PERENV;
-        float v[4];
-        if (!V4) {
-            // bit planes only (v1, v2): float f of the workgroup's range is bit f of the string phase 1 left in LDS,
-            // a 16-byte store is nibble q of it -- a dozen VALU instructions per store, no index arithmetic
-            // (masks per plane and a division per float made this loop ALU-bound: 1 210 VALU per wave on v2)
-            nibble_floats(obits, q, v);
-        } else {
-            // v4-v6: five 0/1 planes and two float planes per env -- the nibble as above, then the floats that fall
-            // into a visit plane are replaced by their samples (2 of 7 planes; a third of the stores touch one)
-            nibble_floats(obits, q, v);
-            if (rem + 3 >= 2 * W25 && !(rem >= 3 * W25 && rem + 3 < 6 * W25)) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    int r = rem + k, l2 = le;
-                    if (r >= PERENV) { r -= PERENV; ++l2; }
-                    if (r >= 2 * W25 && r < 3 * W25) v[k] = vwin[l2 * 2 * W25 + r - 2 * W25];
-                    else if (r >= 6 * W25) v[k] = vwin[l2 * 2 * W25 + r - 5 * W25];
-                }
-            }
-        }
-        if (a.nt) {  // large batches: the observation cannot stay in the Infinity Cache, stream it (+6...12 %)
-            typedef float v4f __attribute__((ext_vector_type(4)));
-            v4f t = {v[0], v[1], v[2], v[3]};
-            stream_store16(reinterpret_cast<v4f*>(obs) + q, t);
-        } else {
-            reinterpret_cast<float4*>(obs)[q] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    }
-    // scalar path: the ragged tail, or every element when some env of the workgroup is skipped
-    for (int f = (nq << 2) + tid; f < R; f += LMAZE_BLOCK) {
-        const int le = f / PERENV;
-        if (flags[le] & 1) continue;
-        obs[f] = element(le, f - le * PERENV);
-    }
-
-    // ---------------- phase 3b (v5/v6): the local observation float[nb*4*25], v5:356-380 ----------------
-    if (V5 && MODE != FM_RESET && !LMAZE_XP(a, 4)) {
-        constexpr int PERLOC = 4 * W25;
-        float* loc = a.b.obs_local + (size_t)blockbase * PERLOC;
-        const int RL = nb * PERLOC;                      // 100 floats per env: a store never straddles two envs
-        for (int q = tid; q < (RL >> 2); q += LMAZE_BLOCK) {
-            const int f = q << 2;
-            const int le = f / PERLOC;
-            if (flags[le] & 1) continue;
-            float v[4];
-            nibble_floats(lbits, q, v);
-            if (a.nt) {   // streamed like the foveal observation (round 3: these 400 B per env were plain stores)
-                typedef float v4f __attribute__((ext_vector_type(4)));
-                v4f t = {v[0], v[1], v[2], v[3]};
-                stream_store16(reinterpret_cast<v4f*>(loc) + q, t);
-            } else {
-                reinterpret_cast<float4*>(loc)[q] = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        }
-    }
-    chunk += gridDim.x;
-    if (chunk >= nchunks) break;                                           // uniform over the workgroup
-    blockbase = chunk * EPB;
-    nb = (int)min((int64_t)EPB, a.n - blockbase);
-    __syncthreads();                                                       // every wave is done with this chunk's strings and flags
-    for (int i = tid; i < EPB * 12; i += LMAZE_BLOCK) obits[i] = 0u;
-    if (V4) for (int i = tid; i < EPB * 2 * W25; i += LMAZE_BLOCK) vwin[i] = 0.0f;
-    if (tid == 0) { any_skip = 0; ndense = 0; }
-    __syncthreads();
-  }
-    if (warmed == 0x7fedcba9 && a.n < 0) a.b.done[0] = 1;   // never true: keeps the warming loads alive
+// T steps of the plain (AR false) or fused step (AR: v1/v2/v4 fused reset, v5/v6 two-level step) in one launch: every
+// chunk runs ro.T steps before the workgroup moves on (FovealRoll).  At least 4 waves per SIMD, the floor of the v4-v6
+// steps: left to itself v5's rollout takes 121-152 VGPRs (3 waves at 64 envs per workgroup); v1/v2/v4 stay below the budget
+template <int VARIANT, int EPB, int GT, bool AR>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void foveal_rollout_kernel(const FovealArgs a, const FovealRoll ro) {
+    constexpr bool ROLL = true;
+    constexpr int MODE = FM_STEP;
+#define LMAZE_FOVEAL_BODY_SITE
+#include "lmaze_foveal_body.h"
+#undef LMAZE_FOVEAL_BODY_SITE
 }
 
 // v6 safeFovealGoal (v6:505-523): one lane per env
@@ -1184,14 +401,31 @@ static size_t lds_limit() {
     return limit;
 }
 
+// dynamic LDS of foveal_body for EPB envs per workgroup
+template <int VARIANT>
+static size_t foveal_lds(const LmazeFovealParams& p, int epb) {
+    const int cells = p.grid * p.grid;
+    const int L = VARIANT == LMAZE_VARIANT_V1 ? 1 : p.n_layouts;
+    // obs bit string 32 B + obs_local bit string 16 B + centres 8 B + flags 4 B + reset centre 4 B per env, row masks, layout characters, visit samples
+    size_t lds = (size_t)epb * 64 + (3 * (size_t)L * p.grid + 2 * (size_t)p.grid) * 8 + (size_t)((L * cells + 15) & ~15);
+    if (VARIANT == LMAZE_VARIANT_V4 || VARIANT == LMAZE_VARIANT_V5)
+        lds += (size_t)epb * (2 * W25 * 4 + 8);   // + visit samples, clock, whole-map list
+    return lds;
+}
+
+// launch_hint bits 0-3 (step and rollout): at most that many workgroups resident per CU, by padding the dynamic LDS
+static size_t lds_for_cap(size_t lds, int per_cu) {
+    if (per_cu >= 1 && per_cu <= 8) {
+        const size_t cap = 160 * 1024;
+        const size_t want = ((cap / per_cu + cap / (per_cu + 1)) / 2) & ~(size_t)255;   // between the two thresholds
+        if (want > lds && want <= lds_limit()) return want;     // per_cu 1 (120 KiB) and 2 (66 KiB) included where the device allows
+    }
+    return lds;
+}
+
 template <int VARIANT, int MODE, int EPB>
 static hipError_t launch_foveal_one(const FovealArgs& a, hipStream_t s) {
-    const int cells = a.p.grid * a.p.grid;
-    const int L = VARIANT == LMAZE_VARIANT_V1 ? 1 : a.p.n_layouts;
-    // obs bit string 32 B + obs_local bit string 16 B + centres 8 B + flags 4 B + reset centre 4 B per env, row masks, layout characters, visit samples
-    size_t lds = (size_t)EPB * 64 + (3 * (size_t)L * a.p.grid + 2 * (size_t)a.p.grid) * 8 + (size_t)((L * cells + 15) & ~15);
-    if (VARIANT == LMAZE_VARIANT_V4 || VARIANT == LMAZE_VARIANT_V5)
-        lds += (size_t)EPB * (2 * W25 * 4 + 8);   // + visit samples, clock, whole-map list
+    size_t lds = foveal_lds<VARIANT>(a.p, EPB);
     // envs per workgroup is a performance knob (launch_hint bits 4-7): a size whose LDS does not fit the device falls
     // back to the next smaller one instead of failing the launch (v4-v6 at 256 envs: 164 KiB)
     if constexpr (EPB > 32) {
@@ -1209,11 +443,7 @@ static hipError_t launch_foveal_one(const FovealArgs& a, hipStream_t s) {
     // launch_hint bits 0-3: at most that many workgroups resident per CU, by padding the dynamic LDS (160 KiB per
     // CU), as the step kernel does in its streaming regime (lmaze_step.hip launch_shared); 0 = no cap
     const int per_cu = a.p.launch_hint & 15;
-    if (MODE == FM_STEP && per_cu >= 1 && per_cu <= 8) {
-        const size_t cap = 160 * 1024;
-        const size_t want = ((cap / per_cu + cap / (per_cu + 1)) / 2) & ~(size_t)255;   // between the two thresholds
-        if (want > lds && want <= lds_limit()) lds = want;     // per_cu 1 (120 KiB) and 2 (66 KiB) included where the device allows
-    }
+    if (MODE == FM_STEP) lds = lds_for_cap(lds, per_cu);
     const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
     if (a.info) {
         char name[96];
@@ -1314,6 +544,79 @@ static hipError_t launch_foveal_mode(const FovealArgs& a0, hipStream_t s) {
             // 32 envs per workgroup: 41 KiB of visit maps streamed + 22 KiB of observation written
             if (MODE == FM_STEP && !a.auto_reset) return launch_foveal_one<LMAZE_VARIANT_V4, MODE, 32>(a, s);
             return launch_foveal_one<LMAZE_VARIANT_V4, MODE, 64>(a, s);
+    }
+}
+
+// ---- the one-launch rollout (lmaze_foveal_rollout) ----
+// Instantiations: envs per workgroup 32 / 64 / 128 (launch_hint bits 4-7 = 2 / 3 / 4; any other code takes the default
+// below), GT 14 (v1) or 18 (v2, v4, v5/v6) or 0, AR plain / fused.  The policy bits never change results.
+template <int VARIANT, int EPB>
+static hipError_t launch_rollout_one(const FovealArgs& a, const FovealRoll& ro, hipStream_t s) {
+    size_t lds = foveal_lds<VARIANT>(a.p, EPB);
+    if constexpr (EPB > 32) {
+        if (lds > lds_limit()) return launch_rollout_one<VARIANT, EPB / 2>(a, ro, s);
+    }
+    const int64_t nchunks = (a.n + EPB - 1) / EPB;
+    const int m = ((a.p.launch_hint >> 8) & 3) + 1;            // bits 8-9: chunks per workgroup - 1
+    const int64_t blocks = (nchunks + m - 1) / m;
+    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
+    const int per_cu = a.p.launch_hint & 15;
+    lds = lds_for_cap(lds, per_cu);
+    FovealArgs b = a;
+    b.nt = 0;                 // plain stores: a chunk's observation is rewritten every step, the lines stay in L2
+    constexpr int GN = VARIANT == LMAZE_VARIANT_V1 ? 14 : 18;
+    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
+    if (a.info) {
+        char name[96];
+        snprintf(name, sizeof(name), "foveal_rollout_kernel<v%d, %d, %d, %s>", VARIANT, EPB, a.p.grid == GN ? GN : 0,
+                 a.auto_reset ? (VARIANT == LMAZE_VARIANT_V5 ? "two-level" : "fused-reset") : "plain");
+        describe_launch(a.info, name, EPB, lds > foveal_lds<VARIANT>(a.p, EPB) ? per_cu : 0, m, false, blocks, LMAZE_BLOCK, lds);
+        return hipSuccess;
+    }
+    if constexpr (VARIANT == LMAZE_VARIANT_V5) {
+        // the two-level step only (the plain v5/v6 step spills at 4 waves per SIMD: lmaze_foveal_rollout refuses it), and
+        // for grids other than 18 only at 32 envs per workgroup (64: 8 bytes of scratch) -- launch_rollout_variant
+        if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
+        else if constexpr (EPB == 32) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, 32, 0, true>), grid, block, lds, s, b, ro);
+        else return hipErrorInvalidConfiguration;
+    } else if (a.auto_reset) {
+        if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
+        else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, 0, true>), grid, block, lds, s, b, ro);
+    } else {
+        if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, false>), grid, block, lds, s, b, ro);
+        else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, 0, false>), grid, block, lds, s, b, ro);
+    }
+    return hipGetLastError();
+}
+
+template <int VARIANT>
+static hipError_t launch_rollout_variant(const FovealArgs& a, const FovealRoll& ro, hipStream_t s) {
+    if (VARIANT == LMAZE_VARIANT_V5 && a.p.grid != 18) return launch_rollout_one<VARIANT, 32>(a, ro, s);
+    switch ((a.p.launch_hint >> 4) & 15) {
+        case 2: return launch_rollout_one<VARIANT, 32>(a, ro, s);
+        case 3: return launch_rollout_one<VARIANT, 64>(a, ro, s);
+        case 4: return launch_rollout_one<VARIANT, 128>(a, ro, s);
+        default: break;
+    }
+    // Default: the workgroup runs T steps of its chunk, so a launch is as many rounds of set-up + T steps as it has
+    // chunks per CU; small batches want many small chunks to cover the CUs, large ones the step's sizes
+    // (tools/bench_foveal_rollout.py: 4 096-65 536 envs 2.0-4.4 us per step for v1/v2 against 7.0-9.5 as T launches).  v1
+    // in the streaming regime: 128 envs per workgroup, 60.6 / 61.4 us (plain / fused, 1M envs, T = 64) against 79.8 / 77.6
+    // at 64 envs, 68.1 / 76.0 at 32 and 72.9 / 74.3 as T step launches; v2 fused 70.3 us (T = 256) against 97.6 at 64 envs
+    // and 109.9 as T launches, 72.1 / 95.8 / 101.7 at T = 64; v4 fused 299-315 us at 64 or 128 alike, 342-346 as T launches
+    // (three interleaved rounds each)
+    if (a.n <= (int64_t)32 * 1024) return launch_rollout_one<VARIANT, 32>(a, ro, s);
+    const int C = VARIANT == LMAZE_VARIANT_V1 ? 4 : (VARIANT == LMAZE_VARIANT_V2 ? 5 : 7);
+    if (VARIANT != LMAZE_VARIANT_V5 && (size_t)a.n * C * W25 * 4 > kFovealStreamBytes) return launch_rollout_one<VARIANT, 128>(a, ro, s);
+    return launch_rollout_one<VARIANT, 64>(a, ro, s);
+}
+
+static hipError_t launch_foveal_rollout(const FovealArgs& a, const FovealRoll& ro, hipStream_t s) {
+    switch (a.p.variant) {
+        case LMAZE_VARIANT_V1: return launch_rollout_variant<LMAZE_VARIANT_V1>(a, ro, s);
+        case LMAZE_VARIANT_V2: return launch_rollout_variant<LMAZE_VARIANT_V2>(a, ro, s);
+        case LMAZE_VARIANT_V4: return launch_rollout_variant<LMAZE_VARIANT_V4>(a, ro, s);
+        default: return launch_rollout_variant<LMAZE_VARIANT_V5>(a, ro, s);
     }
 }
 
@@ -1443,6 +746,75 @@ int lmaze_v5_hier_step(const LmazeFovealParams* params, const uint8_t* layouts, 
     a.epoch_in = epoch_in_dev;
     a.epoch_out = epoch_out_dev;
     return (int)launch_foveal_mode<FM_STEP>(a, (hipStream_t)stream);
+}
+
+// the argument checks of lmaze_foveal_rollout that need no buffers (answered before anything else is looked at)
+static int check_rollout_call(const LmazeFovealParams* params, const int32_t* planner_goals, int32_t T, int64_t n,
+                              int32_t auto_reset) {
+    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    if (!params) return LMAZE_E_NULL;
+    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    if (!v56 && planner_goals) return LMAZE_E_VARIANT;                 // the two-level step is v5/v6's
+    if (v56 && auto_reset && !planner_goals) return LMAZE_E_NULL;      // their episodes restart through plannerStep
+    if (v56 && !planner_goals) return LMAZE_E_VARIANT;                 // their plain step has no one-launch form (see below)
+    return 0;
+}
+
+int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
+                         const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
+                         int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t,
+                         uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t, void* stream) {
+    if (T == 0 || n == 0) return (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) ? LMAZE_E_COUNT : 0;   // nothing to do, nothing read
+    int rc = check_rollout_call(params, planner_goals, T, n, auto_reset);
+    if (rc) return rc;
+    rc = check_foveal(params, layouts, bufs, n);
+    if (rc) return rc;
+    if (!actions) return LMAZE_E_NULL;
+    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
+    a.action = actions;
+    a.goal2 = planner_goals;
+    a.auto_reset = (planner_goals || (!v56 && auto_reset)) ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
+    FovealRoll ro;
+    ro.T = T;
+    ro.reward_t = reward_t;
+    ro.done_t = done_t;
+    ro.freward_t = foveal_reward_t;
+    ro.fdone_t = foveal_done_t;
+    return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
+}
+
+int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                  int32_t two_level, char* text_host, int32_t len) {
+    if (!params || !text_host || len < 1) return LMAZE_E_NULL;
+    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
+        return LMAZE_E_VARIANT;
+    if ((two_level != 0) != v56) return LMAZE_E_VARIANT;                   // v5/v6: the two-level step only
+    if (params->grid < FOV || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
+    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
+    if (n < 0 || n > LMAZE_MAX_ENVS || T < 0) return LMAZE_E_COUNT;
+    text_host[0] = 0;
+    if (n == 0 || T == 0) return 0;
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    LmazeFovealBuffers none;
+    memset(&none, 0, sizeof(none));
+    FovealArgs a = make_foveal_args(params, nullptr, &none, n);     // nothing is dereferenced: the launcher fills `info`
+    a.auto_reset = (two_level || (!v56 && auto_reset)) ? 1 : 0;
+    a.info = &info;
+    FovealRoll ro;
+    memset(&ro, 0, sizeof(ro));
+    ro.T = T;
+    const int rc = (int)launch_foveal_rollout(a, ro, nullptr);
+    if (rc) return rc;
+    snprintf(text_host, (size_t)len, "%s T=%d grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d",
+             info.kernel, T, (long long)info.grid, info.block, (long long)info.lds, info.envs_per_workgroup,
+             info.workgroups_per_cu, info.chunks);
+    return 0;
 }
 
 int lmaze_foveal_reset(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* mask, int32_t place,

@@ -1,5 +1,6 @@
 """LmazeFovealVecEnv: N envs of the foveal variants (v1, v2, v4) as struct-of-arrays torch
-tensors in HBM, stepped by one HIP kernel per step() through lmaze_foveal_* (include/lmaze.h).
+tensors in HBM, stepped by one HIP kernel per step() -- or per rollout() of T steps -- through lmaze_foveal_*
+(include/lmaze.h).
 
 Host side only (buffers, marshalling, stream); the transition, the visit-map update and the
 5x5 window render run in liblmaze_hip.so.  Reference: gym_lmaze/envs/lmaze_env_v1.py,
@@ -168,10 +169,15 @@ class LmazeFovealVecEnv(VecEnvBase):
                                              self.seed & (2 ** 64 - 1), epoch, self.env_base, e_in, e_out, self._stream())
         _abi.check("lmaze_v5_hier_step", rc)
 
-    def rollout(self, actions, goals=None, auto_reset=False, device_epoch=False):
-        """T steps over device tensors int32[T,N], one kernel per step, no host sync: step(actions[t]) -- with the
-        reset fused in when auto_reset -- or, for v5/v6 with `goals`, the two-level step hier_step(actions[t], goals[t]).
-        device_epoch: keep the reset epoch on the device (what capture_rollout uses)."""
+    def rollout(self, actions, goals=None, auto_reset=False, device_epoch=False, trajectory=False):
+        """T steps over device tensors int32[T,N], no host sync: step(actions[t]) -- with the reset fused in when
+        auto_reset (v1, v2, v4) -- or, for v5/v6 with `goals`, the two-level step hier_step(actions[t], goals[t]).
+        The whole rollout is ONE launch (lmaze_foveal_rollout, include/lmaze.h), bit-identical to the T step launches --
+        except the plain v5/v6 step without goals, which stays T launches;
+        the epoch ends where those would leave it (+T with auto_reset or goals).  device_epoch=True keeps the reset
+        epoch on the device and launches T steps instead (what capture_rollout records).  Returns the final
+        (obs, reward, done); trajectory=True adds every step's reward float32[T,N] and done bool[T,N] and, v1 / v5 / v6,
+        foveal_reward float32[T,N] and foveal_done bool[T,N] (the second stream) as well."""
         hier = goals is not None
         self._check_rows("rollout()", actions, goals)
         if hier and (not self._two_level or goals.shape[0] != actions.shape[0]):
@@ -179,13 +185,54 @@ class LmazeFovealVecEnv(VecEnvBase):
         if self._two_level and not hier:
             if auto_reset:
                 raise ValueError("v5/v6 restart episodes through the two-level step: pass goals")
-        base, stride = actions.data_ptr(), self.num_envs * 4
-        for t in range(int(actions.shape[0])):
-            slot = t if device_epoch else None
+        T, N = int(actions.shape[0]), self.num_envs
+        if self._two_level and not hier and not device_epoch:
+            # the plain v5/v6 step has no one-launch form (include/lmaze.h lmaze_foveal_rollout): T launches, rows copied
+            rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
+                    for t in (self.reward, self.done, self.foveal_reward, self.foveal_done)] if trajectory else None
+            base, stride = actions.data_ptr(), N * 4
+            for t in range(T):
+                self.step_raw(base + t * stride)
+                if rows:
+                    for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
+                        r[t].copy_(src)
+            if trajectory:
+                return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
+            return self.obs, self.reward, self.done
+        if not device_epoch:
+            resets = hier or bool(auto_reset)
+            second = self.variant in ("v1", "v5", "v6")
+            rows = None
+            if trajectory:
+                f32, u8 = torch.float32, torch.uint8
+                rows = [torch.empty((T, N), dtype=f32, device=self.device), torch.empty((T, N), dtype=u8, device=self.device)]
+                if second:
+                    rows += [torch.empty((T, N), dtype=f32, device=self.device), torch.empty((T, N), dtype=u8, device=self.device)]
+            ptrs = [r.data_ptr() for r in rows] if rows else []
+            ptrs += [None] * (4 - len(ptrs))
+            if T > 0:
+                with self._guard():
+                    rc = _abi.lib.lmaze_foveal_rollout(self._pp, self._p_layouts, actions.data_ptr(),
+                                                       goals.data_ptr() if hier else None, T, self._pb, N,
+                                                       1 if resets else 0, self.seed & (2 ** 64 - 1), self._epoch,
+                                                       self.env_base, *ptrs, self._stream())
+                _abi.check("lmaze_foveal_rollout", rc)
+                if resets:
+                    self._epoch += T
+            if trajectory:
+                out = [self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool)]
+                if second:
+                    out += [rows[2], rows[3].view(torch.bool)]
+                return tuple(out)
+            return self.obs, self.reward, self.done
+        if trajectory:
+            raise ValueError("rollout(trajectory=True) is not available with a device-resident epoch")
+        base, stride = actions.data_ptr(), N * 4
+        for t in range(T):
             if hier:
-                self.hier_step_raw(base + t * stride, goals.data_ptr() + t * stride, slot)
+                self.hier_step_raw(base + t * stride, goals.data_ptr() + t * stride, t)
             else:
-                self.step_raw(base + t * stride, auto_reset=auto_reset, epoch_slot=slot if auto_reset else None)
+                self.step_raw(base + t * stride, auto_reset=auto_reset, epoch_slot=t if auto_reset else None)
         return self.obs, self.reward, self.done
 
     def capture_rollout(self, actions, goals=None, auto_reset=False):

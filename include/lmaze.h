@@ -450,6 +450,37 @@ int lmaze_v5_hier_step(const LmazeFovealParams* params, const uint8_t* layouts, 
                        void* stream);
 
 /*
+ * T steps of N foveal envs over pre-generated int32[T,N] tensors (row t = step t) as ONE launch, exactly what T calls
+ * would do (v1:114-200, v2:127-225, v4:167-272, v5:104-292):
+ *   planner_goals == NULL, auto_reset == 0   T x lmaze_foveal_step(actions[t])
+ *   planner_goals == NULL, auto_reset != 0   T x lmaze_foveal_step_autoreset(actions[t]), step t drawing with epoch + t
+ *                                            (v1, v2, v4)
+ *   v5/v6, planner_goals != NULL             T x lmaze_v5_hier_step(actions[t], planner_goals[t], epoch + t)
+ * with bit-identical state, visit map, obs and obs_local at the end.  The caller advances its epoch by T whenever resets
+ * are possible.  reward_t / done_t float[T,N] / uint8[T,N] and, v1 and v5/v6, foveal_reward_t / foveal_done_t (all
+ * nullable) receive every step's reward / done / foveal_reward / foveal_done row -- what the buffers of `bufs` hold after
+ * that step.  A workgroup sets up its layout tables once and runs all T steps of its chunk of envs before it takes the
+ * next chunk; the per-env state, visit tiles and observations go through this CU's caches between steps.
+ * The plain v5/v6 step (no planner goals) has no one-launch form: compiled so, it spills at 4 waves per SIMD, its step
+ * kernel's floor; call lmaze_foveal_step T times.
+ * T == 0 or n == 0: 0, nothing read.  LMAZE_E_COUNT: T < 0 or n outside [0, LMAZE_MAX_ENVS].  LMAZE_E_NULL: a required
+ * pointer is NULL (planner_goals included for v5/v6 with auto_reset != 0).  LMAZE_E_VARIANT: planner_goals for v1/v2/v4,
+ * or none for v5/v6.
+ * launch_hint: bits 4-7 = 2 / 3 / 4: 32 / 64 / 128 envs per workgroup (other codes: the default), bits 8-9 chunks per
+ * workgroup - 1, bits 0-3 workgroups per CU, as for the step; they never change results.
+ */
+int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
+                         const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
+                         int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                         float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                         void* stream);
+
+/* As lmaze_describe_foveal_step, for lmaze_foveal_rollout (two_level != 0: v5/v6 with planner goals, the only v5/v6
+ * form); the text also names T. */
+int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                  int32_t two_level, char* text_host, int32_t len);
+
+/*
  * v6 safeFovealGoal() (v6:505-523): for every env one window cell index 0..24 drawn uniformly from the
  * cells of the 5x5 window around the ball that are not 'W' (the reference rejects on np.random; here
  * Philox keyed by (seed, env_base + i, epoch), index (r*count)>>32 among the accepted cells in
