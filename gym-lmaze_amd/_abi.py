@@ -32,7 +32,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_v5_planner_step", "lmaze_v5_hier_step", "lmaze_v6_safe_foveal_goal", "lmaze_expand_planes",
            "lmaze_foveal_visit_bytes", "lmaze_foveal_materialise_visit", "lmaze_foveal_load_visit",
            "lmaze_describe_step", "lmaze_describe_foveal_step", "lmaze_rollout",
-           "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout")
+           "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout",
+           "lmaze_rollout_obs", "lmaze_foveal_rollout_obs")
 
 
 class LmazeParams(C.Structure):
@@ -150,6 +151,10 @@ def _load():
     lib.lmaze_describe_foveal_step.argtypes = [FP, i64, i32, C.c_char_p, i32]
     lib.lmaze_foveal_rollout.restype = C.c_int
     lib.lmaze_foveal_rollout.argtypes = [FP, vp, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp]
+    lib.lmaze_rollout_obs.restype = C.c_int
+    lib.lmaze_rollout_obs.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
+    lib.lmaze_foveal_rollout_obs.restype = C.c_int
+    lib.lmaze_foveal_rollout_obs.argtypes = [FP, vp, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.lmaze_describe_foveal_rollout.restype = C.c_int
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:

@@ -99,6 +99,31 @@ class VecEnvBase(object):
                                       and t.shape[1] == self.num_envs and t.device == self.device and t.is_contiguous()):
                 raise ValueError("%s wants contiguous int32[T,N] tensors on %s" % (who, self.device))
 
+    def _obs_slots(self, T, obs_every, obs_t, like, allow_final=False, name="obs_t"):
+        """Checks a rollout's recording request (obs_every, and its out-parameter obs_t shaped (T // k, N) + like.shape[1:]
+        with like's dtype) before anything is launched; returns k.  allow_final: obs_every = 0, the final planes only
+        (obs_t None), is accepted."""
+        if isinstance(obs_every, bool) or not isinstance(obs_every, (int, np.integer)):
+            raise ValueError("obs_every must be an int")
+        k = int(obs_every)
+        if k < (0 if allow_final else 1):
+            raise ValueError("obs_every must be >= %d%s" % (0 if allow_final else 1,
+                                                            "" if allow_final else " (obs_every=0 is the grid env's)"))
+        if k == 0:
+            if obs_t is not None:
+                raise ValueError("obs_every=0 records the final planes only: %s must be None" % name)
+            return 0
+        shape = (int(T) // k, self.num_envs) + tuple(like.shape[1:])
+        if not isinstance(obs_t, torch.Tensor):
+            raise ValueError("%s must be a tensor of shape %s" % (name, shape))
+        if tuple(obs_t.shape) != shape:
+            raise ValueError("%s has shape %s, expected %s" % (name, tuple(obs_t.shape), shape))
+        if obs_t.dtype != like.dtype:
+            raise ValueError("%s has dtype %s, expected %s" % (name, obs_t.dtype, like.dtype))
+        if obs_t.device != self.device or not obs_t.is_contiguous() or obs_t.data_ptr() % 16:
+            raise ValueError("%s must be contiguous, on %s and 16-byte aligned" % (name, self.device))
+        return k
+
     def host_state(self, raw=None):
         """Every per-env scalar on the host: numpy views of ONE device->host copy of the state block.  raw: bytes of
         the block already on the host (uint8 array the size of `_state`), parsed instead of copying again."""

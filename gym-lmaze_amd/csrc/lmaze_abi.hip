@@ -244,6 +244,32 @@ int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_
     return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream);
 }
 
+int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
+                      float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                      int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream) {
+    // the recording request first: its refusals need nothing else
+    if (obs_every < 0 || (obs_every == 0 && obs_t)) return LMAZE_E_COUNT;
+    if (obs_every > 0 && T / obs_every > 0 && !obs_t) return LMAZE_E_NULL;
+    if (misaligned(obs_t, 16)) return LMAZE_E_ALIGN;
+    int rc = check_params(params, n);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
+    if (T < 0) return LMAZE_E_COUNT;
+    if (T == 0 || n == 0) return 0;                                   // nothing to do, nothing read
+    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
+    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16)) return LMAZE_E_ALIGN;
+    StepArgs a = make_args(params, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count, obs, n);
+    a.auto_reset = auto_reset ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
+    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
+    const RolloutRec rec{obs_every > 0 && T / obs_every > 0 ? obs_t : nullptr, obs_every};
+    return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, &rec);
+}
+
 int lmaze_step_v3_autoreset(const LmazeParams* params, const uint8_t* layout, const int32_t* action,
                             int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
                             uint8_t* done, int32_t* obs, int64_t n, uint64_t seed, uint64_t epoch,

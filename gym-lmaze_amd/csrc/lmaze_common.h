@@ -105,8 +105,14 @@ inline bool grid_ok(int64_t blocks) { return blocks >= 1 && blocks <= (int64_t)0
 
 hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_step_u8(int variant, bool do_step, const StepArgs& a, hipStream_t s);
+// The recording rollout's request (lmaze_rollout_obs): obs_t int32[T / every, N, G, G] (null when every == 0, or when
+// T / every == 0), every = k >= 1, or 0 for the final planes only.  A null RolloutRec* is the plain rollout.
+struct RolloutRec {
+    int32_t* obs_t;
+    int32_t every;
+};
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
-                          uint8_t* done_t, hipStream_t s);
+                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec = nullptr);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

@@ -15,6 +15,7 @@
 // HBM bytes per env-step: v1 454, v2 545, v4 about 1 000 instead of round 2's 3 337.
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "lmaze_common.h"
 #include "lmaze_visit.h"
@@ -66,6 +67,31 @@ struct FovealRoll {
     float* freward_t;       // [T,N] foveal_reward (v1, v5/v6)
     uint8_t* fdone_t;       // [T,N] foveal_done (v1, v5/v6)
 };
+
+// The recording rollout (lmaze_foveal_rollout_obs): foveal_rollout_kernel's overload for this type runs with REC = true.
+// Step t stores its observation (v5/v6: and, when obs_local_t is given, its local observation) into slot j of the
+// caller's tensors when t = (j + 1) every - 1, beside the running obs / obs_local it writes every step.
+struct FovealRollObs : FovealRoll {
+    float* obs_t;           // [T / every, N, C, 5, 5] or null (no slot)
+    float* obs_local_t;     // [T / every, N, 4, 5, 5] or null (v5/v6)
+    int32_t every;          // k >= 1
+};
+
+// The slots step t fills at this workgroup's first env, or null; the plain rollout has none.  Uniform.
+__device__ __forceinline__ float* roll_slot(const FovealRoll&, int64_t, int64_t, int, int) { return nullptr; }
+__device__ __forceinline__ float* roll_slot(const FovealRollObs& ro, int64_t n, int64_t base, int t, int per) {
+    if (ro.obs_t == nullptr || (t + 1) % ro.every != 0) return nullptr;
+    return ro.obs_t + ((size_t)((t + 1) / ro.every - 1) * n + base) * per;
+}
+__device__ __forceinline__ float* roll_lslot(const FovealRoll&, int64_t, int64_t, int) { return nullptr; }
+__device__ __forceinline__ float* roll_lslot(const FovealRollObs& ro, int64_t n, int64_t base, int t) {
+    if (ro.obs_local_t == nullptr || (t + 1) % ro.every != 0) return nullptr;
+    return ro.obs_local_t + ((size_t)((t + 1) / ro.every - 1) * n + base) * (4 * W25);
+}
+__device__ __forceinline__ void roll_store4(const FovealRoll&, float4*, const float*) {}
+__device__ __forceinline__ void roll_store4(const FovealRollObs&, float4* p, const float* v) {
+    *p = make_float4(v[0], v[1], v[2], v[3]);
+}
 
 struct EnvRec {           // one env after its transition (registers only; phase 1 turns it into plane masks)
     int16_t cx, cy;       // centre of the current window (ball after the move)
@@ -224,7 +250,7 @@ __device__ __forceinline__ uint32_t visit_add(uint32_t bits, int E) { return lma
 // ROLL = false: one step over one chunk per workgroup round, as ever; everything the rollout adds is dead code.
 template <int VARIANT, int MODE, int EPB, int GT, bool AR>
 __global__ __launch_bounds__(LMAZE_BLOCK) LMAZE_FOVEAL_ATTR void foveal_kernel(const FovealArgs a) {
-    constexpr bool ROLL = false;
+    constexpr bool ROLL = false, REC = false;
     const FovealRoll ro{};
 #define LMAZE_FOVEAL_BODY_SITE
 #include "lmaze_foveal_body.h"
@@ -236,7 +262,20 @@ __global__ __launch_bounds__(LMAZE_BLOCK) LMAZE_FOVEAL_ATTR void foveal_kernel(c
 // steps: left to itself v5's rollout takes 121-152 VGPRs (3 waves at 64 envs per workgroup); v1/v2/v4 stay below the budget
 template <int VARIANT, int EPB, int GT, bool AR>
 __global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void foveal_rollout_kernel(const FovealArgs a, const FovealRoll ro) {
-    constexpr bool ROLL = true;
+    constexpr bool ROLL = true, REC = false;
+    constexpr int MODE = FM_STEP;
+#define LMAZE_FOVEAL_BODY_SITE
+#include "lmaze_foveal_body.h"
+#undef LMAZE_FOVEAL_BODY_SITE
+}
+
+// the recording form (lmaze_foveal_rollout_obs): the same kernel, with FovealRollObs.  v1 / v2 held to 6 waves per SIMD,
+// the floor of their plain rollouts (left to itself the slot stores take them to 84-89 VGPRs, 5 waves)
+template <int VARIANT, int EPB, int GT, bool AR>
+__global__ __launch_bounds__(LMAZE_BLOCK)
+__attribute__((amdgpu_waves_per_eu(VARIANT == LMAZE_VARIANT_V1 || VARIANT == LMAZE_VARIANT_V2 ? 6 : 4)))
+void foveal_rollout_kernel(const FovealArgs a, const FovealRollObs ro) {
+    constexpr bool ROLL = true, REC = true;
     constexpr int MODE = FM_STEP;
 #define LMAZE_FOVEAL_BODY_SITE
 #include "lmaze_foveal_body.h"
@@ -550,8 +589,10 @@ static hipError_t launch_foveal_mode(const FovealArgs& a0, hipStream_t s) {
 // ---- the one-launch rollout (lmaze_foveal_rollout) ----
 // Instantiations: envs per workgroup 32 / 64 / 128 (launch_hint bits 4-7 = 2 / 3 / 4; any other code takes the default
 // below), GT 14 (v1) or 18 (v2, v4, v5/v6) or 0, AR plain / fused.  The policy bits never change results.
-template <int VARIANT, int EPB>
-static hipError_t launch_rollout_one(const FovealArgs& a, const FovealRoll& ro, hipStream_t s) {
+// RO = FovealRollObs: the recording form, the same instantiations of its overload.
+template <int VARIANT, int EPB, class RO>
+static hipError_t launch_rollout_one(const FovealArgs& a, const RO& ro, hipStream_t s) {
+    constexpr bool REC = std::is_same<RO, FovealRollObs>::value;
     size_t lds = foveal_lds<VARIANT>(a.p, EPB);
     if constexpr (EPB > 32) {
         if (lds > lds_limit()) return launch_rollout_one<VARIANT, EPB / 2>(a, ro, s);
@@ -568,17 +609,25 @@ static hipError_t launch_rollout_one(const FovealArgs& a, const FovealRoll& ro, 
     const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
     if (a.info) {
         char name[96];
-        snprintf(name, sizeof(name), "foveal_rollout_kernel<v%d, %d, %d, %s>", VARIANT, EPB, a.p.grid == GN ? GN : 0,
-                 a.auto_reset ? (VARIANT == LMAZE_VARIANT_V5 ? "two-level" : "fused-reset") : "plain");
+        snprintf(name, sizeof(name), "foveal_rollout_kernel<v%d, %d, %d, %s%s>", VARIANT, EPB, a.p.grid == GN ? GN : 0,
+                 a.auto_reset ? (VARIANT == LMAZE_VARIANT_V5 ? "two-level" : "fused-reset") : "plain", REC ? ", obs_t" : "");
         describe_launch(a.info, name, EPB, lds > foveal_lds<VARIANT>(a.p, EPB) ? per_cu : 0, m, false, blocks, LMAZE_BLOCK, lds);
         return hipSuccess;
     }
     if constexpr (VARIANT == LMAZE_VARIANT_V5) {
         // the two-level step only (the plain v5/v6 step spills at 4 waves per SIMD: lmaze_foveal_rollout refuses it), and
         // for grids other than 18 only at 32 envs per workgroup (64: 8 bytes of scratch) -- launch_rollout_variant
+        // The recording form only at G = 18: at G = 0 it needs 12 bytes of scratch at 4 waves per SIMD, so
+        // lmaze_foveal_rollout_obs refuses other grids for v5/v6 (LMAZE_E_GRID)
         if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
-        else if constexpr (EPB == 32) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, 32, 0, true>), grid, block, lds, s, b, ro);
+        else if constexpr (EPB == 32 && !REC) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, 32, 0, true>), grid, block, lds, s, b, ro);
         else return hipErrorInvalidConfiguration;
+    } else if constexpr (REC && VARIANT == LMAZE_VARIANT_V1) {
+        // v1's recording form only at G = 14: at G = 0 it spills (12 bytes) at the 6 waves per SIMD of v1's rollouts, so
+        // lmaze_foveal_rollout_obs refuses other grids for v1 (LMAZE_E_GRID)
+        if (a.p.grid != GN) return hipErrorInvalidConfiguration;
+        if (a.auto_reset) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
+        else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, false>), grid, block, lds, s, b, ro);
     } else if (a.auto_reset) {
         if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
         else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, 0, true>), grid, block, lds, s, b, ro);
@@ -589,8 +638,8 @@ static hipError_t launch_rollout_one(const FovealArgs& a, const FovealRoll& ro, 
     return hipGetLastError();
 }
 
-template <int VARIANT>
-static hipError_t launch_rollout_variant(const FovealArgs& a, const FovealRoll& ro, hipStream_t s) {
+template <int VARIANT, class RO>
+static hipError_t launch_rollout_variant(const FovealArgs& a, const RO& ro, hipStream_t s) {
     if (VARIANT == LMAZE_VARIANT_V5 && a.p.grid != 18) return launch_rollout_one<VARIANT, 32>(a, ro, s);
     switch ((a.p.launch_hint >> 4) & 15) {
         case 2: return launch_rollout_one<VARIANT, 32>(a, ro, s);
@@ -611,7 +660,8 @@ static hipError_t launch_rollout_variant(const FovealArgs& a, const FovealRoll& 
     return launch_rollout_one<VARIANT, 64>(a, ro, s);
 }
 
-static hipError_t launch_foveal_rollout(const FovealArgs& a, const FovealRoll& ro, hipStream_t s) {
+template <class RO>
+static hipError_t launch_foveal_rollout(const FovealArgs& a, const RO& ro, hipStream_t s) {
     switch (a.p.variant) {
         case LMAZE_VARIANT_V1: return launch_rollout_variant<LMAZE_VARIANT_V1>(a, ro, s);
         case LMAZE_VARIANT_V2: return launch_rollout_variant<LMAZE_VARIANT_V2>(a, ro, s);
@@ -784,6 +834,45 @@ int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts
     ro.done_t = done_t;
     ro.freward_t = foveal_reward_t;
     ro.fdone_t = foveal_done_t;
+    return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
+}
+
+int lmaze_foveal_rollout_obs(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
+                             const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
+                             int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t,
+                             uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t, float* obs_t,
+                             float* obs_local_t, int32_t obs_every, void* stream) {
+    // the recording request first: its refusals need nothing else
+    if (obs_every < 1) return LMAZE_E_COUNT;
+    const int32_t slots = T > 0 ? T / obs_every : 0;
+    if (slots > 0 && !obs_t) return LMAZE_E_NULL;
+    if (((uintptr_t)obs_t & 15) || ((uintptr_t)obs_local_t & 15)) return LMAZE_E_ALIGN;
+    if (T == 0 || n == 0) return (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) ? LMAZE_E_COUNT : 0;   // nothing to do, nothing read
+    int rc = check_rollout_call(params, planner_goals, T, n, auto_reset);
+    if (rc) return rc;
+    rc = check_foveal(params, layouts, bufs, n);
+    if (rc) return rc;
+    if (!actions) return LMAZE_E_NULL;
+    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    if (obs_local_t && !v56) return LMAZE_E_VARIANT;                  // only v5/v6 have a local observation
+    if (v56 && params->grid != 18) return LMAZE_E_GRID;                // their recording form exists at G = 18 only
+    if (params->variant == LMAZE_VARIANT_V1 && params->grid != 14) return LMAZE_E_GRID;   // v1's at G = 14 only
+    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
+    a.action = actions;
+    a.goal2 = planner_goals;
+    a.auto_reset = (planner_goals || (!v56 && auto_reset)) ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
+    FovealRollObs ro;
+    ro.T = T;
+    ro.reward_t = reward_t;
+    ro.done_t = done_t;
+    ro.freward_t = foveal_reward_t;
+    ro.fdone_t = foveal_done_t;
+    ro.obs_t = slots > 0 ? obs_t : nullptr;
+    ro.obs_local_t = slots > 0 ? obs_local_t : nullptr;
+    ro.every = obs_every;
     return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
 }
 

@@ -1,6 +1,8 @@
 // lmaze_foveal_body.h -- the body of foveal_kernel and foveal_rollout_kernel (lmaze_foveal.hip), included into each.
-// In scope: the kernel argument `a` (FovealArgs), `ro` (FovealRoll), and the compile-time VARIANT, MODE, EPB, GT, AR and
-// ROLL (the rollout: every chunk runs ro.T steps before the workgroup takes the next one).  Not a header of its own.
+// In scope: the kernel argument `a` (FovealArgs), `ro` (FovealRoll, or FovealRollObs), and the compile-time VARIANT, MODE,
+// EPB, GT, AR, ROLL (the rollout: every chunk runs ro.T steps before the workgroup takes the next one) and REC (the
+// recording rollout: phases 3 and 3b also store the observations of every k-th step into the caller's slots).  Not a
+// header of its own.
 #ifndef LMAZE_FOVEAL_BODY_SITE
 #error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip"
 #endif
@@ -751,6 +753,10 @@
     };
     float* obs = a.b.obs + (size_t)blockbase * PERENV;
     const int R = (V5 && MODE == FM_PLANNER) ? 0 : nb * PERENV;   // plannerStep returns only the local observation
+    // REC: the slot this step fills, or null (uniform over the workgroup).  The running obs is still written every step:
+    // an env whose step is skipped (flag bit 0) keeps its previous observation, which the scalar path below copies from
+    // there into the slot -- this workgroup stored it (an earlier step: the vmcnt(0) + barrier between steps) or it
+    // predates the launch.  (Named only inside `if constexpr (REC)`: the plain forms keep their code.)
     const int nq = some_skipped ? 0 : (R >> 2);
     if (LMAZE_XP(a, 16) && !V4 && EPB == 128) {
         // experiment: the 4-KiB pieces of 8 consecutive workgroups interleaved (piece k*8 + w of the group's 1024
@@ -799,10 +805,22 @@
         } else {
             reinterpret_cast<float4*>(obs)[q] = make_float4(v[0], v[1], v[2], v[3]);
         }
+        if constexpr (REC) {
+            if (float* slot = roll_slot(ro, a.n, blockbase, t, PERENV)) roll_store4(ro, reinterpret_cast<float4*>(slot) + q, v);
+        }
     }
     // scalar path: the ragged tail, or every element when some env of the workgroup is skipped
     for (int f = (nq << 2) + tid; f < R; f += LMAZE_BLOCK) {
         const int le = f / PERENV;
+        if constexpr (REC) {
+            if (float* slot = roll_slot(ro, a.n, blockbase, t, PERENV)) {
+                if (flags[le] & 1) { slot[f] = obs[f]; continue; }    // skipped: the observation it keeps
+                const float x = element(le, f - le * PERENV);
+                obs[f] = x;
+                slot[f] = x;
+                continue;
+            }
+        }
         if (flags[le] & 1) continue;
         obs[f] = element(le, f - le * PERENV);
     }
@@ -815,9 +833,19 @@
         for (int q = tid; q < (RL >> 2); q += LMAZE_BLOCK) {
             const int f = q << 2;
             const int le = f / PERLOC;
+            if constexpr (REC) {
+                float* lslot = roll_lslot(ro, a.n, blockbase, t);
+                if (lslot && (flags[le] & 1)) {          // skipped: the local observation it keeps
+                    reinterpret_cast<float4*>(lslot)[q] = reinterpret_cast<const float4*>(loc)[q];
+                    continue;
+                }
+            }
             if (flags[le] & 1) continue;
             float v[4];
             nibble_floats(lbits, q, v);
+            if constexpr (REC) {
+                if (float* lslot = roll_lslot(ro, a.n, blockbase, t)) roll_store4(ro, reinterpret_cast<float4*>(lslot) + q, v);
+            }
             if (a.nt) {   // streamed like the foveal observation (round 3: these 400 B per env were plain stores)
                 typedef float v4f __attribute__((ext_vector_type(4)));
                 v4f t = {v[0], v[1], v[2], v[3]};

@@ -1,0 +1,204 @@
+// lmaze_rollout_body.h -- the bodies of the three v0/v3 rollout kernels of lmaze_step.hip, each included into the plain
+// form (RolloutArgs, REC false) and the recording form (RolloutObsArgs, REC true) of its kernel: through a __device__
+// function the plain forms compiled to other register allocations, included they keep their code.  In scope: `a`
+// (StepArgs), `ro`, the compile-time VARIANT, REC and, for the wave-autonomous body, EPW.  LMAZE_ROLLOUT_BODY selects
+// the body: 1 rollout_shared_wave8_kernel, 2 rollout_shared_kernel, 3 rollout_perenv_kernel.  Not a header of its own.
+#ifndef LMAZE_ROLLOUT_BODY
+#error "lmaze_rollout_body.h is the body of the rollout kernels: it is included only inside them, in lmaze_step.hip"
+#endif
+#if LMAZE_ROLLOUT_BODY == 1
+    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
+    constexpr int G = 8, CELLS = 64;
+    const int lane = threadIdx.x & 63;
+    const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * EPW;
+    if (base >= a.n) return;
+    const int nb = (int)min((int64_t)EPW, a.n - base);
+    const bool autoreset = a.auto_reset != 0;
+    const bool live = lane < nb;
+    const int64_t e = base + lane;
+    const int myc = a.layout[lane];
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);
+    int hits = 0, act_next = s.act;
+    const int mypat = cell_bits<VARIANT>((uint8_t)myc);
+    const int p4 = (lane & 15) << 2;
+    const int4 pat4 = make_int4(__shfl(mypat, p4, 64), __shfl(mypat, p4 + 1, 64), __shfl(mypat, p4 + 2, 64),
+                                __shfl(mypat, p4 + 3, 64));
+    const unsigned long long ok[1] = {__ballot(interior(lane, G) && spawn_ok<VARIANT>((uint8_t)myc))};
+    int4* obs4 = a.obs ? reinterpret_cast<int4*>(a.obs + (size_t)base * CELLS) : nullptr;
+    for (int t = 0; t < ro.T; ++t) {
+        s.act = act_next;
+        if (t + 1 < ro.T && live) act_next = ro.actions[(size_t)(t + 1) * a.n + e];      // next step's row, in flight over this step
+        if (autoreset && s.done) {   // as step_shared_wave8_kernel, with this step's epoch
+            int bc, gc;
+            place_from_masks<VARIANT, 1>(ok, __popcll(ok[0]), env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
+            env_reset<VARIANT>(bc, gc, G, s);
+        }
+        // every lane takes part in the __shfl
+        hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return (uint8_t)__shfl(myc, tx * G + ty, 64); }, s) ? 1 : 0;
+        if (live) rollout_record(ro, a.n, t, e, s);
+        if constexpr (!REC) {
+            if (obs4) {
+                const int ball_cell = ball_cell_of(s.b, G);
+                const int goal_cell = goal_cell_of<VARIANT>(s.g, G);
+#pragma unroll
+                for (int k = 0; k < EPW / 4; ++k) {
+                    const int le = (lane >> 4) + 4 * k;
+                    const int bc = __shfl(ball_cell, le, 64);
+                    const int gc = V3 ? __shfl(goal_cell, le, 64) : -8;
+                    int4 v = pat4;
+                    or_at(v, bc - p4, LMAZE_OBS_BALL);
+                    if (V3) or_at(v, gc - p4, LMAZE_OBS_GOAL);
+                    if (le < nb) obs4[lane + 64 * k] = v;
+                }
+            }
+            continue;
+        }
+        // the slot this step fills (uniform over the wave) and, after the last step, the caller's planes: one render,
+        // stored to both when both are due
+        int4* dst = reinterpret_cast<int4*>(rollout_slot(ro, a.n, base, CELLS, t));
+        int4* also = obs4 && t == ro.T - 1 ? obs4 : nullptr;
+        if (dst == nullptr) { dst = also; also = nullptr; }
+        if (dst) {
+            const int ball_cell = ball_cell_of(s.b, G);
+            const int goal_cell = goal_cell_of<VARIANT>(s.g, G);
+#pragma unroll
+            for (int k = 0; k < EPW / 4; ++k) {
+                const int le = (lane >> 4) + 4 * k;
+                const int bc = __shfl(ball_cell, le, 64);
+                const int gc = V3 ? __shfl(goal_cell, le, 64) : -8;
+                int4 v = pat4;
+                or_at(v, bc - p4, LMAZE_OBS_BALL);
+                if (V3) or_at(v, gc - p4, LMAZE_OBS_GOAL);
+                if (le < nb) {
+                    dst[lane + 64 * k] = v;
+                    if (also) also[lane + 64 * k] = v;
+                }
+            }
+        }
+    }
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+#elif LMAZE_ROLLOUT_BODY == 2
+    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
+    const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
+    extern __shared__ int4 lds4[];
+    int* pat = reinterpret_cast<int*>(lds4);                                  // [CELLS] plane bits without ball / goal
+    int* ballflat = pat + CELLS;                                              // [EPB]
+    int* goalflat = ballflat + EPB;                                           // [EPB]
+    uint8_t* lay = reinterpret_cast<uint8_t*>(goalflat + EPB);                // [CELLS]
+    uint16_t* spawn = reinterpret_cast<uint16_t*>(lay + ((CELLS + 15) & ~15));   // [CELLS] accepted spawn cells, row-major
+    __shared__ int spawn_count_s;
+
+    const int tid = threadIdx.x;
+    const int64_t blockbase = (int64_t)blockIdx.x * EPB;
+    const int nb = (int)min((int64_t)EPB, a.n - blockbase);
+    const bool autoreset = a.auto_reset != 0, live = tid < nb;
+    const int64_t e = blockbase + tid;
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
+    int hits = 0, act_next = s.act;
+    for (int i = tid; i < CELLS; i += LMAZE_BLOCK) {
+        const uint8_t c = a.layout[i];
+        lay[i] = c;
+        pat[i] = cell_bits<VARIANT>(c);
+    }
+    if (autoreset && tid < 64) {
+        const int cnt = wave_build_spawn_list<VARIANT>(a.layout, G, CELLS, spawn, tid);
+        if (tid == 0) spawn_count_s = cnt;
+    }
+    __syncthreads();
+    const int spawn_count = autoreset ? spawn_count_s : 0;
+
+    int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
+    for (int t = 0; t < ro.T; ++t) {
+        if (live) {
+            s.act = act_next;
+            if (t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];       // next step's row, in flight over this step
+            if (autoreset && s.done) {                                                // as env_phase1
+                int bc, gc;
+                place_from_list<VARIANT>(spawn, spawn_count, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
+                env_reset<VARIANT>(bc, gc, G, s);
+            }
+            hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
+            rollout_record(ro, a.n, t, e, s);
+            ballflat[tid] = ball_cell_of(s.b, G);
+            if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
+        }
+        if constexpr (REC) {
+            int32_t* slot = rollout_slot(ro, a.n, blockbase, CELLS, t);
+            int32_t* last = t == ro.T - 1 ? obs : nullptr;
+            if (slot == nullptr && last == nullptr) continue;                         // uniform: nothing recorded
+            __syncthreads();
+            if (slot) rollout_render<VARIANT>(slot, nb * CELLS, CELLS, ballflat, goalflat, [&](int, int c) { return pat[c]; }, slot_nt(ro));
+            if (last) rollout_render<VARIANT>(last, nb * CELLS, CELLS, ballflat, goalflat, [&](int, int c) { return pat[c]; });
+            __syncthreads();
+            continue;
+        }
+        if (obs == nullptr) continue;                                                 // uniform
+        __syncthreads();
+        rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat, [&](int, int c) { return pat[c]; });
+        __syncthreads();                                                              // ballflat / goalflat are rewritten by the next step
+    }
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+#elif LMAZE_ROLLOUT_BODY == 3
+    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
+    const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
+    extern __shared__ int4 lds4[];
+    int* ballflat = reinterpret_cast<int*>(lds4);                             // [EPB] cell of the ball
+    int* goalflat = ballflat + EPB;                                           // [EPB]
+    uint8_t* lays = reinterpret_cast<uint8_t*>(goalflat + EPB);               // [EPB * CELLS]
+
+    const int tid = threadIdx.x;
+    const int64_t blockbase = (int64_t)blockIdx.x * EPB;
+    const int nb = (int)min((int64_t)EPB, a.n - blockbase);
+    const bool autoreset = a.auto_reset != 0, live = tid < nb;
+    const int64_t e = blockbase + tid;
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);
+    int hits = 0, act_next = s.act;
+    {   // EPB is a multiple of 4: the workgroup's layouts start on a dword and are whole dwords
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.layout + (size_t)blockbase * CELLS);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(lays);
+        const int nw = (nb * CELLS) >> 2;
+        for (int i = tid; i < nw; i += LMAZE_BLOCK) dst[i] = src[i];
+        for (int i = (nw << 2) + tid; i < nb * CELLS; i += LMAZE_BLOCK) lays[i] = a.layout[(size_t)blockbase * CELLS + i];
+    }
+    __syncthreads();
+
+    int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
+    for (int t = 0; t < ro.T; ++t) {
+        if (tid < 64) {                                                               // wave 0, every lane: the ballots below
+            s.act = act_next;
+            if (live && t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];
+            // reference reset() of the done envs, one whole-wave placement each on the env's own layout
+            unsigned long long todo = __ballot(live && autoreset && s.done);
+            while (todo) {
+                const int j = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                int bc, gc;
+                wave_place<VARIANT>(lays + j * CELLS, G, CELLS, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + blockbase + j), tid, bc, gc);
+                if (tid == j) env_reset<VARIANT>(bc, gc, G, s);
+            }
+            if (live) {
+                hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lays[tid * CELLS + tx * G + ty]; }, s) ? 1 : 0;
+                rollout_record(ro, a.n, t, e, s);
+                ballflat[tid] = ball_cell_of(s.b, G);
+                if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
+            }
+        }
+        if constexpr (REC) {
+            auto bits = [&](int le, int c) { return cell_bits<VARIANT>(lays[le * CELLS + c]); };
+            int32_t* slot = rollout_slot(ro, a.n, blockbase, CELLS, t);
+            int32_t* last = t == ro.T - 1 ? obs : nullptr;
+            if (slot == nullptr && last == nullptr) continue;                         // uniform: nothing recorded
+            __syncthreads();
+            if (slot) rollout_render<VARIANT>(slot, nb * CELLS, CELLS, ballflat, goalflat, bits, slot_nt(ro));
+            if (last) rollout_render<VARIANT>(last, nb * CELLS, CELLS, ballflat, goalflat, bits);
+            __syncthreads();
+            continue;
+        }
+        if (obs == nullptr) continue;                                                 // uniform
+        __syncthreads();
+        rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat,
+                                [&](int le, int c) { return cell_bits<VARIANT>(lays[le * CELLS + c]); });
+        __syncthreads();
+    }
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+#endif

@@ -883,6 +883,26 @@ struct RolloutArgs {
     int32_t T;
 };
 
+// The recording rollout (lmaze_rollout_obs): the kernels below take this type instead of RolloutArgs -- an overload of
+// each kernel, so the plain forms keep their symbols and code.  Step t stores its planes into slot j of obs_t when
+// t = (j + 1) every - 1, into the caller's obs when it is the last step, and nowhere otherwise: the destination of a step
+// is uniform over the workgroup (wave), and a step that records nothing skips its render and its barriers.
+struct RolloutObsArgs : RolloutArgs {
+    int32_t* obs_t;           // [T / every, N, G, G] or null (every == 0: final planes only)
+    int32_t every;            // k >= 1, or 0
+    int32_t nt;               // slot stores: non-temporal (1) or plain (0), chosen by the launcher
+};
+
+// The slot step t of the recording form fills -- slot j when t = (j + 1) every - 1 -- at this workgroup's (wave's) first
+// env `base`, or null.  Uniform: one scalar division per step.
+__device__ __forceinline__ int32_t* rollout_slot(const RolloutObsArgs& ro, int64_t n, int64_t base, int cells, int t) {
+    if (ro.obs_t == nullptr || ro.every <= 0 || (t + 1) % ro.every != 0) return nullptr;
+    return ro.obs_t + ((size_t)((t + 1) / ro.every - 1) * n + base) * cells;
+}
+__device__ __forceinline__ int32_t* rollout_slot(const RolloutArgs&, int64_t, int64_t, int, int) { return nullptr; }
+__device__ __forceinline__ bool slot_nt(const RolloutArgs&) { return false; }
+__device__ __forceinline__ bool slot_nt(const RolloutObsArgs& ro) { return ro.nt != 0; }
+
 // The rollout kernels' registers, loaded once: the env's state with the action row of step 0 in act (a lane without
 // an env holds a neutral one)
 template <int VARIANT>
@@ -921,60 +941,30 @@ __device__ __forceinline__ void rollout_store(const StepArgs& a, const RolloutAr
     }
 }
 
+
 template <int VARIANT, int EPW>
 __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_wave8_kernel(const StepArgs a, const RolloutArgs ro) {
-    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
-    constexpr int G = 8, CELLS = 64;
-    const int lane = threadIdx.x & 63;
-    const int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * EPW;
-    if (base >= a.n) return;
-    const int nb = (int)min((int64_t)EPW, a.n - base);
-    const bool autoreset = a.auto_reset != 0;
-    const bool live = lane < nb;
-    const int64_t e = base + lane;
-    const int myc = a.layout[lane];
-    EnvState s = rollout_load<VARIANT>(a, ro, e, live);
-    int hits = 0, act_next = s.act;
-    const int mypat = cell_bits<VARIANT>((uint8_t)myc);
-    const int p4 = (lane & 15) << 2;
-    const int4 pat4 = make_int4(__shfl(mypat, p4, 64), __shfl(mypat, p4 + 1, 64), __shfl(mypat, p4 + 2, 64),
-                                __shfl(mypat, p4 + 3, 64));
-    const unsigned long long ok[1] = {__ballot(interior(lane, G) && spawn_ok<VARIANT>((uint8_t)myc))};
-    int4* obs4 = a.obs ? reinterpret_cast<int4*>(a.obs + (size_t)base * CELLS) : nullptr;
-    for (int t = 0; t < ro.T; ++t) {
-        s.act = act_next;
-        if (t + 1 < ro.T && live) act_next = ro.actions[(size_t)(t + 1) * a.n + e];      // next step's row, in flight over this step
-        if (autoreset && s.done) {   // as step_shared_wave8_kernel, with this step's epoch
-            int bc, gc;
-            place_from_masks<VARIANT, 1>(ok, __popcll(ok[0]), env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
-            env_reset<VARIANT>(bc, gc, G, s);
-        }
-        // every lane takes part in the __shfl
-        hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return (uint8_t)__shfl(myc, tx * G + ty, 64); }, s) ? 1 : 0;
-        if (live) rollout_record(ro, a.n, t, e, s);
-        if (obs4) {
-            const int ball_cell = ball_cell_of(s.b, G);
-            const int goal_cell = goal_cell_of<VARIANT>(s.g, G);
-#pragma unroll
-            for (int k = 0; k < EPW / 4; ++k) {
-                const int le = (lane >> 4) + 4 * k;
-                const int bc = __shfl(ball_cell, le, 64);
-                const int gc = V3 ? __shfl(goal_cell, le, 64) : -8;
-                int4 v = pat4;
-                or_at(v, bc - p4, LMAZE_OBS_BALL);
-                if (V3) or_at(v, gc - p4, LMAZE_OBS_GOAL);
-                if (le < nb) obs4[lane + 64 * k] = v;
-            }
-        }
-    }
-    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+    constexpr bool REC = false;
+#define LMAZE_ROLLOUT_BODY 1
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+// the recording form (lmaze_rollout_obs)
+template <int VARIANT, int EPW>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void rollout_shared_wave8_kernel(const StepArgs a, const RolloutObsArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 1
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
 }
 
 // One step's planes of a rollout workgroup (R dwords): dword f of the range = cell f % CELLS of env f / CELLS, a lane
 // walking its 16-byte stores 1024 dwords apart, then the ragged tail (nb*G*G not a multiple of 4).  bits(le, c) = the
-// ball-free plane bits of cell c of env le.
+// ball-free plane bits of cell c of env le.  nt: non-temporal 16-byte stores (the recording form's slots).
 template <int VARIANT, class Bits>
-__device__ __forceinline__ void rollout_render(int32_t* obs, int R, int CELLS, const int* ballflat, const int* goalflat, Bits bits) {
+__device__ __forceinline__ void rollout_render(int32_t* obs, int R, int CELLS, const int* ballflat, const int* goalflat, Bits bits,
+                                               bool nt = false) {
     const int tid = threadIdx.x, nq = R >> 2;
     auto value = [&](int le, int c) {
         int v = bits(le, c);
@@ -991,7 +981,8 @@ __device__ __forceinline__ void rollout_render(int32_t* obs, int R, int CELLS, c
             vals[j] = value(l2, c2);
             if (++c2 == CELLS) { c2 = 0; ++l2; }
         }
-        reinterpret_cast<int4*>(obs)[q] = make_int4(vals[0], vals[1], vals[2], vals[3]);
+        if (nt) store16<true>(reinterpret_cast<int4*>(obs) + q, make_int4(vals[0], vals[1], vals[2], vals[3]));
+        else reinterpret_cast<int4*>(obs)[q] = make_int4(vals[0], vals[1], vals[2], vals[3]);
         le += dle; c += dc;
         if (c >= CELLS) { c -= CELLS; ++le; }
     }
@@ -1009,117 +1000,44 @@ __device__ __forceinline__ void rollout_render(int32_t* obs, int R, int CELLS, c
 // independent).  Per-step launches of such a batch are launch-bound (65 536 x 11x11: 8 us per launch for 32 MB of planes
 // that never leave the caches).  Transition, fused reset (placement from the compacted spawn list with the draw of
 // epoch + t) and the v0 reward persistence are the step kernel's own functions: bit-identical by construction and by test.
+
 template <int VARIANT>
 __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_kernel(const StepArgs a, const RolloutArgs ro) {
-    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
-    const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
-    extern __shared__ int4 lds4[];
-    int* pat = reinterpret_cast<int*>(lds4);                                  // [CELLS] plane bits without ball / goal
-    int* ballflat = pat + CELLS;                                              // [EPB]
-    int* goalflat = ballflat + EPB;                                           // [EPB]
-    uint8_t* lay = reinterpret_cast<uint8_t*>(goalflat + EPB);                // [CELLS]
-    uint16_t* spawn = reinterpret_cast<uint16_t*>(lay + ((CELLS + 15) & ~15));   // [CELLS] accepted spawn cells, row-major
-    __shared__ int spawn_count_s;
+    constexpr bool REC = false;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
 
-    const int tid = threadIdx.x;
-    const int64_t blockbase = (int64_t)blockIdx.x * EPB;
-    const int nb = (int)min((int64_t)EPB, a.n - blockbase);
-    const bool autoreset = a.auto_reset != 0, live = tid < nb;
-    const int64_t e = blockbase + tid;
-    EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
-    int hits = 0, act_next = s.act;
-    for (int i = tid; i < CELLS; i += LMAZE_BLOCK) {
-        const uint8_t c = a.layout[i];
-        lay[i] = c;
-        pat[i] = cell_bits<VARIANT>(c);
-    }
-    if (autoreset && tid < 64) {
-        const int cnt = wave_build_spawn_list<VARIANT>(a.layout, G, CELLS, spawn, tid);
-        if (tid == 0) spawn_count_s = cnt;
-    }
-    __syncthreads();
-    const int spawn_count = autoreset ? spawn_count_s : 0;
-
-    int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
-    for (int t = 0; t < ro.T; ++t) {
-        if (live) {
-            s.act = act_next;
-            if (t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];       // next step's row, in flight over this step
-            if (autoreset && s.done) {                                                // as env_phase1
-                int bc, gc;
-                place_from_list<VARIANT>(spawn, spawn_count, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
-                env_reset<VARIANT>(bc, gc, G, s);
-            }
-            hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
-            rollout_record(ro, a.n, t, e, s);
-            ballflat[tid] = ball_cell_of(s.b, G);
-            if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
-        }
-        if (obs == nullptr) continue;                                                 // uniform
-        __syncthreads();
-        rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat, [&](int, int c) { return pat[c]; });
-        __syncthreads();                                                              // ballflat / goalflat are rewritten by the next step
-    }
-    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+// the recording form (lmaze_rollout_obs)
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void rollout_shared_kernel(const StepArgs a, const RolloutObsArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
 }
 
 // The same for per-env layouts: the workgroup's EPB layouts (EPB * G * G bytes) are copied to LDS once and serve the
 // collision check, the planes and -- a done env, fused reset -- the whole-wave placement on the env's own maze (wave_place,
 // the rule of the per-env step kernels) for all T steps.  EPB <= 64: every env's lane sits in wave 0, which places the
 // done envs one after the other.
+
 template <int VARIANT>
 __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_perenv_kernel(const StepArgs a, const RolloutArgs ro) {
-    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
-    const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
-    extern __shared__ int4 lds4[];
-    int* ballflat = reinterpret_cast<int*>(lds4);                             // [EPB] cell of the ball
-    int* goalflat = ballflat + EPB;                                           // [EPB]
-    uint8_t* lays = reinterpret_cast<uint8_t*>(goalflat + EPB);               // [EPB * CELLS]
+    constexpr bool REC = false;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
 
-    const int tid = threadIdx.x;
-    const int64_t blockbase = (int64_t)blockIdx.x * EPB;
-    const int nb = (int)min((int64_t)EPB, a.n - blockbase);
-    const bool autoreset = a.auto_reset != 0, live = tid < nb;
-    const int64_t e = blockbase + tid;
-    EnvState s = rollout_load<VARIANT>(a, ro, e, live);
-    int hits = 0, act_next = s.act;
-    {   // EPB is a multiple of 4: the workgroup's layouts start on a dword and are whole dwords
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.layout + (size_t)blockbase * CELLS);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(lays);
-        const int nw = (nb * CELLS) >> 2;
-        for (int i = tid; i < nw; i += LMAZE_BLOCK) dst[i] = src[i];
-        for (int i = (nw << 2) + tid; i < nb * CELLS; i += LMAZE_BLOCK) lays[i] = a.layout[(size_t)blockbase * CELLS + i];
-    }
-    __syncthreads();
-
-    int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
-    for (int t = 0; t < ro.T; ++t) {
-        if (tid < 64) {                                                               // wave 0, every lane: the ballots below
-            s.act = act_next;
-            if (live && t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];
-            // reference reset() of the done envs, one whole-wave placement each on the env's own layout
-            unsigned long long todo = __ballot(live && autoreset && s.done);
-            while (todo) {
-                const int j = __ffsll((long long)todo) - 1;
-                todo &= todo - 1ull;
-                int bc, gc;
-                wave_place<VARIANT>(lays + j * CELLS, G, CELLS, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + blockbase + j), tid, bc, gc);
-                if (tid == j) env_reset<VARIANT>(bc, gc, G, s);
-            }
-            if (live) {
-                hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lays[tid * CELLS + tx * G + ty]; }, s) ? 1 : 0;
-                rollout_record(ro, a.n, t, e, s);
-                ballflat[tid] = ball_cell_of(s.b, G);
-                if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
-            }
-        }
-        if (obs == nullptr) continue;                                                 // uniform
-        __syncthreads();
-        rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat,
-                                [&](int le, int c) { return cell_bits<VARIANT>(lays[le * CELLS + c]); });
-        __syncthreads();
-    }
-    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+// the recording form (lmaze_rollout_obs)
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) void rollout_perenv_kernel(const StepArgs a, const RolloutObsArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
 }
 
 // ------------------------------------------------------------------------------------
@@ -1453,13 +1371,48 @@ hipError_t launch_step_u8(int variant, bool do_step, const StepArgs& a, hipStrea
     return launch_step_u8_epb<64>(variant, do_step, a, s);
 }
 
+// The rollout kernel of either form: the plain one with RolloutArgs, the recording one (rec != null) with
+// RolloutObsArgs -- an overload of the same kernel template, so `kern` names both
+template <class K0, class K1>
+static hipError_t launch_ro(K0 plain, K1 recording, const RolloutRec* rec, bool nt, dim3 grid, dim3 block, size_t lds,
+                            hipStream_t s, const StepArgs& a, const RolloutArgs& ro) {
+    if (rec) {
+        RolloutObsArgs rr;
+        static_cast<RolloutArgs&>(rr) = ro;
+        rr.obs_t = rec->obs_t;
+        rr.every = rec->every;
+        rr.nt = nt ? 1 : 0;
+        hipLaunchKernelGGL(recording, grid, block, lds, s, a, rr);
+    } else {
+        hipLaunchKernelGGL(plain, grid, block, lds, s, a, ro);
+    }
+    return hipGetLastError();
+}
+
+// Store policy of the recording form's slots: plain.  Measured (tools/bench_rollout_obs.py --sweep, two runs, T = 16,
+// every step recorded; launch_hint bit 15 = non-temporal, for measurement -- results never change), us per step plain / nt:
+//   65 536 x 11x11 shared (507 MB of slots, beyond the 256-MiB Infinity Cache)   6.2-6.5 / 7.2-7.5
+//   1M x 11x11 shared (8.1 GB)  109.5-110.4 / 110.5-110.7     262 144 x 32x32 per-env (17 GB)  219.5-223.9 / 221.1-222.3
+//   16 384 x 11x11 per-env (127 MB, inside it)  4.0 / 3.8 at 16 envs per workgroup (plain runs spread 3.7-4.8)
+// i.e. streaming wins nothing beyond a few per cent inside the cache and loses 12-18 % where the slots are about twice
+// the cache.  The wave-autonomous 8x8 form has no choice: with it, it spills at its twin's 6 waves per SIMD.
+static bool slot_stores_nt(const StepArgs& a, const RolloutRec* rec) {
+    return rec && rec->obs_t && ((a.launch_hint >> 15) & 1);
+}
+
 // T steps: ONE launch (shared layouts: rollout_shared_wave8_kernel for on-die 8x8, rollout_shared_kernel otherwise; per-env
 // layouts: rollout_perenv_kernel); T launches of the step kernel only for T = 1 or when launch_hint bit 8 forces streaming stores, step t with the action row t, epoch + t and, when given, the per-step reward / done rows copied out.
+// rec != null: the recording form of the same kernel (RolloutObsArgs); the T launches give each step its slot, the
+// caller's obs (last step) or nothing.
 hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
-                          uint8_t* done_t, hipStream_t s) {
+                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
+    const bool v3 = variant == LMAZE_VARIANT_V3;
+    const bool nt = slot_stores_nt(a0, rec);
+    // the recording form streams its slots wherever the batch sits; on-die means the batch's planes fit the caches
+    const bool planes = a0.obs != nullptr || (rec && rec->obs_t);
     const bool on_die8 = layout_mode == LMAZE_LAYOUT_SHARED && a0.grid == 8 &&
-                         (a0.obs == nullptr || !beyond_caches(a0.n, 64)) && (a0.launch_hint & 0x100) == 0;
+                         (!planes || !beyond_caches(a0.n, 64)) && (a0.launch_hint & 0x100) == 0;
     if (on_die8) {
         RolloutArgs ro{actions, reward_t, done_t, T};
         const int epw = 64, wpb = a0.n >= 65536 ? 4 : 1;
@@ -1467,15 +1420,24 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
         if (a0.info) {
             char name[96];
-            snprintf(name, sizeof(name), "rollout_shared_wave8_kernel<v%d, %d> T=%d", variant, epw, T);
+            if (rec) snprintf(name, sizeof(name), "rollout_shared_wave8_kernel<v%d, %d, obs_t> T=%d every=%d", variant, epw, T, rec->every);
+            else snprintf(name, sizeof(name), "rollout_shared_wave8_kernel<v%d, %d> T=%d", variant, epw, T);
             describe_launch(a0.info, name, epw * wpb, 0, 1, false, blocks, 64 * wpb, 0);
             return hipSuccess;
         }
-        if (variant == LMAZE_VARIANT_V3)
-            hipLaunchKernelGGL((rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>), dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
-        else
-            hipLaunchKernelGGL((rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>), dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
-        return hipGetLastError();
+        if (!rec) {     // the plain form's launch, as it always was
+            if (variant == LMAZE_VARIANT_V3)
+                hipLaunchKernelGGL((rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>), dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
+            else
+                hipLaunchKernelGGL((rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>), dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
+            return hipGetLastError();
+        }
+        using P = void (*)(const StepArgs, const RolloutArgs);
+        using R = void (*)(const StepArgs, const RolloutObsArgs);
+        if (v3) return launch_ro((P)rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>, (R)rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>,
+                                 rec, nt, dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
+        return launch_ro((P)rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>, (R)rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>,
+                         rec, nt, dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
     }
     // any other shared-layout batch: one launch of rollout_shared_kernel, a workgroup per 16 / 32 / 64 envs so that small
     // batches still fill the chip.  Streaming sizes too: the planes of every step still go out to HBM, but the state stays
@@ -1492,7 +1454,10 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         // 512K x 18x18: 64: 89.2, 16: 98.4, 8: 74.2, 4: 76.2; 256K x 32x32 (no size fits): 146 / 140 / 133.7 / 141.6
         // (profiles/r03/rollout_envs_per_workgroup.txt).  launch_hint bits 12-14 = k > 0 ask for 4 << (k - 1) envs.
         // (Only beyond the Infinity Cache: 262 144 x 11x11, 127 MB of planes, runs 9.9 us per step at 64 envs and 12.9 at 16.)
-        if (beyond_caches(a0.n, a0.grid * a0.grid)) {
+        // The recording form keeps the size by batch (launch_hint bits 12-14 swept, T = 16, us per step for every step
+        // recorded / final planes only): 1M x 11x11 64 envs 109.1 / 16.2, 32: 109.4 / 21.0, 16 (what `fit` picks)
+        // 125.7 / 31.5, 8: 147.6 / 52.8; 65 536 x 11x11 64 or 32 6.5-7.8, 8 / 16 7.6-9.7 (profiles/rollout_obs/)
+        if (!rec && beyond_caches(a0.n, a0.grid * a0.grid)) {
             int fit = 64;
             while (fit > 8 && (size_t)fit * a0.grid * a0.grid * 4 > 12288) fit >>= 1;
             if (fit < a.envs_per_block) a.envs_per_block = fit;
@@ -1504,15 +1469,24 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
         if (a0.info) {
             char name[96];
-            snprintf(name, sizeof(name), "rollout_shared_kernel<v%d> T=%d", variant, T);
-            describe_launch(a0.info, name, a.envs_per_block, 0, 1, false, blocks, LMAZE_BLOCK, lds);
+            if (rec) snprintf(name, sizeof(name), "rollout_shared_kernel<v%d, obs_t> T=%d every=%d", variant, T, rec->every);
+            else snprintf(name, sizeof(name), "rollout_shared_kernel<v%d> T=%d", variant, T);
+            describe_launch(a0.info, name, a.envs_per_block, 0, 1, nt, blocks, LMAZE_BLOCK, lds);
             return hipSuccess;
         }
-        if (variant == LMAZE_VARIANT_V3)
-            hipLaunchKernelGGL((rollout_shared_kernel<LMAZE_VARIANT_V3>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-        else
-            hipLaunchKernelGGL((rollout_shared_kernel<LMAZE_VARIANT_V0>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-        return hipGetLastError();
+        if (!rec) {
+            if (variant == LMAZE_VARIANT_V3)
+                hipLaunchKernelGGL((rollout_shared_kernel<LMAZE_VARIANT_V3>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
+            else
+                hipLaunchKernelGGL((rollout_shared_kernel<LMAZE_VARIANT_V0>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
+            return hipGetLastError();
+        }
+        using P = void (*)(const StepArgs, const RolloutArgs);
+        using R = void (*)(const StepArgs, const RolloutObsArgs);
+        if (v3) return launch_ro((P)rollout_shared_kernel<LMAZE_VARIANT_V3>, (R)rollout_shared_kernel<LMAZE_VARIANT_V3>, rec, nt,
+                                 dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
+        return launch_ro((P)rollout_shared_kernel<LMAZE_VARIANT_V0>, (R)rollout_shared_kernel<LMAZE_VARIANT_V0>, rec, nt,
+                         dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
     }
     // per-env layouts, any size: the layouts are read ONCE per rollout instead of once per step (1M x 32x32: 838 -> 722 us per
     // step, 1M x 11x11 103 -> 100.5, with the fused reset 114 -> 105.7, 512K x 18x18 142 -> 114; only 8 192 x 32x32, where the
@@ -1525,8 +1499,12 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         const int cells = a0.grid * a0.grid;
         int epb = a0.n >= 65536 ? 64 : (a0.n >= 16384 ? 32 : 16);
         while (epb > 4 && (size_t)epb * cells > (size_t)32 << 10) epb >>= 1;         // at most 32 KiB of layouts per workgroup
-        if (beyond_caches(a0.n, cells))                                              // planes that fit the L2s, as above
+        if (!rec && beyond_caches(a0.n, cells))                                      // planes that fit the L2s, as above
             while (epb > 8 && (size_t)epb * cells * 4 > 12288) epb >>= 1;
+        // the recording form (launch_hint bits 12-14 swept, T = 16, every step recorded): 16 384 x 11x11 16 envs 3.7 us
+        // per step, 32 (the plain form's) 4.7, 8 4.4, 64 7.1; 262 144 x 32x32 the plain form's 32 envs 221 us, 16 255,
+        // 8 237, 64 346 -- so only the batches that take 32 by size (16 384 to 65 535 envs) halve
+        if (rec && epb == 32 && a0.n < 65536) epb = 16;
         if ((a0.launch_hint >> 12) & 7) epb = 4 << (((a0.launch_hint >> 12) & 7) - 1);
         if (epb > 64) epb = 64;                                                      // every env's lane sits in wave 0
         a.envs_per_block = epb;
@@ -1535,22 +1513,38 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
         if (a0.info) {
             char name[96];
-            snprintf(name, sizeof(name), "rollout_perenv_kernel<v%d> T=%d", variant, T);
-            describe_launch(a0.info, name, epb, 0, 1, false, blocks, LMAZE_BLOCK, lds);
+            if (rec) snprintf(name, sizeof(name), "rollout_perenv_kernel<v%d, obs_t> T=%d every=%d", variant, T, rec->every);
+            else snprintf(name, sizeof(name), "rollout_perenv_kernel<v%d> T=%d", variant, T);
+            describe_launch(a0.info, name, epb, 0, 1, nt, blocks, LMAZE_BLOCK, lds);
             return hipSuccess;
         }
-        if (variant == LMAZE_VARIANT_V3)
-            hipLaunchKernelGGL((rollout_perenv_kernel<LMAZE_VARIANT_V3>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-        else
-            hipLaunchKernelGGL((rollout_perenv_kernel<LMAZE_VARIANT_V0>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-        return hipGetLastError();
+        if (!rec) {
+            if (variant == LMAZE_VARIANT_V3)
+                hipLaunchKernelGGL((rollout_perenv_kernel<LMAZE_VARIANT_V3>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
+            else
+                hipLaunchKernelGGL((rollout_perenv_kernel<LMAZE_VARIANT_V0>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
+            return hipGetLastError();
+        }
+        using P = void (*)(const StepArgs, const RolloutArgs);
+        using R = void (*)(const StepArgs, const RolloutObsArgs);
+        if (v3) return launch_ro((P)rollout_perenv_kernel<LMAZE_VARIANT_V3>, (R)rollout_perenv_kernel<LMAZE_VARIANT_V3>, rec, nt,
+                                 dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
+        return launch_ro((P)rollout_perenv_kernel<LMAZE_VARIANT_V0>, (R)rollout_perenv_kernel<LMAZE_VARIANT_V0>, rec, nt,
+                         dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
     }
+    const int64_t plane = (int64_t)a0.n * a0.grid * a0.grid;                        // dwords of one step's planes
     for (int32_t t = 0; t < T; ++t) {
         StepArgs a = a0;
         a.action = actions + (size_t)t * a0.n;
         a.epoch = a0.epoch + (uint64_t)t;
+        int32_t* slot = nullptr;                                                     // recording: the slot step t fills
+        if (rec && rec->obs_t && rec->every > 0 && (t + 1) % rec->every == 0)
+            slot = rec->obs_t + (size_t)((t + 1) / rec->every - 1) * plane;
+        if (rec) a.obs = t == T - 1 && a0.obs ? a0.obs : slot;                         // the caller's obs after the last step
         hipError_t rc = launch_step(variant, true, a, layout_mode, s);
         if (rc != hipSuccess || a0.info) return rc;
+        if (slot && a.obs != slot && (rc = hipMemcpyAsync(slot, a.obs, (size_t)plane * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+            return rc;
         if (reward_t && (rc = hipMemcpyAsync(reward_t + (size_t)t * a0.n, a0.reward, (size_t)a0.n * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
         if (done_t && (rc = hipMemcpyAsync(done_t + (size_t)t * a0.n, a0.done, (size_t)a0.n, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
     }

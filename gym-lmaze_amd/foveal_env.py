@@ -169,7 +169,8 @@ class LmazeFovealVecEnv(VecEnvBase):
                                              self.seed & (2 ** 64 - 1), epoch, self.env_base, e_in, e_out, self._stream())
         _abi.check("lmaze_v5_hier_step", rc)
 
-    def rollout(self, actions, goals=None, auto_reset=False, device_epoch=False, trajectory=False):
+    def rollout(self, actions, goals=None, auto_reset=False, device_epoch=False, trajectory=False, obs_t=None,
+                obs_local_t=None, obs_every=None):
         """T steps over device tensors int32[T,N], no host sync: step(actions[t]) -- with the reset fused in when
         auto_reset (v1, v2, v4) -- or, for v5/v6 with `goals`, the two-level step hier_step(actions[t], goals[t]).
         The whole rollout is ONE launch (lmaze_foveal_rollout, include/lmaze.h), bit-identical to the T step launches --
@@ -177,8 +178,24 @@ class LmazeFovealVecEnv(VecEnvBase):
         the epoch ends where those would leave it (+T with auto_reset or goals).  device_epoch=True keeps the reset
         epoch on the device and launches T steps instead (what capture_rollout records).  Returns the final
         (obs, reward, done); trajectory=True adds every step's reward float32[T,N] and done bool[T,N] and, v1 / v5 / v6,
-        foveal_reward float32[T,N] and foveal_done bool[T,N] (the second stream) as well."""
+        foveal_reward float32[T,N] and foveal_done bool[T,N] (the second stream) as well.
+        obs_every=k >= 1 records observations into the caller's obs_t, float32 (T // k, N, C, 5, 5): slot j is what obs
+        holds after step (j + 1) k - 1 (lmaze_foveal_rollout_obs, still one launch; the plain v5/v6 step copies obs after
+        each recorded step launch); v5/v6 also obs_local_t (T // k, N, 4, 5, 5), optional.  The final obs, state and rows
+        are those of the plain rollout.  Not with device_epoch."""
         hier = goals is not None
+        k = None
+        if obs_every is not None:
+            self._check_rows("rollout()", actions, goals)
+            if device_epoch:
+                raise ValueError("rollout(obs_every=...) is not available with a device-resident epoch")
+            if obs_local_t is not None and not self._two_level:
+                raise ValueError("obs_local_t: v5/v6 only")
+            k = self._obs_slots(int(actions.shape[0]), obs_every, obs_t, self.obs)
+            if obs_local_t is not None:
+                self._obs_slots(int(actions.shape[0]), obs_every, obs_local_t, self.obs_local, name="obs_local_t")
+        elif obs_t is not None or obs_local_t is not None:
+            raise ValueError("obs_t / obs_local_t need obs_every")
         self._check_rows("rollout()", actions, goals)
         if hier and (not self._two_level or goals.shape[0] != actions.shape[0]):
             raise ValueError("planner goals: v5/v6 only, one row per step")
@@ -186,6 +203,38 @@ class LmazeFovealVecEnv(VecEnvBase):
             if auto_reset:
                 raise ValueError("v5/v6 restart episodes through the two-level step: pass goals")
         T, N = int(actions.shape[0]), self.num_envs
+        if k is not None and hier and self.grid != 18:
+            # the two-level recording form exists at G = 18 only (include/lmaze.h lmaze_foveal_rollout_obs): T launches
+            base, stride = actions.data_ptr(), N * 4
+            rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
+                    for t in (self.reward, self.done, self.foveal_reward, self.foveal_done)] if trajectory else None
+            for t in range(T):
+                self.hier_step_raw(base + t * stride, goals.data_ptr() + t * stride)
+                if rows:
+                    for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
+                        r[t].copy_(src)
+                if (t + 1) % k == 0:
+                    obs_t[(t + 1) // k - 1].copy_(self.obs)
+                    if obs_local_t is not None:
+                        obs_local_t[(t + 1) // k - 1].copy_(self.obs_local)
+            if trajectory:
+                return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
+            return self.obs, self.reward, self.done
+        if k is not None and self.variant == "v1" and self.grid != 14:
+            # v1's recording form exists at G = 14 only (include/lmaze.h lmaze_foveal_rollout_obs): T launches
+            base, stride = actions.data_ptr(), N * 4
+            rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
+                    for t in (self.reward, self.done, self.foveal_reward, self.foveal_done)] if trajectory else None
+            for t in range(T):
+                self.step_raw(base + t * stride, auto_reset=auto_reset)
+                if rows:
+                    for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
+                        r[t].copy_(src)
+                if (t + 1) % k == 0:
+                    obs_t[(t + 1) // k - 1].copy_(self.obs)
+            if trajectory:
+                return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
+            return self.obs, self.reward, self.done
         if self._two_level and not hier and not device_epoch:
             # the plain v5/v6 step has no one-launch form (include/lmaze.h lmaze_foveal_rollout): T launches, rows copied
             rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
@@ -196,6 +245,10 @@ class LmazeFovealVecEnv(VecEnvBase):
                 if rows:
                     for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
                         r[t].copy_(src)
+                if k is not None and (t + 1) % k == 0:        # a recorded step: its observations into the slots
+                    obs_t[(t + 1) // k - 1].copy_(self.obs)
+                    if obs_local_t is not None:
+                        obs_local_t[(t + 1) // k - 1].copy_(self.obs_local)
             if trajectory:
                 return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
             return self.obs, self.reward, self.done
@@ -211,12 +264,17 @@ class LmazeFovealVecEnv(VecEnvBase):
             ptrs = [r.data_ptr() for r in rows] if rows else []
             ptrs += [None] * (4 - len(ptrs))
             if T > 0:
+                args = (self._pp, self._p_layouts, actions.data_ptr(), goals.data_ptr() if hier else None, T, self._pb, N,
+                        1 if resets else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *ptrs)
                 with self._guard():
-                    rc = _abi.lib.lmaze_foveal_rollout(self._pp, self._p_layouts, actions.data_ptr(),
-                                                       goals.data_ptr() if hier else None, T, self._pb, N,
-                                                       1 if resets else 0, self.seed & (2 ** 64 - 1), self._epoch,
-                                                       self.env_base, *ptrs, self._stream())
-                _abi.check("lmaze_foveal_rollout", rc)
+                    if k is None:
+                        rc = _abi.lib.lmaze_foveal_rollout(*args, self._stream())
+                    else:
+                        some = obs_t.shape[0] > 0
+                        rc = _abi.lib.lmaze_foveal_rollout_obs(*args, obs_t.data_ptr() if some else None,
+                                                               obs_local_t.data_ptr() if some and obs_local_t is not None else None,
+                                                               k, self._stream())
+                _abi.check("lmaze_foveal_rollout" if k is None else "lmaze_foveal_rollout_obs", rc)
                 if resets:
                     self._epoch += T
             if trajectory:
@@ -235,9 +293,12 @@ class LmazeFovealVecEnv(VecEnvBase):
                 self.step_raw(base + t * stride, auto_reset=auto_reset, epoch_slot=t if auto_reset else None)
         return self.obs, self.reward, self.done
 
-    def capture_rollout(self, actions, goals=None, auto_reset=False):
+    def capture_rollout(self, actions, goals=None, auto_reset=False, obs_t=None, obs_local_t=None, obs_every=None):
         """rollout(actions, goals, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().
-        The rollout resets envs with auto_reset or with goals (the two-level step)."""
+        The rollout resets envs with auto_reset or with goals (the two-level step).  Recording observations (obs_t /
+        obs_every) is not captured: ValueError."""
+        if obs_t is not None or obs_local_t is not None or obs_every is not None:
+            raise ValueError("capture_rollout() does not record observations: call rollout(obs_t=..., obs_every=...)")
         resets = bool(auto_reset) or goals is not None
         return self._capture(actions.shape[0], resets,
                              lambda: self.rollout(actions, goals=goals, auto_reset=auto_reset, device_epoch=resets))

@@ -288,30 +288,45 @@ class LmazeVecEnv(VecEnvBase):
         self.observe()
         return timings
 
-    def rollout(self, actions, auto_reset=True, device_epoch=False, trajectory=False):
+    def rollout(self, actions, auto_reset=True, device_epoch=False, trajectory=False, obs_t=None, obs_every=None):
         """T steps over a device tensor int32[T,N] of actions, one kernel per step, no host
         sync (capture_rollout() records it into a hipGraph for launch-bound batch sizes).
         device_epoch: keep the reset epoch on the device (what capture_rollout uses; bit-identical to the
         host-counted epochs when begin_replay(T) precedes it).  Returns the final (obs, reward, done); trajectory=True adds
         every step's reward float32[T,N] and done bool[T,N].  The whole rollout is ONE launch (shared and per-env
         layouts, any batch size; the envs' state stays in registers across the T steps) (include/lmaze.h
-        lmaze_rollout)."""
+        lmaze_rollout).
+        obs_every=k >= 1 records observations into the caller's obs_t, shaped (T // k, N, G, G) with obs's dtype: slot j
+        is what obs holds after step (j + 1) k - 1 (lmaze_rollout_obs, still one launch; the u8 env: T step launches, each
+        storing its slot or nothing).  obs_every=0 stores the final planes only (obs_t None).  Steps that fill no slot store
+        no planes; the final obs, state, rows and epoch are those of the plain rollout.  Not with device_epoch, nor while
+        the online tuner runs."""
         self._check_rows("rollout()", actions)
         base, stride = actions.data_ptr(), self.num_envs * 4
         T, N = int(actions.shape[0]), self.num_envs
+        k = None
+        if obs_every is not None:
+            if device_epoch or self._tuner is not None:
+                raise ValueError("rollout(obs_every=...) is not available with a device-resident epoch or while the online tuner runs")
+            k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
+        elif obs_t is not None:
+            raise ValueError("obs_t needs obs_every")
         if not device_epoch and self._tuner is None and not self._u8:
             # lmaze_rollout: ONE launch (the envs' state stays in registers across the T steps); bit-identical to T
             # step() calls
             rew_t = torch.empty((T, N), dtype=torch.float32, device=self.device) if trajectory else None
             done_t = torch.empty((T, N), dtype=torch.uint8, device=self.device) if trajectory else None
+            args = (self._pp, self._p_layout, base, T, self._p_ball, self._p_goal if self._is_v3 else None, self._p_step,
+                    self._p_reward, self._p_done, None if self._is_v3 else self._p_gc, self._p_obs,
+                    rew_t.data_ptr() if trajectory else None, done_t.data_ptr() if trajectory else None,
+                    N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base)
             with self._guard():
-                rc = _abi.lib.lmaze_rollout(self._pp, self._p_layout, base, T, self._p_ball,
-                                            self._p_goal if self._is_v3 else None, self._p_step, self._p_reward, self._p_done,
-                                            None if self._is_v3 else self._p_gc, self._p_obs,
-                                            rew_t.data_ptr() if trajectory else None, done_t.data_ptr() if trajectory else None,
-                                            N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base,
-                                            self._stream())
-            _abi.check("lmaze_rollout", rc)
+                if k is None:
+                    rc = _abi.lib.lmaze_rollout(*args, self._stream())
+                else:
+                    slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
+                    rc = _abi.lib.lmaze_rollout_obs(*args, slots, k, self._stream())
+            _abi.check("lmaze_rollout" if k is None else "lmaze_rollout_obs", rc)
             if auto_reset:
                 self._epoch += T
             if trajectory:
@@ -321,7 +336,14 @@ class LmazeVecEnv(VecEnvBase):
             raise ValueError("rollout(trajectory=True) is not available with a device-resident epoch or while the online tuner runs")
         with self._guard():
             for t in range(actions.shape[0]):
-                self._launch_step(base + t * stride, self._p_obs, auto_reset, t if device_epoch else None)
+                dst = self._p_obs
+                if k is not None:
+                    # the u8 env's recording: step t stores its slot, nothing, or -- the last step -- the env's obs
+                    slot = obs_t[(t + 1) // k - 1] if k > 0 and (t + 1) % k == 0 else None
+                    dst = self._p_obs if t == T - 1 else (slot.data_ptr() if slot is not None else None)
+                self._launch_step(base + t * stride, dst, auto_reset, t if device_epoch else None)
+                if k is not None and t == T - 1 and slot is not None:
+                    slot.copy_(self.obs)
         return self.obs, self.reward, self.done
 
     def observe(self, mask_ptr=None):
@@ -378,8 +400,11 @@ class LmazeVecEnv(VecEnvBase):
         _abi.check("lmaze_render_expanded", rc)
         return out
 
-    def capture_rollout(self, actions, auto_reset=False):
-        """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay()."""
+    def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
+        """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
+        observations (obs_t / obs_every) is not captured: ValueError."""
+        if obs_t is not None or obs_every is not None:
+            raise ValueError("capture_rollout() does not record observations: call rollout(obs_t=..., obs_every=...)")
         return self._capture(actions.shape[0], auto_reset,
                              lambda: self.rollout(actions, auto_reset=auto_reset, device_epoch=auto_reset))
 

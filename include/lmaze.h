@@ -241,6 +241,27 @@ int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_
                   int64_t env_base, void* stream);
 
 /*
+ * lmaze_rollout that also RECORDS observations: every k-th step's planes go into the caller's obs_t, and a step that
+ * fills no slot stores no planes at all.  Same arguments as lmaze_rollout, then:
+ *   obs_t      int32[T / obs_every, N, G, G], 16-byte aligned, 64-bit offsets (1M x 11x11 is 484 MB per slot).  Slot j
+ *              holds exactly what obs holds after step (j + 1) * obs_every - 1 of T step calls, fused resets included;
+ *              the last T % obs_every steps are not recorded.
+ *   obs_every  k >= 1; or 0: the final planes only (obs_t must then be NULL).
+ * obs (nullable as in lmaze_rollout) still receives the planes after the last step and nothing before; final state, obs,
+ * reward_t / done_t and the epoch the caller advances are bit-identical to lmaze_rollout.  One launch wherever
+ * lmaze_rollout is one (the kernels' recording forms, e.g. "rollout_shared_kernel<v0, obs_t>"); the T-launch fallback
+ * (T == 1, launch_hint bit 8) gives each step launch its slot, NULL (transition only) or obs.  launch_hint bit 15:
+ * the other store policy for the slots (performance only).
+ * Refused before anything is queued: LMAZE_E_COUNT obs_every < 0, or obs_t given with obs_every == 0; LMAZE_E_NULL
+ * obs_t NULL while T / obs_every > 0; LMAZE_E_ALIGN obs_t not 16-byte aligned; then every refusal of lmaze_rollout,
+ * except that T == 0 or n == 0 (once params are valid) returns 0 with nothing read.
+ */
+int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
+                      float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                      int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes
@@ -474,6 +495,26 @@ int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts
                          int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
                          float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
                          void* stream);
+
+/*
+ * lmaze_foveal_rollout that also RECORDS every k-th step's observations, in one launch.  Same arguments, then:
+ *   obs_t        float[T / obs_every, N, C, 5, 5], 16-byte aligned: slot j = what bufs->obs holds after step
+ *                (j + 1) * obs_every - 1 of the T step calls (fused resets included; an env whose step is skipped -- an
+ *                out-of-range v2/v4 action -- keeps, and records, its previous observation)
+ *   obs_local_t  float[T / obs_every, N, 4, 5, 5], 16-byte aligned, nullable: the same for bufs->obs_local (v5/v6 with
+ *                planner goals; LMAZE_E_VARIANT for the other variants)
+ *   obs_every    k >= 1 (there is no final-planes-only form here)
+ * The running obs / obs_local are still written every step; final state, visit map, obs, obs_local and the rows are
+ * bit-identical to lmaze_foveal_rollout, whose refusals (the plain v5/v6 step included) apply unchanged.  Refused first,
+ * before anything is queued: LMAZE_E_COUNT obs_every < 1; LMAZE_E_NULL obs_t NULL while T / obs_every > 0;
+ * LMAZE_E_ALIGN obs_t or obs_local_t not 16-byte aligned.  LMAZE_E_GRID: v5/v6 at G != 18, v1 at G != 14 (those
+ * recording forms would spill at the rollouts' 4 / 6 waves per SIMD; record through T step calls instead).
+ */
+int lmaze_foveal_rollout_obs(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
+                             const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
+                             int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                             float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                             float* obs_t, float* obs_local_t, int32_t obs_every, void* stream);
 
 /* As lmaze_describe_foveal_step, for lmaze_foveal_rollout (two_level != 0: v5/v6 with planner goals, the only v5/v6
  * form); the text also names T. */
