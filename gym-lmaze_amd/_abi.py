@@ -33,7 +33,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_foveal_visit_bytes", "lmaze_foveal_materialise_visit", "lmaze_foveal_load_visit",
            "lmaze_describe_step", "lmaze_describe_foveal_step", "lmaze_rollout",
            "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout",
-           "lmaze_rollout_obs", "lmaze_foveal_rollout_obs")
+           "lmaze_rollout_obs", "lmaze_foveal_rollout_obs", "lmaze_rollout_u8", "lmaze_rollout_obs_u8",
+           "lmaze_describe_rollout")
 
 
 class LmazeParams(C.Structure):
@@ -155,6 +156,12 @@ def _load():
     lib.lmaze_rollout_obs.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
     lib.lmaze_foveal_rollout_obs.restype = C.c_int
     lib.lmaze_foveal_rollout_obs.argtypes = [FP, vp, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.lmaze_rollout_u8.restype = C.c_int
+    lib.lmaze_rollout_u8.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp]
+    lib.lmaze_rollout_obs_u8.restype = C.c_int
+    lib.lmaze_rollout_obs_u8.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
+    lib.lmaze_describe_rollout.restype = C.c_int
+    lib.lmaze_describe_rollout.argtypes = [P, i64, i32, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_describe_foveal_rollout.restype = C.c_int
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
@@ -186,6 +193,17 @@ def describe_step(params, n, auto_reset=False, with_obs=True):
     buf = C.create_string_buffer(256)
     check("lmaze_describe_step", lib.lmaze_describe_step(C.byref(params), int(n), 1 if auto_reset else 0,
                                                          2 if with_obs == "u8" else (1 if with_obs else 0), buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+def describe_rollout(params, n, T, auto_reset=False, with_obs=True, obs_every=None):
+    """The kernel / grid / envs per workgroup a grid rollout would queue for n envs and T steps (lmaze_describe_rollout):
+    with_obs True / False / "u8" picks lmaze_rollout with obs, without obs, or lmaze_rollout_u8; obs_every (None: the
+    plain rollout) the recording entry point with that k."""
+    buf = C.create_string_buffer(256)
+    check("lmaze_describe_rollout", lib.lmaze_describe_rollout(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
+                                                               2 if with_obs == "u8" else (1 if with_obs else 0),
+                                                               -1 if obs_every is None else int(obs_every), buf, 256))
     return buf.value.decode("ascii", "replace")
 
 

@@ -175,8 +175,8 @@ class VecEnvBase(object):
         nothing and never synchronise, so they are capturable as they are.  With resets in the rollout the epoch is a
         device word the launches hand on to each other (epoch_in_dev / epoch_out_dev), so every replay draws fresh
         placements, exactly those the same steps launched eagerly would draw.  What is recorded is what rollout()
-        launches: LmazeVecEnv without auto_reset records its one-launch lmaze_rollout, with auto_reset T step
-        launches; LmazeFovealVecEnv always records T step launches."""
+        launches: LmazeVecEnv without auto_reset records its one-launch lmaze_rollout (u8: lmaze_rollout_u8), with
+        auto_reset T step launches; LmazeFovealVecEnv always records T step launches."""
         if self._tuner is not None:             # still cycling through candidates: a graph bakes the default policy
             self.params.launch_hint = 0
         side = torch.cuda.Stream(device=self.device)

@@ -73,6 +73,33 @@ static int format_launch(const LaunchInfo& i, char* text, int32_t len) {
     return 0;
 }
 
+// lmaze_rollout_u8 and lmaze_rollout_obs_u8 (rec != null) after the recording request's own checks: lmaze_step_u8's
+// refusals, T == 0 or n == 0 answered before any pointer is looked at
+static int rollout_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
+                      float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                      int64_t env_base, const RolloutRec8* rec, void* stream) {
+    int rc = check_params(params, n);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
+    if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
+    if (params->grid < 4) return LMAZE_E_GRID;        // a 16-byte store must not span more than two envs
+    if (T < 0) return LMAZE_E_COUNT;
+    if (T == 0 || n == 0) return 0;                   // nothing to do, nothing read
+    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
+    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs8, 16)) return LMAZE_E_ALIGN;
+    StepArgs a = make_args(params, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count,
+                           nullptr, n);
+    a.obs8 = obs8;
+    a.auto_reset = auto_reset ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
+    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
+    return (int)launch_rollout_u8(params->variant, a, actions, T, reward_t, done_t, (hipStream_t)stream, rec);
+}
+
 extern "C" {
 
 int lmaze_abi_version(void) { return LMAZE_ABI_VERSION; }
@@ -268,6 +295,60 @@ int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const in
     a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
     const RolloutRec rec{obs_every > 0 && T / obs_every > 0 ? obs_t : nullptr, obs_every};
     return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, &rec);
+}
+
+int lmaze_rollout_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                     int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
+                     float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                     int64_t env_base, void* stream) {
+    return rollout_u8(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, reward_t, done_t,
+                      n, auto_reset, seed, epoch, env_base, nullptr, stream);
+}
+
+int lmaze_rollout_obs_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                         int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
+                         float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                         int64_t env_base, uint8_t* obs_t8, int32_t obs_every, void* stream) {
+    // the recording request first, as lmaze_rollout_obs: its refusals need nothing else
+    if (obs_every < 0 || (obs_every == 0 && obs_t8)) return LMAZE_E_COUNT;
+    if (obs_every > 0 && T / obs_every > 0 && !obs_t8) return LMAZE_E_NULL;
+    if (misaligned(obs_t8, 16)) return LMAZE_E_ALIGN;                  // slot 0; the later slots start wherever N G G puts them
+    const RolloutRec8 rec{obs_every > 0 && T / obs_every > 0 ? obs_t8 : nullptr, obs_every};
+    return rollout_u8(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, reward_t, done_t,
+                      n, auto_reset, seed, epoch, env_base, &rec, stream);
+}
+
+int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
+                           char* text_host, int32_t len) {
+    int rc = check_params(params, n);
+    if (rc) return rc;
+    if (params->variant != LMAZE_VARIANT_V0 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
+    if (T < 0) return LMAZE_E_COUNT;
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    if (n == 0 || T == 0) return 0;
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    // nothing is dereferenced: the launcher fills `info` where it would have queued the rollout (fabricated, aligned
+    // addresses stand for the buffers whose presence decides)
+    StepArgs a = make_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           with_obs == 1 ? reinterpret_cast<int32_t*>(16) : nullptr, n);
+    a.auto_reset = auto_reset ? 1 : 0;
+    a.info = &info;
+    const bool recording = obs_every >= 0, slots = obs_every > 0 && T / obs_every > 0;
+    if (with_obs == 2) {             // the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8)
+        if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
+        if (params->grid < 4) return LMAZE_E_GRID;
+        a.obs8 = reinterpret_cast<uint8_t*>(16);
+        const RolloutRec8 rec{slots ? reinterpret_cast<uint8_t*>(32) : nullptr, obs_every};
+        rc = (int)launch_rollout_u8(params->variant, a, nullptr, T, nullptr, nullptr, nullptr, recording ? &rec : nullptr);
+    } else {
+        const RolloutRec rec{slots ? reinterpret_cast<int32_t*>(32) : nullptr, obs_every};
+        rc = (int)launch_rollout(params->variant, a, params->layout_mode, nullptr, T, nullptr, nullptr, nullptr,
+                                 recording ? &rec : nullptr);
+    }
+    if (rc) return rc;
+    return format_launch(info, text_host, len);
 }
 
 int lmaze_step_v3_autoreset(const LmazeParams* params, const uint8_t* layout, const int32_t* action,

@@ -113,6 +113,14 @@ struct RolloutRec {
 };
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec* rec = nullptr);
+// The same for the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8; shared layouts, G >= 4): a.obs8 instead of
+// a.obs, uint8 slots that may start at any byte past slot 0.  A null RolloutRec8* is the plain rollout.
+struct RolloutRec8 {
+    uint8_t* obs_t8;
+    int32_t every;
+};
+hipError_t launch_rollout_u8(int variant, const StepArgs& a, const int32_t* actions, int32_t T, float* reward_t, uint8_t* done_t,
+                             hipStream_t s, const RolloutRec8* rec = nullptr);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

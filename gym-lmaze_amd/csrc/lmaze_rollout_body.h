@@ -2,7 +2,8 @@
 // form (RolloutArgs, REC false) and the recording form (RolloutObsArgs, REC true) of its kernel: through a __device__
 // function the plain forms compiled to other register allocations, included they keep their code.  In scope: `a`
 // (StepArgs), `ro`, the compile-time VARIANT, REC and, for the wave-autonomous body, EPW.  LMAZE_ROLLOUT_BODY selects
-// the body: 1 rollout_shared_wave8_kernel, 2 rollout_shared_kernel, 3 rollout_perenv_kernel.  Not a header of its own.
+// the body: 1 rollout_shared_wave8_kernel, 2 rollout_shared_kernel, 3 rollout_perenv_kernel, 4 rollout_shared_u8_kernel
+// (whose recording form takes RolloutObs8Args).  Not a header of its own.
 #ifndef LMAZE_ROLLOUT_BODY
 #error "lmaze_rollout_body.h is the body of the rollout kernels: it is included only inside them, in lmaze_step.hip"
 #endif
@@ -199,6 +200,78 @@
         rollout_render<VARIANT>(obs, nb * CELLS, CELLS, ballflat, goalflat,
                                 [&](int le, int c) { return cell_bits<VARIANT>(lays[le * CELLS + c]); });
         __syncthreads();
+    }
+    rollout_store<VARIANT>(a, ro, e, live, s, hits);
+#elif LMAZE_ROLLOUT_BODY == 4
+    // body 2 with the narrow planes of step_shared_u8_kernel: the same set-up in LDS (layout, byte-shifted pattern copies,
+    // spawn list), the same transition, and each step's render through rollout_render_u8
+    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
+    const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
+    const int PW = (2 * CELLS + 16 + 3) >> 2;                                 // dwords of one shifted copy, as step_shared_u8_kernel
+    extern __shared__ int4 lds4[];
+    uint32_t* patw = reinterpret_cast<uint32_t*>(lds4);                       // [4][PW] copy s = the doubled pattern from byte s
+    int* ballflat = reinterpret_cast<int*>(patw + 4 * PW);                    // [EPB + 1]
+    int* goalflat = ballflat + EPB + 1;                                       // [EPB + 1]
+    uint16_t* spawn = reinterpret_cast<uint16_t*>(goalflat + EPB + 1);        // [CELLS] accepted spawn cells, row-major
+    uint8_t* lay = reinterpret_cast<uint8_t*>(spawn + ((CELLS + 1) & ~1));    // [CELLS]
+    __shared__ int spawn_count_s;
+
+    const int tid = threadIdx.x;
+    const int64_t blockbase = (int64_t)blockIdx.x * EPB;
+    const int nb = (int)min((int64_t)EPB, a.n - blockbase);
+    const bool autoreset = a.auto_reset != 0, live = tid < nb;
+    const int64_t e = blockbase + tid;
+    EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
+    int hits = 0, act_next = s.act;
+    for (int i = tid; i < CELLS; i += LMAZE_BLOCK) lay[i] = a.layout[i];
+    for (int i = tid; i <= EPB; i += LMAZE_BLOCK) { ballflat[i] = -64; goalflat[i] = -64; }
+    __syncthreads();
+    for (int i = tid; i < 4 * PW; i += LMAZE_BLOCK) {                         // as step_shared_u8_kernel's set-up
+        const int sc = i / PW, k = (i - sc * PW) << 2;
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int c = k + sc + j;
+            c -= c >= CELLS ? CELLS : 0;
+            c -= c >= CELLS ? CELLS : 0;
+            c = min(c, CELLS - 1);
+            w |= (uint32_t)cell_bits<VARIANT>(lay[c]) << (8 * j);
+        }
+        patw[i] = w;
+    }
+    if (autoreset && tid < 64) {
+        const int cnt = wave_build_spawn_list<VARIANT>(lay, G, CELLS, spawn, tid);
+        if (tid == 0) spawn_count_s = cnt;
+    }
+    __syncthreads();
+    const int spawn_count = autoreset ? spawn_count_s : 0;
+
+    // EPB is a multiple of 16: the workgroup's range of obs8 starts on a 16-byte boundary (the ABI checks obs8's base)
+    uint8_t* obs = a.obs8 ? a.obs8 + (size_t)blockbase * CELLS : nullptr;
+    const int R = nb * CELLS;
+    for (int t = 0; t < ro.T; ++t) {
+        if (live) {
+            s.act = act_next;
+            if (t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];       // next step's row, in flight over this step
+            if (autoreset && s.done) {                                                // as env_phase1
+                int bc, gc;
+                place_from_list<VARIANT>(spawn, spawn_count, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
+                env_reset<VARIANT>(bc, gc, G, s);
+            }
+            hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
+            rollout_record(ro, a.n, t, e, s);
+            ballflat[tid] = ball_cell_of(s.b, G);
+            if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
+        }
+        // the slot this step fills (recording form) and the caller's planes: every step in the plain form, as T step
+        // launches would write them; after the last step only in the recording form
+        uint8_t* slot = rollout_slot8(ro, a.n, blockbase, CELLS, t);
+        uint8_t* last = (!REC || t == ro.T - 1) ? obs : nullptr;
+        if (slot == nullptr && last == nullptr) continue;                             // uniform: nothing stored
+        __syncthreads();
+        if (slot) rollout_render_u8<VARIANT>(slot, R, CELLS, nb, patw, PW, ballflat, goalflat);
+        if (last) rollout_render_u8<VARIANT>(last, R, CELLS, nb, patw, PW, ballflat, goalflat);
+        __syncthreads();                                                              // ballflat / goalflat are rewritten by the next step
     }
     rollout_store<VARIANT>(a, ro, e, live, s, hits);
 #endif

@@ -1041,6 +1041,92 @@ __global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))
 }
 
 // ------------------------------------------------------------------------------------
+// T steps of a shared-layout batch with the NARROW planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8): rollout_shared_kernel's
+// workgroup -- EPB envs for all T steps, one lane per env with its state in registers -- set up as step_shared_u8_kernel
+// (layout, byte-shifted pattern copies, spawn list in LDS once) and rendering as it does, 16 cells per 16-byte store.
+// ------------------------------------------------------------------------------------
+
+// The recording form of the u8 rollout: RolloutObsArgs with uint8 slots (a type of its own, so that the int32 recording
+// kernels keep theirs).  Slot j = obs_t8 + j N G G bytes: past slot 0 it starts wherever N G G puts it.
+struct RolloutObs8Args : RolloutArgs {
+    uint8_t* obs_t8;          // [T / every, N, G, G] or null (every == 0: final planes only)
+    int32_t every;            // k >= 1, or 0
+};
+
+__device__ __forceinline__ uint8_t* rollout_slot8(const RolloutObs8Args& ro, int64_t n, int64_t base, int cells, int t) {
+    if (ro.obs_t8 == nullptr || ro.every <= 0 || (t + 1) % ro.every != 0) return nullptr;
+    return ro.obs_t8 + ((size_t)((t + 1) / ro.every - 1) * n + base) * cells;
+}
+__device__ __forceinline__ uint8_t* rollout_slot8(const RolloutArgs&, int64_t, int64_t, int, int) { return nullptr; }
+
+// One step's narrow planes of a u8 rollout workgroup: R = nb G*G bytes at dst, byte f = cell f % CELLS of env f / CELLS.
+// dst is 16-byte aligned for obs8 and slot 0, but slot j > 0 starts j N G G bytes past a 16-byte boundary (N = 777 at
+// 11x11: 5 bytes past one), so no store may assume it.  The range is cut at absolute 16-byte boundaries:
+//   head  bytes [0, h) up to the first boundary at or after dst (h < 16): byte stores
+//   body  the whole aligned granules inside the range: one 16-byte store of 16 cells each, as step_shared_u8_kernel's
+//   tail  the bytes after the last whole granule (< 16): byte stores
+// Why nothing is written twice or outside the range: every 16-byte store covers one aligned granule that lies wholly
+// inside [dst, dst + R); a granule that the range shares with a neighbour -- the next workgroup's range or the next slot,
+// or what lies before and after obs_t8 -- is only ever written here by byte stores to this range's own bytes, and the
+// neighbour writes its own bytes of it the same way.  A byte store is a byte-masked write, not a read-modify-write, so
+// the two sides of a shared granule never overwrite each other, whatever order they land in.
+template <int VARIANT>
+__device__ __forceinline__ void rollout_render_u8(uint8_t* dst, int R, int CELLS, int nb, const uint32_t* patw, int PW,
+                                                  const int* ballflat, const int* goalflat) {
+    constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
+    const int tid = threadIdx.x;
+    const int h = min((int)((16u - ((unsigned)(uintptr_t)dst & 15u)) & 15u), R);
+    const int nq = (R - h) >> 4;
+    uint4* dst4 = reinterpret_cast<uint4*>(dst + h);
+    for (int q = tid; q < nq; q += LMAZE_BLOCK) {
+        const int f0 = h + (q << 4);
+        const int le = f0 / CELLS, c = f0 - le * CELLS;                 // first cell of the store; G >= 4: at most two envs
+        const int sft = c & 3;
+        const uint32_t* src = patw + sft * PW + ((c - sft) >> 2);
+        uint32_t w[4] = {src[0], src[1], src[2], src[3]};
+        const int b0 = ballflat[le] - c;
+        if ((unsigned)b0 < 16u) w[b0 >> 2] |= (uint32_t)LMAZE_OBS_BALL << ((b0 & 3) << 3);
+        if (V3) {
+            const int g0 = goalflat[le] - c;
+            if ((unsigned)g0 < 16u) w[g0 >> 2] |= (uint32_t)LMAZE_OBS_GOAL << ((g0 & 3) << 3);
+        }
+        if (c > CELLS - 16 && le + 1 < nb) {                             // the store runs into env le + 1 at byte CELLS - c
+            const int b1 = CELLS - c + ballflat[le + 1];
+            if ((unsigned)b1 < 16u) w[b1 >> 2] |= (uint32_t)LMAZE_OBS_BALL << ((b1 & 3) << 3);
+            if (V3 && goalflat[le + 1] >= 0) {                           // < 0: no goal on the grid
+                const int g1 = CELLS - c + goalflat[le + 1];
+                if ((unsigned)g1 < 16u) w[g1 >> 2] |= (uint32_t)LMAZE_OBS_GOAL << ((g1 & 3) << 3);
+            }
+        }
+        dst4[q] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    const int t0 = h + (nq << 4);                                        // first byte of the tail
+    if (tid < h + (R - t0)) {                                            // head and tail: at most 30 bytes
+        const int f = tid < h ? tid : t0 + (tid - h);
+        const int le = f / CELLS, c = f - le * CELLS;
+        const uint8_t* patb = reinterpret_cast<const uint8_t*>(patw);   // copy 0: pattern byte c
+        dst[f] = (uint8_t)(patb[c] | (ballflat[le] == c ? LMAZE_OBS_BALL : 0) | (V3 && goalflat[le] == c ? LMAZE_OBS_GOAL : 0));
+    }
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const StepArgs a, const RolloutArgs ro) {
+    constexpr bool REC = false;
+#define LMAZE_ROLLOUT_BODY 4
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+// the recording form (lmaze_rollout_obs_u8)
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const StepArgs a, const RolloutObs8Args ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 4
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+// ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
 
@@ -1549,6 +1635,64 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         if (done_t && (rc = hipMemcpyAsync(done_t + (size_t)t * a0.n, a0.done, (size_t)a0.n, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
     }
     return hipSuccess;
+}
+
+// LDS of rollout_shared_u8_kernel: the four shifted pattern copies, ballflat / goalflat, the spawn list and the layout
+static size_t rollout_u8_lds_bytes(int G, int epb) {
+    const int cells = G * G, pw = (2 * cells + 16 + 3) >> 2;
+    return ((size_t)4 * pw * 4 + 2 * (size_t)(epb + 1) * 4 + (size_t)((cells + 1) & ~1) * 2 + (size_t)cells + 15) & ~(size_t)15;
+}
+
+// T steps with the narrow planes: ONE launch of rollout_shared_u8_kernel (plain or recording form) for any T >= 1 and any
+// batch size.  launch_hint bits 12-14 = k > 0 ask for 4 << (k - 1) envs per workgroup, as for rollout_shared_kernel, rounded
+// up to 16 (a workgroup's byte range of obs8 must start on a 16-byte boundary) and down to what fits 64 KiB of LDS;
+// performance only.  Bit 8 keeps its one meaning of the u8 step (streaming stores there) and is not read here.
+// Envs per workgroup, from tools/bench_rollout_u8.py --sweep (v0, fused reset, T = 16, us per step for 16 / 32 / 64 / 128 /
+// 256 envs; plain rollout, then every step recorded; profiles/rollout_u8/bench_rollout_u8_sweep.json):
+//   65 536 x 8x8     3.41 / 2.54 / 1.90 / 2.08 / 2.31      4.70 / 3.33 / 2.46 / 2.49 / 2.71
+//   65 536 x 11x11   3.94 / 2.93 / 2.46 / 2.79 / 3.70      5.18 / 3.63 / 3.00 / 3.24 / 4.04
+//   16 384 x 12x12   1.66 / 1.77 / 1.95 / 2.28 / 2.98      2.16 / 2.20 / 2.27 / 2.57 / 3.34
+//   262 144 x 11x11  11.5 / 7.08 / 5.70 / 7.07 / 7.07      17.3 / 12.1 / 9.50 / 8.88 / 7.78
+//   1M x 11x11       42.8 / 25.7 / 19.5 / 24.6 / 25.5      73.8 / 51.6 / 39.3 / 29.4 / 29.0
+// i.e. 64 envs from 65 536 envs on and 16 below; the slots of a recording beyond the Infinity Cache (262 144 x 11x11 x 16
+// slots = 507 MB) want the widest workgroups.  The int32 rule of fitting the resident workgroups' planes into L2 does not
+// carry over: 1M x 11x11 with 16 envs is 2.2x slower than with 64.
+hipError_t launch_rollout_u8(int variant, const StepArgs& a0, const int32_t* actions, int32_t T, float* reward_t, uint8_t* done_t,
+                             hipStream_t s, const RolloutRec8* rec) {
+    if (T <= 0 || a0.n == 0) return hipSuccess;
+    StepArgs a = a0;
+    int epb = a0.n >= 65536 ? 64 : 16;
+    if (rec && rec->obs_t8 && a0.n >= 262144) epb = 256;
+    if ((a0.launch_hint >> 12) & 7) epb = 4 << (((a0.launch_hint >> 12) & 7) - 1);
+    if (epb < 16) epb = 16;
+    if (epb > LMAZE_BLOCK) epb = LMAZE_BLOCK;
+    while (epb > 16 && rollout_u8_lds_bytes(a0.grid, epb) > ((size_t)64 << 10)) epb >>= 1;
+    a.envs_per_block = epb;
+    const size_t lds = rollout_u8_lds_bytes(a0.grid, epb);
+    const int64_t blocks = (a0.n + epb - 1) / epb;
+    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
+    if (a0.info) {
+        char name[96];
+        if (rec) snprintf(name, sizeof(name), "rollout_shared_u8_kernel<v%d, obs_t> T=%d every=%d", variant, T, rec->every);
+        else snprintf(name, sizeof(name), "rollout_shared_u8_kernel<v%d> T=%d", variant, T);
+        describe_launch(a0.info, name, epb, 0, 1, false, blocks, LMAZE_BLOCK, lds);
+        return hipSuccess;
+    }
+    RolloutArgs ro{actions, reward_t, done_t, T};
+    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
+    const bool v3 = variant == LMAZE_VARIANT_V3;
+    if (rec) {
+        RolloutObs8Args rr;
+        static_cast<RolloutArgs&>(rr) = ro;
+        rr.obs_t8 = rec->obs_t8;
+        rr.every = rec->every;
+        using R = void (*)(const StepArgs, const RolloutObs8Args);
+        hipLaunchKernelGGL(v3 ? (R)rollout_shared_u8_kernel<LMAZE_VARIANT_V3> : (R)rollout_shared_u8_kernel<LMAZE_VARIANT_V0>, grid, block, lds, s, a, rr);
+    } else {
+        using P = void (*)(const StepArgs, const RolloutArgs);
+        hipLaunchKernelGGL(v3 ? (P)rollout_shared_u8_kernel<LMAZE_VARIANT_V3> : (P)rollout_shared_u8_kernel<LMAZE_VARIANT_V0>, grid, block, lds, s, a, ro);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s) {

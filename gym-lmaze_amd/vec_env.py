@@ -43,7 +43,7 @@ class LmazeVecEnv(VecEnvBase):
                       one (keys the reset draws; see include/lmaze.h lmaze_reset)
     obs_dtype         "int32" (default; the compact planes BASELINE's metric is quoted on) or "u8": the same LMAZE_OBS_* bit
                       mask in one byte per cell, uint8[N,G,G], 37 + G*G bytes per env-step instead of 37 + 4 G*G (shared
-                      layouts, G >= 4; lmaze_step_u8 -- no launch-policy knobs, no one-launch rollout)
+                      layouts, G >= 4; lmaze_step_u8 -- no launch-policy knobs; rollout() is one lmaze_rollout_u8 launch)
     online_autotune   OPT-IN (default False: the library's default launch policy, nothing timed).  True, on
                       large shared-layout batches only (the streaming regime): time the launch policies on
                       the caller's own first ~200 steps, in the caller's own loop -- after 100 untimed steps they cycle
@@ -295,12 +295,12 @@ class LmazeVecEnv(VecEnvBase):
         host-counted epochs when begin_replay(T) precedes it).  Returns the final (obs, reward, done); trajectory=True adds
         every step's reward float32[T,N] and done bool[T,N].  The whole rollout is ONE launch (shared and per-env
         layouts, any batch size; the envs' state stays in registers across the T steps) (include/lmaze.h
-        lmaze_rollout).
+        lmaze_rollout; the u8 env: lmaze_rollout_u8).  With device_epoch it is T step launches.
         obs_every=k >= 1 records observations into the caller's obs_t, shaped (T // k, N, G, G) with obs's dtype: slot j
-        is what obs holds after step (j + 1) k - 1 (lmaze_rollout_obs, still one launch; the u8 env: T step launches, each
-        storing its slot or nothing).  obs_every=0 stores the final planes only (obs_t None).  Steps that fill no slot store
-        no planes; the final obs, state, rows and epoch are those of the plain rollout.  Not with device_epoch, nor while
-        the online tuner runs."""
+        is what obs holds after step (j + 1) k - 1 (lmaze_rollout_obs / lmaze_rollout_obs_u8, still one launch; the u8
+        env's slots may have any N).  obs_every=0 stores the final planes only (obs_t None).  Steps that fill no slot
+        store no planes; the final obs, state, rows and epoch are those of the plain rollout.  Not with device_epoch, nor
+        while the online tuner runs."""
         self._check_rows("rollout()", actions)
         base, stride = actions.data_ptr(), self.num_envs * 4
         T, N = int(actions.shape[0]), self.num_envs
@@ -311,22 +311,23 @@ class LmazeVecEnv(VecEnvBase):
             k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
         elif obs_t is not None:
             raise ValueError("obs_t needs obs_every")
-        if not device_epoch and self._tuner is None and not self._u8:
-            # lmaze_rollout: ONE launch (the envs' state stays in registers across the T steps); bit-identical to T
-            # step() calls
+        if not device_epoch and self._tuner is None:
+            # lmaze_rollout (the u8 env: lmaze_rollout_u8): ONE launch (the envs' state stays in registers across the T
+            # steps); bit-identical to T step() calls
             rew_t = torch.empty((T, N), dtype=torch.float32, device=self.device) if trajectory else None
             done_t = torch.empty((T, N), dtype=torch.uint8, device=self.device) if trajectory else None
             args = (self._pp, self._p_layout, base, T, self._p_ball, self._p_goal if self._is_v3 else None, self._p_step,
                     self._p_reward, self._p_done, None if self._is_v3 else self._p_gc, self._p_obs,
                     rew_t.data_ptr() if trajectory else None, done_t.data_ptr() if trajectory else None,
                     N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base)
+            name = ("lmaze_rollout" if k is None else "lmaze_rollout_obs") + ("_u8" if self._u8 else "")
             with self._guard():
                 if k is None:
-                    rc = _abi.lib.lmaze_rollout(*args, self._stream())
+                    rc = getattr(_abi.lib, name)(*args, self._stream())
                 else:
                     slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
-                    rc = _abi.lib.lmaze_rollout_obs(*args, slots, k, self._stream())
-            _abi.check("lmaze_rollout" if k is None else "lmaze_rollout_obs", rc)
+                    rc = getattr(_abi.lib, name)(*args, slots, k, self._stream())
+            _abi.check(name, rc)
             if auto_reset:
                 self._epoch += T
             if trajectory:
@@ -336,14 +337,7 @@ class LmazeVecEnv(VecEnvBase):
             raise ValueError("rollout(trajectory=True) is not available with a device-resident epoch or while the online tuner runs")
         with self._guard():
             for t in range(actions.shape[0]):
-                dst = self._p_obs
-                if k is not None:
-                    # the u8 env's recording: step t stores its slot, nothing, or -- the last step -- the env's obs
-                    slot = obs_t[(t + 1) // k - 1] if k > 0 and (t + 1) % k == 0 else None
-                    dst = self._p_obs if t == T - 1 else (slot.data_ptr() if slot is not None else None)
-                self._launch_step(base + t * stride, dst, auto_reset, t if device_epoch else None)
-                if k is not None and t == T - 1 and slot is not None:
-                    slot.copy_(self.obs)
+                self._launch_step(base + t * stride, self._p_obs, auto_reset, t if device_epoch else None)
         return self.obs, self.reward, self.done
 
     def observe(self, mask_ptr=None):

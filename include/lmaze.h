@@ -262,6 +262,48 @@ int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const in
                       int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream);
 
 /*
+ * lmaze_rollout with the NARROW planes of lmaze_step_u8: the arguments of lmaze_rollout with uint8_t* obs8 (uint8[N,G,G],
+ * 16-byte aligned, nullable) in place of int32_t* obs.  Replaces T calls of lmaze_step_u8 (auto_reset != 0: its fused
+ * reset, step t drawing with epoch + t) with bit-identical state, obs8 and per-step reward_t / done_t rows.  ONE launch
+ * of rollout_shared_u8_kernel for any T >= 1 and any batch size: a workgroup owns 16-256 envs for the whole rollout, the
+ * layout, its byte-shifted plane patterns and the spawn list in LDS once, and rewrites obs8 every step as T step
+ * launches would.  params->launch_hint bits 12-14 = k > 0: 4 << (k - 1) envs per workgroup (rounded up to 16, down to
+ * what fits LDS) instead of the size the library picks; performance only.  The caller advances its epoch by T.
+ * Refused before anything is queued: lmaze_step_u8's refusals (LMAZE_E_LAYOUT per-env layouts, LMAZE_E_GRID G < 4,
+ * LMAZE_E_ALIGN obs8 not 16-byte aligned, ...) and LMAZE_E_COUNT T < 0; T == 0 or n == 0 (once params are valid)
+ * returns 0 with nothing read.
+ */
+int lmaze_rollout_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                     int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
+                     float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                     int64_t env_base, void* stream);
+
+/*
+ * lmaze_rollout_obs for the narrow planes: replaces the T lmaze_step_u8 calls that recorded a u8 env's observations
+ * (each writing its slot or nothing), in one launch.  Same arguments and obs_every semantics as lmaze_rollout_obs, with
+ *   obs_t8     uint8[T / obs_every, N, G, G]; slot 0 16-byte aligned, slot j starts j N G G bytes further, at any byte
+ *              offset (N = 777 at 11x11: 5 past a 16-byte boundary); no byte outside the slots is written.
+ * obs8 receives the planes after the last step and nothing before.  Refused before anything is queued: LMAZE_E_COUNT
+ * obs_every < 0, or obs_t8 given with obs_every == 0; LMAZE_E_NULL obs_t8 NULL while T / obs_every > 0; LMAZE_E_ALIGN
+ * obs_t8 not 16-byte aligned; then every refusal of lmaze_rollout_u8, with T == 0 or n == 0 returning 0.
+ */
+int lmaze_rollout_obs_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                         int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
+                         float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                         int64_t env_base, uint8_t* obs_t8, int32_t obs_every, void* stream);
+
+/*
+ * As lmaze_describe_step, for the grid rollouts: which kernel, grid and envs per workgroup lmaze_rollout (with_obs 0:
+ * obs NULL, 1: int32 obs) or lmaze_rollout_u8 (with_obs 2) would queue for n envs and T steps -- obs_every < 0 -- or
+ * lmaze_rollout_obs / lmaze_rollout_obs_u8 with that obs_every (obs_t given when T / obs_every > 0), e.g.
+ * "rollout_shared_kernel<v0> T=16 grid=1024 block=256 ...", "rollout_shared_u8_kernel<v3, obs_t> T=16 every=3 ...", or
+ * the step kernel of the T-launch fallback.  Nothing is queued or dereferenced; no reference counterpart.  T == 0 or
+ * n == 0: an empty line.
+ */
+int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                           int32_t obs_every, char* text_host, int32_t len);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes
