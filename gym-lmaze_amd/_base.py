@@ -124,6 +124,20 @@ class VecEnvBase(object):
             raise ValueError("%s must be contiguous, on %s and 16-byte aligned" % (name, self.device))
         return k
 
+    def _traj_rows(self, T, streams=1):
+        """A rollout's trajectory rows: float32[T,N] reward and uint8[T,N] done for each of `streams` streams (the second:
+        foveal_reward / foveal_done)."""
+        return [torch.empty((int(T), self.num_envs), dtype=dt, device=self.device)
+                for _ in range(streams) for dt in (torch.float32, torch.uint8)]
+
+    def _rollout_result(self, rows):
+        """What rollout() returns: the final (obs, reward, done) and, with trajectory rows, each stream's reward row and
+        done row (as bool)."""
+        out = (self.obs, self.reward, self.done)
+        for i in range(0, len(rows or ()), 2):
+            out += (rows[i], rows[i + 1].view(torch.bool))
+        return out
+
     def host_state(self, raw=None):
         """Every per-env scalar on the host: numpy views of ONE device->host copy of the state block.  raw: bytes of
         the block already on the host (uint8 array the size of `_state`), parsed instead of copying again."""

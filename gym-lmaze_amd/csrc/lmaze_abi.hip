@@ -73,31 +73,54 @@ static int format_launch(const LaunchInfo& i, char* text, int32_t len) {
     return 0;
 }
 
-// lmaze_rollout_u8 and lmaze_rollout_obs_u8 (rec != null) after the recording request's own checks: lmaze_step_u8's
-// refusals, T == 0 or n == 0 answered before any pointer is looked at
-static int rollout_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
-                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
-                      float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
-                      int64_t env_base, const RolloutRec8* rec, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-    if (params->grid < 4) return LMAZE_E_GRID;        // a 16-byte store must not span more than two envs
-    if (T < 0) return LMAZE_E_COUNT;
-    if (T == 0 || n == 0) return 0;                   // nothing to do, nothing read
-    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs8, 16)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count,
-                           nullptr, n);
-    a.obs8 = obs8;
+// The recording request of lmaze_rollout_obs / lmaze_rollout_obs_u8: refusals that need nothing else
+static int check_recording(int32_t T, const void* slots, int32_t every) {
+    if (every < 0 || (every == 0 && slots)) return LMAZE_E_COUNT;
+    if (every > 0 && T / every > 0 && !slots) return LMAZE_E_NULL;
+    if (misaligned(slots, 16)) return LMAZE_E_ALIGN;                 // u8: slot 0; the later slots start wherever N G G puts them
+    return 0;
+}
+
+// ... and the request the launcher gets: the slots only where T / every > 0 of them are filled
+static RolloutRec recording(int32_t T, void* slots, int32_t every) {
+    return RolloutRec{every > 0 && T / every > 0 ? slots : nullptr, every};
+}
+
+// The StepArgs of a grid rollout: obs the int32 planes, or with u8 the narrow ones (a.obs8)
+static StepArgs rollout_args(const LmazeParams* p, const uint8_t* layout, const int32_t* actions, int32_t* ball_xy, int32_t* goal_xy,
+                             int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8, int64_t n,
+                             int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base) {
+    const bool v3 = p->variant == LMAZE_VARIANT_V3;
+    StepArgs a = make_args(p, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count,
+                           u8 ? nullptr : static_cast<int32_t*>(obs), n);
+    a.obs8 = u8 ? static_cast<uint8_t*>(obs) : nullptr;
     a.auto_reset = auto_reset ? 1 : 0;
     a.seed = seed;
     a.epoch = epoch;
     a.env_base = env_base;
     a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
-    return (int)launch_rollout_u8(params->variant, a, actions, T, reward_t, done_t, (hipStream_t)stream, rec);
+    return a;
+}
+
+// lmaze_rollout and its three siblings after the recording request's own checks: T == 0 or n == 0 answered once the
+// params are valid, before any pointer is looked at; u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only
+static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+                        int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8,
+                        float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                        int64_t env_base, const RolloutRec* rec, void* stream) {
+    int rc = check_params(params, n);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
+    if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
+    if (u8 && params->grid < 4) return LMAZE_E_GRID;       // a 16-byte store must not span more than two envs
+    if (T < 0) return LMAZE_E_COUNT;
+    if (T == 0 || n == 0) return 0;                        // nothing to do, nothing read
+    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
+    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16))) return LMAZE_E_ALIGN;
+    const StepArgs a = rollout_args(params, layout, actions, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n,
+                                    auto_reset, seed, epoch, env_base);
+    return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
 }
 
 extern "C" {
@@ -255,67 +278,36 @@ int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_
                   int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
                   float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                   int64_t env_base, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (T < 0) return LMAZE_E_COUNT;
-    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count, obs, n);
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
-    return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream);
+    return grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t,
+                        done_t, n, auto_reset, seed, epoch, env_base, nullptr, stream);
 }
 
 int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                       int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
                       float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                       int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream) {
-    // the recording request first: its refusals need nothing else
-    if (obs_every < 0 || (obs_every == 0 && obs_t)) return LMAZE_E_COUNT;
-    if (obs_every > 0 && T / obs_every > 0 && !obs_t) return LMAZE_E_NULL;
-    if (misaligned(obs_t, 16)) return LMAZE_E_ALIGN;
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (T < 0) return LMAZE_E_COUNT;
-    if (T == 0 || n == 0) return 0;                                   // nothing to do, nothing read
-    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count, obs, n);
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
-    const RolloutRec rec{obs_every > 0 && T / obs_every > 0 ? obs_t : nullptr, obs_every};
-    return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, &rec);
+    const int rc = check_recording(T, obs_t, obs_every);
+    const RolloutRec rec = recording(T, obs_t, obs_every);
+    return rc ? rc : grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
+                                  reward_t, done_t, n, auto_reset, seed, epoch, env_base, &rec, stream);
 }
 
 int lmaze_rollout_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
                      float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                      int64_t env_base, void* stream) {
-    return rollout_u8(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, reward_t, done_t,
-                      n, auto_reset, seed, epoch, env_base, nullptr, stream);
+    return grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t,
+                        done_t, n, auto_reset, seed, epoch, env_base, nullptr, stream);
 }
 
 int lmaze_rollout_obs_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                          int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
                          float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                          int64_t env_base, uint8_t* obs_t8, int32_t obs_every, void* stream) {
-    // the recording request first, as lmaze_rollout_obs: its refusals need nothing else
-    if (obs_every < 0 || (obs_every == 0 && obs_t8)) return LMAZE_E_COUNT;
-    if (obs_every > 0 && T / obs_every > 0 && !obs_t8) return LMAZE_E_NULL;
-    if (misaligned(obs_t8, 16)) return LMAZE_E_ALIGN;                  // slot 0; the later slots start wherever N G G puts them
-    const RolloutRec8 rec{obs_every > 0 && T / obs_every > 0 ? obs_t8 : nullptr, obs_every};
-    return rollout_u8(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, reward_t, done_t,
-                      n, auto_reset, seed, epoch, env_base, &rec, stream);
+    const int rc = check_recording(T, obs_t8, obs_every);
+    const RolloutRec rec = recording(T, obs_t8, obs_every);
+    return rc ? rc : grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
+                                  reward_t, done_t, n, auto_reset, seed, epoch, env_base, &rec, stream);
 }
 
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
@@ -327,26 +319,19 @@ int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int3
     if (!text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
     if (n == 0 || T == 0) return 0;
+    const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8)
+    if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
+    if (u8 && params->grid < 4) return LMAZE_E_GRID;
     LaunchInfo info;
     memset(&info, 0, sizeof(info));
     // nothing is dereferenced: the launcher fills `info` where it would have queued the rollout (fabricated, aligned
     // addresses stand for the buffers whose presence decides)
-    StepArgs a = make_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           with_obs == 1 ? reinterpret_cast<int32_t*>(16) : nullptr, n);
-    a.auto_reset = auto_reset ? 1 : 0;
+    StepArgs a = rollout_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, n, auto_reset, 0, 0, 0);
     a.info = &info;
-    const bool recording = obs_every >= 0, slots = obs_every > 0 && T / obs_every > 0;
-    if (with_obs == 2) {             // the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8)
-        if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-        if (params->grid < 4) return LMAZE_E_GRID;
-        a.obs8 = reinterpret_cast<uint8_t*>(16);
-        const RolloutRec8 rec{slots ? reinterpret_cast<uint8_t*>(32) : nullptr, obs_every};
-        rc = (int)launch_rollout_u8(params->variant, a, nullptr, T, nullptr, nullptr, nullptr, recording ? &rec : nullptr);
-    } else {
-        const RolloutRec rec{slots ? reinterpret_cast<int32_t*>(32) : nullptr, obs_every};
-        rc = (int)launch_rollout(params->variant, a, params->layout_mode, nullptr, T, nullptr, nullptr, nullptr,
-                                 recording ? &rec : nullptr);
-    }
+    const RolloutRec rec = recording(T, reinterpret_cast<void*>(32), obs_every);
+    rc = (int)launch_rollout(params->variant, a, params->layout_mode, nullptr, T, nullptr, nullptr, nullptr,
+                             obs_every >= 0 ? &rec : nullptr, u8);
     if (rc) return rc;
     return format_launch(info, text_host, len);
 }

@@ -105,22 +105,16 @@ inline bool grid_ok(int64_t blocks) { return blocks >= 1 && blocks <= (int64_t)0
 
 hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_step_u8(int variant, bool do_step, const StepArgs& a, hipStream_t s);
-// The recording rollout's request (lmaze_rollout_obs): obs_t int32[T / every, N, G, G] (null when every == 0, or when
-// T / every == 0), every = k >= 1, or 0 for the final planes only.  A null RolloutRec* is the plain rollout.
+// T steps of a grid rollout (lmaze_rollout and its siblings).  rec: the recording request (lmaze_rollout_obs /
+// lmaze_rollout_obs_u8) -- obs_t the slots, int32[T / every, N, G, G] (u8: uint8, slots that may start at any byte past
+// slot 0), null when every == 0 or T / every == 0; every = k >= 1, or 0 for the final planes only.  A null RolloutRec* is
+// the plain rollout.  u8: the narrow planes in a.obs8 (shared layouts, G >= 4) instead of a.obs.
 struct RolloutRec {
-    int32_t* obs_t;
+    void* obs_t;
     int32_t every;
 };
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
-                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec = nullptr);
-// The same for the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8; shared layouts, G >= 4): a.obs8 instead of
-// a.obs, uint8 slots that may start at any byte past slot 0.  A null RolloutRec8* is the plain rollout.
-struct RolloutRec8 {
-    uint8_t* obs_t8;
-    int32_t every;
-};
-hipError_t launch_rollout_u8(int variant, const StepArgs& a, const int32_t* actions, int32_t T, float* reward_t, uint8_t* done_t,
-                             hipStream_t s, const RolloutRec8* rec = nullptr);
+                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec, bool u8);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

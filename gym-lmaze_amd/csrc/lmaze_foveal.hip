@@ -810,10 +810,18 @@ static int check_rollout_call(const LmazeFovealParams* params, const int32_t* pl
     return 0;
 }
 
-int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
-                         const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
-                         int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t,
-                         uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t, void* stream) {
+// lmaze_foveal_rollout and, rec != null, lmaze_foveal_rollout_obs (rec: the caller's obs_t, obs_local_t and every)
+static int foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
+                          const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset,
+                          uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t, uint8_t* done_t,
+                          float* foveal_reward_t, uint8_t* foveal_done_t, const FovealRollObs* rec, void* stream) {
+    int32_t slots = 0;
+    if (rec) {                                                         // the recording request first: its refusals need nothing else
+        if (rec->every < 1) return LMAZE_E_COUNT;
+        slots = T > 0 ? T / rec->every : 0;
+        if (slots > 0 && !rec->obs_t) return LMAZE_E_NULL;
+        if (((uintptr_t)rec->obs_t & 15) || ((uintptr_t)rec->obs_local_t & 15)) return LMAZE_E_ALIGN;
+    }
     if (T == 0 || n == 0) return (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) ? LMAZE_E_COUNT : 0;   // nothing to do, nothing read
     int rc = check_rollout_call(params, planner_goals, T, n, auto_reset);
     if (rc) return rc;
@@ -821,6 +829,11 @@ int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts
     if (rc) return rc;
     if (!actions) return LMAZE_E_NULL;
     const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    if (rec) {
+        if (rec->obs_local_t && !v56) return LMAZE_E_VARIANT;          // only v5/v6 have a local observation
+        if (v56 && params->grid != 18) return LMAZE_E_GRID;            // their recording form exists at G = 18 only
+        if (params->variant == LMAZE_VARIANT_V1 && params->grid != 14) return LMAZE_E_GRID;   // v1's at G = 14 only
+    }
     FovealArgs a = make_foveal_args(params, layouts, bufs, n);
     a.action = actions;
     a.goal2 = planner_goals;
@@ -828,13 +841,18 @@ int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts
     a.seed = seed;
     a.epoch = epoch;
     a.env_base = env_base;
-    FovealRoll ro;
-    ro.T = T;
-    ro.reward_t = reward_t;
-    ro.done_t = done_t;
-    ro.freward_t = foveal_reward_t;
-    ro.fdone_t = foveal_done_t;
-    return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
+    const FovealRoll ro{T, reward_t, done_t, foveal_reward_t, foveal_done_t};
+    if (!rec) return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
+    const FovealRollObs rr{ro, slots > 0 ? rec->obs_t : nullptr, slots > 0 ? rec->obs_local_t : nullptr, rec->every};
+    return (int)launch_foveal_rollout(a, rr, (hipStream_t)stream);
+}
+
+int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
+                         const int32_t* planner_goals, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
+                         int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t,
+                         uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t, void* stream) {
+    return foveal_rollout(params, layouts, actions, planner_goals, T, bufs, n, auto_reset, seed, epoch, env_base, reward_t, done_t,
+                          foveal_reward_t, foveal_done_t, nullptr, stream);
 }
 
 int lmaze_foveal_rollout_obs(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
@@ -842,38 +860,9 @@ int lmaze_foveal_rollout_obs(const LmazeFovealParams* params, const uint8_t* lay
                              int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t,
                              uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t, float* obs_t,
                              float* obs_local_t, int32_t obs_every, void* stream) {
-    // the recording request first: its refusals need nothing else
-    if (obs_every < 1) return LMAZE_E_COUNT;
-    const int32_t slots = T > 0 ? T / obs_every : 0;
-    if (slots > 0 && !obs_t) return LMAZE_E_NULL;
-    if (((uintptr_t)obs_t & 15) || ((uintptr_t)obs_local_t & 15)) return LMAZE_E_ALIGN;
-    if (T == 0 || n == 0) return (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) ? LMAZE_E_COUNT : 0;   // nothing to do, nothing read
-    int rc = check_rollout_call(params, planner_goals, T, n, auto_reset);
-    if (rc) return rc;
-    rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    if (!actions) return LMAZE_E_NULL;
-    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
-    if (obs_local_t && !v56) return LMAZE_E_VARIANT;                  // only v5/v6 have a local observation
-    if (v56 && params->grid != 18) return LMAZE_E_GRID;                // their recording form exists at G = 18 only
-    if (params->variant == LMAZE_VARIANT_V1 && params->grid != 14) return LMAZE_E_GRID;   // v1's at G = 14 only
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.action = actions;
-    a.goal2 = planner_goals;
-    a.auto_reset = (planner_goals || (!v56 && auto_reset)) ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    FovealRollObs ro;
-    ro.T = T;
-    ro.reward_t = reward_t;
-    ro.done_t = done_t;
-    ro.freward_t = foveal_reward_t;
-    ro.fdone_t = foveal_done_t;
-    ro.obs_t = slots > 0 ? obs_t : nullptr;
-    ro.obs_local_t = slots > 0 ? obs_local_t : nullptr;
-    ro.every = obs_every;
-    return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
+    const FovealRollObs rec{{}, obs_t, obs_local_t, obs_every};
+    return foveal_rollout(params, layouts, actions, planner_goals, T, bufs, n, auto_reset, seed, epoch, env_base, reward_t, done_t,
+                          foveal_reward_t, foveal_done_t, &rec, stream);
 }
 
 int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,

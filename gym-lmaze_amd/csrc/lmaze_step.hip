@@ -1457,24 +1457,6 @@ hipError_t launch_step_u8(int variant, bool do_step, const StepArgs& a, hipStrea
     return launch_step_u8_epb<64>(variant, do_step, a, s);
 }
 
-// The rollout kernel of either form: the plain one with RolloutArgs, the recording one (rec != null) with
-// RolloutObsArgs -- an overload of the same kernel template, so `kern` names both
-template <class K0, class K1>
-static hipError_t launch_ro(K0 plain, K1 recording, const RolloutRec* rec, bool nt, dim3 grid, dim3 block, size_t lds,
-                            hipStream_t s, const StepArgs& a, const RolloutArgs& ro) {
-    if (rec) {
-        RolloutObsArgs rr;
-        static_cast<RolloutArgs&>(rr) = ro;
-        rr.obs_t = rec->obs_t;
-        rr.every = rec->every;
-        rr.nt = nt ? 1 : 0;
-        hipLaunchKernelGGL(recording, grid, block, lds, s, a, rr);
-    } else {
-        hipLaunchKernelGGL(plain, grid, block, lds, s, a, ro);
-    }
-    return hipGetLastError();
-}
-
 // Store policy of the recording form's slots: plain.  Measured (tools/bench_rollout_obs.py --sweep, two runs, T = 16,
 // every step recorded; launch_hint bit 15 = non-temporal, for measurement -- results never change), us per step plain / nt:
 //   65 536 x 11x11 shared (507 MB of slots, beyond the 256-MiB Infinity Cache)   6.2-6.5 / 7.2-7.5
@@ -1486,156 +1468,19 @@ static bool slot_stores_nt(const StepArgs& a, const RolloutRec* rec) {
     return rec && rec->obs_t && ((a.launch_hint >> 15) & 1);
 }
 
-// T steps: ONE launch (shared layouts: rollout_shared_wave8_kernel for on-die 8x8, rollout_shared_kernel otherwise; per-env
-// layouts: rollout_perenv_kernel); T launches of the step kernel only for T = 1 or when launch_hint bit 8 forces streaming stores, step t with the action row t, epoch + t and, when given, the per-step reward / done rows copied out.
-// rec != null: the recording form of the same kernel (RolloutObsArgs); the T launches give each step its slot, the
-// caller's obs (last step) or nothing.
-hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
-                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec) {
-    if (T <= 0 || a0.n == 0) return hipSuccess;
-    const bool v3 = variant == LMAZE_VARIANT_V3;
-    const bool nt = slot_stores_nt(a0, rec);
-    // the recording form streams its slots wherever the batch sits; on-die means the batch's planes fit the caches
-    const bool planes = a0.obs != nullptr || (rec && rec->obs_t);
-    const bool on_die8 = layout_mode == LMAZE_LAYOUT_SHARED && a0.grid == 8 &&
-                         (!planes || !beyond_caches(a0.n, 64)) && (a0.launch_hint & 0x100) == 0;
-    if (on_die8) {
-        RolloutArgs ro{actions, reward_t, done_t, T};
-        const int epw = 64, wpb = a0.n >= 65536 ? 4 : 1;
-        const int64_t waves = (a0.n + epw - 1) / epw, blocks = (waves + wpb - 1) / wpb;
-        if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-        if (a0.info) {
-            char name[96];
-            if (rec) snprintf(name, sizeof(name), "rollout_shared_wave8_kernel<v%d, %d, obs_t> T=%d every=%d", variant, epw, T, rec->every);
-            else snprintf(name, sizeof(name), "rollout_shared_wave8_kernel<v%d, %d> T=%d", variant, epw, T);
-            describe_launch(a0.info, name, epw * wpb, 0, 1, false, blocks, 64 * wpb, 0);
-            return hipSuccess;
-        }
-        if (!rec) {     // the plain form's launch, as it always was
-            if (variant == LMAZE_VARIANT_V3)
-                hipLaunchKernelGGL((rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>), dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
-            else
-                hipLaunchKernelGGL((rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>), dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
-            return hipGetLastError();
-        }
-        using P = void (*)(const StepArgs, const RolloutArgs);
-        using R = void (*)(const StepArgs, const RolloutObsArgs);
-        if (v3) return launch_ro((P)rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>, (R)rollout_shared_wave8_kernel<LMAZE_VARIANT_V3, 64>,
-                                 rec, nt, dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
-        return launch_ro((P)rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>, (R)rollout_shared_wave8_kernel<LMAZE_VARIANT_V0, 64>,
-                         rec, nt, dim3((unsigned)blocks), dim3(64 * wpb), 0, s, a0, ro);
-    }
-    // any other shared-layout batch: one launch of rollout_shared_kernel, a workgroup per 16 / 32 / 64 envs so that small
-    // batches still fill the chip.  Streaming sizes too: the planes of every step still go out to HBM, but the state stays
-    // in registers and there is no per-step set-up -- 1M x 11x11 75.4 us per step (fused reset 75.6) against 86.4 (92.5) as T
-    // launches from inside this call, 4M envs 297.8 against 329.7 (profiles/r03/rollout_streaming.txt)
-    const bool on_die = layout_mode == LMAZE_LAYOUT_SHARED && T > 1 && (a0.launch_hint & 0x100) == 0;
-    if (on_die) {
-        RolloutArgs ro{actions, reward_t, done_t, T};
-        StepArgs a = a0;
-        a.envs_per_block = a0.n >= 65536 ? 64 : (a0.n >= 16384 ? 32 : 16);
-        // Batches whose planes do not fit the caches: few enough envs per workgroup that what the resident workgroups of an XCD
-        // rewrite step after step (8 per CU x 32 CUs x envs x 4 G^2 bytes) stays inside its 4-MiB L2 -- then most of the
-        // intermediate planes never travel to DRAM.  1M x 11x11: 64 envs 77.7 us per step, 32: 78.6, 16: 51.0, 8: 64.2, 4: 109;
-        // 512K x 18x18: 64: 89.2, 16: 98.4, 8: 74.2, 4: 76.2; 256K x 32x32 (no size fits): 146 / 140 / 133.7 / 141.6
-        // (profiles/r03/rollout_envs_per_workgroup.txt).  launch_hint bits 12-14 = k > 0 ask for 4 << (k - 1) envs.
-        // (Only beyond the Infinity Cache: 262 144 x 11x11, 127 MB of planes, runs 9.9 us per step at 64 envs and 12.9 at 16.)
-        // The recording form keeps the size by batch (launch_hint bits 12-14 swept, T = 16, us per step for every step
-        // recorded / final planes only): 1M x 11x11 64 envs 109.1 / 16.2, 32: 109.4 / 21.0, 16 (what `fit` picks)
-        // 125.7 / 31.5, 8: 147.6 / 52.8; 65 536 x 11x11 64 or 32 6.5-7.8, 8 / 16 7.6-9.7 (profiles/rollout_obs/)
-        if (!rec && beyond_caches(a0.n, a0.grid * a0.grid)) {
-            int fit = 64;
-            while (fit > 8 && (size_t)fit * a0.grid * a0.grid * 4 > 12288) fit >>= 1;
-            if (fit < a.envs_per_block) a.envs_per_block = fit;
-        }
-        if ((a0.launch_hint >> 12) & 7) a.envs_per_block = 4 << (((a0.launch_hint >> 12) & 7) - 1);
-        const int cells = a0.grid * a0.grid;
-        const size_t lds = (size_t)cells * 4 + 2 * (size_t)a.envs_per_block * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
-        const int64_t blocks = (a0.n + a.envs_per_block - 1) / a.envs_per_block;
-        if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-        if (a0.info) {
-            char name[96];
-            if (rec) snprintf(name, sizeof(name), "rollout_shared_kernel<v%d, obs_t> T=%d every=%d", variant, T, rec->every);
-            else snprintf(name, sizeof(name), "rollout_shared_kernel<v%d> T=%d", variant, T);
-            describe_launch(a0.info, name, a.envs_per_block, 0, 1, nt, blocks, LMAZE_BLOCK, lds);
-            return hipSuccess;
-        }
-        if (!rec) {
-            if (variant == LMAZE_VARIANT_V3)
-                hipLaunchKernelGGL((rollout_shared_kernel<LMAZE_VARIANT_V3>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-            else
-                hipLaunchKernelGGL((rollout_shared_kernel<LMAZE_VARIANT_V0>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-            return hipGetLastError();
-        }
-        using P = void (*)(const StepArgs, const RolloutArgs);
-        using R = void (*)(const StepArgs, const RolloutObsArgs);
-        if (v3) return launch_ro((P)rollout_shared_kernel<LMAZE_VARIANT_V3>, (R)rollout_shared_kernel<LMAZE_VARIANT_V3>, rec, nt,
-                                 dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-        return launch_ro((P)rollout_shared_kernel<LMAZE_VARIANT_V0>, (R)rollout_shared_kernel<LMAZE_VARIANT_V0>, rec, nt,
-                         dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-    }
-    // per-env layouts, any size: the layouts are read ONCE per rollout instead of once per step (1M x 32x32: 838 -> 722 us per
-    // step, 1M x 11x11 103 -> 100.5, with the fused reset 114 -> 105.7, 512K x 18x18 142 -> 114; only 8 192 x 32x32, where the
-    // register-tiled step kernel is neither launch- nor layout-bound, is 3 % slower: 10.2 -> 10.5;
-    // profiles/r03/rollout_streaming_perenv.txt, rollout_sizes_perenv.txt)
-    const bool on_die_perenv = layout_mode == LMAZE_LAYOUT_PER_ENV && T > 1 && (a0.launch_hint & 0x100) == 0;
-    if (on_die_perenv) {
-        RolloutArgs ro{actions, reward_t, done_t, T};
-        StepArgs a = a0;
-        const int cells = a0.grid * a0.grid;
-        int epb = a0.n >= 65536 ? 64 : (a0.n >= 16384 ? 32 : 16);
-        while (epb > 4 && (size_t)epb * cells > (size_t)32 << 10) epb >>= 1;         // at most 32 KiB of layouts per workgroup
-        if (!rec && beyond_caches(a0.n, cells))                                      // planes that fit the L2s, as above
-            while (epb > 8 && (size_t)epb * cells * 4 > 12288) epb >>= 1;
-        // the recording form (launch_hint bits 12-14 swept, T = 16, every step recorded): 16 384 x 11x11 16 envs 3.7 us
-        // per step, 32 (the plain form's) 4.7, 8 4.4, 64 7.1; 262 144 x 32x32 the plain form's 32 envs 221 us, 16 255,
-        // 8 237, 64 346 -- so only the batches that take 32 by size (16 384 to 65 535 envs) halve
-        if (rec && epb == 32 && a0.n < 65536) epb = 16;
-        if ((a0.launch_hint >> 12) & 7) epb = 4 << (((a0.launch_hint >> 12) & 7) - 1);
-        if (epb > 64) epb = 64;                                                      // every env's lane sits in wave 0
-        a.envs_per_block = epb;
-        const size_t lds = 2 * (size_t)epb * 4 + (((size_t)epb * cells + 15) & ~(size_t)15);
-        const int64_t blocks = (a0.n + epb - 1) / epb;
-        if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-        if (a0.info) {
-            char name[96];
-            if (rec) snprintf(name, sizeof(name), "rollout_perenv_kernel<v%d, obs_t> T=%d every=%d", variant, T, rec->every);
-            else snprintf(name, sizeof(name), "rollout_perenv_kernel<v%d> T=%d", variant, T);
-            describe_launch(a0.info, name, epb, 0, 1, nt, blocks, LMAZE_BLOCK, lds);
-            return hipSuccess;
-        }
-        if (!rec) {
-            if (variant == LMAZE_VARIANT_V3)
-                hipLaunchKernelGGL((rollout_perenv_kernel<LMAZE_VARIANT_V3>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-            else
-                hipLaunchKernelGGL((rollout_perenv_kernel<LMAZE_VARIANT_V0>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-            return hipGetLastError();
-        }
-        using P = void (*)(const StepArgs, const RolloutArgs);
-        using R = void (*)(const StepArgs, const RolloutObsArgs);
-        if (v3) return launch_ro((P)rollout_perenv_kernel<LMAZE_VARIANT_V3>, (R)rollout_perenv_kernel<LMAZE_VARIANT_V3>, rec, nt,
-                                 dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-        return launch_ro((P)rollout_perenv_kernel<LMAZE_VARIANT_V0>, (R)rollout_perenv_kernel<LMAZE_VARIANT_V0>, rec, nt,
-                         dim3((unsigned)blocks), dim3(LMAZE_BLOCK), lds, s, a, ro);
-    }
-    const int64_t plane = (int64_t)a0.n * a0.grid * a0.grid;                        // dwords of one step's planes
-    for (int32_t t = 0; t < T; ++t) {
-        StepArgs a = a0;
-        a.action = actions + (size_t)t * a0.n;
-        a.epoch = a0.epoch + (uint64_t)t;
-        int32_t* slot = nullptr;                                                     // recording: the slot step t fills
-        if (rec && rec->obs_t && rec->every > 0 && (t + 1) % rec->every == 0)
-            slot = rec->obs_t + (size_t)((t + 1) / rec->every - 1) * plane;
-        if (rec) a.obs = t == T - 1 && a0.obs ? a0.obs : slot;                         // the caller's obs after the last step
-        hipError_t rc = launch_step(variant, true, a, layout_mode, s);
-        if (rc != hipSuccess || a0.info) return rc;
-        if (slot && a.obs != slot && (rc = hipMemcpyAsync(slot, a.obs, (size_t)plane * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess)
-            return rc;
-        if (reward_t && (rc = hipMemcpyAsync(reward_t + (size_t)t * a0.n, a0.reward, (size_t)a0.n * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
-        if (done_t && (rc = hipMemcpyAsync(done_t + (size_t)t * a0.n, a0.done, (size_t)a0.n, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
-    }
-    return hipSuccess;
-}
+// What a grid rollout queues (rollout_plan): one launch of a rollout kernel -- the family, its envs per workgroup, block,
+// blocks, LDS and slot store policy -- or T launches of the step kernel
+enum RolloutFamily { RO_WAVE8, RO_SHARED, RO_PERENV, RO_U8, RO_STEPS };
+static const char* const kRolloutKernel[] = {"rollout_shared_wave8_kernel", "rollout_shared_kernel", "rollout_perenv_kernel",
+                                             "rollout_shared_u8_kernel"};
+struct RolloutPlan {
+    RolloutFamily family;
+    int epb;                  // envs per workgroup (wave8: envs per wave x waves per workgroup)
+    int block;
+    int64_t blocks;
+    size_t lds;
+    bool nt;                  // the recording form's slot stores: non-temporal
+};
 
 // LDS of rollout_shared_u8_kernel: the four shifted pattern copies, ballflat / goalflat, the spawn list and the layout
 static size_t rollout_u8_lds_bytes(int G, int epb) {
@@ -1643,55 +1488,150 @@ static size_t rollout_u8_lds_bytes(int G, int epb) {
     return ((size_t)4 * pw * 4 + 2 * (size_t)(epb + 1) * 4 + (size_t)((cells + 1) & ~1) * 2 + (size_t)cells + 15) & ~(size_t)15;
 }
 
-// T steps with the narrow planes: ONE launch of rollout_shared_u8_kernel (plain or recording form) for any T >= 1 and any
-// batch size.  launch_hint bits 12-14 = k > 0 ask for 4 << (k - 1) envs per workgroup, as for rollout_shared_kernel, rounded
-// up to 16 (a workgroup's byte range of obs8 must start on a 16-byte boundary) and down to what fits 64 KiB of LDS;
-// performance only.  Bit 8 keeps its one meaning of the u8 step (streaming stores there) and is not read here.
-// Envs per workgroup, from tools/bench_rollout_u8.py --sweep (v0, fused reset, T = 16, us per step for 16 / 32 / 64 / 128 /
-// 256 envs; plain rollout, then every step recorded; profiles/rollout_u8/bench_rollout_u8_sweep.json):
-//   65 536 x 8x8     3.41 / 2.54 / 1.90 / 2.08 / 2.31      4.70 / 3.33 / 2.46 / 2.49 / 2.71
-//   65 536 x 11x11   3.94 / 2.93 / 2.46 / 2.79 / 3.70      5.18 / 3.63 / 3.00 / 3.24 / 4.04
-//   16 384 x 12x12   1.66 / 1.77 / 1.95 / 2.28 / 2.98      2.16 / 2.20 / 2.27 / 2.57 / 3.34
-//   262 144 x 11x11  11.5 / 7.08 / 5.70 / 7.07 / 7.07      17.3 / 12.1 / 9.50 / 8.88 / 7.78
-//   1M x 11x11       42.8 / 25.7 / 19.5 / 24.6 / 25.5      73.8 / 51.6 / 39.3 / 29.4 / 29.0
-// i.e. 64 envs from 65 536 envs on and 16 below; the slots of a recording beyond the Infinity Cache (262 144 x 11x11 x 16
-// slots = 507 MB) want the widest workgroups.  The int32 rule of fitting the resident workgroups' planes into L2 does not
-// carry over: 1M x 11x11 with 16 envs is 2.2x slower than with 64.
-hipError_t launch_rollout_u8(int variant, const StepArgs& a0, const int32_t* actions, int32_t T, float* reward_t, uint8_t* done_t,
-                             hipStream_t s, const RolloutRec8* rec) {
+// T >= 1 steps of a.n >= 1 envs (rec != null: the recording form; u8: the narrow planes, shared layouts).  int32 planes: ONE
+// launch (shared layouts: rollout_shared_wave8_kernel for on-die 8x8, rollout_shared_kernel otherwise; per-env layouts:
+// rollout_perenv_kernel); T launches of the step kernel only for T = 1 or when launch_hint bit 8 forces streaming stores.
+// u8: ONE launch of rollout_shared_u8_kernel for any T and any batch size.
+static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8) {
+    const int cells = a.grid * a.grid;
+    const int hint_epb = (a.launch_hint >> 12) & 7;       // bits 12-14 = k > 0 ask for 4 << (k - 1) envs per workgroup
+    // the recording form streams its slots wherever the batch sits; on-die means the batch's planes fit the caches
+    const bool planes = a.obs != nullptr || (rec && rec->obs_t);
+    RolloutPlan p{RO_STEPS, 0, LMAZE_BLOCK, 0, 0, false};
+    if (u8) {
+        // launch_hint bits 12-14 rounded up to 16 (a workgroup's byte range of obs8 must start on a 16-byte boundary) and down
+        // to what fits 64 KiB of LDS; performance only.  Bit 8 keeps its one meaning of the u8 step (streaming stores there)
+        // and is not read here.  Envs per workgroup, from tools/bench_rollout_u8.py --sweep (v0, fused reset, T = 16, us per
+        // step for 16 / 32 / 64 / 128 / 256 envs; plain rollout, then every step recorded;
+        // profiles/rollout_u8/bench_rollout_u8_sweep.json):
+        //   65 536 x 8x8     3.41 / 2.54 / 1.90 / 2.08 / 2.31      4.70 / 3.33 / 2.46 / 2.49 / 2.71
+        //   65 536 x 11x11   3.94 / 2.93 / 2.46 / 2.79 / 3.70      5.18 / 3.63 / 3.00 / 3.24 / 4.04
+        //   16 384 x 12x12   1.66 / 1.77 / 1.95 / 2.28 / 2.98      2.16 / 2.20 / 2.27 / 2.57 / 3.34
+        //   262 144 x 11x11  11.5 / 7.08 / 5.70 / 7.07 / 7.07      17.3 / 12.1 / 9.50 / 8.88 / 7.78
+        //   1M x 11x11       42.8 / 25.7 / 19.5 / 24.6 / 25.5      73.8 / 51.6 / 39.3 / 29.4 / 29.0
+        // i.e. 64 envs from 65 536 envs on and 16 below; the slots of a recording beyond the Infinity Cache (262 144 x 11x11 x
+        // 16 slots = 507 MB) want the widest workgroups.  The int32 rule of fitting the resident workgroups' planes into L2
+        // does not carry over: 1M x 11x11 with 16 envs is 2.2x slower than with 64.
+        int epb = a.n >= 65536 ? 64 : 16;
+        if (rec && rec->obs_t && a.n >= 262144) epb = 256;
+        if (hint_epb) epb = 4 << (hint_epb - 1);
+        if (epb < 16) epb = 16;
+        if (epb > LMAZE_BLOCK) epb = LMAZE_BLOCK;
+        while (epb > 16 && rollout_u8_lds_bytes(a.grid, epb) > ((size_t)64 << 10)) epb >>= 1;
+        p.family = RO_U8;
+        p.epb = epb;
+        p.lds = rollout_u8_lds_bytes(a.grid, epb);
+    } else if (layout_mode == LMAZE_LAYOUT_SHARED && a.grid == 8 && (!planes || !beyond_caches(a.n, 64)) &&
+               (a.launch_hint & 0x100) == 0) {
+        // on-die 8x8: 64 envs per wave, one wave per workgroup below 65 536 envs and 4 from there on
+        p.family = RO_WAVE8;
+        p.block = 64 * (a.n >= 65536 ? 4 : 1);
+        p.epb = p.block;
+    } else if (T > 1 && (a.launch_hint & 0x100) == 0) {
+        const bool perenv = layout_mode == LMAZE_LAYOUT_PER_ENV;
+        p.family = perenv ? RO_PERENV : RO_SHARED;
+        // shared layouts: a workgroup per 16 / 32 / 64 envs so that small batches still fill the chip.  Streaming sizes too:
+        // the planes of every step still go out to HBM, but the state stays in registers and there is no per-step set-up --
+        // 1M x 11x11 75.4 us per step (fused reset 75.6) against 86.4 (92.5) as T launches from inside this call, 4M envs
+        // 297.8 against 329.7 (profiles/r03/rollout_streaming.txt).  Per-env layouts, any size: the layouts are read ONCE
+        // per rollout instead of once per step (1M x 32x32: 838 -> 722 us per step, 1M x 11x11 103 -> 100.5, with the fused
+        // reset 114 -> 105.7, 512K x 18x18 142 -> 114; only 8 192 x 32x32, where the register-tiled step kernel is neither
+        // launch- nor layout-bound, is 3 % slower: 10.2 -> 10.5; profiles/r03/rollout_streaming_perenv.txt,
+        // rollout_sizes_perenv.txt)
+        int epb = a.n >= 65536 ? 64 : (a.n >= 16384 ? 32 : 16);
+        if (perenv)
+            while (epb > 4 && (size_t)epb * cells > (size_t)32 << 10) epb >>= 1;        // at most 32 KiB of layouts per workgroup
+        // Batches whose planes do not fit the caches: few enough envs per workgroup that what the resident workgroups of an XCD
+        // rewrite step after step (8 per CU x 32 CUs x envs x 4 G^2 bytes) stays inside its 4-MiB L2 -- then most of the
+        // intermediate planes never travel to DRAM.  1M x 11x11: 64 envs 77.7 us per step, 32: 78.6, 16: 51.0, 8: 64.2, 4: 109;
+        // 512K x 18x18: 64: 89.2, 16: 98.4, 8: 74.2, 4: 76.2; 256K x 32x32 (no size fits): 146 / 140 / 133.7 / 141.6
+        // (profiles/r03/rollout_envs_per_workgroup.txt).
+        // (Only beyond the Infinity Cache: 262 144 x 11x11, 127 MB of planes, runs 9.9 us per step at 64 envs and 12.9 at 16.)
+        // The recording form keeps the size by batch (launch_hint bits 12-14 swept, T = 16, us per step for every step
+        // recorded / final planes only): 1M x 11x11 64 envs 109.1 / 16.2, 32: 109.4 / 21.0, 16 (what the fit picks)
+        // 125.7 / 31.5, 8: 147.6 / 52.8; 65 536 x 11x11 64 or 32 6.5-7.8, 8 / 16 7.6-9.7 (profiles/rollout_obs/)
+        if (!rec && beyond_caches(a.n, cells))
+            while (epb > 8 && (size_t)epb * cells * 4 > 12288) epb >>= 1;
+        // the per-env recording form (launch_hint bits 12-14 swept, T = 16, every step recorded): 16 384 x 11x11 16 envs 3.7 us
+        // per step, 32 (the plain form's) 4.7, 8 4.4, 64 7.1; 262 144 x 32x32 the plain form's 32 envs 221 us, 16 255,
+        // 8 237, 64 346 -- so only the batches that take 32 by size (16 384 to 65 535 envs) halve
+        if (perenv && rec && epb == 32 && a.n < 65536) epb = 16;
+        if (hint_epb) epb = 4 << (hint_epb - 1);
+        if (perenv && epb > 64) epb = 64;                                               // every env's lane sits in wave 0
+        p.epb = epb;
+        p.lds = perenv ? 2 * (size_t)epb * 4 + (((size_t)epb * cells + 15) & ~(size_t)15)
+                       : (size_t)cells * 4 + 2 * (size_t)epb * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
+        p.nt = slot_stores_nt(a, rec);
+    }
+    if (p.family != RO_STEPS) p.blocks = (a.n + p.epb - 1) / p.epb;
+    return p;
+}
+
+// The kernel of a planned rollout: the plain form (RolloutArgs) or the recording one (RolloutObsArgs, u8:
+// RolloutObs8Args), overloads of one kernel template.  Named in the order the code object has always held them.
+template <class F>
+static const void* kernel_of(int variant, F v3, F v0) { return (const void*)(variant == LMAZE_VARIANT_V3 ? v3 : v0); }
+
+static const void* rollout_kernel(RolloutFamily f, int variant, bool rec) {
+    using P = void (*)(const StepArgs, const RolloutArgs);
+    using R = void (*)(const StepArgs, const RolloutObsArgs);
+    using R8 = void (*)(const StepArgs, const RolloutObs8Args);
+    constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
+    switch (f) {
+        case RO_WAVE8: return !rec ? kernel_of<P>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>)
+                                   : kernel_of<R>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>);
+        case RO_SHARED: return !rec ? kernel_of<P>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                                    : kernel_of<R>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
+        case RO_PERENV: return !rec ? kernel_of<P>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                                    : kernel_of<R>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
+        default: return rec ? kernel_of<R8>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
+                            : kernel_of<P>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>);
+    }
+}
+
+// T steps as rollout_plan decides.  T launches: step t with the action row t, epoch + t and, when given, the per-step
+// reward / done rows copied out; recording, each step gets its slot, the caller's obs (last step) or nothing.
+hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec, bool u8) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
-    StepArgs a = a0;
-    int epb = a0.n >= 65536 ? 64 : 16;
-    if (rec && rec->obs_t8 && a0.n >= 262144) epb = 256;
-    if ((a0.launch_hint >> 12) & 7) epb = 4 << (((a0.launch_hint >> 12) & 7) - 1);
-    if (epb < 16) epb = 16;
-    if (epb > LMAZE_BLOCK) epb = LMAZE_BLOCK;
-    while (epb > 16 && rollout_u8_lds_bytes(a0.grid, epb) > ((size_t)64 << 10)) epb >>= 1;
-    a.envs_per_block = epb;
-    const size_t lds = rollout_u8_lds_bytes(a0.grid, epb);
-    const int64_t blocks = (a0.n + epb - 1) / epb;
-    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-    if (a0.info) {
-        char name[96];
-        if (rec) snprintf(name, sizeof(name), "rollout_shared_u8_kernel<v%d, obs_t> T=%d every=%d", variant, T, rec->every);
-        else snprintf(name, sizeof(name), "rollout_shared_u8_kernel<v%d> T=%d", variant, T);
-        describe_launch(a0.info, name, epb, 0, 1, false, blocks, LMAZE_BLOCK, lds);
+    const RolloutPlan p = rollout_plan(a0, layout_mode, T, rec, u8);
+    if (p.family == RO_STEPS) {
+        int32_t* obs_t = rec ? static_cast<int32_t*>(rec->obs_t) : nullptr;
+        const int64_t plane = (int64_t)a0.n * a0.grid * a0.grid;                    // dwords of one step's planes
+        for (int32_t t = 0; t < T; ++t) {
+            StepArgs a = a0;
+            a.action = actions + (size_t)t * a0.n;
+            a.epoch = a0.epoch + (uint64_t)t;
+            int32_t* slot = nullptr;                                                 // recording: the slot step t fills
+            if (obs_t && rec->every > 0 && (t + 1) % rec->every == 0)
+                slot = obs_t + (size_t)((t + 1) / rec->every - 1) * plane;
+            if (rec) a.obs = t == T - 1 && a0.obs ? a0.obs : slot;                     // the caller's obs after the last step
+            hipError_t rc = launch_step(variant, true, a, layout_mode, s);
+            if (rc != hipSuccess || a0.info) return rc;
+            if (slot && a.obs != slot && (rc = hipMemcpyAsync(slot, a.obs, (size_t)plane * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+                return rc;
+            if (reward_t && (rc = hipMemcpyAsync(reward_t + (size_t)t * a0.n, a0.reward, (size_t)a0.n * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
+            if (done_t && (rc = hipMemcpyAsync(done_t + (size_t)t * a0.n, a0.done, (size_t)a0.n, hipMemcpyDeviceToDevice, s)) != hipSuccess) return rc;
+        }
         return hipSuccess;
     }
-    RolloutArgs ro{actions, reward_t, done_t, T};
-    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
-    const bool v3 = variant == LMAZE_VARIANT_V3;
-    if (rec) {
-        RolloutObs8Args rr;
-        static_cast<RolloutArgs&>(rr) = ro;
-        rr.obs_t8 = rec->obs_t8;
-        rr.every = rec->every;
-        using R = void (*)(const StepArgs, const RolloutObs8Args);
-        hipLaunchKernelGGL(v3 ? (R)rollout_shared_u8_kernel<LMAZE_VARIANT_V3> : (R)rollout_shared_u8_kernel<LMAZE_VARIANT_V0>, grid, block, lds, s, a, rr);
-    } else {
-        using P = void (*)(const StepArgs, const RolloutArgs);
-        hipLaunchKernelGGL(v3 ? (P)rollout_shared_u8_kernel<LMAZE_VARIANT_V3> : (P)rollout_shared_u8_kernel<LMAZE_VARIANT_V0>, grid, block, lds, s, a, ro);
+    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
+    if (a0.info) {
+        char name[96], every[24] = "";
+        if (rec) snprintf(every, sizeof(every), " every=%d", rec->every);
+        snprintf(name, sizeof(name), "%s<v%d%s%s> T=%d%s", kRolloutKernel[p.family], variant, p.family == RO_WAVE8 ? ", 64" : "",
+                 rec ? ", obs_t" : "", T, every);
+        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
+        return hipSuccess;
     }
+    StepArgs a = a0;
+    a.envs_per_block = p.epb;
+    RolloutArgs plain{actions, reward_t, done_t, T};
+    RolloutObsArgs ro{plain, rec ? static_cast<int32_t*>(rec->obs_t) : nullptr, rec ? rec->every : 0, p.nt ? 1 : 0};
+    RolloutObs8Args ro8{plain, rec ? static_cast<uint8_t*>(rec->obs_t) : nullptr, rec ? rec->every : 0};
+    void* args[] = {&a, !rec ? (void*)&plain : u8 ? (void*)&ro8 : (void*)&ro};
+    const void* kernel = rollout_kernel(p.family, variant, rec != nullptr);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
     return hipGetLastError();
 }
 

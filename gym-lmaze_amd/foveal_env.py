@@ -203,95 +203,56 @@ class LmazeFovealVecEnv(VecEnvBase):
             if auto_reset:
                 raise ValueError("v5/v6 restart episodes through the two-level step: pass goals")
         T, N = int(actions.shape[0]), self.num_envs
-        if k is not None and hier and self.grid != 18:
-            # the two-level recording form exists at G = 18 only (include/lmaze.h lmaze_foveal_rollout_obs): T launches
-            base, stride = actions.data_ptr(), N * 4
-            rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
-                    for t in (self.reward, self.done, self.foveal_reward, self.foveal_done)] if trajectory else None
-            for t in range(T):
-                self.hier_step_raw(base + t * stride, goals.data_ptr() + t * stride)
-                if rows:
-                    for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
-                        r[t].copy_(src)
-                if (t + 1) % k == 0:
-                    obs_t[(t + 1) // k - 1].copy_(self.obs)
-                    if obs_local_t is not None:
-                        obs_local_t[(t + 1) // k - 1].copy_(self.obs_local)
+        base, stride = actions.data_ptr(), N * 4
+
+        def launch(t, slot=None):                       # step t as its own launch (slot: its index under capture)
+            if hier:
+                self.hier_step_raw(base + t * stride, goals.data_ptr() + t * stride, slot)
+            else:
+                self.step_raw(base + t * stride, auto_reset=auto_reset, epoch_slot=slot if auto_reset else None)
+
+        if device_epoch:
             if trajectory:
-                return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
+                raise ValueError("rollout(trajectory=True) is not available with a device-resident epoch")
+            self._step_loop(T, lambda t: launch(t, t))
             return self.obs, self.reward, self.done
-        if k is not None and self.variant == "v1" and self.grid != 14:
-            # v1's recording form exists at G = 14 only (include/lmaze.h lmaze_foveal_rollout_obs): T launches
-            base, stride = actions.data_ptr(), N * 4
-            rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
-                    for t in (self.reward, self.done, self.foveal_reward, self.foveal_done)] if trajectory else None
-            for t in range(T):
-                self.step_raw(base + t * stride, auto_reset=auto_reset)
-                if rows:
-                    for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
-                        r[t].copy_(src)
-                if (t + 1) % k == 0:
-                    obs_t[(t + 1) // k - 1].copy_(self.obs)
-            if trajectory:
-                return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
-            return self.obs, self.reward, self.done
-        if self._two_level and not hier and not device_epoch:
-            # the plain v5/v6 step has no one-launch form (include/lmaze.h lmaze_foveal_rollout): T launches, rows copied
-            rows = [torch.empty((T, N), dtype=t.dtype, device=self.device)
-                    for t in (self.reward, self.done, self.foveal_reward, self.foveal_done)] if trajectory else None
-            base, stride = actions.data_ptr(), N * 4
-            for t in range(T):
-                self.step_raw(base + t * stride)
-                if rows:
-                    for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
-                        r[t].copy_(src)
-                if k is not None and (t + 1) % k == 0:        # a recorded step: its observations into the slots
-                    obs_t[(t + 1) // k - 1].copy_(self.obs)
-                    if obs_local_t is not None:
-                        obs_local_t[(t + 1) // k - 1].copy_(self.obs_local)
-            if trajectory:
-                return (self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool), rows[2], rows[3].view(torch.bool))
-            return self.obs, self.reward, self.done
-        if not device_epoch:
+        rows = self._traj_rows(T, 2 if self.variant in ("v1", "v5", "v6") else 1) if trajectory else None
+        if ((k is not None and ((hier and self.grid != 18) or (self.variant == "v1" and self.grid != 14)))
+                or (self._two_level and not hier)):
+            # T launches: the two-level recording form exists at G = 18 only, v1's at G = 14 only (include/lmaze.h
+            # lmaze_foveal_rollout_obs), and the plain v5/v6 step has no one-launch form (lmaze_foveal_rollout)
+            self._step_loop(T, launch, rows, k, obs_t, obs_local_t)
+        elif T > 0:
             resets = hier or bool(auto_reset)
-            second = self.variant in ("v1", "v5", "v6")
-            rows = None
-            if trajectory:
-                f32, u8 = torch.float32, torch.uint8
-                rows = [torch.empty((T, N), dtype=f32, device=self.device), torch.empty((T, N), dtype=u8, device=self.device)]
-                if second:
-                    rows += [torch.empty((T, N), dtype=f32, device=self.device), torch.empty((T, N), dtype=u8, device=self.device)]
             ptrs = [r.data_ptr() for r in rows] if rows else []
             ptrs += [None] * (4 - len(ptrs))
-            if T > 0:
-                args = (self._pp, self._p_layouts, actions.data_ptr(), goals.data_ptr() if hier else None, T, self._pb, N,
-                        1 if resets else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *ptrs)
-                with self._guard():
-                    if k is None:
-                        rc = _abi.lib.lmaze_foveal_rollout(*args, self._stream())
-                    else:
-                        some = obs_t.shape[0] > 0
-                        rc = _abi.lib.lmaze_foveal_rollout_obs(*args, obs_t.data_ptr() if some else None,
-                                                               obs_local_t.data_ptr() if some and obs_local_t is not None else None,
-                                                               k, self._stream())
-                _abi.check("lmaze_foveal_rollout" if k is None else "lmaze_foveal_rollout_obs", rc)
-                if resets:
-                    self._epoch += T
-            if trajectory:
-                out = [self.obs, self.reward, self.done, rows[0], rows[1].view(torch.bool)]
-                if second:
-                    out += [rows[2], rows[3].view(torch.bool)]
-                return tuple(out)
-            return self.obs, self.reward, self.done
-        if trajectory:
-            raise ValueError("rollout(trajectory=True) is not available with a device-resident epoch")
-        base, stride = actions.data_ptr(), N * 4
+            args = (self._pp, self._p_layouts, base, goals.data_ptr() if hier else None, T, self._pb, N,
+                    1 if resets else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *ptrs)
+            with self._guard():
+                if k is None:
+                    rc = _abi.lib.lmaze_foveal_rollout(*args, self._stream())
+                else:
+                    some = obs_t.shape[0] > 0
+                    rc = _abi.lib.lmaze_foveal_rollout_obs(*args, obs_t.data_ptr() if some else None,
+                                                           obs_local_t.data_ptr() if some and obs_local_t is not None else None,
+                                                           k, self._stream())
+            _abi.check("lmaze_foveal_rollout" if k is None else "lmaze_foveal_rollout_obs", rc)
+            if resets:
+                self._epoch += T
+        return self._rollout_result(rows)
+
+    def _step_loop(self, T, launch, rows=None, k=None, obs_t=None, obs_local_t=None):
+        """rollout() as T launches: launch(t) queues step t; then its rows of the trajectory are copied out and, every k-th
+        step, its observations into their slots."""
         for t in range(T):
-            if hier:
-                self.hier_step_raw(base + t * stride, goals.data_ptr() + t * stride, t)
-            else:
-                self.step_raw(base + t * stride, auto_reset=auto_reset, epoch_slot=t if auto_reset else None)
-        return self.obs, self.reward, self.done
+            launch(t)
+            if rows:
+                for r, src in zip(rows, (self.reward, self.done, self.foveal_reward, self.foveal_done)):
+                    r[t].copy_(src)
+            if k and (t + 1) % k == 0:
+                obs_t[(t + 1) // k - 1].copy_(self.obs)
+                if obs_local_t is not None:
+                    obs_local_t[(t + 1) // k - 1].copy_(self.obs_local)
 
     def capture_rollout(self, actions, goals=None, auto_reset=False, obs_t=None, obs_local_t=None, obs_every=None):
         """rollout(actions, goals, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().

@@ -314,11 +314,10 @@ class LmazeVecEnv(VecEnvBase):
         if not device_epoch and self._tuner is None:
             # lmaze_rollout (the u8 env: lmaze_rollout_u8): ONE launch (the envs' state stays in registers across the T
             # steps); bit-identical to T step() calls
-            rew_t = torch.empty((T, N), dtype=torch.float32, device=self.device) if trajectory else None
-            done_t = torch.empty((T, N), dtype=torch.uint8, device=self.device) if trajectory else None
+            rows = self._traj_rows(T) if trajectory else None
             args = (self._pp, self._p_layout, base, T, self._p_ball, self._p_goal if self._is_v3 else None, self._p_step,
                     self._p_reward, self._p_done, None if self._is_v3 else self._p_gc, self._p_obs,
-                    rew_t.data_ptr() if trajectory else None, done_t.data_ptr() if trajectory else None,
+                    rows[0].data_ptr() if rows else None, rows[1].data_ptr() if rows else None,
                     N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base)
             name = ("lmaze_rollout" if k is None else "lmaze_rollout_obs") + ("_u8" if self._u8 else "")
             with self._guard():
@@ -330,9 +329,7 @@ class LmazeVecEnv(VecEnvBase):
             _abi.check(name, rc)
             if auto_reset:
                 self._epoch += T
-            if trajectory:
-                return self.obs, self.reward, self.done, rew_t, done_t.view(torch.bool)
-            return self.obs, self.reward, self.done
+            return self._rollout_result(rows)
         if trajectory:
             raise ValueError("rollout(trajectory=True) is not available with a device-resident epoch or while the online tuner runs")
         with self._guard():

@@ -234,6 +234,7 @@ int lmaze_observe_u8(const LmazeParams* params, const uint8_t* layout, const int
  * rollout form; params->launch_hint bits 12-14 = k > 0: 4 << (k - 1) envs per workgroup of the shared-layout form
  * instead of the size the library picks -- for batches beyond the L2s the largest that keeps the resident workgroups'
  * planes inside them).  The caller advances its epoch by T.
+ * LMAZE_E_COUNT T < 0.  T == 0 or n == 0 (once params are valid) returns 0 with nothing read: no pointer is looked at.
  */
 int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                   int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
@@ -253,8 +254,7 @@ int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_
  * (T == 1, launch_hint bit 8) gives each step launch its slot, NULL (transition only) or obs.  launch_hint bit 15:
  * the other store policy for the slots (performance only).
  * Refused before anything is queued: LMAZE_E_COUNT obs_every < 0, or obs_t given with obs_every == 0; LMAZE_E_NULL
- * obs_t NULL while T / obs_every > 0; LMAZE_E_ALIGN obs_t not 16-byte aligned; then every refusal of lmaze_rollout,
- * except that T == 0 or n == 0 (once params are valid) returns 0 with nothing read.
+ * obs_t NULL while T / obs_every > 0; LMAZE_E_ALIGN obs_t not 16-byte aligned; then every refusal of lmaze_rollout.
  */
 int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                       int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,

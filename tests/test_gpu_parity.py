@@ -640,6 +640,25 @@ def test_rollout_in_one_launch_equals_T_step_calls(variant, auto_reset, T):
             assert int(one.goal_count.sum().item()) == int(ref.goal_count.sum().item())
 
 
+@pytest.mark.parametrize("variant", ["v0", "v3"])
+@pytest.mark.parametrize("auto_reset", [False, True])
+def test_rollout_of_zero_steps_changes_nothing(variant, auto_reset):
+    """An empty int32[0,N] action tensor (its data pointer NULL): lmaze_rollout returns before it looks at any pointer --
+    obs, state and epoch untouched; with trajectory=True the rows are (0, N)."""
+    N = 1000
+    env = PKG.LmazeVecEnv(N, variant=variant, layout=PKG.layouts.GRID_8_BORDERED, seed=4)
+    env.step(torch.randint(0, 4, (N,), dtype=torch.int32, device="cuda"), auto_reset=auto_reset)
+    obs0, state0, epoch0 = env.obs.clone(), env._state.clone(), env._epoch
+    acts = torch.empty((0, N), dtype=torch.int32, device="cuda")
+    obs, rew, done = env.rollout(acts, auto_reset=auto_reset)
+    torch.cuda.synchronize()
+    assert (obs == obs0).all() and (env._state == state0).all() and env._epoch == epoch0
+    out = env.rollout(acts, auto_reset=auto_reset, trajectory=True)
+    torch.cuda.synchronize()
+    assert len(out) == 5 and tuple(out[3].shape) == (0, N) and tuple(out[4].shape) == (0, N) and out[4].dtype == torch.bool
+    assert (env.obs == obs0).all() and (env._state == state0).all() and env._epoch == epoch0
+
+
 @pytest.mark.parametrize("variant,G,N,T", [("v0", 11, 5000, 9), ("v3", 11, 70000, 40), ("v0", 12, 1000, 130), ("v3", 18, 300, 25),
                                            ("v0", 33, 100, 12), ("v3", 5, 17, 60), ("v0", 11, 65536, 16), ("v3", 64, 33, 7)])
 @pytest.mark.parametrize("auto_reset", [False, True])

@@ -50,6 +50,20 @@ def test_grid_refusals_need_no_device(abi):
     assert _grid(abi, 6, None, 0, n=-1) == E_COUNT
 
 
+@pytest.mark.parametrize("variant", ["v0", "v3"])
+@pytest.mark.parametrize("T,n", [(0, 100), (6, 0), (0, 0)])
+def test_plain_rollout_with_nothing_to_do_reads_no_pointer(abi, variant, T, n):
+    """lmaze_rollout answers T == 0 or n == 0 with 0 once params are valid, before it looks at any pointer, as its siblings
+    do: every pointer NULL, nothing launched."""
+    p = abi.make_params(abi.VARIANT_V3 if variant == "v3" else abi.VARIANT_V0, 11, abi.LAYOUT_SHARED, 100, -1.0, -0.01, 100.0)
+    assert abi.lib.lmaze_rollout(C.byref(p), None, None, T, None, None, None, None, None, None, None, None, None, n, 1, 1, 0, 0,
+                                 None) == 0
+    assert abi.lib.lmaze_rollout(C.byref(p), None, None, -1, None, None, None, None, None, None, None, None, None, n, 1, 1, 0, 0,
+                                 None) == E_COUNT                  # T < 0 still refused
+    assert abi.lib.lmaze_rollout(None, None, None, T, None, None, None, None, None, None, None, None, None, n, 1, 1, 0, 0,
+                                 None) == E_NULL                   # params first
+
+
 def _foveal(abi, variant, T, obs_t, loc_t, every, goals=None, grid=18, n_layouts=5):
     p = abi.LmazeFovealParams(variant, grid, n_layouts, 50, 50, -1.0, -0.01, 100.0, 0)
     bufs = abi.LmazeFovealBuffers()

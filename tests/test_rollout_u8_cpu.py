@@ -90,6 +90,50 @@ def test_describe_int32_names_launch_rollouts_kernels(abi):
     assert d(_params(abi, "v0", 11), 0, 16) == "" and d(_params(abi, "v0", 11), 100, 0, with_obs="u8") == ""
 
 
+def test_describe_int32_sizing_rules(abi):
+    """Every sizing rule of the grid rollouts, pinned by the launcher's own description."""
+    d = abi.describe_rollout
+    PER_ENV = abi.LAYOUT_PER_ENV
+    tail = " block=256 lds=%d envs_per_workgroup=%d workgroups_per_cu=0 chunks=1"
+    # shared layouts: 16 / 32 / 64 envs by batch size; beyond the caches the L2 fit (1M x 11x11: 16), but not for the
+    # recording form, which keeps the size by batch
+    assert d(_params(abi, "v0", 11), 4096, 16) == "rollout_shared_kernel<v0> T=16 grid=256" + tail % (996, 16)
+    assert d(_params(abi, "v0", 11), 1 << 20, 16) == "rollout_shared_kernel<v0> T=16 grid=65536" + tail % (996, 16)
+    assert d(_params(abi, "v0", 11), 1 << 20, 16, obs_every=1) == \
+        "rollout_shared_kernel<v0, obs_t> T=16 every=1 grid=16384" + tail % (1380, 64)
+    # per-env layouts: at most 32 KiB of layouts per workgroup (777 x 64x64: 8), the L2 fit (262 144 x 32x32: 8), and
+    # the recording form's halving of 32 envs at 16 384 to 65 535 envs
+    assert d(_params(abi, "v3", 64, PER_ENV), 777, 16) == "rollout_perenv_kernel<v3> T=16 grid=98" + tail % (32832, 8)
+    assert d(_params(abi, "v0", 32, PER_ENV), 262144, 16) == "rollout_perenv_kernel<v0> T=16 grid=32768" + tail % (8256, 8)
+    assert d(_params(abi, "v0", 11, PER_ENV), 16384, 16) == "rollout_perenv_kernel<v0> T=16 grid=512" + tail % (4128, 32)
+    assert d(_params(abi, "v0", 11, PER_ENV), 16384, 16, obs_every=1) == \
+        "rollout_perenv_kernel<v0, obs_t> T=16 every=1 grid=1024" + tail % (2064, 16)
+    # launch_hint bits 12-14 = k: 4 << (k - 1) envs per workgroup, over the L2 fit; per-env at most 64; the on-die 8x8
+    # form does not read them
+    assert d(_params(abi, "v0", 11, hint=0x1000), 1 << 20, 16) == "rollout_shared_kernel<v0> T=16 grid=262144" + tail % (900, 4)
+    assert d(_params(abi, "v0", 11, hint=0x3000), 1 << 20, 16) == "rollout_shared_kernel<v0> T=16 grid=65536" + tail % (996, 16)
+    assert d(_params(abi, "v0", 11, hint=0x5000), 65536, 16) == "rollout_shared_kernel<v0> T=16 grid=1024" + tail % (1380, 64)
+    assert d(_params(abi, "v0", 11, PER_ENV, hint=0x2000), 4096, 16) == "rollout_perenv_kernel<v0> T=16 grid=512" + tail % (1040, 8)
+    assert d(_params(abi, "v0", 11, PER_ENV, hint=0x7000), 4096, 16) == "rollout_perenv_kernel<v0> T=16 grid=64" + tail % (8256, 64)
+    assert d(_params(abi, "v3", 11, PER_ENV, hint=0x7000), 16384, 16, auto_reset=True, with_obs=False, obs_every=17) == \
+        "rollout_perenv_kernel<v3, obs_t> T=16 every=17 grid=256" + tail % (8256, 64)
+    assert d(_params(abi, "v3", 8, hint=0x7000), 65536, 16) == \
+        "rollout_shared_wave8_kernel<v3, 64> T=16 grid=256 block=256 lds=0 envs_per_workgroup=256 workgroups_per_cu=0 chunks=1"
+
+
+def test_describe_u8_sizing_rules(abi):
+    d = abi.describe_rollout
+    tail = " block=256 lds=%d envs_per_workgroup=%d workgroups_per_cu=0 chunks=1"
+    # 64 envs from 65 536 on; recording slots at >= 262 144 envs: 256
+    assert d(_params(abi, "v0", 11), 262144, 16, auto_reset=True, with_obs="u8") == \
+        "rollout_shared_u8_kernel<v0> T=16 grid=4096" + tail % (1936, 64)
+    assert d(_params(abi, "v0", 11), 262144, 16, auto_reset=True, with_obs="u8", obs_every=3) == \
+        "rollout_shared_u8_kernel<v0, obs_t> T=16 every=3 grid=1024" + tail % (3472, 256)
+    # launch_hint bits 12-14 over that rule, rounded up to 16
+    assert d(_params(abi, "v3", 32, hint=0x1000), 1 << 20, 16, auto_reset=True, with_obs="u8", obs_every=1) == \
+        "rollout_shared_u8_kernel<v3, obs_t> T=16 every=1 grid=65536" + tail % (11472, 16)
+
+
 def test_describe_refusals(abi):
     buf = C.create_string_buffer(256)
     f = abi.lib.lmaze_describe_rollout
