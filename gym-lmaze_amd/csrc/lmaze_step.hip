@@ -1558,9 +1558,17 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
         if (perenv && rec && epb == 32 && a.n < 65536) epb = 16;
         if (hint_epb) epb = 4 << (hint_epb - 1);
         if (perenv && epb > 64) epb = 64;                                               // every env's lane sits in wave 0
+        auto lds_of = [&](int k) {
+            return perenv ? 2 * (size_t)k * 4 + (((size_t)k * cells + 15) & ~(size_t)15)
+                          : (size_t)cells * 4 + 2 * (size_t)k * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
+        };
+        // per-env layouts past G = 50 at 64 envs outgrow one workgroup's LDS (the hint is applied after the 32-KiB rule above):
+        // halve to what fits, the device's 160 KiB as lds_for_workgroups_per_cu takes it, so that lmaze_describe_rollout
+        // answers the same without a device.  Stays a multiple of 4 (body 3 copies the layouts as dwords).
+        if (perenv)
+            while (epb > 4 && lds_of(epb) > (size_t)160 * 1024) epb >>= 1;
         p.epb = epb;
-        p.lds = perenv ? 2 * (size_t)epb * 4 + (((size_t)epb * cells + 15) & ~(size_t)15)
-                       : (size_t)cells * 4 + 2 * (size_t)epb * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
+        p.lds = lds_of(epb);
         p.nt = slot_stores_nt(a, rec);
     }
     if (p.family != RO_STEPS) p.blocks = (a.n + p.epb - 1) / p.epb;
@@ -1619,8 +1627,8 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
     if (a0.info) {
         char name[96], every[24] = "";
         if (rec) snprintf(every, sizeof(every), " every=%d", rec->every);
-        snprintf(name, sizeof(name), "%s<v%d%s%s> T=%d%s", kRolloutKernel[p.family], variant, p.family == RO_WAVE8 ? ", 64" : "",
-                 rec ? ", obs_t" : "", T, every);
+        snprintf(name, sizeof(name), "%s<v%d%s%s%s> T=%d%s", kRolloutKernel[p.family], variant, p.family == RO_WAVE8 ? ", 64" : "",
+                 rec ? ", obs_t" : "", p.nt ? ", nt" : "", T, every);
         describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
         return hipSuccess;
     }

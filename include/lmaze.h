@@ -231,9 +231,10 @@ int lmaze_observe_u8(const LmazeParams* params, const uint8_t* layout, const int
  * layouts -- in LDS, read once per rollout), the planes are rewritten every step as T launches would, the per-env state
  * goes back once at the end (65 536 x 8x8: a step costs 6 us as a launch of its own, a third of it launch gap, 2.3-2.5 us
  * here; 1M x 32x32 per-env layouts 838 -> 722 us per step; lmaze_describe_step names the step kernel, this call its
- * rollout form; params->launch_hint bits 12-14 = k > 0: 4 << (k - 1) envs per workgroup of the shared-layout form
- * instead of the size the library picks -- for batches beyond the L2s the largest that keeps the resident workgroups'
- * planes inside them).  The caller advances its epoch by T.
+ * rollout form; params->launch_hint bits 12-14 = k > 0: 4 << (k - 1) envs per workgroup instead of the size the library
+ * picks -- for batches beyond the L2s the largest that keeps the resident workgroups' planes inside them; with per-env
+ * layouts at most 64, and halved until their layouts fit one workgroup's 160 KiB of LDS (G > 50: 32); performance only).
+ * The caller advances its epoch by T.
  * LMAZE_E_COUNT T < 0.  T == 0 or n == 0 (once params are valid) returns 0 with nothing read: no pointer is looked at.
  */
 int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
@@ -296,8 +297,9 @@ int lmaze_rollout_obs_u8(const LmazeParams* params, const uint8_t* layout, const
  * As lmaze_describe_step, for the grid rollouts: which kernel, grid and envs per workgroup lmaze_rollout (with_obs 0:
  * obs NULL, 1: int32 obs) or lmaze_rollout_u8 (with_obs 2) would queue for n envs and T steps -- obs_every < 0 -- or
  * lmaze_rollout_obs / lmaze_rollout_obs_u8 with that obs_every (obs_t given when T / obs_every > 0), e.g.
- * "rollout_shared_kernel<v0> T=16 grid=1024 block=256 ...", "rollout_shared_u8_kernel<v3, obs_t> T=16 every=3 ...", or
- * the step kernel of the T-launch fallback.  Nothing is queued or dereferenced; no reference counterpart.  T == 0 or
+ * "rollout_shared_kernel<v0> T=16 grid=1024 block=256 ...", "rollout_shared_u8_kernel<v3, obs_t> T=16 every=3 ...",
+ * "rollout_perenv_kernel<v0, obs_t, nt> ..." (launch_hint bit 15: the slots' non-temporal stores), or the step kernel of
+ * the T-launch fallback.  Nothing is queued or dereferenced; no reference counterpart.  T == 0 or
  * n == 0: an empty line.
  */
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
