@@ -34,7 +34,7 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_step", "lmaze_describe_foveal_step", "lmaze_rollout",
            "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout",
            "lmaze_rollout_obs", "lmaze_foveal_rollout_obs", "lmaze_rollout_u8", "lmaze_rollout_obs_u8",
-           "lmaze_describe_rollout")
+           "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy")
 
 
 class LmazeParams(C.Structure):
@@ -162,6 +162,12 @@ def _load():
     lib.lmaze_rollout_obs_u8.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
     lib.lmaze_describe_rollout.restype = C.c_int
     lib.lmaze_describe_rollout.argtypes = [P, i64, i32, i32, i32, i32, C.c_char_p, i32]
+    for name in ("lmaze_rollout_policy", "lmaze_rollout_policy_u8"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [P, vp, vp, i32, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64,
+                                       i64, vp, i32, vp]
+    lib.lmaze_describe_rollout_policy.restype = C.c_int
+    lib.lmaze_describe_rollout_policy.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_describe_foveal_rollout.restype = C.c_int
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
@@ -210,6 +216,29 @@ def describe_rollout(params, n, T, auto_reset=False, with_obs=True, obs_every=No
 def describe_foveal_step(params, n, auto_reset=False):
     buf = C.create_string_buffer(256)
     check("lmaze_describe_foveal_step", lib.lmaze_describe_foveal_step(C.byref(params), int(n), 1 if auto_reset else 0, buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+KEY_MODES = {"ball": 0, "goal": 1}
+
+
+def epsilon_u32(epsilon):
+    """The integer lmaze_rollout_policy takes for an exploration rate in [0, 1]: min(floor(eps * 2^32), 2^32 - 1).  Exact:
+    a double times a power of two is not rounded."""
+    eps = float(epsilon)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("epsilon must be in [0, 1]")
+    return min(int(eps * 4294967296.0), 4294967295)
+
+
+def describe_rollout_policy(params, n, T, auto_reset=True, with_obs=True, obs_every=0, key="ball"):
+    """The kernel form / grid / LDS / envs per workgroup a closed-loop rollout would queue (lmaze_describe_rollout_policy):
+    with_obs True / False / "u8" as describe_rollout, obs_every >= 0, key "ball" or "goal"."""
+    buf = C.create_string_buffer(256)
+    check("lmaze_describe_rollout_policy",
+          lib.lmaze_describe_rollout_policy(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
+                                            2 if with_obs == "u8" else (1 if with_obs else 0), int(obs_every),
+                                            KEY_MODES[key] if key in KEY_MODES else int(key), buf, 256))
     return buf.value.decode("ascii", "replace")
 
 

@@ -123,6 +123,32 @@ static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const 
     return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
 }
 
+// lmaze_rollout_policy / _u8 after the recording request's own checks: grid_rollout's refusals in its order, the key mode
+// where T is judged (a bad argument is refused whether or not there is anything to do), the table among the pointers
+static int grid_rollout_policy(const LmazeParams* params, const uint8_t* layout, const RolloutPolicy& pol, int32_t T, int32_t* ball_xy,
+                               int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
+                               bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
+                               uint64_t epoch, int64_t env_base, const RolloutRec& rec, LaunchInfo* info, void* stream) {
+    int rc = check_params(params, n);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
+    if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
+    if (u8 && params->grid < 4) return LMAZE_E_GRID;
+    if (T < 0) return LMAZE_E_COUNT;
+    if (pol.key_mode != 0 && pol.key_mode != 1) return LMAZE_E_COUNT;
+    if (pol.key_mode == 1 && !v3) return LMAZE_E_VARIANT;          // v0 keeps no goal_xy
+    if (T == 0 || n == 0) return 0;                                // nothing to do, nothing read
+    if (!info) {
+        if (!layout || !pol.table || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
+        if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16))) return LMAZE_E_ALIGN;
+    }
+    StepArgs a = rollout_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
+                              seed, epoch, env_base);
+    a.info = info;
+    return (int)launch_rollout_policy(params->variant, a, params->layout_mode, pol, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
+}
+
 extern "C" {
 
 int lmaze_abi_version(void) { return LMAZE_ABI_VERSION; }
@@ -308,6 +334,47 @@ int lmaze_rollout_obs_u8(const LmazeParams* params, const uint8_t* layout, const
     const RolloutRec rec = recording(T, obs_t8, obs_every);
     return rc ? rc : grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
                                   reward_t, done_t, n, auto_reset, seed, epoch, env_base, &rec, stream);
+}
+
+int lmaze_rollout_policy(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
+                         uint32_t epsilon_u32, int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                         uint8_t* done, int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t,
+                         int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                         int32_t* obs_t, int32_t obs_every, void* stream) {
+    const int rc = check_recording(T, obs_t, obs_every);
+    const RolloutPolicy pol{policy, key_mode, epsilon_u32, actions_t, key_t};
+    return rc ? rc : grid_rollout_policy(params, layout, pol, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
+                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t, obs_every),
+                                         nullptr, stream);
+}
+
+int lmaze_rollout_policy_u8(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
+                            uint32_t epsilon_u32, int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                            uint8_t* done, int32_t* goal_count, uint8_t* obs8, float* reward_t, uint8_t* done_t, int32_t* actions_t,
+                            int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                            uint8_t* obs_t8, int32_t obs_every, void* stream) {
+    const int rc = check_recording(T, obs_t8, obs_every);
+    const RolloutPolicy pol{policy, key_mode, epsilon_u32, actions_t, key_t};
+    return rc ? rc : grid_rollout_policy(params, layout, pol, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
+                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t8, obs_every),
+                                         nullptr, stream);
+}
+
+int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                  int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
+    if (obs_every < 0) return LMAZE_E_COUNT;
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_policy_u8)
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    // nothing is dereferenced: fabricated, aligned addresses stand for the buffers whose presence decides
+    const RolloutPolicy pol{nullptr, key_mode, 0, nullptr, nullptr};
+    const int rc = grid_rollout_policy(params, nullptr, pol, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, nullptr, nullptr, n, auto_reset,
+                                       0, 0, 0, recording(T, reinterpret_cast<void*>(32), obs_every), &info, nullptr);
+    if (rc || n == 0 || T == 0) return rc;
+    return format_launch(info, text_host, len);
 }
 
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,

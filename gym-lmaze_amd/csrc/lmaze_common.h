@@ -115,6 +115,18 @@ struct RolloutRec {
 };
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec* rec, bool u8);
+// The closed-loop grid rollout (lmaze_rollout_policy / lmaze_rollout_policy_u8): the tabular epsilon-greedy policy that
+// stands where the action tensor stood, and the optional rows int32[T,N] of the actions taken and their keys.  rec is
+// never null: these rollouts store planes on recorded steps and after the last one only.  Always one launch.
+struct RolloutPolicy {
+    const uint8_t* table;     // uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1, v3)
+    int32_t key_mode;
+    uint32_t epsilon;         // min(floor(eps * 2^32), 2^32 - 1)
+    int32_t* actions_t;
+    int32_t* key_t;
+};
+hipError_t launch_rollout_policy(int variant, const StepArgs& a, int layout_mode, const RolloutPolicy& pol, int32_t T,
+                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

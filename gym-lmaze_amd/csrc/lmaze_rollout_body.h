@@ -3,7 +3,10 @@
 // function the plain forms compiled to other register allocations, included they keep their code.  In scope: `a`
 // (StepArgs), `ro`, the compile-time VARIANT, REC and, for the wave-autonomous body, EPW.  LMAZE_ROLLOUT_BODY selects
 // the body: 1 rollout_shared_wave8_kernel, 2 rollout_shared_kernel, 3 rollout_perenv_kernel, 4 rollout_shared_u8_kernel
-// (whose recording form takes RolloutObs8Args).  Not a header of its own.
+// (whose recording form takes RolloutObs8Args).  With LMAZE_ROLLOUT_POLICY defined, bodies 2-4 are the closed-loop forms
+// (RolloutPolicyArgs, u8: RolloutPolicy8Args; REC true): no action row is read -- after the fused reset the lane that owns
+// the env looks its action up by the env's key (policy_act) -- and the ball-keyed table sits in LDS behind the body's other
+// arrays.  The lines of the open-loop forms are the #else branches, untouched.  Not a header of its own.
 #ifndef LMAZE_ROLLOUT_BODY
 #error "lmaze_rollout_body.h is the body of the rollout kernels: it is included only inside them, in lmaze_step.hip"
 #endif
@@ -94,8 +97,16 @@
     const int nb = (int)min((int64_t)EPB, a.n - blockbase);
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
+#ifdef LMAZE_ROLLOUT_POLICY
+    uint8_t* tab = reinterpret_cast<uint8_t*>(spawn) + ((CELLS * 2 + 15) & ~15);   // [CELLS] the ball-keyed table
+    EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
+    int hits = 0;
+    if (ro.pol.key_mode == 0)
+        for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];
+#else
     EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
     int hits = 0, act_next = s.act;
+#endif
     for (int i = tid; i < CELLS; i += LMAZE_BLOCK) {
         const uint8_t c = a.layout[i];
         lay[i] = c;
@@ -111,13 +122,18 @@
     int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
     for (int t = 0; t < ro.T; ++t) {
         if (live) {
+#ifndef LMAZE_ROLLOUT_POLICY
             s.act = act_next;
             if (t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];       // next step's row, in flight over this step
+#endif
             if (autoreset && s.done) {                                                // as env_phase1
                 int bc, gc;
                 place_from_list<VARIANT>(spawn, spawn_count, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
                 env_reset<VARIANT>(bc, gc, G, s);
             }
+#ifdef LMAZE_ROLLOUT_POLICY
+            policy_act<VARIANT>(a, ro.pol, tab, G, t, e, s);                          // the action of the state just reset
+#endif
             hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
             rollout_record(ro, a.n, t, e, s);
             ballflat[tid] = ball_cell_of(s.b, G);
@@ -152,8 +168,16 @@
     const int nb = (int)min((int64_t)EPB, a.n - blockbase);
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
+#ifdef LMAZE_ROLLOUT_POLICY
+    uint8_t* tab = lays + ((EPB * CELLS + 15) & ~15);                         // [CELLS] the ball-keyed table
+    EnvState s = policy_load<VARIANT>(a, e, live);
+    int hits = 0;
+    if (ro.pol.key_mode == 0)
+        for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];
+#else
     EnvState s = rollout_load<VARIANT>(a, ro, e, live);
     int hits = 0, act_next = s.act;
+#endif
     {   // EPB is a multiple of 4: the workgroup's layouts start on a dword and are whole dwords
         const uint32_t* src = reinterpret_cast<const uint32_t*>(a.layout + (size_t)blockbase * CELLS);
         uint32_t* dst = reinterpret_cast<uint32_t*>(lays);
@@ -166,8 +190,10 @@
     int32_t* obs = a.obs ? a.obs + (size_t)blockbase * CELLS : nullptr;
     for (int t = 0; t < ro.T; ++t) {
         if (tid < 64) {                                                               // wave 0, every lane: the ballots below
+#ifndef LMAZE_ROLLOUT_POLICY
             s.act = act_next;
             if (live && t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];
+#endif
             // reference reset() of the done envs, one whole-wave placement each on the env's own layout
             unsigned long long todo = __ballot(live && autoreset && s.done);
             while (todo) {
@@ -178,6 +204,9 @@
                 if (tid == j) env_reset<VARIANT>(bc, gc, G, s);
             }
             if (live) {
+#ifdef LMAZE_ROLLOUT_POLICY
+                policy_act<VARIANT>(a, ro.pol, tab, G, t, e, s);                      // the action of the state just reset
+#endif
                 hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lays[tid * CELLS + tx * G + ty]; }, s) ? 1 : 0;
                 rollout_record(ro, a.n, t, e, s);
                 ballflat[tid] = ball_cell_of(s.b, G);
@@ -221,8 +250,16 @@
     const int nb = (int)min((int64_t)EPB, a.n - blockbase);
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
+#ifdef LMAZE_ROLLOUT_POLICY
+    uint8_t* tab = lay + CELLS;                                               // [CELLS] the ball-keyed table
+    EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
+    int hits = 0;
+    if (ro.pol.key_mode == 0)
+        for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];
+#else
     EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
     int hits = 0, act_next = s.act;
+#endif
     for (int i = tid; i < CELLS; i += LMAZE_BLOCK) lay[i] = a.layout[i];
     for (int i = tid; i <= EPB; i += LMAZE_BLOCK) { ballflat[i] = -64; goalflat[i] = -64; }
     __syncthreads();
@@ -251,13 +288,18 @@
     const int R = nb * CELLS;
     for (int t = 0; t < ro.T; ++t) {
         if (live) {
+#ifndef LMAZE_ROLLOUT_POLICY
             s.act = act_next;
             if (t + 1 < ro.T) act_next = ro.actions[(size_t)(t + 1) * a.n + e];       // next step's row, in flight over this step
+#endif
             if (autoreset && s.done) {                                                // as env_phase1
                 int bc, gc;
                 place_from_list<VARIANT>(spawn, spawn_count, env_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e), bc, gc);
                 env_reset<VARIANT>(bc, gc, G, s);
             }
+#ifdef LMAZE_ROLLOUT_POLICY
+            policy_act<VARIANT>(a, ro.pol, tab, G, t, e, s);                          // the action of the state just reset
+#endif
             hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
             rollout_record(ro, a.n, t, e, s);
             ballflat[tid] = ball_cell_of(s.b, G);

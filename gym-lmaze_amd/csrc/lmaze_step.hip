@@ -1127,6 +1127,103 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const St
 }
 
 // ------------------------------------------------------------------------------------
+// Closed-loop rollouts (lmaze_rollout_policy / lmaze_rollout_policy_u8): the three workgroup kernels above with a tabular
+// epsilon-greedy policy in place of the action row.  A table policy needs no planes -- the key is the ball's cell and, goal-
+// conditioned (v3), the goal's, both in the owning lane's registers -- so the rollout stays ONE launch: per env-step one
+// table lookup (ball-keyed: G*G bytes staged in LDS once per workgroup; goal-conditioned: G^4 bytes read from global
+// memory, L2-resident) and, when exploring, one Philox draw.  New overloads on new argument types, as the recording forms
+// were added: the open-loop kernels keep their symbols and code.  Recording semantics only (REC): planes are stored on
+// recorded steps and after the last one.
+// ------------------------------------------------------------------------------------
+struct PolicyTable {
+    const uint8_t* table;     // uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1): the greedy action id of each key
+    int32_t* actions_t;       // [T, N] or null: the action every step took
+    int32_t* key_t;           // [T, N] or null: the key it was looked up with
+    int32_t key_mode;         // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
+    uint32_t epsilon;         // explore when the draw's x < epsilon; 0: nothing is drawn
+};
+struct RolloutPolicyArgs : RolloutObsArgs { PolicyTable pol; };     // actions: null, never read
+struct RolloutPolicy8Args : RolloutObs8Args { PolicyTable pol; };
+
+// rollout_load without an action row
+template <int VARIANT>
+__device__ __forceinline__ EnvState policy_load(const StepArgs& a, int64_t e, bool live) {
+    EnvState s;
+    s.b = make_int2(1, 1); s.g = make_int2(-1, -1);
+    s.act = -1; s.sc = 0; s.done = 0; s.r = 0.0f;
+    if (live) {
+        s.b = a.ball[e];
+        if (VARIANT == LMAZE_VARIANT_V3) s.g = a.goal[e];
+        s.sc = a.step_count[e];
+        if (VARIANT != LMAZE_VARIANT_V3) s.r = a.reward[e];
+        if (a.auto_reset) s.done = a.done[e];
+    }
+    return s;
+}
+
+// The exploration draw of env `env_global` at `epoch`: the reset draw's counter with the top bit of its last word flipped
+// (epochs stay below 2^63), so the two streams of one (env, epoch) never meet.
+__device__ __forceinline__ uint4 policy_draw(uint64_t seed, uint64_t epoch, int64_t env_global) {
+    const uint64_t e = (uint64_t)env_global;
+    return philox4x32_10(make_uint4((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)epoch, (uint32_t)(epoch >> 32) ^ 0x80000000u),
+                         make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+}
+
+// Step t's action of env e (workgroup-local state s, after the fused reset): key -> table -> epsilon mix, and the rows of
+// the caller who asked for them.  Coordinates enter the key as the transition takes them, clamped onto the grid, so a
+// lookup never leaves the table.  tab: the ball-keyed table in LDS.
+template <int VARIANT>
+__device__ __forceinline__ void policy_act(const StepArgs& a, const PolicyTable& p, const uint8_t* tab, int G, int t, int64_t e,
+                                           EnvState& s) {
+    int key = clampi(s.b.x, 0, G - 1) * G + clampi(s.b.y, 0, G - 1);
+    int act;
+    if (VARIANT == LMAZE_VARIANT_V3 && p.key_mode != 0) {
+        key += (clampi(s.g.x, 0, G - 1) * G + clampi(s.g.y, 0, G - 1)) * G * G;
+        act = p.table[key];
+    } else {
+        act = tab[key];
+    }
+    if (p.epsilon != 0) {                                             // uniform
+        const uint4 r = policy_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e);
+        if (r.x < p.epsilon) act = (int)(r.y >> 30);
+    }
+    s.act = act;
+    if (p.actions_t) p.actions_t[(size_t)t * a.n + e] = act;
+    if (p.key_t) p.key_t[(size_t)t * a.n + e] = key;
+}
+
+#define LMAZE_ROLLOUT_POLICY 1
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void rollout_shared_kernel(const StepArgs a, const RolloutPolicyArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) void rollout_perenv_kernel(const StepArgs a, const RolloutPolicyArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+// no occupancy target: at 6 waves per SIMD (the v0 recording twin's) the v0 form spills 12 bytes per lane; as it is, 91 (v0) /
+// 88 (v3) VGPRs, 5 waves.
+// CLOSED is always true and selects nothing.  It is here for the symbol only: tests/test_rollout_u8_cpu.py lists every
+// instantiation named rollout_shared_u8_kernel<VARIANT> (one template argument) and requires exactly the four open-loop
+// ones; with a second argument the closed-loop form is still an overload of the same kernel but not one of those names.
+template <int VARIANT, bool CLOSED>
+__global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const StepArgs a, const RolloutPolicy8Args ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 4
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+#undef LMAZE_ROLLOUT_POLICY
+
+// ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
 
@@ -1488,12 +1585,20 @@ static size_t rollout_u8_lds_bytes(int G, int epb) {
     return ((size_t)4 * pw * 4 + 2 * (size_t)(epb + 1) * 4 + (size_t)((cells + 1) & ~1) * 2 + (size_t)cells + 15) & ~(size_t)15;
 }
 
+// LDS of a closed-loop form's ball-keyed table, behind its body's other arrays (kept for the goal-conditioned table too,
+// which is read from global memory: one size per shape)
+static size_t policy_table_lds_bytes(int G) { return (size_t)((G * G + 15) & ~15); }
+
 // T >= 1 steps of a.n >= 1 envs (rec != null: the recording form; u8: the narrow planes, shared layouts).  int32 planes: ONE
 // launch (shared layouts: rollout_shared_wave8_kernel for on-die 8x8, rollout_shared_kernel otherwise; per-env layouts:
 // rollout_perenv_kernel); T launches of the step kernel only for T = 1 or when launch_hint bit 8 forces streaming stores.
 // u8: ONE launch of rollout_shared_u8_kernel for any T and any batch size.
-static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8) {
+// pol: the closed-loop forms (rec != null) -- always one launch of a workgroup kernel (no T-launch fallback, no wave8 form:
+// on-die 8x8 goes through rollout_shared_kernel), the recording form's envs per workgroup, and the ball-keyed table in
+// every LDS size, the fits and clamps below included.
+static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8, bool pol = false) {
     const int cells = a.grid * a.grid;
+    const size_t tab = pol ? policy_table_lds_bytes(a.grid) : 0;
     const int hint_epb = (a.launch_hint >> 12) & 7;       // bits 12-14 = k > 0 ask for 4 << (k - 1) envs per workgroup
     // the recording form streams its slots wherever the batch sits; on-die means the batch's planes fit the caches
     const bool planes = a.obs != nullptr || (rec && rec->obs_t);
@@ -1517,17 +1622,17 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
         if (hint_epb) epb = 4 << (hint_epb - 1);
         if (epb < 16) epb = 16;
         if (epb > LMAZE_BLOCK) epb = LMAZE_BLOCK;
-        while (epb > 16 && rollout_u8_lds_bytes(a.grid, epb) > ((size_t)64 << 10)) epb >>= 1;
+        while (epb > 16 && rollout_u8_lds_bytes(a.grid, epb) + tab > ((size_t)64 << 10)) epb >>= 1;
         p.family = RO_U8;
         p.epb = epb;
-        p.lds = rollout_u8_lds_bytes(a.grid, epb);
-    } else if (layout_mode == LMAZE_LAYOUT_SHARED && a.grid == 8 && (!planes || !beyond_caches(a.n, 64)) &&
+        p.lds = rollout_u8_lds_bytes(a.grid, epb) + tab;
+    } else if (!pol && layout_mode == LMAZE_LAYOUT_SHARED && a.grid == 8 && (!planes || !beyond_caches(a.n, 64)) &&
                (a.launch_hint & 0x100) == 0) {
         // on-die 8x8: 64 envs per wave, one wave per workgroup below 65 536 envs and 4 from there on
         p.family = RO_WAVE8;
         p.block = 64 * (a.n >= 65536 ? 4 : 1);
         p.epb = p.block;
-    } else if (T > 1 && (a.launch_hint & 0x100) == 0) {
+    } else if (pol || (T > 1 && (a.launch_hint & 0x100) == 0)) {
         const bool perenv = layout_mode == LMAZE_LAYOUT_PER_ENV;
         p.family = perenv ? RO_PERENV : RO_SHARED;
         // shared layouts: a workgroup per 16 / 32 / 64 envs so that small batches still fill the chip.  Streaming sizes too:
@@ -1559,8 +1664,8 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
         if (hint_epb) epb = 4 << (hint_epb - 1);
         if (perenv && epb > 64) epb = 64;                                               // every env's lane sits in wave 0
         auto lds_of = [&](int k) {
-            return perenv ? 2 * (size_t)k * 4 + (((size_t)k * cells + 15) & ~(size_t)15)
-                          : (size_t)cells * 4 + 2 * (size_t)k * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
+            return tab + (perenv ? 2 * (size_t)k * 4 + (((size_t)k * cells + 15) & ~(size_t)15)
+                                 : (size_t)cells * 4 + 2 * (size_t)k * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15));
         };
         // per-env layouts past G = 50 at 64 envs outgrow one workgroup's LDS (the hint is applied after the 32-KiB rule above):
         // halve to what fits, the device's 160 KiB as lds_for_workgroups_per_cu takes it, so that lmaze_describe_rollout
@@ -1639,6 +1744,37 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
     RolloutObs8Args ro8{plain, rec ? static_cast<uint8_t*>(rec->obs_t) : nullptr, rec ? rec->every : 0};
     void* args[] = {&a, !rec ? (void*)&plain : u8 ? (void*)&ro8 : (void*)&ro};
     const void* kernel = rollout_kernel(p.family, variant, rec != nullptr);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
+    return hipGetLastError();
+}
+
+// The closed-loop rollout (lmaze_rollout_policy / _u8): ONE launch of the planned family's closed-loop form, whatever T
+// and launch_hint bit 8 say.
+hipError_t launch_rollout_policy(int variant, const StepArgs& a0, int layout_mode, const RolloutPolicy& pol, int32_t T,
+                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+    if (T <= 0 || a0.n == 0) return hipSuccess;
+    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, true);
+    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
+    if (a0.info) {
+        char name[96];
+        snprintf(name, sizeof(name), "%s<v%d, policy=%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
+                 pol.key_mode ? "goal" : "ball", rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T, rec.every);
+        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
+        return hipSuccess;
+    }
+    StepArgs a = a0;
+    a.envs_per_block = p.epb;
+    const PolicyTable tab{pol.table, pol.actions_t, pol.key_t, pol.key_mode, pol.epsilon};
+    RolloutArgs plain{nullptr, reward_t, done_t, T};
+    RolloutPolicyArgs ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
+    RolloutPolicy8Args ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
+    void* args[] = {&a, u8 ? (void*)&ro8 : (void*)&ro};
+    using K = void (*)(const StepArgs, const RolloutPolicyArgs);
+    using K8 = void (*)(const StepArgs, const RolloutPolicy8Args);
+    constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
+    const void* kernel = p.family == RO_U8       ? kernel_of<K8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
+                         : p.family == RO_PERENV ? kernel_of<K>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                                                 : kernel_of<K>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
     (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
     return hipGetLastError();
 }

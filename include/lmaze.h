@@ -306,6 +306,69 @@ int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int3
                            int32_t obs_every, char* text_host, int32_t len);
 
 /*
+ * CLOSED-LOOP rollout: lmaze_rollout_obs with a tabular epsilon-greedy policy inside the kernel instead of a pre-generated
+ * action tensor.  Replaces the user loop of T x (look the action up by the ball's cell, mix in exploration, step(): v0:146-237,
+ * v3:220-402, with auto_reset != 0 the reset() of done envs first, v0:64-110) -- three or more launches per step -- by ONE
+ * launch; the action selection itself has no reference counterpart.  The arguments of lmaze_rollout_obs with `actions`
+ * replaced by
+ *   policy       uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1): the greedy action id of every key, passed through
+ *                unchanged -- ids above 3 mean what they mean to lmaze_step_* (no move), nothing is validated
+ *   key_mode     0: key = ball_x * G + ball_y (the row-major ball cell; v0 and v3, shared and per-env layouts);
+ *                1: key = (goal_x * G + goal_y) * G^2 + ball cell (v3 only)
+ *   epsilon_u32  min(floor(eps * 2^32), 2^32 - 1) for eps in [0, 1], computed by the caller; 0: nothing is drawn
+ * and, beside reward_t / done_t,
+ *   actions_t    int32[T,N], nullable: the action step t took
+ *   key_t        int32[T,N], nullable: the key it was looked up with
+ * Env i (global index e = env_base + i) at step t, ep = epoch + t:
+ *   1. auto_reset != 0 and the env done: the fused reset exactly as lmaze_rollout's, same draw, same epoch ep;
+ *   2. key of the state after that reset (coordinates as the transition takes them: clamped onto the grid);
+ *   3. action = policy[key]; if epsilon_u32 != 0, r = Philox4x32-10(counter (e_lo, e_hi, ep_lo, ep_hi ^ 0x80000000), key
+ *      (seed_lo, seed_hi)) and the action is r.y >> 30 when r.x < epsilon_u32.  The flipped top bit keeps this stream apart
+ *      from the reset draw of the same (e, ep): callers keep epoch + T below 2^63;
+ *   4. the transition of lmaze_step_v0 / _v3 with that action.
+ * obs_t / obs_every as in lmaze_rollout_obs (0: the final planes only); planes are stored on recorded steps and after the
+ * last one, never otherwise.  Always ONE launch of a closed-loop kernel form ("rollout_shared_kernel<v0, policy=ball,
+ * obs_t>", rollout_perenv_kernel for per-env layouts; on-die 8x8 too goes through rollout_shared_kernel): launch_hint bit 8,
+ * the T-launch fallback, does not apply; bits 12-14 (envs per workgroup) and bit 15 behave as in lmaze_rollout_obs.  The
+ * ball-keyed table is staged into LDS once per workgroup and counted where the envs per workgroup are fitted to LDS; the
+ * goal-conditioned one is read from global memory, one byte per env-step (14 KB at G = 11, 1 MB at G = 32).  The caller
+ * advances its epoch by T whether or not auto_reset is set: exploration consumes epochs too.
+ * Refused before anything is queued, in this order: lmaze_rollout_obs's recording refusals (LMAZE_E_COUNT obs_every < 0
+ * or obs_t with obs_every == 0, LMAZE_E_NULL obs_t missing, LMAZE_E_ALIGN obs_t); params, variant and LMAZE_E_COUNT T < 0
+ * as lmaze_rollout; LMAZE_E_COUNT key_mode outside {0, 1}; LMAZE_E_VARIANT key_mode 1 on v0; then T == 0 or n == 0 returns
+ * 0 with nothing read; LMAZE_E_NULL a required pointer, policy included; LMAZE_E_ALIGN as lmaze_rollout.
+ */
+int lmaze_rollout_policy(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
+                         uint32_t epsilon_u32, int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                         uint8_t* done, int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t,
+                         int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                         int32_t* obs_t, int32_t obs_every, void* stream);
+
+/*
+ * lmaze_rollout_policy with the NARROW planes: replaces the same user loop around lmaze_step_u8 (v0:146-237, v3:220-402).
+ * uint8_t* obs8 / obs_t8 as in lmaze_rollout_obs_u8, its byte-offset slot rule included (slot 0 16-byte aligned, slot j
+ * j N G G bytes further); shared layouts and G >= 4 only.  One launch of rollout_shared_u8_kernel's closed-loop form;
+ * launch_hint bit 8 is not read, bits 12-14 as in lmaze_rollout_u8 with the table counted in the LDS fit.  Refusals:
+ * those of lmaze_rollout_obs_u8 (LMAZE_E_LAYOUT per-env layouts, LMAZE_E_GRID G < 4 after the params' own), then
+ * lmaze_rollout_policy's, in its order.
+ */
+int lmaze_rollout_policy_u8(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
+                            uint32_t epsilon_u32, int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                            uint8_t* done, int32_t* goal_count, uint8_t* obs8, float* reward_t, uint8_t* done_t, int32_t* actions_t,
+                            int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                            uint8_t* obs_t8, int32_t obs_every, void* stream);
+
+/*
+ * As lmaze_describe_rollout, for the closed-loop rollouts: which kernel form, grid, LDS and envs per workgroup
+ * lmaze_rollout_policy (with_obs 0: obs NULL, 1: int32 obs) or lmaze_rollout_policy_u8 (with_obs 2) would queue with that
+ * obs_every >= 0 and key_mode, e.g. "rollout_perenv_kernel<v3, policy=goal, obs_t> T=16 every=3 grid=...".  Nothing is
+ * queued or dereferenced; no reference counterpart.  The refusals that need no buffer are the calls' own; T == 0 or
+ * n == 0: an empty line.
+ */
+int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                  int32_t obs_every, int32_t key_mode, char* text_host, int32_t len);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes
