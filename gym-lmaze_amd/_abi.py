@@ -34,7 +34,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_step", "lmaze_describe_foveal_step", "lmaze_rollout",
            "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout",
            "lmaze_rollout_obs", "lmaze_foveal_rollout_obs", "lmaze_rollout_u8", "lmaze_rollout_obs_u8",
-           "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy")
+           "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy",
+           "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns")
 
 
 class LmazeParams(C.Structure):
@@ -168,6 +169,13 @@ def _load():
                                        i64, vp, i32, vp]
     lib.lmaze_describe_rollout_policy.restype = C.c_int
     lib.lmaze_describe_rollout_policy.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
+    for name in ("lmaze_rollout_sample", "lmaze_rollout_sample_u8"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [P, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
+    lib.lmaze_describe_rollout_sample.restype = C.c_int
+    lib.lmaze_describe_rollout_sample.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_returns.restype = C.c_int
+    lib.lmaze_returns.argtypes = [vp, vp, vp, C.c_float, vp, i32, i64, vp]
     lib.lmaze_describe_foveal_rollout.restype = C.c_int
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
@@ -240,6 +248,41 @@ def describe_rollout_policy(params, n, T, auto_reset=True, with_obs=True, obs_ev
                                             2 if with_obs == "u8" else (1 if with_obs else 0), int(obs_every),
                                             KEY_MODES[key] if key in KEY_MODES else int(key), buf, 256))
     return buf.value.decode("ascii", "replace")
+
+
+def describe_rollout_sample(params, n, T, auto_reset=True, with_obs=True, obs_every=0, key="ball"):
+    """As describe_rollout_policy, for the sampling rollouts (lmaze_describe_rollout_sample): the line names where the
+    threshold table lives, table=lds or table=global."""
+    buf = C.create_string_buffer(256)
+    check("lmaze_describe_rollout_sample",
+          lib.lmaze_describe_rollout_sample(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
+                                            2 if with_obs == "u8" else (1 if with_obs else 0), int(obs_every),
+                                            KEY_MODES[key] if key in KEY_MODES else int(key), buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+def sampling_thresholds(probs):
+    """The threshold table lmaze_rollout_sample takes, uint32[S, 4] on probs' device, of a float tensor probs[S, 4] of
+    non-negative weights (a row need not sum to 1).  In float64, with this association:
+        a0 = p0; a1 = a0 + p1; a2 = a1 + p2; s = a2 + p3;   c_k = min(floor(a_k / s * 2**32 + 0.5), 2**32 - 1)
+    and word 3, reserved, is 0.  Action k is then taken with probability (c_k - c_(k-1)) / 2**32, c_(-1) = 0, c_3 = 2**32.
+    A cumulative probability of exactly 1 is stored as 1 - 2**-32 (2**32 does not fit the word): a one-hot row lets one
+    draw in 2**32 through to action 3 -- deterministic policies belong to rollout_policy().  Refuses negative or
+    non-finite entries and rows whose sum is not positive."""
+    if not (isinstance(probs, torch.Tensor) and probs.dim() == 2 and probs.shape[1] == 4 and probs.is_floating_point()):
+        raise ValueError("probs must be a float tensor [S, 4]")
+    p = probs.detach().to(torch.float64)
+    if not bool(torch.isfinite(p).all()) or bool((p < 0).any()):
+        raise ValueError("probs must be finite and non-negative")
+    a0 = p[:, 0]
+    a1 = a0 + p[:, 1]
+    a2 = a1 + p[:, 2]
+    s = a2 + p[:, 3]
+    if not bool(torch.isfinite(s).all()) or bool((s <= 0).any()):
+        raise ValueError("every row of probs must have a positive, finite sum")
+    c = torch.stack([torch.floor(a / s * 4294967296.0 + 0.5) for a in (a0, a1, a2)] + [torch.zeros_like(s)], dim=1)
+    c = c.clamp_(max=4294967295.0).to(torch.int64)
+    return torch.where(c >= 2147483648, c - 4294967296, c).to(torch.int32).view(torch.uint32)   # the same 32 bits
 
 
 def describe_foveal_rollout(params, n, T, auto_reset=False, two_level=False):

@@ -123,12 +123,14 @@ static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const 
     return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
 }
 
-// lmaze_rollout_policy / _u8 after the recording request's own checks: grid_rollout's refusals in its order, the key mode
-// where T is judged (a bad argument is refused whether or not there is anything to do), the table among the pointers
-static int grid_rollout_policy(const LmazeParams* params, const uint8_t* layout, const RolloutPolicy& pol, int32_t T, int32_t* ball_xy,
-                               int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
-                               bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
-                               uint64_t epoch, int64_t env_base, const RolloutRec& rec, LaunchInfo* info, void* stream) {
+// The refusals of the closed-loop rollouts (lmaze_rollout_policy / lmaze_rollout_sample and their _u8 forms) after the
+// recording request's own checks: grid_rollout's in its order, the key mode where T is judged (a bad argument is refused
+// whether or not there is anything to do), the table among the pointers and, where it has an alignment (the 16-byte rows
+// of the sampling thresholds), among the alignment refusals.  *go: something is left to queue or describe.
+static int check_closed_loop(const LmazeParams* params, const uint8_t* layout, const void* table, uintptr_t table_align,
+                             int32_t key_mode, int32_t T, const int32_t* ball_xy, const int32_t* goal_xy, const int32_t* step_count,
+                             const float* reward, const uint8_t* done, const void* obs, bool u8, int64_t n, bool describing, bool* go) {
+    *go = false;
     int rc = check_params(params, n);
     if (rc) return rc;
     const bool v3 = params->variant == LMAZE_VARIANT_V3;
@@ -136,17 +138,45 @@ static int grid_rollout_policy(const LmazeParams* params, const uint8_t* layout,
     if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
     if (u8 && params->grid < 4) return LMAZE_E_GRID;
     if (T < 0) return LMAZE_E_COUNT;
-    if (pol.key_mode != 0 && pol.key_mode != 1) return LMAZE_E_COUNT;
-    if (pol.key_mode == 1 && !v3) return LMAZE_E_VARIANT;          // v0 keeps no goal_xy
+    if (key_mode != 0 && key_mode != 1) return LMAZE_E_COUNT;
+    if (key_mode == 1 && !v3) return LMAZE_E_VARIANT;              // v0 keeps no goal_xy
     if (T == 0 || n == 0) return 0;                                // nothing to do, nothing read
-    if (!info) {
-        if (!layout || !pol.table || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-        if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16))) return LMAZE_E_ALIGN;
+    if (!describing) {
+        if (!layout || !table || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
+        if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16)) ||
+            misaligned(table, table_align))
+            return LMAZE_E_ALIGN;
     }
+    *go = true;
+    return 0;
+}
+
+static int grid_rollout_policy(const LmazeParams* params, const uint8_t* layout, const RolloutPolicy& pol, int32_t T, int32_t* ball_xy,
+                               int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
+                               bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
+                               uint64_t epoch, int64_t env_base, const RolloutRec& rec, LaunchInfo* info, void* stream) {
+    bool go;
+    const int rc = check_closed_loop(params, layout, pol.table, 1, pol.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs, u8,
+                                     n, info != nullptr, &go);
+    if (!go) return rc;
     StepArgs a = rollout_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
                               seed, epoch, env_base);
     a.info = info;
     return (int)launch_rollout_policy(params->variant, a, params->layout_mode, pol, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
+}
+
+static int grid_rollout_sample(const LmazeParams* params, const uint8_t* layout, const RolloutSample& smp, int32_t T, int32_t* ball_xy,
+                               int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
+                               bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
+                               uint64_t epoch, int64_t env_base, const RolloutRec& rec, LaunchInfo* info, void* stream) {
+    bool go;
+    const int rc = check_closed_loop(params, layout, smp.thresholds, 16, smp.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs,
+                                     u8, n, info != nullptr, &go);
+    if (!go) return rc;
+    StepArgs a = rollout_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
+                              seed, epoch, env_base);
+    a.info = info;
+    return (int)launch_rollout_sample(params->variant, a, params->layout_mode, smp, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
 }
 
 extern "C" {
@@ -375,6 +405,54 @@ int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t 
                                        0, 0, 0, recording(T, reinterpret_cast<void*>(32), obs_every), &info, nullptr);
     if (rc || n == 0 || T == 0) return rc;
     return format_launch(info, text_host, len);
+}
+
+int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
+                         int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count,
+                         int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t, int64_t n,
+                         int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t, int32_t obs_every,
+                         void* stream) {
+    const int rc = check_recording(T, obs_t, obs_every);
+    const RolloutSample smp{thresholds, key_mode, actions_t, key_t};
+    return rc ? rc : grid_rollout_sample(params, layout, smp, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
+                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t, obs_every),
+                                         nullptr, stream);
+}
+
+int lmaze_rollout_sample_u8(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
+                            int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
+                            int32_t* goal_count, uint8_t* obs8, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
+                            int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, uint8_t* obs_t8,
+                            int32_t obs_every, void* stream) {
+    const int rc = check_recording(T, obs_t8, obs_every);
+    const RolloutSample smp{thresholds, key_mode, actions_t, key_t};
+    return rc ? rc : grid_rollout_sample(params, layout, smp, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
+                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t8, obs_every),
+                                         nullptr, stream);
+}
+
+int lmaze_describe_rollout_sample(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                  int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
+    if (obs_every < 0) return LMAZE_E_COUNT;
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_sample_u8)
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    // nothing is dereferenced: fabricated, aligned addresses stand for the buffers whose presence decides
+    const RolloutSample smp{nullptr, key_mode, nullptr, nullptr};
+    const int rc = grid_rollout_sample(params, nullptr, smp, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, nullptr, nullptr, n, auto_reset,
+                                       0, 0, 0, recording(T, reinterpret_cast<void*>(32), obs_every), &info, nullptr);
+    if (rc || n == 0 || T == 0) return rc;
+    return format_launch(info, text_host, len);
+}
+
+int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t, int32_t T,
+                  int64_t n, void* stream) {
+    if (!reward_t || !done_t || !returns_t) return LMAZE_E_NULL;
+    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    return (int)launch_returns(reward_t, done_t, tail, gamma, returns_t, T, n, (hipStream_t)stream);
 }
 
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,

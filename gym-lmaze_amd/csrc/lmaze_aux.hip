@@ -269,6 +269,55 @@ hipError_t launch_episode_stats(const uint8_t* done, const float* reward, const 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// Discounted returns-to-go over trajectory rows (lmaze_returns): ret[t] = r[t] where done[t], else r[t] + gamma * ret[t+1],
+// ret[T] = tail (0 when null) -- a reverse scan with a restart at every done.  One lane per env walks t = T-1 .. 0; the
+// product and the sum are rounded separately (never an fma), so a float32 loop on the host reproduces every bit.  Only
+// ret is a dependent chain: the rows are loaded RETURNS_ROWS at a time before it, all in flight at once, and stored after.
+// A lane reads row t of its own column before it stores it and touches no other column, so returns_t may be reward_t.
+// ------------------------------------------------------------------------------------
+#define RETURNS_ROWS 8
+// r + gamma * ret as two roundings, __fadd_rn(r, __fmul_rn(gamma, ret)) in effect: those two are inline functions whose
+// operators carry the translation unit's contraction licence and fuse into one v_fma_f32, so the operators stand here
+// themselves, under a pragma that takes the licence away
+__device__ __forceinline__ float returns_step(float r, float gamma, float ret) {
+#pragma clang fp contract(off)
+    const float discounted = gamma * ret;
+    return r + discounted;
+}
+__global__ __launch_bounds__(LMAZE_BLOCK) void returns_kernel(const float* reward_t, const uint8_t* done_t, const float* tail,
+                                                              float gamma, float* returns_t, int32_t T, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * LMAZE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    float ret = tail ? tail[i] : 0.0f;
+    for (int t0 = T - 1; t0 >= 0; t0 -= RETURNS_ROWS) {
+        float r[RETURNS_ROWS];
+        uint8_t d[RETURNS_ROWS];
+#pragma unroll
+        for (int j = 0; j < RETURNS_ROWS; ++j) {
+            const bool in = t0 - j >= 0;
+            const size_t at = (size_t)(in ? t0 - j : 0) * n + i;
+            r[j] = in ? reward_t[at] : 0.0f;
+            d[j] = in ? done_t[at] : (uint8_t)0;
+        }
+#pragma unroll
+        for (int j = 0; j < RETURNS_ROWS; ++j) {
+            if (t0 - j < 0) break;
+            ret = d[j] ? r[j] : returns_step(r[j], gamma, ret);
+            returns_t[(size_t)(t0 - j) * n + i] = ret;
+        }
+    }
+}
+
+hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t,
+                          int32_t T, int64_t n, hipStream_t s) {
+    if (T <= 0 || n == 0) return hipSuccess;
+    const int64_t blocks = (n + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
+    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(returns_kernel, dim3((unsigned)blocks), dim3(LMAZE_BLOCK), 0, s, reward_t, done_t, tail, gamma, returns_t, T, n);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // measured ceilings of the box ("a measured fill/copy-kernel ceiling on the same box"):
 // ONE 16-byte access per thread in launch order, the pattern that reaches the highest write rate here.

@@ -127,6 +127,19 @@ struct RolloutPolicy {
 };
 hipError_t launch_rollout_policy(int variant, const StepArgs& a, int layout_mode, const RolloutPolicy& pol, int32_t T,
                                  float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+// The sampling closed-loop grid rollout (lmaze_rollout_sample / lmaze_rollout_sample_u8): a categorical table policy, one
+// uint32[4] of cumulative thresholds per key (include/lmaze.h), where RolloutPolicy holds the greedy table.
+struct RolloutSample {
+    const uint32_t* thresholds;   // uint32[G^2, 4] (key_mode 0) or uint32[G^4, 4] (key_mode 1, v3), 16-byte aligned
+    int32_t key_mode;
+    int32_t* actions_t;
+    int32_t* key_t;
+};
+hipError_t launch_rollout_sample(int variant, const StepArgs& a, int layout_mode, const RolloutSample& smp, int32_t T,
+                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+// Discounted returns-to-go over trajectory rows (lmaze_returns, lmaze_aux.hip)
+hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t,
+                          int32_t T, int64_t n, hipStream_t s);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

@@ -6,7 +6,9 @@
 // (whose recording form takes RolloutObs8Args).  With LMAZE_ROLLOUT_POLICY defined, bodies 2-4 are the closed-loop forms
 // (RolloutPolicyArgs, u8: RolloutPolicy8Args; REC true): no action row is read -- after the fused reset the lane that owns
 // the env looks its action up by the env's key (policy_act) -- and the ball-keyed table sits in LDS behind the body's other
-// arrays.  The lines of the open-loop forms are the #else branches, untouched.  Not a header of its own.
+// arrays.  The lines of the open-loop forms are the #else branches, untouched.  LMAZE_ROLLOUT_POLICY == 2: the sampling
+// forms (RolloutSampleArgs, u8: RolloutSample8Args) -- the same lines, but the table holds one sample_row_t of thresholds per key
+// and sits, when staged, on the first 16-byte boundary behind the other arrays.  Not a header of its own.
 #ifndef LMAZE_ROLLOUT_BODY
 #error "lmaze_rollout_body.h is the body of the rollout kernels: it is included only inside them, in lmaze_step.hip"
 #endif
@@ -98,11 +100,19 @@
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
 #ifdef LMAZE_ROLLOUT_POLICY
+#if LMAZE_ROLLOUT_POLICY == 2
+    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds4) + ((CELLS * 4 + EPB * 8 + ((CELLS + 15) & ~15) + ((CELLS * 2 + 15) & ~15) + 15) >> 4);   // [CELLS] staged thresholds
+    EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
+    int hits = 0;
+    if (ro.pol.staged)
+        for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
+#else
     uint8_t* tab = reinterpret_cast<uint8_t*>(spawn) + ((CELLS * 2 + 15) & ~15);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
     int hits = 0;
     if (ro.pol.key_mode == 0)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];
+#endif
 #else
     EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
     int hits = 0, act_next = s.act;
@@ -169,11 +179,19 @@
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
 #ifdef LMAZE_ROLLOUT_POLICY
+#if LMAZE_ROLLOUT_POLICY == 2
+    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds4) + ((EPB * 8 + ((EPB * CELLS + 15) & ~15) + 15) >> 4);   // [CELLS] staged thresholds
+    EnvState s = policy_load<VARIANT>(a, e, live);
+    int hits = 0;
+    if (ro.pol.staged)
+        for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
+#else
     uint8_t* tab = lays + ((EPB * CELLS + 15) & ~15);                         // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);
     int hits = 0;
     if (ro.pol.key_mode == 0)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];
+#endif
 #else
     EnvState s = rollout_load<VARIANT>(a, ro, e, live);
     int hits = 0, act_next = s.act;
@@ -251,11 +269,19 @@
     const bool autoreset = a.auto_reset != 0, live = tid < nb;
     const int64_t e = blockbase + tid;
 #ifdef LMAZE_ROLLOUT_POLICY
+#if LMAZE_ROLLOUT_POLICY == 2
+    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds4) + ((4 * PW * 4 + 2 * (EPB + 1) * 4 + ((CELLS + 1) & ~1) * 2 + CELLS + 15) >> 4);   // [CELLS] staged thresholds
+    EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
+    int hits = 0;
+    if (ro.pol.staged)
+        for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
+#else
     uint8_t* tab = lay + CELLS;                                               // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
     int hits = 0;
     if (ro.pol.key_mode == 0)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];
+#endif
 #else
     EnvState s = rollout_load<VARIANT>(a, ro, e, live);                       // in flight over the set-up
     int hits = 0, act_next = s.act;

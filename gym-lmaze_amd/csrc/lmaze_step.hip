@@ -1224,6 +1224,82 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const St
 #undef LMAZE_ROLLOUT_POLICY
 
 // ------------------------------------------------------------------------------------
+// Sampling closed-loop rollouts (lmaze_rollout_sample / lmaze_rollout_sample_u8): the closed-loop forms above with a
+// categorical table policy -- per key one uint4 (c0, c1, c2, reserved) of cumulative thresholds, and per env-step one
+// Philox draw r = policy_draw(...).x compared against them: action = (r >= c0) + (r >= c1) + (r >= c2) (include/lmaze.h).
+// The ball-keyed table of G <= 32 (at most 16 KiB) is staged in LDS once per workgroup with 16-byte copies and read with
+// one 128-bit LDS read per env-step; every other table (goal-conditioned, or G > 32) is read from global memory, one
+// 16-byte read per env-step, L2- or Infinity-Cache-resident.  The host decides (rollout_plan) and passes `staged`.
+// Again new overloads on new argument types, bodies 2-4 with LMAZE_ROLLOUT_POLICY == 2.
+// ------------------------------------------------------------------------------------
+typedef uint32_t sample_row_t __attribute__((ext_vector_type(4)));      // one key's row: c0, c1, c2, reserved
+struct SampleTable {
+    const sample_row_t* table;   // uint32[S, 4]: S = G^2 (key_mode 0) or G^4 (key_mode 1); words 0-2 c0 <= c1 <= c2, word 3 ignored
+    int32_t* actions_t;          // [T, N] or null: the action every step took
+    int32_t* key_t;              // [T, N] or null: the key it was drawn for
+    int32_t key_mode;            // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
+    int32_t staged;              // != 0: the workgroup copies the ball-keyed table into LDS and reads it there
+};
+struct RolloutSampleArgs : RolloutObsArgs { SampleTable pol; };     // actions: null, never read
+struct RolloutSample8Args : RolloutObs8Args { SampleTable pol; };
+
+// Step t's action of env e (workgroup-local state s, after the fused reset): key -> thresholds -> three unsigned compares
+// of the draw, and the rows of the caller who asked for them.  The key is policy_act's: clamped onto the grid.  tab: the
+// staged table in LDS.  Nothing is validated: any row yields an action in 0..3.
+// The two reads go through pointers of their own address spaces: as two generic loads the compiler merged them into one
+// flat load of a selected pointer, which waits on both counters and is neither an LDS read nor a global one.  The row is
+// read whole -- word 3 is kept alive to the end -- so it is one 128-bit read on either path, issued before the draw.
+template <int VARIANT>
+__device__ __forceinline__ void policy_act(const StepArgs& a, const SampleTable& p, const sample_row_t* tab, int G, int t, int64_t e,
+                                           EnvState& s) {
+    typedef const __attribute__((address_space(3))) sample_row_t* lds_rows;
+    typedef const __attribute__((address_space(1))) sample_row_t* global_rows;
+    int key = clampi(s.b.x, 0, G - 1) * G + clampi(s.b.y, 0, G - 1);
+    sample_row_t c;
+    if (VARIANT == LMAZE_VARIANT_V3 && p.key_mode != 0) {
+        key += (clampi(s.g.x, 0, G - 1) * G + clampi(s.g.y, 0, G - 1)) * G * G;
+        c = ((global_rows)p.table)[key];
+    } else if (p.staged) {
+        c = ((lds_rows)tab)[key];
+    } else {
+        c = ((global_rows)p.table)[key];
+    }
+    const uint32_t r = policy_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e).x;
+    const int act = (int)(r >= c.x) + (int)(r >= c.y) + (int)(r >= c.z);
+    asm volatile("" ::"v"(c.w));
+    s.act = act;
+    if (p.actions_t) p.actions_t[(size_t)t * a.n + e] = act;
+    if (p.key_t) p.key_t[(size_t)t * a.n + e] = key;
+}
+
+#define LMAZE_ROLLOUT_POLICY 2
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void rollout_shared_kernel(const StepArgs a, const RolloutSampleArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) void rollout_perenv_kernel(const StepArgs a, const RolloutSampleArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+// CLOSED as in the epsilon-greedy form: for the symbol only
+template <int VARIANT, bool CLOSED>
+__global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const StepArgs a, const RolloutSample8Args ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 4
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+#undef LMAZE_ROLLOUT_POLICY
+
+// ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
 
@@ -1595,10 +1671,14 @@ static size_t policy_table_lds_bytes(int G) { return (size_t)((G * G + 15) & ~15
 // u8: ONE launch of rollout_shared_u8_kernel for any T and any batch size.
 // pol: the closed-loop forms (rec != null) -- always one launch of a workgroup kernel (no T-launch fallback, no wave8 form:
 // on-die 8x8 goes through rollout_shared_kernel), the recording form's envs per workgroup, and the ball-keyed table in
-// every LDS size, the fits and clamps below included.
-static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8, bool pol = false) {
+// every LDS size, the fits and clamps below included.  PLAN_SAMPLE_LDS / PLAN_SAMPLE_GLOBAL: the sampling forms, planned
+// as the closed-loop ones; the staged threshold table (16 G^2 bytes, on a 16-byte boundary behind the other arrays) is
+// counted in the same places, a table read from global memory reserves nothing.
+enum { PLAN_OPEN = 0, PLAN_POLICY = 1, PLAN_SAMPLE_LDS = 2, PLAN_SAMPLE_GLOBAL = 3 };
+static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8, int pol = PLAN_OPEN) {
     const int cells = a.grid * a.grid;
-    const size_t tab = pol ? policy_table_lds_bytes(a.grid) : 0;
+    const bool sample = pol == PLAN_SAMPLE_LDS || pol == PLAN_SAMPLE_GLOBAL;
+    const size_t tab = pol == PLAN_POLICY ? policy_table_lds_bytes(a.grid) : pol == PLAN_SAMPLE_LDS ? (size_t)16 * cells : 0;
     const int hint_epb = (a.launch_hint >> 12) & 7;       // bits 12-14 = k > 0 ask for 4 << (k - 1) envs per workgroup
     // the recording form streams its slots wherever the batch sits; on-die means the batch's planes fit the caches
     const bool planes = a.obs != nullptr || (rec && rec->obs_t);
@@ -1664,8 +1744,9 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
         if (hint_epb) epb = 4 << (hint_epb - 1);
         if (perenv && epb > 64) epb = 64;                                               // every env's lane sits in wave 0
         auto lds_of = [&](int k) {
-            return tab + (perenv ? 2 * (size_t)k * 4 + (((size_t)k * cells + 15) & ~(size_t)15)
-                                 : (size_t)cells * 4 + 2 * (size_t)k * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15));
+            const size_t own = perenv ? 2 * (size_t)k * 4 + (((size_t)k * cells + 15) & ~(size_t)15)
+                                      : (size_t)cells * 4 + 2 * (size_t)k * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
+            return tab + (sample ? (own + 15) & ~(size_t)15 : own);                     // the thresholds start on a 16-byte boundary
         };
         // per-env layouts past G = 50 at 64 envs outgrow one workgroup's LDS (the hint is applied after the 32-KiB rule above):
         // halve to what fits, the device's 160 KiB as lds_for_workgroups_per_cu takes it, so that lmaze_describe_rollout
@@ -1753,7 +1834,7 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
 hipError_t launch_rollout_policy(int variant, const StepArgs& a0, int layout_mode, const RolloutPolicy& pol, int32_t T,
                                  float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
-    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, true);
+    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, PLAN_POLICY);
     if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
     if (a0.info) {
         char name[96];
@@ -1771,6 +1852,39 @@ hipError_t launch_rollout_policy(int variant, const StepArgs& a0, int layout_mod
     void* args[] = {&a, u8 ? (void*)&ro8 : (void*)&ro};
     using K = void (*)(const StepArgs, const RolloutPolicyArgs);
     using K8 = void (*)(const StepArgs, const RolloutPolicy8Args);
+    constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
+    const void* kernel = p.family == RO_U8       ? kernel_of<K8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
+                         : p.family == RO_PERENV ? kernel_of<K>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                                                 : kernel_of<K>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
+    return hipGetLastError();
+}
+
+// The sampling closed-loop rollout (lmaze_rollout_sample / _u8): launch_rollout_policy with the threshold table.  The
+// table is staged in LDS by rule -- ball-keyed and G <= 32, i.e. at most 16 KiB -- and read from global memory otherwise.
+hipError_t launch_rollout_sample(int variant, const StepArgs& a0, int layout_mode, const RolloutSample& smp, int32_t T,
+                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+    if (T <= 0 || a0.n == 0) return hipSuccess;
+    const bool staged = smp.key_mode == 0 && a0.grid <= 32;
+    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, staged ? PLAN_SAMPLE_LDS : PLAN_SAMPLE_GLOBAL);
+    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
+    if (a0.info) {
+        char name[96];
+        snprintf(name, sizeof(name), "%s<v%d, sample=%s, table=%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
+                 smp.key_mode ? "goal" : "ball", staged ? "lds" : "global", rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T,
+                 rec.every);
+        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
+        return hipSuccess;
+    }
+    StepArgs a = a0;
+    a.envs_per_block = p.epb;
+    const SampleTable tab{reinterpret_cast<const sample_row_t*>(smp.thresholds), smp.actions_t, smp.key_t, smp.key_mode, staged ? 1 : 0};
+    RolloutArgs plain{nullptr, reward_t, done_t, T};
+    RolloutSampleArgs ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
+    RolloutSample8Args ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
+    void* args[] = {&a, u8 ? (void*)&ro8 : (void*)&ro};
+    using K = void (*)(const StepArgs, const RolloutSampleArgs);
+    using K8 = void (*)(const StepArgs, const RolloutSample8Args);
     constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
     const void* kernel = p.family == RO_U8       ? kernel_of<K8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
                          : p.family == RO_PERENV ? kernel_of<K>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)

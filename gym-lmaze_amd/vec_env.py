@@ -408,6 +408,71 @@ class LmazeVecEnv(VecEnvBase):
         out = self._rollout_result(rows)
         return out + (actions_t, key_t) if trajectory else out
 
+    def rollout_sample(self, T, probs=None, logits=None, temperature=1.0, thresholds=None, key="ball", auto_reset=True,
+                       trajectory=False, actions_t=None, key_t=None, obs_t=None, obs_every=0):
+        """T steps in ONE launch with a categorical table policy inside the kernel (include/lmaze.h lmaze_rollout_sample;
+        the u8 env: lmaze_rollout_sample_u8): every env-step draws its action from the distribution of its key.  Exactly
+        one of
+        probs       float device tensor [S, 4] of non-negative weights, converted by _abi.sampling_thresholds();
+        logits      float device tensor [S, 4]: sampling_thresholds(softmax(logits.double() / temperature)), temperature > 0
+                    (a Boltzmann policy);
+        thresholds  the table itself, uint32 (or int32, the same bits) device tensor [S, 4], contiguous and 16-byte
+                    aligned: cumulative thresholds c0 <= c1 <= c2 and a reserved word per key.
+        S = G*G for key="ball" (ball_x * G + ball_y), G**4 for key="goal" (v3: goal cell * G*G + ball cell).  The action is
+        (r >= c0) + (r >= c1) + (r >= c2) for one Philox value r per (seed, env, epoch); a cumulative probability of 1 is
+        stored as 1 - 2**-32, so deterministic policies belong to rollout_policy().  Returns what rollout_policy() returns;
+        obs_t / obs_every, the rows and the restrictions are its own too.  The epoch advances by T."""
+        if self._tuner is not None or torch.cuda.is_current_stream_capturing():
+            raise ValueError("rollout_sample() is not available with a device-resident epoch or while the online tuner runs")
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
+            raise ValueError("T must be an int >= 0")
+        T, N, G = int(T), self.num_envs, self.grid
+        if sum(x is not None for x in (probs, logits, thresholds)) != 1:
+            raise ValueError("rollout_sample() wants exactly one of probs=, logits= and thresholds=")
+        if key not in _abi.KEY_MODES:
+            raise ValueError("key must be 'ball' or 'goal'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        entries = G ** 4 if key == "goal" else G * G
+        if thresholds is None:
+            src, name = (probs, "probs") if logits is None else (logits, "logits")
+            if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
+                    and tuple(src.shape) == (entries, 4)):
+                raise ValueError("%s must be a float tensor [%d, 4] on %s (key=%r, G=%d)" % (name, entries, self.device, key, G))
+            if logits is not None:
+                if not float(temperature) > 0.0:
+                    raise ValueError("temperature must be > 0")
+                src = torch.softmax(logits.double() / float(temperature), -1)
+            thresholds = _abi.sampling_thresholds(src)
+        if not (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
+                and thresholds.device == self.device and thresholds.is_contiguous() and tuple(thresholds.shape) == (entries, 4)
+                and thresholds.data_ptr() % 16 == 0):
+            raise ValueError("thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, 4] on %s (key=%r, G=%d)"
+                             % (entries, self.device, key, G))
+        self._check_rows("rollout_sample()", actions_t, key_t)
+        for name, t in (("actions_t", actions_t), ("key_t", key_t)):
+            if t is not None and t.shape[0] != T:
+                raise ValueError("%s must have T = %d rows" % (name, T))
+        k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
+        rows = self._traj_rows(T) if trajectory else None
+        if trajectory:
+            actions_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
+            key_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if key_t is None else key_t
+        name = "lmaze_rollout_sample" + ("_u8" if self._u8 else "")
+        slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
+        with self._guard():
+            rc = getattr(_abi.lib, name)(
+                self._pp, self._p_layout, thresholds.data_ptr(), _abi.KEY_MODES[key], T, self._p_ball,
+                self._p_goal if self._is_v3 else None, self._p_step, self._p_reward, self._p_done,
+                None if self._is_v3 else self._p_gc, self._p_obs, rows[0].data_ptr() if rows else None,
+                rows[1].data_ptr() if rows else None, None if actions_t is None else actions_t.data_ptr(),
+                None if key_t is None else key_t.data_ptr(), N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch,
+                self.env_base, slots, k, self._stream())
+        _abi.check(name, rc)
+        self._epoch += T
+        out = self._rollout_result(rows)
+        return out + (actions_t, key_t) if trajectory else out
+
     def observe(self, mask_ptr=None):
         """Re-render the compact planes of the current state (no transition)."""
         if self._u8:
@@ -480,6 +545,37 @@ class LmazeVecEnv(VecEnvBase):
             rc = _abi.lib.lmaze_render_expanded(self._p_obs, G, 1, self._cmask, Cn, out.data_ptr(), N, self._stream())
         _abi.check("lmaze_render_expanded", rc)
         return out
+
+
+def discounted_returns(reward_t, done_t, gamma, tail=None, out=None):
+    """Discounted returns-to-go over trajectory rows, in ONE launch (include/lmaze.h lmaze_returns): walking t = T-1 .. 0,
+    ret = reward_t[t] where done_t[t], else reward_t[t] + gamma * ret, starting from `tail` (float32[N], the value behind
+    the last row; default 0).  reward_t float32[T,N] and done_t bool / uint8[T,N], contiguous on one GPU -- the rows of
+    any rollout(trajectory=True), rollout_policy() or rollout_sample(), grid or foveal.  float32 with the product and the
+    sum rounded separately, so a float32 loop on the host gives the same bits.  out: float32[T,N] to fill (it may be
+    reward_t itself); default a new tensor.  Returns it."""
+    def rows(t, dtypes):
+        return (isinstance(t, torch.Tensor) and t.dtype in dtypes and t.dim() == 2 and t.is_cuda and t.is_contiguous()
+                and t.device == reward_t.device and tuple(t.shape) == tuple(reward_t.shape))
+    if not (isinstance(reward_t, torch.Tensor) and rows(reward_t, (torch.float32,))):
+        raise ValueError("reward_t must be a contiguous float32[T,N] tensor on a GPU")
+    if not rows(done_t, (torch.bool, torch.uint8)):
+        raise ValueError("done_t must be a contiguous bool or uint8 tensor of reward_t's shape, on its device")
+    T, N = reward_t.shape
+    if tail is not None and not (isinstance(tail, torch.Tensor) and tail.dtype == torch.float32 and tail.device == reward_t.device
+                                 and tail.is_contiguous() and tuple(tail.shape) == (N,)):
+        raise ValueError("tail must be a contiguous float32[N] tensor on reward_t's device")
+    if out is None:
+        out = torch.empty_like(reward_t)
+    elif not rows(out, (torch.float32,)):
+        raise ValueError("out must be a contiguous float32 tensor of reward_t's shape, on its device")
+    if T == 0 or N == 0:          # nothing to do; an empty tensor has no address to pass
+        return out
+    with torch.cuda.device(reward_t.device):
+        rc = _abi.lib.lmaze_returns(reward_t.data_ptr(), done_t.data_ptr(), None if tail is None else tail.data_ptr(), float(gamma),
+                                    out.data_ptr(), T, N, torch.cuda.current_stream(reward_t.device).cuda_stream)
+    _abi.check("lmaze_returns", rc)
+    return out
 
 
 def _validate_on_device(lay, need_goal=True):

@@ -369,6 +369,78 @@ int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t 
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len);
 
 /*
+ * SAMPLING closed-loop rollout: lmaze_rollout_policy with a categorical table policy -- an action drawn from a per-key
+ * distribution over the four actions -- in place of the epsilon-greedy one.  Replaces the user loop of T x (gather
+ * probs[key], draw the action (a multinomial), step(): v0:146-237, v3:220-402, with auto_reset != 0 the reset() of done
+ * envs first, v0:64-110) -- several launches per step -- by ONE launch; the action selection itself has no reference
+ * counterpart.  The arguments of lmaze_rollout_policy with `policy, key_mode, epsilon_u32` replaced by
+ *   thresholds   uint32[S, 4], 16 bytes per key and 16-byte aligned; S = G^2 for key_mode 0 and G^4 for key_mode 1, the
+ *                keys of lmaze_rollout_policy.  Words 0-2 are the cumulative thresholds c0 <= c1 <= c2 of the key's row;
+ *                word 3 is reserved: it is loaded with the rest, as one 128-bit read, and ignored
+ *   key_mode     as lmaze_rollout_policy
+ * The sampling rule.  Env i (global index e = env_base + i) at step t, ep = epoch + t:
+ *   1. auto_reset != 0 and the env done: the fused reset exactly as lmaze_rollout's, same draw, same epoch ep;
+ *   2. key of the state after that reset (coordinates clamped onto the grid), (c0, c1, c2) = thresholds[key];
+ *   3. r = the .x word of lmaze_rollout_policy's exploration draw: Philox4x32-10(counter (e_lo, e_hi, ep_lo,
+ *      ep_hi ^ 0x80000000), key (seed_lo, seed_hi)), the reset draw's counter with the top bit of its last word flipped;
+ *      action = (r >= c0) + (r >= c1) + (r >= c2), unsigned compares.  Always in 0..3, drawn on every env-step;
+ *   4. the transition of lmaze_step_v0 / _v3 with that action.
+ * So action k has probability (c_k - c_(k-1)) / 2^32 with c_(-1) = 0 and c_3 = 2^32.  The table is not validated: a
+ * non-monotone row still yields an action in 0..3 by that formula.  A cumulative probability of exactly 1 cannot be stored
+ * (it would be 2^32): a converter stores 2^32 - 1, i.e. 1 - 2^-32, so a row (1, 0, 0, 0) takes action 0 except for the one
+ * draw r = 0xFFFFFFFF in 2^32, which takes action 3; deterministic policies belong to lmaze_rollout_policy.  Converting
+ * probabilities p0..p3 (float64): a0 = p0, a1 = a0 + p1, a2 = a1 + p2, s = a2 + p3,
+ * c_k = min(floor(a_k / s * 2^32 + 0.5), 2^32 - 1).
+ * actions_t / key_t / reward_t / done_t rows, obs_t / obs_every and the planes as in lmaze_rollout_policy.  Always ONE
+ * launch of a sampling kernel form ("rollout_shared_kernel<v0, sample=ball, table=lds, obs_t>"): launch_hint bit 8 is not
+ * read; bits 12-14 and bit 15 behave as in lmaze_rollout_policy.  Where the table lives is decided by rule: ball-keyed and
+ * G <= 32 (at most 16 KiB) it is staged into LDS once per workgroup (table=lds) and counted where the envs per workgroup
+ * are fitted to LDS; otherwise (goal-conditioned, or G > 32) every env-step makes one 16-byte read from global memory
+ * (table=global) and no LDS is reserved for it.  The caller advances its epoch by T whether or not auto_reset is set:
+ * every env-step consumes a draw.
+ * Refusals: lmaze_rollout_policy's, in its order, with `thresholds` in the place of `policy`; LMAZE_E_ALIGN for a table
+ * that is not 16-byte aligned joins the other alignment refusals.
+ */
+int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
+                         int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count,
+                         int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t, int64_t n,
+                         int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t, int32_t obs_every,
+                         void* stream);
+
+/*
+ * lmaze_rollout_sample with the NARROW planes: replaces the same user loop around lmaze_step_u8 (v0:146-237, v3:220-402).
+ * obs8 / obs_t8, shapes and refusals as lmaze_rollout_policy_u8, then lmaze_rollout_sample's; one launch of
+ * rollout_shared_u8_kernel's sampling form, the staged table counted in its 64-KiB LDS fit.  The epoch advances by T.
+ */
+int lmaze_rollout_sample_u8(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
+                            int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
+                            int32_t* goal_count, uint8_t* obs8, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
+                            int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, uint8_t* obs_t8,
+                            int32_t obs_every, void* stream);
+
+/*
+ * As lmaze_describe_rollout_policy, for the sampling rollouts, e.g. "rollout_shared_kernel<v0, sample=ball, table=lds,
+ * obs_t> T=16 every=3 grid=..."; table=global where the thresholds are read from global memory.  Nothing is queued or
+ * dereferenced; no reference counterpart.
+ */
+int lmaze_describe_rollout_sample(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                  int32_t obs_every, int32_t key_mode, char* text_host, int32_t len);
+
+/*
+ * Discounted returns-to-go over the [T, N] rows a rollout writes; no reference counterpart (the reference keeps no
+ * trajectories).  Replaces the T dependent steps of a host-driven reverse loop by ONE launch, one lane per env:
+ *   ret = tail[i] (0 when tail is NULL); for t = T-1 .. 0:
+ *   ret = reward_t[t, i] where done_t[t, i] != 0, else reward_t[t, i] + gamma * ret;  returns_t[t, i] = ret
+ * in float32 with the product and the sum rounded separately (round to nearest even, never a fused multiply-add), so a
+ * float32 loop on the host reproduces every bit.  reward_t float[T,N], done_t uint8[T,N], tail float[N] or NULL (the
+ * value estimate behind the last row), returns_t float[T,N]; returns_t may be reward_t.  Refused: LMAZE_E_NULL reward_t,
+ * done_t or returns_t missing; LMAZE_E_COUNT T < 0 or n outside [0, LMAZE_MAX_ENVS].  T == 0 or n == 0 returns 0 with
+ * nothing read.
+ */
+int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t, int32_t T,
+                  int64_t n, void* stream);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes

@@ -1,0 +1,481 @@
+"""GPU: the sampling closed-loop one-launch rollouts (lmaze_rollout_sample / lmaze_rollout_sample_u8) against the C oracle,
+step by step, with the sampling rule of include/lmaze.h restated here in numpy -- never against the library's own
+rollouts.  Bit-exact: keys, actions, float32 bit patterns of reward, done, every recorded slot, the final state, planes and
+goal counts.  And lmaze_returns against a float32 numpy loop, bit for bit."""
+import functools
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import oracle_lib as O
+from helpers import bordered_random_layouts, f32_bits
+
+pytestmark = pytest.mark.gpu
+
+PKG = importlib.import_module("gym-lmaze_amd")
+ABI = importlib.import_module("gym-lmaze_amd._abi")
+DEV = torch.device("cuda", 0)
+M32 = np.uint64(0xFFFFFFFF)
+TOP = 0xFFFFFFFF
+ENV_BASE = (1 << 33) + 1000          # both words of the global env index and of the epoch enter the draws
+EPOCH = (1 << 35) + 77
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def philox(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on uint64 arrays holding 32-bit words (Salmon et al., SC'11); checked against the oracle's below."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0) & M32, np.uint64(k1) & M32
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M32, p0 & M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
+    return c0, c1, c2, c3
+
+
+def test_numpy_philox_is_the_oracles():
+    rs = np.random.RandomState(5)
+    w = rs.randint(0, 1 << 32, (64, 6), dtype=np.uint64)
+    w[0] = 0
+    w[1] = (1 << 32) - 1
+    got = np.stack(philox(w[:, 0], w[:, 1], w[:, 2], w[:, 3], w[0, 4], w[0, 5]), axis=1)
+    for i in range(64):
+        assert [int(x) for x in got[i]] == O.philox4x32_10([int(x) for x in w[i, :4]], [int(w[0, 4]), int(w[0, 5])]), i
+
+
+def sample_draw(seed, ep, env_global):
+    """r of (env, epoch): the .x word of the closed loop's draw -- the reset draw's counter with the top bit of its last
+    word flipped."""
+    e = np.asarray(env_global, dtype=np.uint64)
+    ep = np.uint64(ep)
+    return philox(e & M32, e >> np.uint64(32), ep & M32, ((ep >> np.uint64(32)) & M32) ^ np.uint64(0x80000000),
+                  np.uint64(seed) & M32, np.uint64(seed) >> np.uint64(32))[0]
+
+
+def sample_action(rows, r):
+    """(r >= c0) + (r >= c1) + (r >= c2), unsigned, whatever the row holds."""
+    c = rows.astype(np.uint64)
+    return ((r >= c[:, 0]).astype(np.int32) + (r >= c[:, 1]) + (r >= c[:, 2])).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _layouts(kind, G, N):
+    if kind == "per_env":
+        if N > 8192:                                        # a streaming batch: 4 099 mazes, tiled
+            return np.ascontiguousarray(np.resize(bordered_random_layouts(4099, G, 300 + G), (N, G, G)))
+        return bordered_random_layouts(N, G, 300 + G)
+    return bordered_random_layouts(1, G, 300 + G)[0]
+
+
+def _env(kind, variant, G, N, seed=21, step_limit=7, env_base=ENV_BASE, epoch=EPOCH, hint=0):
+    lay = _layouts(kind, G, N)
+    kw = dict(variant=variant, seed=seed, step_limit=step_limit, env_base=env_base)
+    if kind == "per_env":
+        env = PKG.LmazeVecEnv(N, per_env_layouts=lay, **kw)
+    else:
+        env = PKG.LmazeVecEnv(N, layout=lay, obs_dtype="u8" if kind == "u8" else "int32", **kw)
+    env._epoch = epoch
+    env.params.launch_hint = hint
+    # a spread of episode phases: some envs already done, some about to run into the step limit
+    rs = np.random.RandomState(G + N)
+    env.set_state(step_count=rs.randint(0, step_limit, N).astype(np.int32), done=(rs.rand(N) < 0.2).astype(np.uint8),
+                  reward=np.where(rs.rand(N) < 0.5, -0.01, -1.0).astype(np.float32))
+    return env, lay
+
+
+@functools.lru_cache(maxsize=None)
+def _thresholds(G, key, seed):
+    """uint32[S, 4] of explicit integer rows: mostly sorted random triples; a fifth with equal thresholds (actions of
+    probability zero), some all zero (always 3), some all 0xFFFFFFFF (always 0); the rows of ball cell (1, 1) -- one row
+    with the ball key -- deliberately NOT monotone; word 3 random, to be ignored."""
+    rs = np.random.RandomState(seed)
+    n = G ** 4 if key == "goal" else G * G
+    tab = np.sort(rs.randint(0, 1 << 32, (n, 3), dtype=np.uint64), axis=1)
+    kind = rs.randint(0, 20, n)
+    tab[kind == 0, 1] = tab[kind == 0, 0]                   # c0 == c1: action 1 never
+    tab[kind == 1, 2] = tab[kind == 1, 1]                   # c1 == c2: action 2 never
+    tab[kind == 2] = tab[kind == 2, :1]                     # all equal: 0 or 3
+    tab[kind == 3, 0] = 0                                   # c0 == 0: action 0 never
+    tab[kind == 4] = 0
+    tab[kind == 5] = TOP
+    tab[(G + 1)::G * G] = (3 << 30, 1 << 30, 1 << 31)       # not monotone: the formula still answers in 0..3
+    out = np.concatenate([tab, rs.randint(0, 1 << 32, (n, 1), dtype=np.uint64)], axis=1).astype(np.uint32)
+    return np.ascontiguousarray(out)
+
+
+def _dev_table(tab):
+    return torch.from_numpy(tab.view(np.int32)).to(DEV)     # the same bits
+
+
+def _replay(kind, variant, G, N, T, auto_reset, k, key, hint=0, seed=21, step_limit=7, table=None, env=None, lay=None, window=None,
+            **how):
+    """One rollout_sample() call against the oracle stepped T times from the env's host_state(); window = (first env,
+    count): the oracle replays that contiguous range of the batch only (streaming sizes).  Returns the oracle's sequences
+    and the call's outputs.  how: probs= / logits= instead of the explicit thresholds (table is then what they must become)."""
+    if env is None:
+        env, lay = _env(kind, variant, G, N, seed=seed, step_limit=step_limit, hint=hint)
+    v3 = variant == "v3"
+    tab = _thresholds(G, key, G * 7 + N % 1000) if table is None else table
+    lo, cnt = window if window else (0, N)
+    sl = slice(lo, lo + cnt)
+    st = {name: np.array(v[sl], copy=True) for name, v in env.host_state().items()}
+    p = O.params(O.VARIANT_V3 if v3 else O.VARIANT_V0, G, O.LAYOUT_PER_ENV if kind == "per_env" else O.LAYOUT_SHARED,
+                 env.step_limit, *env.rewards)
+    lay_c = np.ascontiguousarray(lay[sl] if kind == "per_env" else lay)
+    epoch0 = env._epoch
+    S = T // k if k else 0
+    obs_t = torch.full((S, N, G, G), 113, dtype=env.obs.dtype, device=DEV) if k else None
+    env.obs.fill_(113)
+    if not how:
+        how = dict(thresholds=_dev_table(tab))
+    out = env.rollout_sample(T, key=key, auto_reset=auto_reset, trajectory=True, obs_t=obs_t, obs_every=k, **how)
+    assert len(out) == 7 and env._epoch == epoch0 + T
+    reward_t, done_t, actions_t, key_t = (np.ascontiguousarray(_np(x[:, sl])) for x in out[3:])
+    slots = np.ascontiguousarray(_np(obs_t[:, sl])) if k else None
+    obs_ref = np.zeros((cnt, G, G), np.int32)
+    seq = {name: np.zeros((T, cnt), dt) for name, dt in (("key", np.int32), ("act", np.int32), ("reward", np.float32),
+                                                         ("done", np.uint8))}
+    eg = np.arange(cnt, dtype=np.uint64) + np.uint64(env.env_base + lo)
+    n_reset = 0
+    for t in range(T):
+        if auto_reset and st["done"].any():                # reset(mask = done) with the library's draw rule
+            n_reset += int(st["done"].sum())
+            O.reset(p, lay_c, st["done"].copy(), env.seed, epoch0 + t, st["ball_xy"], st["goal_xy"], st["step_count"],
+                    st["reward"], st["done"], env_base=env.env_base + lo)
+        key_ref = st["ball_xy"][:, 0] * G + st["ball_xy"][:, 1]
+        if key == "goal":
+            key_ref = (st["goal_xy"][:, 0] * G + st["goal_xy"][:, 1]) * G * G + key_ref
+        act = sample_action(tab[key_ref], sample_draw(env.seed, epoch0 + t, eg))
+        seq["key"][t], seq["act"][t] = key_ref, act
+        if v3:
+            O.step_v3(p, lay_c, act, st["ball_xy"], st["goal_xy"], st["step_count"], st["reward"], st["done"], obs_ref)
+        else:
+            O.step_v0(p, lay_c, act, st["ball_xy"], st["step_count"], st["reward"], st["done"], st["goal_count"], obs_ref)
+        seq["reward"][t], seq["done"][t] = st["reward"], st["done"]
+        assert (key_t[t] == key_ref).all(), ("key", t)
+        assert (actions_t[t] == act).all(), ("action", t)
+        assert (f32_bits(reward_t[t]) == f32_bits(st["reward"])).all(), ("reward", t)
+        assert (done_t[t].view(np.uint8) == st["done"]).all(), ("done", t)
+        if k and (t + 1) % k == 0:
+            assert (slots[(t + 1) // k - 1] == obs_ref.astype(slots.dtype)).all(), ("slot", t)
+    if T:
+        h = env.host_state()
+        for name in h:
+            assert (np.ascontiguousarray(h[name][sl]).view(np.uint8) == np.ascontiguousarray(st[name]).view(np.uint8)).all(), name
+        got = _np(env.obs[sl])
+        assert (got == obs_ref.astype(got.dtype)).all(), "final planes"
+    if k and T % k:                                        # the steps past the last slot store no planes
+        assert slots.shape[0] == T // k
+    return dict(seq=seq, out=out, final=st, resets=n_reset, actions=np.bincount(seq["act"].reshape(-1), minlength=4), env=env)
+
+
+KINDS = ["shared", "u8", "per_env"]
+KEYS = {"v0": ["ball"], "v3": ["ball", "goal"]}
+# (N, T, auto_reset, obs_every): N = 777 and 4 099 leave a partial last workgroup at every envs-per-workgroup size; the fused
+# reset on and off crossed with obs_every 0, 1 and 3
+CROSS = [(777, 13, False, 0), (4099, 11, True, 3), (777, 10, True, 1), (4099, 7, False, 1), (4099, 9, True, 0), (777, 8, False, 3)]
+# the same cross where a batch of 4 099 every-step slots would be hundreds of MB
+CROSS_LARGE = [(777, 13, False, 0), (4099, 7, True, 3), (777, 8, True, 1), (777, 7, False, 1), (4099, 9, True, 0), (777, 8, False, 3)]
+
+
+# ------------------------------------------------------------- 1. every kernel form, grid size and ragged batch
+@pytest.mark.parametrize("G", [8, 11, 12, 18, 32])
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("variant", ["v0", "v3"])
+def test_every_step_against_the_oracle(variant, kind, G):
+    """Ball-keyed tables here are staged in LDS (G <= 32), goal-keyed ones are read from global memory."""
+    resets, actions = 0, np.zeros(4, np.int64)
+    for N, T, auto_reset, k in CROSS:
+        for key in KEYS[variant]:
+            r = _replay(kind, variant, G, N, T, auto_reset, k, key)
+            resets += r["resets"]
+            actions += r["actions"]
+    assert resets > 777 and (actions > 0).all(), (resets, actions)
+
+
+@pytest.mark.parametrize("G", [33, 64])
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("variant", ["v0", "v3"])
+def test_ball_keyed_table_in_global_memory(variant, kind, G):
+    """G > 32: the ball-keyed table is too large to stage (16 G^2 > 16 KiB) and every env-step reads it from global memory."""
+    assert "table=global" in ABI.describe_rollout_sample(_env(kind, variant, G, 16)[0].params, 777, 8,
+                                                         with_obs="u8" if kind == "u8" else True)
+    resets, actions = 0, np.zeros(4, np.int64)
+    for N, T, auto_reset, k in CROSS_LARGE:
+        r = _replay(kind, variant, G, N, T, auto_reset, k, "ball")
+        resets += r["resets"]
+        actions += r["actions"]
+    assert resets > 777 and (actions > 0).all(), (resets, actions)
+
+
+# ------------------------------------------------------------- 2. every value of launch_hint bits 12-14; bits 8 and 15
+@pytest.mark.parametrize("sel", range(1, 8))
+@pytest.mark.parametrize("variant,kind,G,key", [("v0", "shared", 11, "ball"), ("v3", "shared", 12, "goal"), ("v3", "u8", 11, "ball"),
+                                                ("v0", "u8", 18, "ball"), ("v0", "per_env", 11, "ball"),
+                                                ("v3", "per_env", 18, "goal")])
+def test_envs_per_workgroup_hints(variant, kind, G, key, sel):
+    _replay(kind, variant, G, 4099, 9, True, 2, key, hint=sel << 12)
+
+
+@pytest.mark.parametrize("hint", [0x100, 1 << 15, 0x100 | (1 << 15) | (3 << 12)])
+@pytest.mark.parametrize("variant,kind", [("v0", "shared"), ("v3", "per_env"), ("v0", "u8")])
+def test_bit_8_is_not_read_and_bit_15_changes_nothing(variant, kind, hint):
+    _replay(kind, variant, 11, 4099, 8, True, 3, "ball", hint=hint)
+
+
+# ------------------------------------------------------------- 3. a streaming size
+@pytest.mark.parametrize("variant,kind,key", [("v0", "shared", "ball"), ("v3", "shared", "goal"), ("v0", "u8", "ball"),
+                                              ("v3", "u8", "ball"), ("v0", "per_env", "ball"), ("v3", "per_env", "goal")])
+def test_streaming_size(variant, kind, key):
+    """1M x 11x11: 484 MB of int32 planes per step, beyond every cache.  The oracle replays a sample of the batch: a
+    contiguous range, since the reset draw is indexed by the global env -- the first envs, a range across the middle that
+    starts inside a workgroup, and the last ones."""
+    N, T = 1 << 20, 4
+    env, lay = _env(kind, variant, 11, N, step_limit=3)
+    first = {name: np.array(v, copy=True) for name, v in env.host_state().items()}
+    resets = 0
+    for lo, cnt in ((0, 4099), (N // 2 - 1001, 4099), (N - 4099, 4099)):
+        env.set_state(**first)
+        env._epoch = EPOCH
+        resets += _replay(kind, variant, 11, N, T, True, 3, key, env=env, lay=lay, window=(lo, cnt))["resets"]
+    assert resets > 4099
+
+
+def test_t_zero_and_single_step():
+    for kind in KINDS:
+        env, lay = _env(kind, "v0", 11, 777)
+        before = {k: v.copy() for k, v in env.host_state().items()}
+        tab = torch.zeros((121, 4), dtype=torch.int32, device=DEV)
+        epoch = env._epoch
+        assert len(env.rollout_sample(0, thresholds=tab)) == 3
+        assert env._epoch == epoch
+        for k, v in env.host_state().items():
+            assert (v == before[k]).all()
+        _replay(kind, "v0", 11, 777, 1, True, 1, "ball", env=env, lay=lay)
+
+
+def test_off_grid_state_keys_are_clamped_onto_the_grid():
+    """State injected off the grid: the key takes the coordinates clamped, so no lookup leaves the table -- staged (G = 11)
+    or in global memory (the goal key; G = 33)."""
+    N = 777
+    for variant, key, G in (("v0", "ball", 11), ("v3", "goal", 11), ("v0", "ball", 33)):
+        env, _ = _env("shared", variant, G, N)
+        rs = np.random.RandomState(4)
+        ball = rs.randint(-5, G + 5, (N, 2)).astype(np.int32)
+        goal = rs.randint(-5, G + 5, (N, 2)).astype(np.int32)
+        env.set_state(ball_xy=ball, goal_xy=goal if variant == "v3" else None)
+        tab = _thresholds(G, key, 2)
+        epoch = env._epoch
+        out = env.rollout_sample(1, thresholds=_dev_table(tab), key=key, auto_reset=False, trajectory=True)
+        b, g = np.clip(ball, 0, G - 1), np.clip(goal, 0, G - 1)
+        want = b[:, 0] * G + b[:, 1] + ((g[:, 0] * G + g[:, 1]) * G * G if key == "goal" else 0)
+        r = sample_draw(env.seed, epoch, np.arange(N, dtype=np.uint64) + np.uint64(env.env_base))
+        assert (_np(out[6])[0] == want).all() and (_np(out[5])[0] == sample_action(tab[want], r)).all()
+
+
+def test_epoch_advances_by_t_and_results_follow_it():
+    G, N = 11, 777
+    tab = _dev_table(_thresholds(G, "ball", 1))
+    for auto_reset in (False, True):
+        env, _ = _env("shared", "v0", G, N)
+        e0 = env._epoch
+        out = env.rollout_sample(5, thresholds=tab, auto_reset=auto_reset)
+        assert len(out) == 3 and out[0] is env.obs and env._epoch == e0 + 5
+        env.rollout_sample(3, thresholds=tab, auto_reset=auto_reset)
+        assert env._epoch == e0 + 8
+    # the same call at another epoch draws other actions; T steps in one call are two calls of T / 2
+    a, _ = _env("shared", "v0", G, N)
+    b, _ = _env("shared", "v0", G, N)
+    c, _ = _env("shared", "v0", G, N)
+    b._epoch += 1
+    xa = a.rollout_sample(6, thresholds=tab, trajectory=True)[5]
+    xb = b.rollout_sample(6, thresholds=tab, trajectory=True)[5]
+    assert not torch.equal(xa, xb)
+    xc = torch.cat([c.rollout_sample(3, thresholds=tab, trajectory=True)[5], c.rollout_sample(3, thresholds=tab, trajectory=True)[5]])
+    assert torch.equal(xa, xc) and torch.equal(a._state, c._state)
+
+
+# ------------------------------------------------------------- 4. probs= and logits=
+@pytest.mark.parametrize("variant,kind,key", [("v0", "shared", "ball"), ("v3", "per_env", "goal"), ("v0", "u8", "ball")])
+def test_probs_are_sampling_thresholds_of_the_definition(variant, kind, key):
+    """probs= is thresholds=sampling_thresholds(probs): the conversion on the device is the float64 definition computed
+    here in numpy, word for word, and the rollout replays with that table."""
+    G, N = 11, 777
+    rs = np.random.RandomState(8)
+    S = G ** 4 if key == "goal" else G * G
+    probs = (rs.rand(S, 4) * (rs.rand(S, 4) < 0.8)).astype(np.float32)
+    probs[probs.sum(axis=1) == 0, 2] = 1.0
+    probs[:3] = [[0.7, 0.1, 0.15, 0.05], [1, 0, 0, 0], [0, 0, 0, 1]]
+    p64 = probs.astype(np.float64)
+    a0 = p64[:, 0]
+    a1 = a0 + p64[:, 1]
+    a2 = a1 + p64[:, 2]
+    s = a2 + p64[:, 3]
+    want = np.stack([np.minimum(np.floor(a / s * 4294967296.0 + 0.5), 4294967295.0) for a in (a0, a1, a2)] + [np.zeros(S)], axis=1)
+    want = want.astype(np.uint64).astype(np.uint32)
+    dev = torch.from_numpy(probs).to(DEV)
+    got = ABI.sampling_thresholds(dev)
+    assert got.dtype == torch.uint32 and got.device == dev.device and got.data_ptr() % 16 == 0
+    assert (_np(got.view(torch.int32)).view(np.uint32) == want).all()
+    r = _replay(kind, variant, G, N, 12, True, 3, key, table=want, probs=dev)
+    assert (r["actions"] > 0).all()
+
+
+def test_logits_are_a_softmax_with_a_temperature():
+    """logits= means sampling_thresholds(softmax(logits.double() / temperature)).  Against a numpy float64 softmax: exp may
+    differ in its last bit, 1e-7 of a count, so only a rounding tie can move a threshold -- by one."""
+    G, N = 11, 777
+    rs = np.random.RandomState(9)
+    logits = (rs.randn(G * G, 4) * 3).astype(np.float32)
+    dev = torch.from_numpy(logits).to(DEV)
+    for temperature in (1.0, 0.25, 7.5):
+        want = ABI.sampling_thresholds(torch.softmax(dev.double() / temperature, -1))
+        z = logits.astype(np.float64) / temperature
+        e = np.exp(z - z.max(axis=1, keepdims=True))
+        p = e / e.sum(axis=1, keepdims=True)
+        a = np.cumsum(p, axis=1)
+        ref = np.minimum(np.floor(a[:, :3] / a[:, 3:] * 4294967296.0 + 0.5), 4294967295.0).astype(np.int64)
+        tab = _np(want.view(torch.int32)).view(np.uint32)
+        assert np.abs(tab[:, :3].astype(np.int64) - ref).max() <= 1
+        r = _replay("shared", "v0", G, N, 9, True, 0, "ball", table=tab, logits=dev, temperature=temperature)
+        assert (r["actions"] > 0).all()
+    # a cold policy is nearly greedy, a hot one nearly uniform
+    cold = _replay("shared", "v0", G, N, 9, True, 0, "ball", logits=dev, temperature=1e-3,
+                   table=_np(ABI.sampling_thresholds(torch.softmax(dev.double() / 1e-3, -1)).view(torch.int32)).view(np.uint32))
+    greedy = logits.argmax(axis=1)
+    assert (cold["seq"]["act"] == greedy[cold["seq"]["key"]]).mean() > 0.999
+
+
+def test_python_surface_refusals():
+    G, N = 11, 64
+    env, _ = _env("shared", "v0", G, N)
+    v3, _ = _env("shared", "v3", G, N)
+    thr = torch.zeros((G * G, 4), dtype=torch.int32, device=DEV)
+    probs = torch.full((G * G, 4), 0.25, device=DEV)
+    rows = torch.empty((6, N), dtype=torch.int32, device=DEV)
+    ok = torch.empty((2, N, G, G), dtype=torch.int32, device=DEV)
+    odd = torch.zeros((G * G + 1, 4), dtype=torch.int32, device=DEV).reshape(-1)[2:2 + G * G * 4].reshape(G * G, 4)   # 8 bytes off
+    neg = probs.clone()
+    neg[5, 1] = -0.1
+    nan = probs.clone()
+    nan[7, 0] = float("nan")
+    zero = probs.clone()
+    zero[9] = 0
+    bad = [dict(), dict(probs=probs, logits=probs), dict(probs=probs, thresholds=thr), dict(logits=probs, thresholds=thr),
+           dict(probs=probs, logits=probs, thresholds=thr),                                   # exactly one of the three
+           dict(thresholds=thr.to(torch.int64)), dict(thresholds=thr.float()), dict(thresholds=thr[:-1]), dict(thresholds=thr.cpu()),
+           dict(thresholds=thr[:, :3]), dict(thresholds=thr.reshape(-1)), dict(thresholds=odd),
+           dict(thresholds=torch.zeros((G ** 4, 4), dtype=torch.int32, device=DEV)),         # the goal-keyed size, ball key
+           dict(thresholds=thr, key="goal"), dict(thresholds=thr, key="cell"),                # v0 keeps no goal
+           dict(probs=probs[:, :3]), dict(probs=probs.to(torch.int32)), dict(probs=probs.cpu()), dict(probs=probs[:5]),
+           dict(probs=probs.reshape(-1)), dict(probs=neg), dict(probs=nan), dict(probs=zero),
+           dict(logits=probs.cpu()), dict(logits=probs[:5]), dict(logits=probs, temperature=0.0),
+           dict(logits=probs, temperature=-1.0), dict(logits=probs, temperature=float("nan")), dict(logits=nan),
+           dict(thresholds=thr, actions_t=rows[:5], trajectory=True), dict(thresholds=thr, key_t=rows.to(torch.int64)),
+           dict(thresholds=thr, obs_t=ok, obs_every=0), dict(thresholds=thr, obs_t=None, obs_every=3),
+           dict(thresholds=thr, obs_every=-1), dict(thresholds=thr, obs_t=ok[:1], obs_every=3), dict(thresholds=thr, obs_every=None)]
+    epoch = env._epoch
+    for kw in bad:
+        with pytest.raises(ValueError):
+            env.rollout_sample(6, **kw)
+    for T in (-1, 2.5, None, True):
+        with pytest.raises(ValueError):
+            env.rollout_sample(T, thresholds=thr)
+    with pytest.raises(ValueError):
+        v3.rollout_sample(6, thresholds=thr, key="goal")                                     # G**2 rows, G**4 wanted
+    assert env._epoch == epoch                                                                # a refusal consumes nothing
+    big = PKG.LmazeVecEnv(1 << 20, variant="v0", layout=PKG.layouts.open_room(11, (5, 5)), online_autotune=True)
+    assert big.tuning_progress() is not None
+    with pytest.raises(ValueError, match="device-resident epoch or while the online tuner runs"):
+        big.rollout_sample(2, thresholds=thr)
+    del big
+    out = env.rollout_sample(6, thresholds=thr.view(torch.uint32), trajectory=True, actions_t=rows, obs_t=ok, obs_every=3)
+    assert len(out) == 7 and out[5] is rows and out[6].shape == (6, N) and out[6].dtype == torch.int32
+    assert (out[5] == 3).all()                                                                # all-zero rows: always action 3
+    assert len(v3.rollout_sample(6, thresholds=torch.zeros((G ** 4, 4), dtype=torch.int32, device=DEV), key="goal")) == 3
+
+
+# ------------------------------------------------------------- 5. discounted returns
+def returns_ref(reward, done, gamma, tail=None):
+    """The float32 loop of include/lmaze.h: a float32 multiply, then a float32 add."""
+    T, N = reward.shape
+    g = np.float32(gamma)
+    ret = np.zeros(N, np.float32) if tail is None else tail.astype(np.float32).copy()
+    out = np.empty((T, N), np.float32)
+    for t in range(T - 1, -1, -1):
+        disc = (g * ret).astype(np.float32)
+        ret = np.where(done[t] != 0, reward[t], (reward[t] + disc).astype(np.float32)).astype(np.float32)
+        out[t] = ret
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _rows(T, N, rate):
+    rs = np.random.RandomState(T * 1000 + N + rate)
+    reward = rs.choice(np.array([-0.0, 0.0, -0.01, -1.0, 100.0, 1e-30, 1e30], np.float32), (T, N))
+    mix = rs.rand(T, N) < 0.3
+    reward[mix] = rs.randn(int(mix.sum())).astype(np.float32)
+    done = (rs.rand(T, N) * 100 < rate).astype(np.uint8)
+    tail = rs.randn(N).astype(np.float32)
+    reward.setflags(write=False), done.setflags(write=False), tail.setflags(write=False)
+    return reward, done, tail
+
+
+@pytest.mark.parametrize("gamma", [0.0, 0.99, 1.0])
+@pytest.mark.parametrize("T,N", [(1, 1), (13, 777), (64, 4099)])
+def test_discounted_returns_bit_exact(T, N, gamma):
+    """T = 13 and 64 are no multiples of the rows a lane keeps in flight and a multiple of them; N = 777 and 4 099 leave
+    a partial last workgroup.  Rewards hold the literal -0.0 and magnitudes from 1e-30 to 1e30, whose sums round away the
+    small terms; nothing overflows, so no NaN's payload is compared."""
+    for rate in (0, 20, 100):
+        reward, done, tail = _rows(T, N, rate)
+        r_dev, d_dev, tail_dev = (torch.from_numpy(x.copy()).to(DEV) for x in (reward, done, tail))
+        for tl, tl_dev in ((None, None), (tail, tail_dev)):
+            want = returns_ref(reward, done, gamma, tl)
+            assert np.isfinite(want).all()
+            got = PKG.discounted_returns(r_dev, d_dev, gamma, tail=tl_dev)
+            assert got.shape == (T, N) and got.dtype == torch.float32 and got.data_ptr() != r_dev.data_ptr()
+            assert (f32_bits(_np(got)) == f32_bits(want)).all(), (rate, tl is None)
+            assert (f32_bits(_np(r_dev)) == f32_bits(reward)).all()                          # the input is left alone
+            out = torch.empty_like(r_dev)
+            assert PKG.discounted_returns(r_dev, d_dev.view(torch.bool), gamma, tail=tl_dev, out=out) is out
+            assert torch.equal(out.view(torch.int32), got.view(torch.int32))
+            alias = r_dev.clone()                                                            # returns_t onto reward_t
+            assert PKG.discounted_returns(alias, d_dev, gamma, tail=tl_dev, out=alias) is alias
+            assert torch.equal(alias.view(torch.int32), got.view(torch.int32))
+        if rate == 100:
+            assert (f32_bits(_np(got)) == f32_bits(reward)).all()                             # every row restarts
+
+
+def test_discounted_returns_of_rollout_rows():
+    """Fed straight from rollout_sample(trajectory=True) -- float32 rows and bool done rows -- and from a foveal rollout."""
+    env, _ = _env("shared", "v0", 11, 4099)
+    out = env.rollout_sample(40, probs=torch.full((121, 4), 0.25, device=DEV), trajectory=True)
+    ret = PKG.discounted_returns(out[3], out[4], 0.95)
+    want = returns_ref(_np(out[3]), _np(out[4]).view(np.uint8), 0.95)
+    assert (f32_bits(_np(ret)) == f32_bits(want)).all() and _np(out[4]).any() and not _np(out[4]).all()
+    fov = PKG.LmazeFovealVecEnv(777, variant="v2", seed=3)
+    acts = torch.randint(0, 4, (30, 777), dtype=torch.int32, device=DEV)
+    fo = fov.rollout(acts, auto_reset=True, trajectory=True)
+    tail = torch.randn(777, device=DEV)
+    ret = PKG.discounted_returns(fo[3], fo[4], 0.9, tail=tail)
+    assert (f32_bits(_np(ret)) == f32_bits(returns_ref(_np(fo[3]), _np(fo[4]).view(np.uint8), 0.9, _np(tail)))).all()
+
+
+def test_discounted_returns_refusals():
+    r = torch.zeros((5, 64), device=DEV)
+    d = torch.zeros((5, 64), dtype=torch.uint8, device=DEV)
+    for kw in (dict(reward_t=r.cpu()), dict(reward_t=r.double()), dict(reward_t=r[0]), dict(reward_t=r.t()), dict(done_t=d[:4]),
+               dict(done_t=d.float()), dict(done_t=d.cpu()), dict(done_t=d.t().contiguous()), dict(tail=torch.zeros(63, device=DEV)),
+               dict(tail=torch.zeros(64)), dict(tail=torch.zeros(64, dtype=torch.float64, device=DEV)), dict(out=r[:4]),
+               dict(out=r.double()), dict(out=r.cpu())):
+        args = dict(reward_t=r, done_t=d, gamma=0.9)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            PKG.discounted_returns(**args)
+    assert PKG.discounted_returns(r[:0], d[:0], 0.9).shape == (0, 64)
