@@ -35,7 +35,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout",
            "lmaze_rollout_obs", "lmaze_foveal_rollout_obs", "lmaze_rollout_u8", "lmaze_rollout_obs_u8",
            "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy",
-           "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns")
+           "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns",
+           "lmaze_describe_foveal_rollout_obs")
 
 
 class LmazeParams(C.Structure):
@@ -178,6 +179,8 @@ def _load():
     lib.lmaze_returns.argtypes = [vp, vp, vp, C.c_float, vp, i32, i64, vp]
     lib.lmaze_describe_foveal_rollout.restype = C.c_int
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_describe_foveal_rollout_obs.restype = C.c_int
+    lib.lmaze_describe_foveal_rollout_obs.argtypes = [FP, i64, i32, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -285,12 +288,18 @@ def sampling_thresholds(probs):
     return torch.where(c >= 2147483648, c - 4294967296, c).to(torch.int32).view(torch.uint32)   # the same 32 bits
 
 
-def describe_foveal_rollout(params, n, T, auto_reset=False, two_level=False):
-    """The kernel / grid / launch policy lmaze_foveal_rollout would queue for n envs and T steps."""
+def describe_foveal_rollout(params, n, T, auto_reset=False, two_level=False, obs_every=None):
+    """The kernel / grid / launch policy lmaze_foveal_rollout would queue for n envs and T steps; obs_every (None: the plain
+    rollout): lmaze_foveal_rollout_obs with that k (lmaze_describe_foveal_rollout_obs)."""
     buf = C.create_string_buffer(256)
-    check("lmaze_describe_foveal_rollout", lib.lmaze_describe_foveal_rollout(C.byref(params), int(n), int(T),
-                                                                             1 if auto_reset else 0, 1 if two_level else 0,
-                                                                             buf, 256))
+    if obs_every is None:
+        check("lmaze_describe_foveal_rollout", lib.lmaze_describe_foveal_rollout(C.byref(params), int(n), int(T),
+                                                                                 1 if auto_reset else 0, 1 if two_level else 0,
+                                                                                 buf, 256))
+    else:
+        check("lmaze_describe_foveal_rollout_obs",
+              lib.lmaze_describe_foveal_rollout_obs(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
+                                                    1 if two_level else 0, int(obs_every), buf, 256))
     return buf.value.decode("ascii", "replace")
 
 

@@ -865,9 +865,11 @@ int lmaze_foveal_rollout_obs(const LmazeFovealParams* params, const uint8_t* lay
                           foveal_reward_t, foveal_done_t, &rec, stream);
 }
 
-int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
-                                  int32_t two_level, char* text_host, int32_t len) {
+// lmaze_describe_foveal_rollout and, obs_every != null, lmaze_describe_foveal_rollout_obs
+static int describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t two_level,
+                                   const int32_t* obs_every, char* text_host, int32_t len) {
     if (!params || !text_host || len < 1) return LMAZE_E_NULL;
+    if (obs_every && *obs_every < 1) return LMAZE_E_COUNT;                 // the recording request first, as the entry point
     const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
     if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
         return LMAZE_E_VARIANT;
@@ -877,6 +879,10 @@ int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, in
     if (n < 0 || n > LMAZE_MAX_ENVS || T < 0) return LMAZE_E_COUNT;
     text_host[0] = 0;
     if (n == 0 || T == 0) return 0;
+    if (obs_every) {
+        if (v56 && params->grid != 18) return LMAZE_E_GRID;                // their recording form exists at G = 18 only
+        if (params->variant == LMAZE_VARIANT_V1 && params->grid != 14) return LMAZE_E_GRID;   // v1's at G = 14 only
+    }
     LaunchInfo info;
     memset(&info, 0, sizeof(info));
     LmazeFovealBuffers none;
@@ -884,15 +890,27 @@ int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, in
     FovealArgs a = make_foveal_args(params, nullptr, &none, n);     // nothing is dereferenced: the launcher fills `info`
     a.auto_reset = (two_level || (!v56 && auto_reset)) ? 1 : 0;
     a.info = &info;
-    FovealRoll ro;
-    memset(&ro, 0, sizeof(ro));
-    ro.T = T;
-    const int rc = (int)launch_foveal_rollout(a, ro, nullptr);
+    FovealRollObs rr;
+    memset(&rr, 0, sizeof(rr));
+    rr.T = T;
+    rr.every = obs_every ? *obs_every : 1;
+    const int rc = obs_every ? (int)launch_foveal_rollout(a, rr, nullptr)
+                             : (int)launch_foveal_rollout(a, static_cast<const FovealRoll&>(rr), nullptr);
     if (rc) return rc;
     snprintf(text_host, (size_t)len, "%s T=%d grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d",
              info.kernel, T, (long long)info.grid, info.block, (long long)info.lds, info.envs_per_workgroup,
              info.workgroups_per_cu, info.chunks);
     return 0;
+}
+
+int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                  int32_t two_level, char* text_host, int32_t len) {
+    return describe_foveal_rollout(params, n, T, auto_reset, two_level, nullptr, text_host, len);
+}
+
+int lmaze_describe_foveal_rollout_obs(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                      int32_t two_level, int32_t obs_every, char* text_host, int32_t len) {
+    return describe_foveal_rollout(params, n, T, auto_reset, two_level, &obs_every, text_host, len);
 }
 
 int lmaze_foveal_reset(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* mask, int32_t place,

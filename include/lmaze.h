@@ -700,6 +700,11 @@ int lmaze_foveal_rollout_obs(const LmazeFovealParams* params, const uint8_t* lay
 int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
                                   int32_t two_level, char* text_host, int32_t len);
 
+/* The same for lmaze_foveal_rollout_obs with this obs_every: the recording form of the kernel ("..., obs_t>" in the text).
+ * Its refusals are the entry point's: LMAZE_E_COUNT obs_every < 1; LMAZE_E_GRID v5/v6 at G != 18, v1 at G != 14. */
+int lmaze_describe_foveal_rollout_obs(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                      int32_t two_level, int32_t obs_every, char* text_host, int32_t len);
+
 /*
  * v6 safeFovealGoal() (v6:505-523): for every env one window cell index 0..24 drawn uniformly from the
  * cells of the 5x5 window around the ball that are not 'W' (the reference rejects on np.random; here
