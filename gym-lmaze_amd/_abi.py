@@ -36,7 +36,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_rollout_obs", "lmaze_foveal_rollout_obs", "lmaze_rollout_u8", "lmaze_rollout_obs_u8",
            "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy",
            "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns",
-           "lmaze_describe_foveal_rollout_obs")
+           "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
+           "lmaze_describe_table_stats")
 
 
 class LmazeParams(C.Structure):
@@ -177,6 +178,14 @@ def _load():
     lib.lmaze_describe_rollout_sample.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_returns.restype = C.c_int
     lib.lmaze_returns.argtypes = [vp, vp, vp, C.c_float, vp, i32, i64, vp]
+    lib.lmaze_advantages.restype = C.c_int
+    lib.lmaze_advantages.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, i64, vp]
+    lib.lmaze_advantages_table.restype = C.c_int
+    lib.lmaze_advantages_table.argtypes = [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, i32, i64, vp]
+    lib.lmaze_table_stats.restype = C.c_int
+    lib.lmaze_table_stats.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp]
+    lib.lmaze_describe_table_stats.restype = C.c_int
+    lib.lmaze_describe_table_stats.argtypes = [i64, i64, i32, C.c_char_p, i32]
     lib.lmaze_describe_foveal_rollout.restype = C.c_int
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_describe_foveal_rollout_obs.restype = C.c_int
@@ -261,6 +270,14 @@ def describe_rollout_sample(params, n, T, auto_reset=True, with_obs=True, obs_ev
           lib.lmaze_describe_rollout_sample(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
                                             2 if with_obs == "u8" else (1 if with_obs else 0), int(obs_every),
                                             KEY_MODES[key] if key in KEY_MODES else int(key), buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+def describe_table_stats(m, keys, actions=4):
+    """The kernel / grid / LDS lmaze_table_stats would queue for m samples and a [keys, actions] table
+    (lmaze_describe_table_stats): table_stats_kernel<lds> up to 4096 bins, <global> above; "" for m == 0."""
+    buf = C.create_string_buffer(256)
+    check("lmaze_describe_table_stats", lib.lmaze_describe_table_stats(int(m), int(keys), int(actions), buf, 256))
     return buf.value.decode("ascii", "replace")
 
 

@@ -455,6 +455,60 @@ int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tai
     return (int)launch_returns(reward_t, done_t, tail, gamma, returns_t, T, n, (hipStream_t)stream);
 }
 
+static int advantages(const AdvantageArgs& a, bool required, int64_t keys, void* stream) {
+    if (!required) return LMAZE_E_NULL;
+    if (a.T < 0 || a.n < 0 || a.n > LMAZE_MAX_ENVS || keys < 1) return LMAZE_E_COUNT;
+    return (int)launch_advantages(a, (hipStream_t)stream);
+}
+
+int lmaze_advantages(const float* reward_t, const uint8_t* done_t, const float* value_t, const float* tail, float gamma, float lambda,
+                     float* adv_t, float* target_t, int32_t T, int64_t n, void* stream) {
+    const AdvantageArgs a{reward_t, done_t, value_t, tail, nullptr, nullptr, nullptr, 0, gamma, gamma * lambda, adv_t, target_t, T, n};
+    return advantages(a, reward_t && done_t && value_t && adv_t, 1, stream);
+}
+
+int lmaze_advantages_table(const float* reward_t, const uint8_t* done_t, const int32_t* key_t, const int32_t* key_tail,
+                           const float* values, int64_t keys, float gamma, float lambda, float* adv_t, float* target_t, int32_t T,
+                           int64_t n, void* stream) {
+    // an int32 key is compared unsigned: a table beyond 2^31 entries has no key that could reach past it
+    const uint32_t ku = keys > ((int64_t)1 << 31) ? (uint32_t)1 << 31 : (uint32_t)(keys < 0 ? 0 : keys);
+    const AdvantageArgs a{reward_t, done_t, nullptr, nullptr, key_t, key_tail, values, ku, gamma, gamma * lambda, adv_t, target_t, T, n};
+    return advantages(a, reward_t && done_t && key_t && values && adv_t, keys, stream);
+}
+
+static int check_table_stats(const void* key_t, const void* actions_t, const void* weight_t, int64_t m, int64_t keys, int32_t actions,
+                             const void* count, const void* total) {
+    if (!key_t || !count) return LMAZE_E_NULL;
+    if ((weight_t != nullptr) != (total != nullptr)) return LMAZE_E_NULL;
+    if (m < 0 || keys < 1 || actions < 1 || actions > 255 || keys > ((int64_t)1 << 28) || keys * actions > ((int64_t)1 << 28))
+        return LMAZE_E_COUNT;
+    if (!actions_t && actions != 1) return LMAZE_E_COUNT;
+    return 0;
+}
+
+int lmaze_table_stats(const int32_t* key_t, const int32_t* actions_t, const float* weight_t, int64_t m, int64_t keys, int32_t actions,
+                      int64_t* count, int64_t* total_q24, void* stream) {
+    const int rc = check_table_stats(key_t, actions_t, weight_t, m, keys, actions, count, total_q24);
+    if (rc || m == 0) return rc;
+    if (misaligned(key_t, 4) || misaligned(actions_t, 4) || misaligned(weight_t, 4) || misaligned(count, 8) || misaligned(total_q24, 8))
+        return LMAZE_E_ALIGN;
+    const TableStatsArgs a{key_t, actions_t, weight_t, m, (uint32_t)keys, (uint32_t)actions,
+                           reinterpret_cast<unsigned long long*>(count), reinterpret_cast<unsigned long long*>(total_q24)};
+    return (int)launch_table_stats(a, (hipStream_t)stream);
+}
+
+int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* text_host, int32_t len) {
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    // nothing is dereferenced: fabricated addresses stand for the rows, whose presence decides nothing the line reports
+    const int rc = check_table_stats(text_host, actions == 1 ? nullptr : text_host, nullptr, m, keys, actions, text_host, nullptr);
+    if (rc || m == 0) return rc;
+    const TableStatsPlan p = plan_table_stats(m, keys, actions);
+    snprintf(text_host, (size_t)len, "table_stats_kernel<%s> grid=%lld block=%d lds=%lld bins=%lld", p.lds ? "lds" : "global",
+             (long long)p.grid, LMAZE_BLOCK, (long long)p.lds_bytes, (long long)p.bins);
+    return 0;
+}
+
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
                            char* text_host, int32_t len) {
     int rc = check_params(params, n);

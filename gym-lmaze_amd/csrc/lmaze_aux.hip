@@ -2,6 +2,7 @@
 // (reference reset(): lmaze_env.py:64-110, lmaze_env_v3.py:134-167) and the
 // reference-layout x E nearest-neighbour render (lmaze_env.py:217-234).
 #include "lmaze_common.h"
+#include "lmaze_learn.h"
 
 namespace lmaze {
 
@@ -315,6 +316,162 @@ hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const fl
     const int64_t blocks = (n + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
     if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(returns_kernel, dim3((unsigned)blocks), dim3(LMAZE_BLOCK), 0, s, reward_t, done_t, tail, gamma, returns_t, T, n);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// GAE(lambda) over trajectory rows (lmaze_advantages / lmaze_advantages_table): returns_kernel's shape -- one lane per env
+// walks t = T-1 .. 0, the rows are loaded ADV_ROWS at a time before the dependent chain (adv, and the value of the row
+// behind) and stored after it.  TABLE: a value is values[key] for 0 <= key < keys and 0 otherwise; the eight key loads, then
+// the eight gathers are issued before the chain, each gather unconditional on an index that is 0 for a key out of range
+// (keys >= 1), so nothing is read past the table and no load waits on a branch.  A lane reads the rows of its own column
+// before it stores them and touches no other column: adv_t may be reward_t and target_t may be value_t.
+// ------------------------------------------------------------------------------------
+#define ADV_ROWS 8
+__device__ __forceinline__ float table_value(const float* values, uint32_t keys, int32_t key) {
+    const bool in = (uint32_t)key < keys;
+    const float v = values[in ? key : 0];
+    return in ? v : 0.0f;
+}
+template <bool TABLE>
+__global__ __launch_bounds__(LMAZE_BLOCK) void advantages_kernel(const AdvantageArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * LMAZE_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const size_t n = (size_t)a.n;
+    float v_next;
+    if (TABLE) v_next = a.key_tail ? table_value(a.values, a.keys, a.key_tail[i]) : 0.0f;
+    else v_next = a.tail ? a.tail[i] : 0.0f;
+    float adv = 0.0f;
+    for (int t0 = a.T - 1; t0 >= 0; t0 -= ADV_ROWS) {
+        float r[ADV_ROWS], v[ADV_ROWS], out[ADV_ROWS];
+        uint8_t d[ADV_ROWS];
+        int32_t k[ADV_ROWS];
+#pragma unroll
+        for (int j = 0; j < ADV_ROWS; ++j) {
+            const bool in = t0 - j >= 0;
+            const size_t at = (size_t)(in ? t0 - j : 0) * n + i;
+            r[j] = in ? a.reward_t[at] : 0.0f;
+            d[j] = in ? a.done_t[at] : (uint8_t)0;
+            if (TABLE) k[j] = in ? a.key_t[at] : -1;
+            else v[j] = in ? a.value_t[at] : 0.0f;
+        }
+        if (TABLE) {
+#pragma unroll
+            for (int j = 0; j < ADV_ROWS; ++j) v[j] = table_value(a.values, a.keys, k[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < ADV_ROWS; ++j) {
+            if (t0 - j < 0) break;
+            adv = lmaze_gae_step(r[j], d[j], v[j], v_next, a.gamma, a.gl, adv);
+            out[j] = adv;
+            v_next = v[j];
+        }
+#pragma unroll
+        for (int j = 0; j < ADV_ROWS; ++j) {
+            if (t0 - j < 0) break;
+            const size_t at = (size_t)(t0 - j) * n + i;
+            a.adv_t[at] = out[j];
+            if (a.target_t) a.target_t[at] = lmaze_gae_target(out[j], v[j]);
+        }
+    }
+}
+
+hipError_t launch_advantages(const AdvantageArgs& a, hipStream_t s) {
+    if (a.T <= 0 || a.n == 0) return hipSuccess;
+    const int64_t blocks = (a.n + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
+    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
+    if (a.values) hipLaunchKernelGGL(advantages_kernel<true>, dim3((unsigned)blocks), dim3(LMAZE_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(advantages_kernel<false>, dim3((unsigned)blocks), dim3(LMAZE_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// Counts and Q24 sums per (key, action) (lmaze_table_stats).  Integer accumulation: the sums do not depend on the order
+// the samples arrive in, so the two paths and any two runs give the same 64 bits.
+//   LDS:    every workgroup keeps count[bins] and sum[bins] (8 bytes each) in LDS, grid-strides over the samples with LDS
+//           atomics and flushes its non-zero bins with one 64-bit global atomic add each.
+//   global: 64-bit global atomics per sample.
+// The rows are read as 16-byte vectors between a scalar head (up to the first 16-byte boundary of key_t) and a scalar tail
+// where the given rows share key_t's offset within 16 bytes; otherwise (rows sliced differently) sample by sample.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void table_add(unsigned long long* cnt, unsigned long long* sum, const TableStatsArgs& a, int32_t key,
+                                          int32_t action, float w) {
+    const int32_t bin = lmaze_table_bin(key, action, a.keys, a.actions);
+    if (bin < 0) return;
+    if (sum && !lmaze_q24_ok(w)) return;
+    atomicAdd(cnt + bin, 1ull);
+    if (sum) atomicAdd(sum + bin, (unsigned long long)lmaze_q24(w));
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(LMAZE_BLOCK) void table_stats_kernel(const TableStatsArgs a, int32_t bins, int32_t head, int64_t nvec) {
+    extern __shared__ int4 lds4[];
+    unsigned long long* cnt = a.count;
+    unsigned long long* sum = a.total;
+    if (LDS) {
+        unsigned long long* tab = reinterpret_cast<unsigned long long*>(lds4);       // count[bins], sum[bins]
+        for (int b = threadIdx.x; b < 2 * bins; b += LMAZE_BLOCK) tab[b] = 0;
+        __syncthreads();
+        cnt = tab;
+        sum = a.total ? tab + bins : nullptr;
+    }
+    const int64_t tid = (int64_t)blockIdx.x * LMAZE_BLOCK + threadIdx.x, stride = (int64_t)gridDim.x * LMAZE_BLOCK;
+    const int64_t vend = head + 4 * nvec, nscalar = a.m - 4 * nvec;   // samples [0, head) and [vend, m) one by one
+    for (int64_t s = tid; s < nscalar; s += stride) {
+        const int64_t at = s < head ? s : s - head + vend;
+        table_add(cnt, sum, a, a.key_t[at], a.actions_t ? a.actions_t[at] : 0, a.weight_t ? a.weight_t[at] : 0.0f);
+    }
+    const int4* k4 = reinterpret_cast<const int4*>(a.key_t + head);
+    const int4* a4 = a.actions_t ? reinterpret_cast<const int4*>(a.actions_t + head) : nullptr;
+    const float4* w4 = a.weight_t ? reinterpret_cast<const float4*>(a.weight_t + head) : nullptr;
+    for (int64_t q = tid; q < nvec; q += stride) {
+        const int4 k = k4[q];
+        const int4 ac = a4 ? a4[q] : make_int4(0, 0, 0, 0);
+        const float4 w = w4 ? w4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        table_add(cnt, sum, a, k.x, ac.x, w.x);
+        table_add(cnt, sum, a, k.y, ac.y, w.y);
+        table_add(cnt, sum, a, k.z, ac.z, w.z);
+        table_add(cnt, sum, a, k.w, ac.w, w.w);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int b = threadIdx.x; b < bins; b += LMAZE_BLOCK) {
+            const unsigned long long c = cnt[b];
+            if (!c) continue;                                    // a bin no sample of this workgroup fell into
+            atomicAdd(a.count + b, c);
+            if (sum && sum[b]) atomicAdd(a.total + b, sum[b]);
+        }
+    }
+}
+
+// Where the table lives is a rule (include/lmaze.h): up to LMAZE_TABLE_LDS_BINS bins in LDS, sized to the table.  One
+// launch for any m: a lane takes four samples per turn and the grid is capped, as episode_stats_kernel's.
+TableStatsPlan plan_table_stats(int64_t m, int64_t keys, int32_t actions) {
+    TableStatsPlan p;
+    p.bins = keys * actions;
+    p.lds = p.bins <= LMAZE_TABLE_LDS_BINS;
+    p.lds_bytes = p.lds ? 16 * p.bins : 0;
+    p.grid = (m + 4 * LMAZE_BLOCK - 1) / (4 * LMAZE_BLOCK);
+    const int64_t cap = p.lds ? 1024 : 2048;                     // LDS: every workgroup also flushes its table
+    if (p.grid > cap) p.grid = cap;
+    if (p.grid < 1) p.grid = 1;
+    return p;
+}
+
+hipError_t launch_table_stats(const TableStatsArgs& a, hipStream_t s) {
+    if (a.m == 0) return hipSuccess;
+    const TableStatsPlan p = plan_table_stats(a.m, a.keys, (int32_t)a.actions);
+    const uintptr_t off = (uintptr_t)a.key_t & 15;
+    const bool vec = (!a.actions_t || ((uintptr_t)a.actions_t & 15) == off) && (!a.weight_t || ((uintptr_t)a.weight_t & 15) == off);
+    int64_t head = vec ? (int64_t)(((16 - off) & 15) >> 2) : 0;
+    if (head > a.m) head = a.m;
+    const int64_t nvec = vec ? (a.m - head) >> 2 : 0;
+    if (p.lds)
+        hipLaunchKernelGGL(table_stats_kernel<true>, dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a,
+                           (int32_t)p.bins, (int32_t)head, nvec);
+    else
+        hipLaunchKernelGGL(table_stats_kernel<false>, dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), 0, s, a, (int32_t)p.bins,
+                           (int32_t)head, nvec);
     return hipGetLastError();
 }
 

@@ -140,6 +140,42 @@ hipError_t launch_rollout_sample(int variant, const StepArgs& a, int layout_mode
 // Discounted returns-to-go over trajectory rows (lmaze_returns, lmaze_aux.hip)
 hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t,
                           int32_t T, int64_t n, hipStream_t s);
+// GAE(lambda) over trajectory rows (lmaze_advantages / lmaze_advantages_table, lmaze_aux.hip).  The rows form reads
+// value_t / tail; the table form (values != null) gathers values[key_t] / values[key_tail], 0 for a key outside [0, keys).
+struct AdvantageArgs {
+    const float* reward_t;    // [T, N]
+    const uint8_t* done_t;    // [T, N]
+    const float* value_t;     // rows form: [T, N]
+    const float* tail;        // rows form: [N] or null (0)
+    const int32_t* key_t;     // table form: [T, N]
+    const int32_t* key_tail;  // table form: [N] or null (0)
+    const float* values;      // table form: [keys]
+    uint32_t keys;            // table form: min(keys, 2^31), an int32 key compares against it unsigned
+    float gamma, gl;          // gl = gamma * lambda, one float32 product
+    float* adv_t;             // [T, N]; may be reward_t
+    float* target_t;          // [T, N] or null; rows form: may be value_t
+    int32_t T;
+    int64_t n;
+};
+hipError_t launch_advantages(const AdvantageArgs& a, hipStream_t s);
+// Counts and Q24 sums per (key, action) over m samples (lmaze_table_stats, lmaze_aux.hip).  The plan is what the launcher
+// decides from the counts alone -- where the table lives, the grid -- and what lmaze_describe_table_stats prints.
+struct TableStatsArgs {
+    const int32_t* key_t;      // [m]
+    const int32_t* actions_t;  // [m] or null (action 0)
+    const float* weight_t;     // [m] or null (counts only)
+    int64_t m;
+    uint32_t keys, actions;
+    unsigned long long* count;  // [keys * actions], added onto
+    unsigned long long* total;  // [keys * actions] or null, added onto
+};
+struct TableStatsPlan {
+    bool lds;                  // a private table per workgroup in LDS, flushed once; otherwise global atomics per sample
+    int64_t grid, lds_bytes, bins;
+};
+#define LMAZE_TABLE_LDS_BINS 4096   // 16 bytes per bin: at most 64 KiB
+TableStatsPlan plan_table_stats(int64_t m, int64_t keys, int32_t actions);
+hipError_t launch_table_stats(const TableStatsArgs& a, hipStream_t s);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

@@ -527,6 +527,22 @@ class LmazeVecEnv(VecEnvBase):
         _abi.check("lmaze_render_expanded", rc)
         return out
 
+    def state_keys(self, key="ball"):
+        """int32[N]: the key of every env's CURRENT state, by the rule the key_t rows of rollout_policy() / rollout_sample()
+        are written with -- coordinates clamped onto the grid, ball_x * G + ball_y, and for key="goal" (v3 only) goal cell
+        * G*G + ball cell.  Right after a rollout this is gae()'s key_tail.  Plain torch ops on ball_xy / goal_xy."""
+        if key not in _abi.KEY_MODES:
+            raise ValueError("key must be 'ball' or 'goal'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        G = self.grid
+        b = self.ball_xy.clamp(0, G - 1)
+        k = b[:, 0] * G + b[:, 1]
+        if key == "goal":
+            g = self.goal_xy.clamp(0, G - 1)
+            k = k + (g[:, 0] * G + g[:, 1]) * (G * G)
+        return k.to(torch.int32).contiguous()
+
     def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
         """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
         observations (obs_t / obs_every) is not captured: ValueError."""
@@ -576,6 +592,141 @@ def discounted_returns(reward_t, done_t, gamma, tail=None, out=None):
                                     out.data_ptr(), T, N, torch.cuda.current_stream(reward_t.device).cuda_stream)
     _abi.check("lmaze_returns", rc)
     return out
+
+
+def _rows_like(ref, t, dtypes):
+    return (isinstance(t, torch.Tensor) and t.dtype in dtypes and t.dim() == 2 and t.is_cuda and t.is_contiguous()
+            and t.device == ref.device and tuple(t.shape) == tuple(ref.shape))
+
+
+def gae(reward_t, done_t, gamma, lam, value_t=None, tail=None, values=None, key_t=None, key_tail=None, out=None, targets=True):
+    """Generalised advantage estimation GAE(lambda) over trajectory rows, in ONE launch (include/lmaze.h lmaze_advantages /
+    lmaze_advantages_table): walking t = T-1 .. 0 with v the value of row t and v_next the value of the row behind,
+        adv = reward_t[t] - v where done_t[t], else ((reward_t[t] + gamma * v_next) - v) + (gamma * lam) * adv
+    in float32, every operation rounded on its own, so a float32 loop on the host gives the same bits.  A done row cuts the
+    bootstrap and the trace; the done of a step limit is terminal like any other.  Exactly one value source:
+    value_t         rows form: float32[T,N] values, and tail float32[N], the value behind the last row (default 0);
+    values + key_t  table form: values float32[S], key_t int32[T,N] (the key_t rows of rollout_policy() / rollout_sample()),
+                    v = values[key] for 0 <= key < S and 0 otherwise; key_tail int32[N] keys the state behind the last row
+                    (LmazeVecEnv.state_keys() of the env whose rollout has just returned; default: value 0).
+    reward_t float32[T,N], done_t bool / uint8[T,N], contiguous on one GPU.  out: float32[T,N] to fill with the advantages
+    (it may be reward_t); default a new tensor.  targets: True allocates the value targets adv + v, a float32[T,N] tensor
+    fills it (rows form: it may be value_t), False skips them.  Returns (adv_t, target_t or None)."""
+    if not (isinstance(reward_t, torch.Tensor) and _rows_like(reward_t, reward_t, (torch.float32,))):
+        raise ValueError("reward_t must be a contiguous float32[T,N] tensor on a GPU")
+    if not _rows_like(reward_t, done_t, (torch.bool, torch.uint8)):
+        raise ValueError("done_t must be a contiguous bool or uint8 tensor of reward_t's shape, on its device")
+    T, N = reward_t.shape
+    dev = reward_t.device
+    table = values is not None or key_t is not None
+    if table == (value_t is not None):
+        raise ValueError("gae() wants exactly one value source: value_t=, or values= with key_t=")
+
+    def per_env(t, dtype):
+        return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous() and tuple(t.shape) == (N,))
+    if table:
+        if tail is not None:
+            raise ValueError("tail= belongs to the rows form; the table form takes key_tail=")
+        if not (isinstance(values, torch.Tensor) and values.dtype == torch.float32 and values.dim() == 1 and values.numel() >= 1
+                and values.device == dev and values.is_contiguous()):
+            raise ValueError("values must be a contiguous float32[S] tensor, S >= 1, on reward_t's device")
+        if not _rows_like(reward_t, key_t, (torch.int32,)):
+            raise ValueError("key_t must be a contiguous int32 tensor of reward_t's shape, on its device")
+        if key_tail is not None and not per_env(key_tail, torch.int32):
+            raise ValueError("key_tail must be a contiguous int32[N] tensor on reward_t's device")
+    else:
+        if key_tail is not None:
+            raise ValueError("key_tail= belongs to the table form; the rows form takes tail=")
+        if not _rows_like(reward_t, value_t, (torch.float32,)):
+            raise ValueError("value_t must be a contiguous float32 tensor of reward_t's shape, on its device")
+        if tail is not None and not per_env(tail, torch.float32):
+            raise ValueError("tail must be a contiguous float32[N] tensor on reward_t's device")
+    if out is None:
+        out = torch.empty_like(reward_t)
+    elif not _rows_like(reward_t, out, (torch.float32,)):
+        raise ValueError("out must be a contiguous float32 tensor of reward_t's shape, on its device")
+    if targets is True:
+        targets = torch.empty_like(reward_t)
+    elif targets is False or targets is None:
+        targets = None
+    elif not _rows_like(reward_t, targets, (torch.float32,)):
+        raise ValueError("targets must be True, False or a contiguous float32 tensor of reward_t's shape, on its device")
+    if T == 0 or N == 0:          # nothing to do; an empty tensor has no address to pass
+        return out, targets
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if table:
+            name = "lmaze_advantages_table"
+            rc = _abi.lib.lmaze_advantages_table(reward_t.data_ptr(), done_t.data_ptr(), key_t.data_ptr(), ptr(key_tail),
+                                                 values.data_ptr(), values.numel(), float(gamma), float(lam), out.data_ptr(),
+                                                 ptr(targets), T, N, stream)
+        else:
+            name = "lmaze_advantages"
+            rc = _abi.lib.lmaze_advantages(reward_t.data_ptr(), done_t.data_ptr(), value_t.data_ptr(), ptr(tail), float(gamma),
+                                           float(lam), out.data_ptr(), ptr(targets), T, N, stream)
+    _abi.check(name, rc)
+    return out, targets
+
+
+def table_stats(key_t, actions_t=None, weight_t=None, *, keys, actions=4, count=None, total=None):
+    """Counts and sums per (key, action) over trajectory rows, in ONE launch and bitwise reproducible (include/lmaze.h
+    lmaze_table_stats): for every sample, bin = (key, action) -- action 0 when actions_t is None, which needs actions=1 --
+    count[bin] += 1 and total[bin] += rint(weight * 2**24), in int64.  A sample is skipped entirely when its key is outside
+    [0, keys), its action outside [0, actions) (rollout_policy() writes ids above 3 for "no move"), or its weight is not
+    finite or |w| >= 2**31.  key_t, actions_t int32 and weight_t float32: contiguous tensors of one shape on one GPU (the
+    [T, N] rows of a rollout, or any slice that stays contiguous).  count, total: int64[keys, actions] tables that are ADDED
+    ONTO (so statistics can span rollouts); a missing one is allocated as zeros.  Returns (count, total), total None when
+    weight_t is; table_means() turns them into means.  Integer sums do not depend on the order of the additions: the tables
+    of several ranks are summed exactly by torch.distributed.all_reduce(count) / all_reduce(total) -- the library adds no
+    collective of its own."""
+    if not (isinstance(key_t, torch.Tensor) and key_t.dtype == torch.int32 and key_t.is_cuda and key_t.is_contiguous()):
+        raise ValueError("key_t must be a contiguous int32 tensor on a GPU")
+    dev = key_t.device
+    for name, t, dt in (("actions_t", actions_t, torch.int32), ("weight_t", weight_t, torch.float32)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous()
+                                  and tuple(t.shape) == tuple(key_t.shape)):
+            raise ValueError("%s must be a contiguous %s tensor of key_t's shape, on its device" % (name, str(dt).split(".")[-1]))
+    for name, v in (("keys", keys), ("actions", actions)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("%s must be an int >= 1" % name)
+    keys, actions = int(keys), int(actions)
+    if actions > 255 or keys * actions > 1 << 28:
+        raise ValueError("actions must be <= 255 and keys * actions <= 2**28")
+    if actions_t is None and actions != 1:
+        raise ValueError("actions_t=None needs actions=1")
+    if total is not None and weight_t is None:
+        raise ValueError("total= needs weight_t=")
+    for name, t in (("count", count), ("total", total)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.device == dev and t.is_contiguous()
+                                  and tuple(t.shape) == (keys, actions)):
+            raise ValueError("%s must be a contiguous int64[%d, %d] tensor on key_t's device" % (name, keys, actions))
+    if count is None:
+        count = torch.zeros((keys, actions), dtype=torch.int64, device=dev)
+    if total is None and weight_t is not None:
+        total = torch.zeros((keys, actions), dtype=torch.int64, device=dev)
+    m = key_t.numel()
+    if m == 0:
+        return count, total
+    with torch.cuda.device(dev):
+        rc = _abi.lib.lmaze_table_stats(key_t.data_ptr(), None if actions_t is None else actions_t.data_ptr(),
+                                        None if weight_t is None else weight_t.data_ptr(), m, keys, actions, count.data_ptr(),
+                                        None if total is None else total.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _abi.check("lmaze_table_stats", rc)
+    return count, total
+
+
+def table_means(count, total, fill=0.0):
+    """Per-(key, action) means of table_stats()' tables, float64[keys, actions]: total / 2**24 / count where count > 0,
+    `fill` elsewhere.  Plain torch on the tables' device; after an all_reduce of both tables, the mean over every rank."""
+    if not (isinstance(count, torch.Tensor) and isinstance(total, torch.Tensor) and count.dtype == torch.int64
+            and total.dtype == torch.int64 and count.shape == total.shape and count.device == total.device):
+        raise ValueError("count and total must be int64 tensors of one shape on one device")
+    seen = count > 0
+    mean = total.to(torch.float64) / 16777216.0 / count.clamp(min=1).to(torch.float64)
+    return torch.where(seen, mean, torch.full_like(mean, float(fill)))
 
 
 def _validate_on_device(lay, need_goal=True):

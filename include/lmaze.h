@@ -441,6 +441,66 @@ int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tai
                   int64_t n, void* stream);
 
 /*
+ * Generalised advantage estimation, GAE(lambda), over the [T, N] rows a rollout writes, in ONE launch, one lane per env; no
+ * reference counterpart.  Replaces the T dependent steps of a host-driven reverse loop.  With v(t, i) the value of row t and
+ * v(T, i) the value behind the last row:
+ *   gl = gamma * lambda (one float32 product, computed once);  v_next = v(T, i);  adv = 0;  for t = T-1 .. 0:
+ *     v = v(t, i)
+ *     adv = reward_t[t, i] - v                                      where done_t[t, i] != 0
+ *     adv = ((reward_t[t, i] + gamma * v_next) - v) + gl * adv      otherwise
+ *     adv_t[t, i] = adv;  target_t[t, i] = adv + v (when target_t is given);  v_next = v
+ * in float32, every operation rounded on its own (round to nearest even, never a fused multiply-add), so a float32 loop on
+ * the host reproduces every bit.  A done row cuts both the bootstrap and the trace, as in lmaze_returns: the done of a step
+ * limit is treated as terminal like any other (the rows do not tell the two apart).
+ *   lmaze_advantages        v(t, i) = value_t[t, i], value_t float[T,N];  v(T, i) = tail[i], tail float[N] or NULL (0).
+ *   lmaze_advantages_table  v(t, i) = values[key_t[t, i]] where 0 <= key < keys and 0 otherwise (one unsigned compare, never
+ *                           a read outside the table), key_t int32[T,N] as the closed-loop rollouts write it, values
+ *                           float[keys];  v(T, i) the same lookup of key_tail[i], key_tail int32[N] or NULL (0).
+ * reward_t float[T,N], done_t uint8[T,N], adv_t float[T,N], target_t float[T,N] or NULL.  adv_t may be reward_t, and in the
+ * rows form target_t may be value_t: a lane reads a row of its own column before it stores it and touches no other column.
+ * Refused, in this order: LMAZE_E_NULL reward_t, done_t, adv_t, value_t (rows form) or key_t / values (table form) missing;
+ * LMAZE_E_COUNT T < 0, n outside [0, LMAZE_MAX_ENVS] or keys < 1.  T == 0 or n == 0 returns 0 with nothing read.
+ */
+int lmaze_advantages(const float* reward_t, const uint8_t* done_t, const float* value_t, const float* tail, float gamma,
+                     float lambda, float* adv_t, float* target_t, int32_t T, int64_t n, void* stream);
+int lmaze_advantages_table(const float* reward_t, const uint8_t* done_t, const int32_t* key_t, const int32_t* key_tail,
+                           const float* values, int64_t keys, float gamma, float lambda, float* adv_t, float* target_t, int32_t T,
+                           int64_t n, void* stream);
+
+/*
+ * Counts and sums per (key, action) over m samples -- the flattened [T, N] rows of a rollout -- bitwise reproducible; no
+ * reference counterpart.  For sample j: bin = key_t[j] * actions + a, a = actions_t[j] (0 when actions_t is NULL, which
+ * requires actions == 1).  A sample is skipped entirely -- neither counted nor summed -- when its key is outside [0, keys),
+ * its action is outside [0, actions) (lmaze_rollout_policy writes ids above 3 for "no move"), or a weight row is given and
+ * its weight is not finite or |w| >= 2^31.  Otherwise count[bin] += 1 and total_q24[bin] += q(w), where q(w) is w * 2^24
+ * rounded to the nearest integer, ties to even: the product is exact in float32, so this is one rounding in all; on the
+ * host, rint(double(w) * 2^24).  A mean is total_q24 / 2^24 / count.  Integer accumulation: the sums do not depend on the
+ * order the samples arrive in, so any two runs, and the two kernels below, give the same 64 bits.
+ *   key_t int32[m];  actions_t int32[m] or NULL;  weight_t float[m] and total_q24 int64[keys * actions], NULL together
+ *   (counts only);  count int64[keys * actions].  Rows 4-byte aligned, tables 8-byte aligned (LMAZE_E_ALIGN).
+ * The call adds onto what count / total_q24 hold -- the caller zeroes them -- so statistics can span several rollouts, and
+ * several GPUs sum their tables exactly with one int64 all_reduce.  Range is the caller's: the sum of |w| per bin stays
+ * below 2^39; beyond that the sum wraps, it never faults.
+ * Where the table lives is a rule: up to 4096 bins (keys * actions <= 4096, every ball-keyed table up to G = 32) each
+ * workgroup keeps a private table in LDS, 16 bytes per bin and sized to the table, accumulates into it with LDS atomics and
+ * adds its non-zero bins to the global table with one 64-bit atomic each; above that, 64-bit global atomics per sample.
+ * Always one launch.
+ * Refused, in this order: LMAZE_E_NULL key_t or count missing; LMAZE_E_NULL exactly one of weight_t / total_q24 given;
+ * LMAZE_E_COUNT m < 0, keys < 1, actions outside [1, 255], keys * actions > 2^28, or actions_t NULL with actions != 1.
+ * m == 0 then returns 0 with nothing read.
+ */
+int lmaze_table_stats(const int32_t* key_t, const int32_t* actions_t, const float* weight_t, int64_t m, int64_t keys,
+                      int32_t actions, int64_t* count, int64_t* total_q24, void* stream);
+
+/*
+ * The launch lmaze_table_stats would queue for these counts, one line in text_host (HOST, len bytes), e.g.
+ * "table_stats_kernel<lds> grid=1024 block=256 lds=7744 bins=484", or "table_stats_kernel<global> ... lds=0 ...": written
+ * by the code that launches, nothing queued or dereferenced.  An empty line for m == 0.  LMAZE_E_NULL text_host NULL or
+ * len < 1, then lmaze_table_stats' LMAZE_E_COUNT refusals (actions != 1 stands for a given actions_t).
+ */
+int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* text_host, int32_t len);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes
