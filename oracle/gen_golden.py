@@ -478,6 +478,46 @@ def gen_v1():
 EV_RESET, EV_PLANNER, EV_STEP = 0, 1, 2
 
 
+def _v56_rec(E, seed, T):
+    return dict(E=np.int32(E), seed=np.int64(seed), layouts=five_layouts(),
+                ev_type=np.zeros(T, np.int32), ev_arg=np.zeros(T, np.int32), raised=np.zeros(T, np.uint8),
+                ball0=np.zeros((T, 2), np.int32), ball1=np.zeros((T, 2), np.int32), goal=np.zeros((T, 2), np.int32),
+                fgoal=np.zeros((T, 2), np.int32), fovea0=np.zeros((T, 2), np.int32), fovea1=np.zeros((T, 2), np.int32),
+                layout_id=np.zeros(T, np.int32), step_count=np.zeros(T, np.int32),
+                foveal_step_count=np.zeros(T, np.int32),
+                global_reward=np.zeros(T, np.float64), local_reward=np.zeros(T, np.float64),
+                global_done=np.zeros(T, np.uint8), local_done=np.zeros(T, np.uint8),
+                visit=np.zeros((T, 18, 18), np.float32),
+                fov_planes=np.zeros((T, 7, 5, 5), np.float32), loc_planes=np.zeros((T, 4, 5, 5), np.float32),
+                fov_hash=np.zeros(T, np.uint64), loc_hash=np.zeros(T, np.uint64),
+                fgoal_plane=np.zeros((T, 5, 5), np.float32))
+
+
+def _v56_record(rec, env, E, t, fov, loc):
+    """the full state after event t, and the observations the event returned"""
+    rec["ball0"][t] = (env.ball_x0, env.ball_y0)
+    rec["ball1"][t] = (env.ball_x1, env.ball_y1)
+    rec["goal"][t] = (env.goal_x, env.goal_y)
+    rec["fgoal"][t] = (env.f_goal_x0, env.f_goal_y0)
+    rec["fovea0"][t] = (env.fovea_x0, env.fovea_y0)
+    rec["fovea1"][t] = (env.fovea_x1, env.fovea_y1)
+    rec["layout_id"][t] = layout_id_of(env.grid)
+    rec["step_count"][t] = env.stepCount
+    rec["foveal_step_count"][t] = env.fovealStepCount
+    rec["global_reward"][t] = env.globalReward
+    rec["local_reward"][t] = env.originalReward
+    rec["global_done"][t] = env.globalDone
+    rec["local_done"][t] = env.localDone
+    rec["visit"][t] = env.state[2]
+    rec["fgoal_plane"][t] = env.fovealGoal[0]
+    if fov is not None:
+        rec["fov_planes"][t] = unexpand(fov, E)
+        rec["fov_hash"][t] = obs_hash(fov)
+    if loc is not None:
+        rec["loc_planes"][t] = unexpand(loc, E)
+        rec["loc_hash"][t] = obs_hash(loc)
+
+
 def rollout_v56(variant, n_events, seed, safe_goals=False, calm=False):
     import contextlib
     import io
@@ -488,18 +528,7 @@ def rollout_v56(variant, n_events, seed, safe_goals=False, calm=False):
     env = ref_loader.make(variant)
     E = env.expansionRatio
     T = n_events
-    rec = dict(E=np.int32(E), seed=np.int64(seed), layouts=five_layouts(),
-               ev_type=np.zeros(T, np.int32), ev_arg=np.zeros(T, np.int32), raised=np.zeros(T, np.uint8),
-               ball0=np.zeros((T, 2), np.int32), ball1=np.zeros((T, 2), np.int32), goal=np.zeros((T, 2), np.int32),
-               fgoal=np.zeros((T, 2), np.int32), fovea0=np.zeros((T, 2), np.int32), fovea1=np.zeros((T, 2), np.int32),
-               layout_id=np.zeros(T, np.int32), step_count=np.zeros(T, np.int32),
-               foveal_step_count=np.zeros(T, np.int32),
-               global_reward=np.zeros(T, np.float64), local_reward=np.zeros(T, np.float64),
-               global_done=np.zeros(T, np.uint8), local_done=np.zeros(T, np.uint8),
-               visit=np.zeros((T, 18, 18), np.float32),
-               fov_planes=np.zeros((T, 7, 5, 5), np.float32), loc_planes=np.zeros((T, 4, 5, 5), np.float32),
-               fov_hash=np.zeros(T, np.uint64), loc_hash=np.zeros(T, np.uint64),
-               fgoal_plane=np.zeros((T, 5, 5), np.float32))
+    rec = _v56_rec(E, seed, T)
     state = "reset"
     extra = 0
     for t in range(T):
@@ -543,27 +572,7 @@ def rollout_v56(variant, n_events, seed, safe_goals=False, calm=False):
         except IndexError:
             rec["raised"][t] = 1                                     # buildLocalObservation indexed outside 5x5
             state = "reset"
-        rec["ball0"][t] = (env.ball_x0, env.ball_y0)
-        rec["ball1"][t] = (env.ball_x1, env.ball_y1)
-        rec["goal"][t] = (env.goal_x, env.goal_y)
-        rec["fgoal"][t] = (env.f_goal_x0, env.f_goal_y0)
-        rec["fovea0"][t] = (env.fovea_x0, env.fovea_y0)
-        rec["fovea1"][t] = (env.fovea_x1, env.fovea_y1)
-        rec["layout_id"][t] = layout_id_of(env.grid)
-        rec["step_count"][t] = env.stepCount
-        rec["foveal_step_count"][t] = env.fovealStepCount
-        rec["global_reward"][t] = env.globalReward
-        rec["local_reward"][t] = env.originalReward
-        rec["global_done"][t] = env.globalDone
-        rec["local_done"][t] = env.localDone
-        rec["visit"][t] = env.state[2]
-        rec["fgoal_plane"][t] = env.fovealGoal[0]
-        if fov is not None:
-            rec["fov_planes"][t] = unexpand(fov, E)
-            rec["fov_hash"][t] = obs_hash(fov)
-        if loc is not None:
-            rec["loc_planes"][t] = unexpand(loc, E)
-            rec["loc_hash"][t] = obs_hash(loc)
+        _v56_record(rec, env, E, t, fov, loc)
     return rec
 
 
@@ -575,7 +584,133 @@ def save_events(name, rec):
                                                         os.path.getsize(path) / 1024.0))
 
 
+MOVES = {(1, 0): 0, (-1, 0): 1, (0, 1): 2, (0, -1): 3}               # lmaze_env_v5.py:205-217
+DEEP_DECAY_STAYS = (112, 125, 131, 136, 142, 150, 170)               # map updates spent away from a region, as deep_decay_actions()
+
+
+def _bfs(free, src):
+    """{cell: predecessor} over the free cells reachable from src"""
+    prev, todo = {src: None}, [src]
+    for c in todo:
+        for d in MOVES:
+            n = (c[0] + d[0], c[1] + d[1])
+            if free[n] and n not in prev:
+                prev[n] = c
+                todo.append(n)
+    return prev
+
+
+def _path(free, src, dst):
+    prev = _bfs(free, src)
+    out = [dst]
+    while out[-1] != src:
+        out.append(prev[out[-1]])
+    return out[::-1][1:]
+
+
+def rollout_v5_noreset_deepdecay(seed, stays=DEEP_DECAY_STAYS):
+    """A scripted v5 walk of one reset() and then plannerStep / step only (no reset after globalDone, no event raises) that
+    takes the visit map through the far range: two regions A and B of the layout in force whose windows never overlap; the
+    ball stays around one of them with localDone set -- every step() then updates the map (lmaze_env_v5.py:315-318) -- for
+    `stay` updates while the other region halves `stay` times (below 2^-126 from about 126 on, to zero from about 150 on), and
+    then walks back over it with localDone clear, so that the window shows the decayed cells as they are.  The walk back
+    dawdles (ids that do not move, bumps into walls) to show them more than once.
+
+    Two limits shape the script.  From fovealStepCount >= foveal_step_limit on every step() sets localDone (v5:269-271), so
+    every shown window would be freshly updated: the whole walk spends fewer than 50 plannerStep calls.  And
+    buildLocalObservation indexes (ball - fovea1 + 2) into 5x5 (v5:365), so the ball stays within 2 cells of where the last
+    plannerStep was called, and a walk with localDone clear takes fewer than step_limit steps per plannerStep."""
+    import contextlib
+    import io
+    rs = np.random.RandomState(seed + 1000)
+    five_layouts()
+    random.seed(seed)
+    np.random.seed(seed)
+    env = ref_loader.make("v5")
+    E = env.expansionRatio
+    cap = 4000
+    rec = _v56_rec(E, seed, cap)
+    n = [0, 0]                                                       # events, map updates
+
+    def event(ev, arg=0):
+        t = n[0]
+        fov = loc = None
+        rec["ev_type"][t], rec["ev_arg"][t] = ev, arg
+        if ev == EV_RESET:
+            fov = env.reset()
+        elif ev == EV_PLANNER:
+            loc = env.plannerStep(arg)
+        else:
+            with contextlib.redirect_stdout(io.StringIO()):
+                out = env.step(arg)
+            fov, loc = out[0], out[1]
+            assert out[4] == env.globalDone and out[5] == env.localDone and out[7] == arg
+            n[1] += bool(env.localDone)
+        _v56_record(rec, env, E, t, fov, loc)
+        n[0] += 1
+
+    event(EV_RESET)
+    free = env.grid != "W"
+    cells = [tuple(c) for c in np.argwhere(free)]
+    ball = lambda: (int(env.ball_x0), int(env.ball_y0))              # noqa: E731
+    cheb = lambda a, b: max(abs(a[0] - b[0]), abs(a[1] - b[1]))      # noqa: E731
+    # A, B: 6 apart or more (a stay reaches 1 cell around its centre, a window 2 more: 3 + 2 < 6), shortest way between them
+    far = [(a, b) for a in cells for b in cells if a < b and cheb(a, b) >= 6]
+    A, B = min((ab for ab in far if ab[1] in _bfs(free, ab[0])), key=lambda ab: (len(_path(free, *ab)), ab))
+
+    def idle():
+        """an action that leaves the ball where it is: an id outside 0..3, or a move into a wall"""
+        walls = [a for d, a in MOVES.items() if not free[ball()[0] + d[0], ball()[1] + d[1]]]
+        return int(rs.choice(walls)) if walls and rs.rand() < 0.5 else int(rs.choice([-1, 4, 5, 6]))
+
+    def walk(dst):
+        """to dst with localDone clear: a plannerStep whose goal is none of the next three positions, two moves, some idling"""
+        path = _path(free, ball(), dst)
+        while path:
+            two, path = path[:2], path[2:]
+            while True:
+                g = int(rs.randint(0, 25))
+                if (ball()[0] + g // 5 - 2, ball()[1] + g % 5 - 2) not in [ball()] + two:
+                    break
+            event(EV_PLANNER, g)
+            steps = [MOVES[(c[0] - p[0], c[1] - p[1])] for p, c in zip([ball()] + two, two)]
+            for _ in range(int(rs.randint(0, 4))):
+                steps.insert(int(rs.randint(0, len(steps) + 1)), None)
+            for a in steps:
+                event(EV_STEP, idle() if a is None else a)
+                assert not env.localDone
+
+    def stay(centre, updates):
+        """a plannerStep at `centre` whose goal is a neighbour, the step onto it (localDone), then moves within one cell of
+        the centre and idling, never another plannerStep: each step updates the map"""
+        assert ball() == centre
+        near = [c for c in cells if cheb(c, centre) <= 1]
+        first = [c for c in near if (c[0] - centre[0], c[1] - centre[1]) in MOVES][0]
+        event(EV_PLANNER, (first[0] - centre[0] + 2) * 5 + first[1] - centre[1] + 2)
+        event(EV_STEP, MOVES[(first[0] - centre[0], first[1] - centre[1])])
+        start = n[1] - 1
+        while n[1] - start < updates:
+            opts = [a for d, a in MOVES.items() if (ball()[0] + d[0], ball()[1] + d[1]) in near]
+            event(EV_STEP, int(rs.choice(opts)) if rs.rand() < 0.8 else idle())
+            assert env.localDone
+
+    walk(A)
+    here, there = A, B
+    stay(here, 12)
+    for k in stays:
+        walk(there)
+        stay(there, k)
+        here, there = there, here
+    walk(there)
+    assert env.fovealStepCount < env.foveal_step_limit and n[0] <= cap
+    for k, v in rec.items():
+        if k not in ("E", "seed", "layouts"):
+            rec[k] = v[:n[0]]
+    return rec
+
+
 def gen_v5():
+    save_events("v5_noreset_deepdecay_seed7", rollout_v5_noreset_deepdecay(seed=7))
     save_events("v5_seed0", rollout_v56("v5", 700, seed=0))
     save_events("v5_seed1", rollout_v56("v5", 500, seed=1))
     save_events("v5_calm_seed3", rollout_v56("v5", 700, seed=3, calm=True))

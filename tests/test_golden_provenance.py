@@ -33,7 +33,7 @@ def test_v5_and_v6_recordings_do_not_depend_on_generator_order(tmp_path):
     alone.mkdir(); after.mkdir()
     a = _generate(alone, "v5", "v6")
     b = _generate(after, "v4", "v6", "v5")
-    assert set(a) <= set(b) and "v5_seed0.npz" in a and "v6_seed0.npz" in a
+    assert set(a) <= set(b) and "v5_seed0.npz" in a and "v6_seed0.npz" in a and "v5_noreset_deepdecay_seed7.npz" in a
     for f in b:
         assert filecmp.cmp(os.path.join(str(after), f), os.path.join(GOLDEN, f), shallow=False), f
     for f in a:

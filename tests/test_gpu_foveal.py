@@ -402,15 +402,13 @@ def test_v56_batched_two_level_loop_vs_oracle(N):
             _same56(env, st, ("reset", t))
 
 
-def test_dropin_v6_seeded_event_rollout():
-    """The reference's usage loop on the drop-in object: same `random` / `np.random` draws (placement,
-    safeFovealGoal), same 8-tuples, IndexError where the reference raises."""
+def _dropin_event_rollout(name, env_id):
     import random
     import gym_lmaze
-    g = load_golden("v6_seed0")
+    g = load_golden(name)
     random.seed(int(g["seed"]))
     np.random.seed(int(g["seed"]))
-    env = gym_lmaze.make("lmaze-v6")
+    env = gym_lmaze.make(env_id)
     for t in range(len(g["ev_type"])):
         ev, arg = int(g["ev_type"][t]), int(g["ev_arg"][t])
         if ev == 0:
@@ -419,10 +417,11 @@ def test_dropin_v6_seeded_event_rollout():
         elif ev == 1:
             # the generator either called safeFovealGoal() (which consumes np.random) or drew the goal from
             # its own stream; the goal id recorded in the fixture tells which it was
-            before = np.random.get_state()
-            sg = env.safeFovealGoal()
-            if sg != arg:
-                np.random.set_state(before)
+            if env_id == "lmaze-v6":
+                before = np.random.get_state()
+                sg = env.safeFovealGoal()
+                if sg != arg:
+                    np.random.set_state(before)
             loc = env.plannerStep(arg)
             assert obs_hash(loc) == g["loc_hash"][t], t
         else:
@@ -438,6 +437,18 @@ def test_dropin_v6_seeded_event_rollout():
                 assert (out[6][0] == g["fgoal_plane"][t]).all()
         assert (env.ball_x0, env.ball_y0) == tuple(g["ball0"][t]), t
         assert (env.goal_x, env.goal_y) == tuple(g["goal"][t]), t
+
+
+def test_dropin_v6_seeded_event_rollout():
+    """The reference's usage loop on the drop-in object: same `random` / `np.random` draws (placement,
+    safeFovealGoal), same 8-tuples, IndexError where the reference raises."""
+    _dropin_event_rollout("v6_seed0", "lmaze-v6")
+
+
+def test_dropin_v5_event_rollout_without_resets_through_deep_decay():
+    """LmazeEnv_v5 on the recording of one reset() and 1 114 plannerStep / step events: 978 map updates (the clock reaches the
+    rewrite threshold six times), windows that show cells decayed below 2^-126 and to zero -- the expanded observations' hashes."""
+    _dropin_event_rollout("v5_noreset_deepdecay_seed7", "lmaze-v5")
 
 
 @pytest.mark.parametrize("variant", ["v1", "v2", "v4"])
