@@ -37,7 +37,7 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy",
            "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns",
            "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
-           "lmaze_describe_table_stats")
+           "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy")
 
 
 class LmazeParams(C.Structure):
@@ -190,6 +190,11 @@ def _load():
     lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_describe_foveal_rollout_obs.restype = C.c_int
     lib.lmaze_describe_foveal_rollout_obs.argtypes = [FP, i64, i32, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_foveal_rollout_policy.restype = C.c_int
+    lib.lmaze_foveal_rollout_policy.argtypes = [FP, vp, vp, C.c_uint32, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                i32, vp]
+    lib.lmaze_describe_foveal_rollout_policy.restype = C.c_int
+    lib.lmaze_describe_foveal_rollout_policy.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -317,6 +322,15 @@ def describe_foveal_rollout(params, n, T, auto_reset=False, two_level=False, obs
         check("lmaze_describe_foveal_rollout_obs",
               lib.lmaze_describe_foveal_rollout_obs(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
                                                     1 if two_level else 0, int(obs_every), buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+def describe_foveal_rollout_policy(params, n, T, auto_reset=False, obs_every=0):
+    """The kernel / grid / launch policy lmaze_foveal_rollout_policy would queue for n envs and T steps (obs_every=0: no
+    recording), and where its table lives: "... table=lds ..." or "... table=global ..."."""
+    buf = C.create_string_buffer(256)
+    check("lmaze_describe_foveal_rollout_policy",
+          lib.lmaze_describe_foveal_rollout_policy(C.byref(params), int(n), int(T), 1 if auto_reset else 0, int(obs_every), buf, 256))
     return buf.value.decode("ascii", "replace")
 
 

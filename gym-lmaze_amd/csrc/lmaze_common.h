@@ -280,6 +280,15 @@ __device__ __forceinline__ uint4 env_draw(uint64_t seed, uint64_t epoch, int64_t
                          make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
+// The exploration draw of env `env_global` at `epoch` (the closed-loop rollouts of the grid and of the foveal envs): the
+// reset draw's counter with the top bit of its last word flipped (epochs stay below 2^63), so the two streams of one
+// (env, epoch) never meet.
+__device__ __forceinline__ uint4 policy_draw(uint64_t seed, uint64_t epoch, int64_t env_global) {
+    const uint64_t e = (uint64_t)env_global;
+    return philox4x32_10(make_uint4((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)epoch, (uint32_t)(epoch >> 32) ^ 0x80000000u),
+                         make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+}
+
 // cells the reference's rejection loops accept.  v0:73 ball: not 'W', not 'X'.
 // v3:149 goal: not 'W' (the ball list is the same list minus the goal cell, v3:158).
 template <int VARIANT>

@@ -1,10 +1,18 @@
 // lmaze_foveal_body.h -- the body of foveal_kernel and foveal_rollout_kernel (lmaze_foveal.hip), included into each.
 // In scope: the kernel argument `a` (FovealArgs), `ro` (FovealRoll, or FovealRollObs), and the compile-time VARIANT, MODE,
-// EPB, GT, AR, ROLL (the rollout: every chunk runs ro.T steps before the workgroup takes the next one) and REC (the
-// recording rollout: phases 3 and 3b also store the observations of every k-th step into the caller's slots).  Not a
-// header of its own.
+// EPB, GT, AR, ROLL (the rollout: every chunk runs ro.T steps before the workgroup takes the next one), REC (the
+// recording rollout: phases 3 and 3b also store the observations of every k-th step into the caller's slots) and POL (the
+// closed-loop rollout of v1/v2/v4, lmaze_foveal_policy.hip: phase 1 takes the action from a table keyed by the env's state,
+// mixed with an exploration draw, instead of from the action tensor, and stores the action and key rows).  POL is the
+// include site's LMAZE_FOVEAL_POLICY_SITE: what it adds stands under the preprocessor, so that every other kernel compiles
+// from the text it always had.  Not a header of its own.
 #ifndef LMAZE_FOVEAL_BODY_SITE
-#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip"
+#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip and lmaze_foveal_policy.hip"
+#endif
+#ifdef LMAZE_FOVEAL_POLICY_SITE
+#define LMAZE_POL 1
+#else
+#define LMAZE_POL 0
 #endif
     constexpr bool V1 = VARIANT == LMAZE_VARIANT_V1, V5 = VARIANT == LMAZE_VARIANT_V5;
     constexpr bool V4 = VARIANT == LMAZE_VARIANT_V4 || V5;   // "has a visit map"
@@ -34,6 +42,11 @@
     uint64_t* rowwall = rowball + L * G;                                   // [G] v1: 'W'
     uint64_t* rowx = rowwall + G;                                          // [G] v1: 'X'
     uint8_t* lays = reinterpret_cast<uint8_t*>(rowx + G);                  // [L*CELLS]
+#if LMAZE_POL
+    uint8_t* ptab = lays + ((L * CELLS + 15) & ~15);                       // [L*CELLS] the policy table, when it is staged
+    const FovealPol pol = ro.pol;
+    const bool pstage = pol.in_lds != 0;
+#endif
     static_assert(PERENV <= 8 * 32 - 32 && 4 * W25 <= 4 * 32 - 4, "bit strings fit the 32 B / 16 B per env reserved for them");
     __shared__ int any_skip, ndense;
 
@@ -88,6 +101,16 @@
             for (int j = 0; j < 2; ++j)
                 if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) cw[j] = reinterpret_cast<const uint32_t*>(a.layouts)[tid + j * LMAZE_BLOCK];
         }
+#if LMAZE_POL
+        // the table is as large as the characters and indexed like them; its dwords are requested with theirs
+        const bool pdwords = pstage && ((reinterpret_cast<uintptr_t>(pol.table) | (uintptr_t)(L * CELLS)) & 3) == 0;
+        uint32_t pw[2] = {0u, 0u};
+        if (pdwords) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) pw[j] = reinterpret_cast<const uint32_t*>(pol.table)[tid + j * LMAZE_BLOCK];
+        }
+#endif
         for (int r00 = 0; r00 < rows; r00 += UNR * 4 * RPW) {
             uint8_t cc[UNR];
 #pragma unroll
@@ -128,8 +151,22 @@
         } else {
             for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
         }
+#if LMAZE_POL
+        if (pdwords) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) reinterpret_cast<uint32_t*>(ptab)[tid + j * LMAZE_BLOCK] = pw[j];
+            for (int i = tid + 2 * LMAZE_BLOCK; i < (L * CELLS) >> 2; i += LMAZE_BLOCK)     // more than 2 KiB of table
+                reinterpret_cast<uint32_t*>(ptab)[i] = reinterpret_cast<const uint32_t*>(pol.table)[i];
+        } else if (pstage) {
+            for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) ptab[i] = pol.table[i];
+        }
+#endif
     } else {
     for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
+#if LMAZE_POL
+    if (pstage) for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) ptab[i] = pol.table[i];
+#endif
     __syncthreads();
     for (int i = tid; i < L * G; i += LMAZE_BLOCK) {
         uint64_t fr = 0, wl = 0, xx = 0;
@@ -173,12 +210,22 @@
         // on another loaded value (the done flag of the fused reset, localDone of the two-level step) is a second global
         // round trip in series -- v4's fused reset cost +58...95 us per launch that way (round 3, tools/_ar_study)
         // rollout: step t takes row t of the actions and planner goals (ROLL_ROW), and its resets draw with epoch + t (ROLL_EP)
+#if LMAZE_POL
+        const int act_in = 0;                 // no action tensor: the table and the draw, after the fused reset
+#else
         const int act_in = (MODE == FM_STEP) ? a.action[ROLL_ROW(e)] : 0;
+#endif
         const int sc_ld = (MODE == FM_STEP) ? a.b.step_count[e] : 0;
         const int done_in = (MODE == FM_STEP && AR) ? a.b.done[e] : 0;
         const int goal2_in = (MODE == FM_STEP && AR && V5) ? a.goal2[ROLL_ROW(e)] : 0;
         const int vword = (V4 && !(V5 && MODE == FM_PLANNER)) ? a.b.visit_clock[e] : 0;
         const int vclock = vword & 0xff;
+#if LMAZE_POL
+        // the exploration draw, only when there is exploration (uniform over the launch).  It depends on nothing loaded, so
+        // it stands in front of the fused reset's placement chain and runs under the loads above.
+        uint4 pr = make_uint4(0u, 0u, 0u, 0u);
+        if (pol.epsilon != 0u) pr = policy_draw(a.seed, ROLL_EP, a.env_base + e);
+#endif
         r.px = (int16_t)bx; r.py = (int16_t)by;
         if (MODE != FM_STEP && a.mask && !a.mask[e]) r.skip = 1;
         if (V1) {
@@ -191,7 +238,11 @@
                         if (lays[c] == 'S') { bx = c / G; by = c % G; break; }
                     sc_in = 0;
                 }
+#if LMAZE_POL
+                const int act = foveal_pol_action(pol, pstage, ptab, 0, bx, by, G, 1, 4, pr, ROLL_ROW(e));   // the key is the placed ball's
+#else
                 const int act = act_in;
+#endif
                 const int sc = sc_in + 1;                              // v1:117
                 const int fsc = a.b.foveal_step_count[e] + 1;          // v1:118
                 float fr = -0.0f, rw = -0.0f;                          // v1:120-121
@@ -417,7 +468,11 @@
                 sc_in = sc_ld;
             }
             if (MODE == FM_STEP) {
+#if LMAZE_POL
+                const int act = foveal_pol_action(pol, pstage, ptab, lid, bx, by, G, L, W25, pr, ROLL_ROW(e));   // the row the step uses
+#else
                 const int act = act_in;
+#endif
                 if (act < 0 || act >= W25) {
                     if (fresh) nostep = true;                          // reset, then the reference's step() raises
                     else r.skip = 1;                                   // the reference raises before touching anything
@@ -604,7 +659,13 @@
         // map, Appendix B-7 -- are left in vwin for phase 3.
         {
             // SUB envs at a time (one barrier each): the loads of a pass are held in registers, 9 per row
+#if LMAZE_POL
+            // the plain recording form of the closed loop has no registers for a third window row per lane
+            constexpr int IPE = 2 * FOV, SUB = EPB < ((REC && !AR) ? 32 : LMAZE_WIN_SUB) ? EPB : ((REC && !AR) ? 32 : LMAZE_WIN_SUB);
+            constexpr int NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
+#else
             constexpr int IPE = 2 * FOV, SUB = EPB < LMAZE_WIN_SUB ? EPB : LMAZE_WIN_SUB, NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
+#endif
           for (int sb = 0; sb < nb; sb += SUB) {
             const int items = LMAZE_XP(a, 256) ? 0 : min(SUB, nb - sb) * IPE;
             uint4 va[NIT], vb[NIT];
@@ -878,3 +939,4 @@
     if (warmed == 0x7fedcba9 && a.n < 0) a.b.done[0] = 1;   // never true: keeps the warming loads alive
 #undef ROLL_ROW
 #undef ROLL_EP
+#undef LMAZE_POL

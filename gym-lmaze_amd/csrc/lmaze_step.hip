@@ -1161,14 +1161,6 @@ __device__ __forceinline__ EnvState policy_load(const StepArgs& a, int64_t e, bo
     return s;
 }
 
-// The exploration draw of env `env_global` at `epoch`: the reset draw's counter with the top bit of its last word flipped
-// (epochs stay below 2^63), so the two streams of one (env, epoch) never meet.
-__device__ __forceinline__ uint4 policy_draw(uint64_t seed, uint64_t epoch, int64_t env_global) {
-    const uint64_t e = (uint64_t)env_global;
-    return philox4x32_10(make_uint4((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)epoch, (uint32_t)(epoch >> 32) ^ 0x80000000u),
-                         make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-}
-
 // Step t's action of env e (workgroup-local state s, after the fused reset): key -> table -> epsilon mix, and the rows of
 // the caller who asked for them.  Coordinates enter the key as the transition takes them, clamped onto the grid, so a
 // lookup never leaves the table.  tab: the ball-keyed table in LDS.

@@ -241,6 +241,83 @@ class LmazeFovealVecEnv(VecEnvBase):
                 self._epoch += T
         return self._rollout_result(rows)
 
+    def rollout_policy(self, T, policy=None, q=None, epsilon=0.0, auto_reset=True, trajectory=False, actions_t=None, key_t=None,
+                       obs_t=None, obs_every=None):
+        """T steps in ONE launch with a tabular epsilon-greedy policy inside the kernel (include/lmaze.h
+        lmaze_foveal_rollout_policy; v1, v2, v4): no action tensor, no per-step launches.
+        policy   uint8 device tensor of L*G*G entries, the greedy action id of every key = layout row * G*G + ball_x * G +
+                 ball_y (v1: one layout).  Ids mean what they mean to step(): v1 above 3 no move, v2/v4 above 24 untouched.
+        q        instead of policy: a float tensor [L*G*G, A] of action values, reduced on the device by greedy_table().
+        epsilon  exploration rate in [0, 1]: with that probability (in steps of 2**-32) the step takes a uniform action
+                 (0-3 for v1, 0-24 for v2/v4), drawn by Philox from (seed, env, epoch); 0 draws nothing.
+        Returns what rollout() returns -- the final (obs, reward, done), with trajectory=True also every stream's rows --
+        and then, with trajectory=True, actions_t and key_t int32[T,N] (the caller's, or allocated).  obs_every=k >= 1
+        records into obs_t as rollout() does.  The epoch advances by T whether or not auto_reset is set: exploration
+        consumes epochs too.  Not for v5/v6 (their closed loop needs two tables), nor with a device-resident epoch (under
+        stream capture: the host's epoch would be frozen into the graph)."""
+        if self._two_level:
+            raise ValueError("rollout_policy() is not available for v5/v6: their two-level step needs two tables")
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
+            raise ValueError("T must be an int >= 0")
+        T, N = int(T), self.num_envs
+        if (policy is None) == (q is None):
+            raise ValueError("rollout_policy() wants exactly one of policy= and q=")
+        eps = _abi.epsilon_u32(epsilon)
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("rollout_policy() is not available with a device-resident epoch (under stream capture)")
+        entries = self.n_layouts * self.grid * self.grid
+        if q is not None:
+            if not isinstance(q, torch.Tensor) or q.device != self.device:
+                raise ValueError("q must be a float tensor [S, A] on %s" % self.device)
+            policy = self.greedy_table(q)
+        if not (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.device == self.device
+                and policy.is_contiguous() and policy.numel() == entries):
+            raise ValueError("policy must be a contiguous uint8 tensor of %d entries on %s (L=%d, G=%d)"
+                             % (entries, self.device, self.n_layouts, self.grid))
+        self._check_rows("rollout_policy()", actions_t, key_t)
+        for name, t in (("actions_t", actions_t), ("key_t", key_t)):
+            if t is not None and t.shape[0] != T:
+                raise ValueError("%s must have T = %d rows" % (name, T))
+        k = 0
+        if obs_every is not None:
+            k = self._obs_slots(T, obs_every, obs_t, self.obs)
+        elif obs_t is not None:
+            raise ValueError("obs_t needs obs_every")
+        rows = self._traj_rows(T, 2 if self.variant == "v1" else 1) if trajectory else None
+        if trajectory:
+            actions_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
+            key_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if key_t is None else key_t
+        ptrs = [r.data_ptr() for r in rows] if rows else []
+        ptrs += [None] * (4 - len(ptrs))
+        slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
+        with self._guard():
+            rc = _abi.lib.lmaze_foveal_rollout_policy(
+                self._pp, self._p_layouts, policy.data_ptr(), eps, T, self._pb, N, 1 if auto_reset else 0,
+                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *ptrs,
+                None if actions_t is None else actions_t.data_ptr(), None if key_t is None else key_t.data_ptr(), slots, k,
+                self._stream())
+        _abi.check("lmaze_foveal_rollout_policy", rc)
+        self._epoch += T
+        out = self._rollout_result(rows)
+        return out + (actions_t, key_t) if trajectory else out
+
+    @staticmethod
+    def greedy_table(q):
+        """LmazeVecEnv.greedy_table: the first maximum of every row of q[S, A] as uint8[S]."""
+        from .vec_env import LmazeVecEnv
+        return LmazeVecEnv.greedy_table(q)
+
+    def state_keys(self):
+        """int32[N]: the key of every env's CURRENT state, by the rule the key_t rows of rollout_policy() are written with --
+        layout row (clamped to 0..L-1; 0 for v1) * G*G + ball_x * G + ball_y, coordinates clamped onto the grid.  Right after
+        a rollout this is gae()'s key_tail.  Plain torch ops on layout_id / ball_xy."""
+        G = self.grid
+        b = self.ball_xy.clamp(0, G - 1)
+        k = b[:, 0] * G + b[:, 1]
+        if self.variant != "v1":
+            k = k + self.layout_id.clamp(0, self.n_layouts - 1) * (G * G)
+        return k.to(torch.int32).contiguous()
+
     def _step_loop(self, T, launch, rows=None, k=None, obs_t=None, obs_local_t=None):
         """rollout() as T launches: launch(t) queues step t; then its rows of the trajectory are copied out and, every k-th
         step, its observations into their slots."""

@@ -766,6 +766,63 @@ int lmaze_describe_foveal_rollout_obs(const LmazeFovealParams* params, int64_t n
                                       int32_t two_level, int32_t obs_every, char* text_host, int32_t len);
 
 /*
+ * CLOSED-LOOP foveal rollout (v1, v2, v4): lmaze_foveal_rollout / lmaze_foveal_rollout_obs with a tabular epsilon-greedy
+ * policy inside the kernel instead of a pre-generated action tensor.  Replaces the user loop of T x (look the action up by
+ * layout row and ball, mix in exploration, lmaze_foveal_step / lmaze_foveal_step_autoreset) -- three or more launches per
+ * step -- by ONE launch; the action selection itself has no reference counterpart.  The arguments of lmaze_foveal_rollout
+ * with `actions` / `planner_goals` replaced by
+ *   policy       uint8[L*G*G] (L = 1 for v1): the greedy action id of every key, passed through unchanged, nothing is
+ *                validated.  An id means what it means to lmaze_foveal_step -- v1: 0..3, anything else is no move; v2/v4:
+ *                0..24, anything else leaves the env untouched (after a fused reset: reset, then no step)
+ *   epsilon_u32  as in lmaze_rollout_policy; 0: nothing is drawn
+ * and, beside reward_t / done_t (v1: foveal_reward_t / foveal_done_t too, as in lmaze_foveal_rollout),
+ *   actions_t    int32[T,N], nullable: the action step t took
+ *   key_t        int32[T,N], nullable: the key it was looked up with
+ *   obs_t, obs_every   obs_every == 0: no recording, obs_t must be NULL (the running bufs->obs is still written every step;
+ *                there is no final-observation-only form here either); obs_every = k >= 1: the slots float[T / k, N, C, 5, 5]
+ *                exactly as in lmaze_foveal_rollout_obs
+ * Env i (global index e = env_base + i) at step t, ep = epoch + t:
+ *   1. auto_reset != 0 and the env done on entry: the fused reset of lmaze_foveal_step_autoreset, same draw, epoch ep (v2:
+ *      placed on the current layout, then layout_id redrawn; v4: layout_id first);
+ *   2. key = lid * G^2 + bx * G + by of the state after that reset: lid the layout row the step will use, clamped to
+ *      0..L-1 (0 for v1), bx and by clamped to 0..G-1;
+ *   3. action = policy[key]; if epsilon_u32 != 0, r = the exploration draw of lmaze_rollout_policy -- Philox4x32-10(counter
+ *      (e_lo, e_hi, ep_lo, ep_hi ^ 0x80000000), key (seed_lo, seed_hi)) -- and where r.x < epsilon_u32 the action becomes
+ *      (r.y * A) >> 32 with A = 4 for v1 and A = 25 for v2/v4 (A = 4: r.y >> 30, the grid envs' rule);
+ *   4. the transition, visit-map update (v4) and observation of lmaze_foveal_step with that action;
+ *   5. actions_t[t,i] = the action, key_t[t,i] = the key -- for every env, skipped ones included.
+ * The caller advances its epoch by T whether or not auto_reset is set: exploration consumes epochs too.
+ * The table is staged in LDS once per workgroup, behind the layout characters, when L*G*G <= 8192 bytes (196 B for v1,
+ * 1 620 B for the five 18 x 18 layouts of v2/v4); above that it is read from global memory, one byte per env-step.  This is
+ * a rule, not a measurement; lmaze_describe_foveal_rollout_policy reports it as table=lds / table=global.
+ * v5/v6 are refused: their two-level step sits at 128 VGPRs and a closed loop there needs two tables (action and planner
+ * goal).  No grid size is refused: every form exists for any G (v1's recording form at G != 14 runs at 4 waves per SIMD).
+ * Refused before anything is queued, in this order:
+ *   1. the recording request: LMAZE_E_COUNT obs_every < 0, or obs_t given with obs_every == 0; LMAZE_E_NULL obs_t missing
+ *      while T / obs_every > 0; LMAZE_E_ALIGN obs_t not 16-byte aligned;
+ *   2. the params' own: LMAZE_E_NULL params; LMAZE_E_VARIANT an unknown variant; LMAZE_E_GRID; LMAZE_E_LAYOUT n_layouts or
+ *      launch_hint;
+ *   3. LMAZE_E_VARIANT v5/v6;
+ *   4. LMAZE_E_COUNT T < 0 or n outside [0, LMAZE_MAX_ENVS];
+ *   5. T == 0 or n == 0 returns 0 with nothing read;
+ *   6. LMAZE_E_NULL a required pointer (layouts, bufs and its members as for lmaze_foveal_step, policy), then LMAZE_E_ALIGN
+ *      as lmaze_foveal_step.
+ * launch_hint bits 0-3, 4-7 and 8-9 as in lmaze_foveal_rollout; they never change results.
+ */
+int lmaze_foveal_rollout_policy(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* policy,
+                                uint32_t epsilon_u32, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
+                                int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
+                                float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                                int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream);
+
+/* As lmaze_describe_foveal_rollout, for lmaze_foveal_rollout_policy with this obs_every (0: no recording):
+ * "foveal_rollout_policy_kernel<v2, 32, 18, fused-reset, obs_t> table=lds T=24 grid=...".  LMAZE_E_NULL text_host NULL or
+ * len < 1, then the entry point's refusals 1-4 in their order (obs_every > 0 stands for a given obs_t); an empty line for
+ * T == 0 or n == 0.  Nothing is queued or dereferenced. */
+int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                         int32_t obs_every, char* text_host, int32_t len);
+
+/*
  * v6 safeFovealGoal() (v6:505-523): for every env one window cell index 0..24 drawn uniformly from the
  * cells of the 5x5 window around the ball that are not 'W' (the reference rejects on np.random; here
  * Philox keyed by (seed, env_base + i, epoch), index (r*count)>>32 among the accepted cells in
