@@ -219,29 +219,32 @@ def device_info(device=0):
     return {"cu_count": cu.value, "arch": name.value.decode("ascii", "replace")}
 
 
+def _describe(symbol, *args):
+    """The line of the library's `symbol`(*args, text, 256), one of its lmaze_describe_* functions."""
+    buf = C.create_string_buffer(256)
+    check(symbol, getattr(lib, symbol)(*args, buf, 256))
+    return buf.value.decode("ascii", "replace")
+
+
+def _planes(with_obs):
+    return 2 if with_obs == "u8" else (1 if with_obs else 0)
+
+
 def describe_step(params, n, auto_reset=False, with_obs=True):
     """The kernel / grid / launch policy the library would queue for n envs with these LmazeParams (lmaze_describe_step)."""
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_step", lib.lmaze_describe_step(C.byref(params), int(n), 1 if auto_reset else 0,
-                                                         2 if with_obs == "u8" else (1 if with_obs else 0), buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe("lmaze_describe_step", C.byref(params), int(n), 1 if auto_reset else 0, _planes(with_obs))
 
 
 def describe_rollout(params, n, T, auto_reset=False, with_obs=True, obs_every=None):
     """The kernel / grid / envs per workgroup a grid rollout would queue for n envs and T steps (lmaze_describe_rollout):
     with_obs True / False / "u8" picks lmaze_rollout with obs, without obs, or lmaze_rollout_u8; obs_every (None: the
     plain rollout) the recording entry point with that k."""
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_rollout", lib.lmaze_describe_rollout(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
-                                                               2 if with_obs == "u8" else (1 if with_obs else 0),
-                                                               -1 if obs_every is None else int(obs_every), buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe("lmaze_describe_rollout", C.byref(params), int(n), int(T), 1 if auto_reset else 0, _planes(with_obs),
+                     -1 if obs_every is None else int(obs_every))
 
 
 def describe_foveal_step(params, n, auto_reset=False):
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_foveal_step", lib.lmaze_describe_foveal_step(C.byref(params), int(n), 1 if auto_reset else 0, buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe("lmaze_describe_foveal_step", C.byref(params), int(n), 1 if auto_reset else 0)
 
 
 KEY_MODES = {"ball": 0, "goal": 1}
@@ -256,34 +259,27 @@ def epsilon_u32(epsilon):
     return min(int(eps * 4294967296.0), 4294967295)
 
 
+def _describe_closed(symbol, params, n, T, auto_reset, with_obs, obs_every, key):
+    return _describe(symbol, C.byref(params), int(n), int(T), 1 if auto_reset else 0, _planes(with_obs), int(obs_every),
+                     KEY_MODES[key] if key in KEY_MODES else int(key))
+
+
 def describe_rollout_policy(params, n, T, auto_reset=True, with_obs=True, obs_every=0, key="ball"):
     """The kernel form / grid / LDS / envs per workgroup a closed-loop rollout would queue (lmaze_describe_rollout_policy):
     with_obs True / False / "u8" as describe_rollout, obs_every >= 0, key "ball" or "goal"."""
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_rollout_policy",
-          lib.lmaze_describe_rollout_policy(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
-                                            2 if with_obs == "u8" else (1 if with_obs else 0), int(obs_every),
-                                            KEY_MODES[key] if key in KEY_MODES else int(key), buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe_closed("lmaze_describe_rollout_policy", params, n, T, auto_reset, with_obs, obs_every, key)
 
 
 def describe_rollout_sample(params, n, T, auto_reset=True, with_obs=True, obs_every=0, key="ball"):
     """As describe_rollout_policy, for the sampling rollouts (lmaze_describe_rollout_sample): the line names where the
     threshold table lives, table=lds or table=global."""
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_rollout_sample",
-          lib.lmaze_describe_rollout_sample(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
-                                            2 if with_obs == "u8" else (1 if with_obs else 0), int(obs_every),
-                                            KEY_MODES[key] if key in KEY_MODES else int(key), buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe_closed("lmaze_describe_rollout_sample", params, n, T, auto_reset, with_obs, obs_every, key)
 
 
 def describe_table_stats(m, keys, actions=4):
     """The kernel / grid / LDS lmaze_table_stats would queue for m samples and a [keys, actions] table
     (lmaze_describe_table_stats): table_stats_kernel<lds> up to 4096 bins, <global> above; "" for m == 0."""
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_table_stats", lib.lmaze_describe_table_stats(int(m), int(keys), int(actions), buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe("lmaze_describe_table_stats", int(m), int(keys), int(actions))
 
 
 def sampling_thresholds(probs):
@@ -313,25 +309,16 @@ def sampling_thresholds(probs):
 def describe_foveal_rollout(params, n, T, auto_reset=False, two_level=False, obs_every=None):
     """The kernel / grid / launch policy lmaze_foveal_rollout would queue for n envs and T steps; obs_every (None: the plain
     rollout): lmaze_foveal_rollout_obs with that k (lmaze_describe_foveal_rollout_obs)."""
-    buf = C.create_string_buffer(256)
+    args = (C.byref(params), int(n), int(T), 1 if auto_reset else 0, 1 if two_level else 0)
     if obs_every is None:
-        check("lmaze_describe_foveal_rollout", lib.lmaze_describe_foveal_rollout(C.byref(params), int(n), int(T),
-                                                                                 1 if auto_reset else 0, 1 if two_level else 0,
-                                                                                 buf, 256))
-    else:
-        check("lmaze_describe_foveal_rollout_obs",
-              lib.lmaze_describe_foveal_rollout_obs(C.byref(params), int(n), int(T), 1 if auto_reset else 0,
-                                                    1 if two_level else 0, int(obs_every), buf, 256))
-    return buf.value.decode("ascii", "replace")
+        return _describe("lmaze_describe_foveal_rollout", *args)
+    return _describe("lmaze_describe_foveal_rollout_obs", *args, int(obs_every))
 
 
 def describe_foveal_rollout_policy(params, n, T, auto_reset=False, obs_every=0):
     """The kernel / grid / launch policy lmaze_foveal_rollout_policy would queue for n envs and T steps (obs_every=0: no
     recording), and where its table lives: "... table=lds ..." or "... table=global ..."."""
-    buf = C.create_string_buffer(256)
-    check("lmaze_describe_foveal_rollout_policy",
-          lib.lmaze_describe_foveal_rollout_policy(C.byref(params), int(n), int(T), 1 if auto_reset else 0, int(obs_every), buf, 256))
-    return buf.value.decode("ascii", "replace")
+    return _describe("lmaze_describe_foveal_rollout_policy", C.byref(params), int(n), int(T), 1 if auto_reset else 0, int(obs_every))
 
 
 def make_params(variant, grid, layout_mode, step_limit, reward_wall, reward_move, reward_goal):

@@ -138,6 +138,59 @@ class VecEnvBase(object):
             out += (rows[i], rows[i + 1].view(torch.bool))
         return out
 
+    # ------------------------------------------------------------------ closed-loop rollouts (rollout_policy() and its kin)
+    @staticmethod
+    def _steps(T):
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
+            raise ValueError("T must be an int >= 0")
+        return int(T)
+
+    @staticmethod
+    def greedy_table(q):
+        """The greedy action table uint8[S] of a float tensor q[S, A] (A <= 255), on q's device: the FIRST maximum of every
+        row, spelled out (the lowest index whose value equals the row's maximum) and not left to argmax's tie behaviour.
+        A row that holds a NaN equals its maximum nowhere and gets the id A, which every step treats as no move."""
+        if not (isinstance(q, torch.Tensor) and q.dim() == 2 and q.is_floating_point() and 1 <= q.shape[1] <= 255):
+            raise ValueError("q must be a float tensor [S, A] with 1 <= A <= 255")
+        A = q.shape[1]
+        idx = torch.arange(A, device=q.device, dtype=torch.int32).expand_as(q)
+        first = torch.where(q == q.max(dim=1, keepdim=True).values, idx, torch.full_like(idx, A)).min(dim=1).values
+        return first.to(torch.uint8)
+
+    def _greedy_policy(self, policy, q, entries, shape):
+        """rollout_policy()'s table: policy itself, or greedy_table(q), as a contiguous uint8 tensor of `entries` entries
+        on the device.  shape: what the refusal says of the table's size."""
+        if q is not None:
+            if not isinstance(q, torch.Tensor) or q.device != self.device:
+                raise ValueError("q must be a float tensor [S, A] on %s" % self.device)
+            policy = self.greedy_table(q)
+        if not (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.device == self.device
+                and policy.is_contiguous() and policy.numel() == entries):
+            raise ValueError("policy must be a contiguous uint8 tensor of %d entries on %s (%s)" % (entries, self.device, shape))
+        return policy
+
+    def _closed_loop(self, who, name, call, T, k, obs_t, trajectory, actions_t, key_t, streams=1):
+        """What every closed-loop rollout does around its ABI call `name`, once its table and its recording request (k =
+        _obs_slots()) are checked: the actions_t / key_t rows (checked; allocated under trajectory=True), the trajectory
+        rows of `streams` streams, the launch -- call(row addresses, actions_t's, key_t's, the slots') returns the ABI's
+        code -- the epoch, which advances by T, and the result: rollout()'s, then under trajectory=True actions_t, key_t."""
+        self._check_rows(who, actions_t, key_t)
+        for label, t in (("actions_t", actions_t), ("key_t", key_t)):
+            if t is not None and t.shape[0] != T:
+                raise ValueError("%s must have T = %d rows" % (label, T))
+        rows = self._traj_rows(T, streams) if trajectory else None
+        if trajectory:
+            actions_t = torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
+            key_t = torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device) if key_t is None else key_t
+        slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
+        with self._guard():
+            rc = call([r.data_ptr() for r in rows or ()], None if actions_t is None else actions_t.data_ptr(),
+                      None if key_t is None else key_t.data_ptr(), slots)
+        _abi.check(name, rc)
+        self._epoch += T
+        out = self._rollout_result(rows)
+        return out + (actions_t, key_t) if trajectory else out
+
     def host_state(self, raw=None):
         """Every per-env scalar on the host: numpy views of ONE device->host copy of the state block.  raw: bytes of
         the block already on the host (uint8 array the size of `_state`), parsed instead of copying again."""

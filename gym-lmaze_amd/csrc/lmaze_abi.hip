@@ -65,14 +65,16 @@ void describe_launch(LaunchInfo* info, const char* kernel, int epb, int per_cu, 
     info->block = block;
     info->lds = (int64_t)lds;
 }
-}  // namespace lmaze
 
-static int format_launch(const LaunchInfo& i, char* text, int32_t len) {
+int format_launch(const LaunchInfo& i, char* text, int32_t len, int32_t T) {
     if (!text || len < 1) return LMAZE_E_NULL;
-    snprintf(text, (size_t)len, "%s grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d", i.kernel,
+    char steps[16] = "";
+    if (T >= 0) snprintf(steps, sizeof(steps), " T=%d", T);
+    snprintf(text, (size_t)len, "%s%s grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d", i.kernel, steps,
              (long long)i.grid, i.block, (long long)i.lds, i.envs_per_workgroup, i.workgroups_per_cu, i.chunks);
     return 0;
 }
+}  // namespace lmaze
 
 // The recording request of lmaze_rollout_obs / lmaze_rollout_obs_u8: refusals that need nothing else
 static int check_recording(int32_t T, const void* slots, int32_t every) {
@@ -152,32 +154,43 @@ static int check_closed_loop(const LmazeParams* params, const uint8_t* layout, c
     return 0;
 }
 
-static int grid_rollout_policy(const LmazeParams* params, const uint8_t* layout, const RolloutPolicy& pol, int32_t T, int32_t* ball_xy,
+// lmaze_rollout_policy / lmaze_rollout_sample and their _u8 forms, and with info != null their describes (then only the
+// params, the counts and key_mode are judged).  tab: a PolicyTable or a SampleTable; an entry's size is the alignment the
+// table needs (1 or 16).  slots / every: the recording request as the caller gave it, refused first.
+template <class Table>
+static int grid_rollout_closed(const LmazeParams* params, const uint8_t* layout, const Table& tab, int32_t T, int32_t* ball_xy,
                                int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
                                bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
-                               uint64_t epoch, int64_t env_base, const RolloutRec& rec, LaunchInfo* info, void* stream) {
+                               uint64_t epoch, int64_t env_base, void* slots, int32_t every, LaunchInfo* info, void* stream) {
+    int rc = info ? 0 : check_recording(T, slots, every);
+    if (rc) return rc;
     bool go;
-    const int rc = check_closed_loop(params, layout, pol.table, 1, pol.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs, u8,
-                                     n, info != nullptr, &go);
+    rc = check_closed_loop(params, layout, tab.table, sizeof(*tab.table), tab.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs,
+                           u8, n, info != nullptr, &go);
     if (!go) return rc;
     StepArgs a = rollout_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
                               seed, epoch, env_base);
     a.info = info;
-    return (int)launch_rollout_policy(params->variant, a, params->layout_mode, pol, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
+    return (int)launch_rollout_closed(params->variant, a, params->layout_mode, tab, T, reward_t, done_t, (hipStream_t)stream,
+                                      recording(T, slots, every), u8);
 }
 
-static int grid_rollout_sample(const LmazeParams* params, const uint8_t* layout, const RolloutSample& smp, int32_t T, int32_t* ball_xy,
-                               int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
-                               bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
-                               uint64_t epoch, int64_t env_base, const RolloutRec& rec, LaunchInfo* info, void* stream) {
-    bool go;
-    const int rc = check_closed_loop(params, layout, smp.thresholds, 16, smp.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs,
-                                     u8, n, info != nullptr, &go);
-    if (!go) return rc;
-    StepArgs a = rollout_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
-                              seed, epoch, env_base);
-    a.info = info;
-    return (int)launch_rollout_sample(params->variant, a, params->layout_mode, smp, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
+// lmaze_describe_rollout_policy / lmaze_describe_rollout_sample
+template <class Table>
+static int describe_rollout_closed(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
+    if (obs_every < 0) return LMAZE_E_COUNT;
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const bool u8 = with_obs == 2;   // the narrow planes (the _u8 entry points)
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    // nothing is dereferenced: fabricated, aligned addresses stand for the buffers whose presence decides
+    const int rc = grid_rollout_closed(params, nullptr, Table{nullptr, nullptr, nullptr, key_mode, 0}, T, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, nullptr, with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8,
+                                       nullptr, nullptr, n, auto_reset, 0, 0, 0, reinterpret_cast<void*>(32), obs_every, &info, nullptr);
+    if (rc || n == 0 || T == 0) return rc;
+    return format_launch(info, text_host, len);
 }
 
 extern "C" {
@@ -372,11 +385,9 @@ int lmaze_rollout_policy(const LmazeParams* params, const uint8_t* layout, const
                          uint8_t* done, int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t,
                          int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
                          int32_t* obs_t, int32_t obs_every, void* stream) {
-    const int rc = check_recording(T, obs_t, obs_every);
-    const RolloutPolicy pol{policy, key_mode, epsilon_u32, actions_t, key_t};
-    return rc ? rc : grid_rollout_policy(params, layout, pol, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
-                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t, obs_every),
-                                         nullptr, stream);
+    const PolicyTable tab{policy, actions_t, key_t, key_mode, epsilon_u32};
+    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t,
+                               n, auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_rollout_policy_u8(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
@@ -384,28 +395,14 @@ int lmaze_rollout_policy_u8(const LmazeParams* params, const uint8_t* layout, co
                             uint8_t* done, int32_t* goal_count, uint8_t* obs8, float* reward_t, uint8_t* done_t, int32_t* actions_t,
                             int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
                             uint8_t* obs_t8, int32_t obs_every, void* stream) {
-    const int rc = check_recording(T, obs_t8, obs_every);
-    const RolloutPolicy pol{policy, key_mode, epsilon_u32, actions_t, key_t};
-    return rc ? rc : grid_rollout_policy(params, layout, pol, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
-                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t8, obs_every),
-                                         nullptr, stream);
+    const PolicyTable tab{policy, actions_t, key_t, key_mode, epsilon_u32};
+    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t, done_t,
+                               n, auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
 }
 
 int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
-    if (obs_every < 0) return LMAZE_E_COUNT;
-    if (!text_host || len < 1) return LMAZE_E_NULL;
-    text_host[0] = 0;
-    const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_policy_u8)
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    // nothing is dereferenced: fabricated, aligned addresses stand for the buffers whose presence decides
-    const RolloutPolicy pol{nullptr, key_mode, 0, nullptr, nullptr};
-    const int rc = grid_rollout_policy(params, nullptr, pol, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                       with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, nullptr, nullptr, n, auto_reset,
-                                       0, 0, 0, recording(T, reinterpret_cast<void*>(32), obs_every), &info, nullptr);
-    if (rc || n == 0 || T == 0) return rc;
-    return format_launch(info, text_host, len);
+    return describe_rollout_closed<PolicyTable>(params, n, T, auto_reset, with_obs, obs_every, key_mode, text_host, len);
 }
 
 // The closed-loop foveal rollout (lmaze_foveal_policy.hip).  info != null: describe instead of launching -- then nothing
@@ -474,10 +471,7 @@ int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_
                                          nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, obs_every, &info,
                                          nullptr);
     if (rc || n == 0 || T == 0) return rc;
-    snprintf(text_host, (size_t)len, "%s T=%d grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d",
-             info.kernel, T, (long long)info.grid, info.block, (long long)info.lds, info.envs_per_workgroup,
-             info.workgroups_per_cu, info.chunks);
-    return 0;
+    return format_launch(info, text_host, len, T);
 }
 
 int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
@@ -485,11 +479,9 @@ int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const
                          int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t, int64_t n,
                          int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t, int32_t obs_every,
                          void* stream) {
-    const int rc = check_recording(T, obs_t, obs_every);
-    const RolloutSample smp{thresholds, key_mode, actions_t, key_t};
-    return rc ? rc : grid_rollout_sample(params, layout, smp, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
-                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t, obs_every),
-                                         nullptr, stream);
+    const SampleTable tab{reinterpret_cast<const sample_row_t*>(thresholds), actions_t, key_t, key_mode, 0};
+    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t,
+                               n, auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_rollout_sample_u8(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
@@ -497,28 +489,14 @@ int lmaze_rollout_sample_u8(const LmazeParams* params, const uint8_t* layout, co
                             int32_t* goal_count, uint8_t* obs8, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
                             int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, uint8_t* obs_t8,
                             int32_t obs_every, void* stream) {
-    const int rc = check_recording(T, obs_t8, obs_every);
-    const RolloutSample smp{thresholds, key_mode, actions_t, key_t};
-    return rc ? rc : grid_rollout_sample(params, layout, smp, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
-                                         reward_t, done_t, n, auto_reset, seed, epoch, env_base, recording(T, obs_t8, obs_every),
-                                         nullptr, stream);
+    const SampleTable tab{reinterpret_cast<const sample_row_t*>(thresholds), actions_t, key_t, key_mode, 0};
+    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t, done_t,
+                               n, auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
 }
 
 int lmaze_describe_rollout_sample(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
-    if (obs_every < 0) return LMAZE_E_COUNT;
-    if (!text_host || len < 1) return LMAZE_E_NULL;
-    text_host[0] = 0;
-    const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_sample_u8)
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    // nothing is dereferenced: fabricated, aligned addresses stand for the buffers whose presence decides
-    const RolloutSample smp{nullptr, key_mode, nullptr, nullptr};
-    const int rc = grid_rollout_sample(params, nullptr, smp, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                       with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, nullptr, nullptr, n, auto_reset,
-                                       0, 0, 0, recording(T, reinterpret_cast<void*>(32), obs_every), &info, nullptr);
-    if (rc || n == 0 || T == 0) return rc;
-    return format_launch(info, text_host, len);
+    return describe_rollout_closed<SampleTable>(params, n, T, auto_reset, with_obs, obs_every, key_mode, text_host, len);
 }
 
 int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t, int32_t T,

@@ -33,6 +33,9 @@ struct LaunchInfo {
     int64_t grid, lds;
 };
 void describe_launch(LaunchInfo* info, const char* kernel, int epb, int per_cu, int chunks, bool nt, int64_t grid, int block, size_t lds);
+// The line of every lmaze_describe_* that reports a launch: "<kernel>[ T=<T>] grid=... block=... lds=...", T >= 0 for the
+// foveal rollouts, whose kernel names do not carry it (lmaze_abi.hip)
+int format_launch(const LaunchInfo& info, char* text, int32_t len, int32_t T = -1);
 
 // Everything a step/observe launch needs, passed by value in the kernarg segment.
 struct StepArgs {
@@ -115,27 +118,31 @@ struct RolloutRec {
 };
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec* rec, bool u8);
-// The closed-loop grid rollout (lmaze_rollout_policy / lmaze_rollout_policy_u8): the tabular epsilon-greedy policy that
-// stands where the action tensor stood, and the optional rows int32[T,N] of the actions taken and their keys.  rec is
-// never null: these rollouts store planes on recorded steps and after the last one only.  Always one launch.
-struct RolloutPolicy {
-    const uint8_t* table;     // uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1, v3)
-    int32_t key_mode;
-    uint32_t epsilon;         // min(floor(eps * 2^32), 2^32 - 1)
-    int32_t* actions_t;
-    int32_t* key_t;
+// The closed-loop grid rollouts: a table policy stands where the action tensor stood, and the optional rows int32[T,N] of
+// the actions taken and their keys.  The table structs are what the kernels take (members of their argument structs): the
+// ABI fills them, the launcher sets what it decides itself (SampleTable::staged).  rec is never null: these rollouts store
+// planes on recorded steps and after the last one only.  Always one launch.
+// lmaze_rollout_policy / lmaze_rollout_policy_u8: the tabular epsilon-greedy policy
+struct PolicyTable {
+    const uint8_t* table;     // uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1): the greedy action id of each key
+    int32_t* actions_t;       // [T, N] or null: the action every step took
+    int32_t* key_t;           // [T, N] or null: the key it was looked up with
+    int32_t key_mode;         // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
+    uint32_t epsilon;         // explore when the draw's x < epsilon, min(floor(eps * 2^32), 2^32 - 1); 0: nothing is drawn
 };
-hipError_t launch_rollout_policy(int variant, const StepArgs& a, int layout_mode, const RolloutPolicy& pol, int32_t T,
+// lmaze_rollout_sample / lmaze_rollout_sample_u8: a categorical table policy, one row of cumulative thresholds per key
+// (include/lmaze.h), 16-byte aligned
+typedef uint32_t sample_row_t __attribute__((ext_vector_type(4)));      // one key's row: c0, c1, c2, reserved
+struct SampleTable {
+    const sample_row_t* table;   // uint32[S, 4]: S = G^2 (key_mode 0) or G^4 (key_mode 1); words 0-2 c0 <= c1 <= c2, word 3 ignored
+    int32_t* actions_t;          // [T, N] or null: the action every step took
+    int32_t* key_t;              // [T, N] or null: the key it was drawn for
+    int32_t key_mode;            // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
+    int32_t staged;              // != 0: the workgroup copies the ball-keyed table into LDS and reads it there
+};
+hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T,
                                  float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
-// The sampling closed-loop grid rollout (lmaze_rollout_sample / lmaze_rollout_sample_u8): a categorical table policy, one
-// uint32[4] of cumulative thresholds per key (include/lmaze.h), where RolloutPolicy holds the greedy table.
-struct RolloutSample {
-    const uint32_t* thresholds;   // uint32[G^2, 4] (key_mode 0) or uint32[G^4, 4] (key_mode 1, v3), 16-byte aligned
-    int32_t key_mode;
-    int32_t* actions_t;
-    int32_t* key_t;
-};
-hipError_t launch_rollout_sample(int variant, const StepArgs& a, int layout_mode, const RolloutSample& smp, int32_t T,
+hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const SampleTable& tab, int32_t T,
                                  float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
 // Discounted returns-to-go over trajectory rows (lmaze_returns, lmaze_aux.hip)
 hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t,

@@ -597,11 +597,7 @@ static int describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, i
     rr.every = obs_every ? *obs_every : 1;
     const int rc = obs_every ? (int)launch_foveal_rollout(a, rr, nullptr)
                              : (int)launch_foveal_rollout(a, static_cast<const FovealRoll&>(rr), nullptr);
-    if (rc) return rc;
-    snprintf(text_host, (size_t)len, "%s T=%d grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d",
-             info.kernel, T, (long long)info.grid, info.block, (long long)info.lds, info.envs_per_workgroup,
-             info.workgroups_per_cu, info.chunks);
-    return 0;
+    return rc ? rc : format_launch(info, text_host, len, T);
 }
 
 int lmaze_describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
@@ -689,10 +685,7 @@ int lmaze_describe_foveal_step(const LmazeFovealParams* params, int64_t n, int32
     a.auto_reset = auto_reset ? 1 : 0;
     a.info = &info;
     const int rc = (int)launch_foveal_mode<FM_STEP>(a, nullptr);
-    if (rc) return rc;
-    snprintf(text_host, (size_t)len, "%s grid=%lld block=%d lds=%lld envs_per_workgroup=%d workgroups_per_cu=%d chunks=%d", info.kernel,
-             (long long)info.grid, info.block, (long long)info.lds, info.envs_per_workgroup, info.workgroups_per_cu, info.chunks);
-    return 0;
+    return rc ? rc : format_launch(info, text_host, len);
 }
 
 int64_t lmaze_foveal_visit_bytes(int32_t grid, int64_t n) {

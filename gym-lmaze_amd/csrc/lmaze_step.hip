@@ -1135,13 +1135,7 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const St
 // were added: the open-loop kernels keep their symbols and code.  Recording semantics only (REC): planes are stored on
 // recorded steps and after the last one.
 // ------------------------------------------------------------------------------------
-struct PolicyTable {
-    const uint8_t* table;     // uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1): the greedy action id of each key
-    int32_t* actions_t;       // [T, N] or null: the action every step took
-    int32_t* key_t;           // [T, N] or null: the key it was looked up with
-    int32_t key_mode;         // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
-    uint32_t epsilon;         // explore when the draw's x < epsilon; 0: nothing is drawn
-};
+// PolicyTable: lmaze_common.h
 struct RolloutPolicyArgs : RolloutObsArgs { PolicyTable pol; };     // actions: null, never read
 struct RolloutPolicy8Args : RolloutObs8Args { PolicyTable pol; };
 
@@ -1224,14 +1218,7 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const St
 // 16-byte read per env-step, L2- or Infinity-Cache-resident.  The host decides (rollout_plan) and passes `staged`.
 // Again new overloads on new argument types, bodies 2-4 with LMAZE_ROLLOUT_POLICY == 2.
 // ------------------------------------------------------------------------------------
-typedef uint32_t sample_row_t __attribute__((ext_vector_type(4)));      // one key's row: c0, c1, c2, reserved
-struct SampleTable {
-    const sample_row_t* table;   // uint32[S, 4]: S = G^2 (key_mode 0) or G^4 (key_mode 1); words 0-2 c0 <= c1 <= c2, word 3 ignored
-    int32_t* actions_t;          // [T, N] or null: the action every step took
-    int32_t* key_t;              // [T, N] or null: the key it was drawn for
-    int32_t key_mode;            // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
-    int32_t staged;              // != 0: the workgroup copies the ball-keyed table into LDS and reads it there
-};
+// sample_row_t, SampleTable: lmaze_common.h
 struct RolloutSampleArgs : RolloutObsArgs { SampleTable pol; };     // actions: null, never read
 struct RolloutSample8Args : RolloutObs8Args { SampleTable pol; };
 
@@ -1821,29 +1808,31 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
     return hipGetLastError();
 }
 
-// The closed-loop rollout (lmaze_rollout_policy / _u8): ONE launch of the planned family's closed-loop form, whatever T
-// and launch_hint bit 8 say.
-hipError_t launch_rollout_policy(int variant, const StepArgs& a0, int layout_mode, const RolloutPolicy& pol, int32_t T,
-                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+// The closed-loop rollouts: ONE launch of the planned family's closed-loop form, whatever T and launch_hint bit 8 say.
+// Args / Args8: the kernel argument structs that carry `tab` (int32 / narrow planes); plan: a PLAN_* of the form; form and
+// table_note: what the describe name says of the policy, "<form>=<ball|goal><table_note>".
+template <class Args, class Args8, class Table>
+static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode, const Table& tab, int plan, const char* form,
+                                const char* table_note, int32_t T, float* reward_t, uint8_t* done_t, hipStream_t s,
+                                const RolloutRec& rec, bool u8) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
-    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, PLAN_POLICY);
+    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, plan);
     if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
     if (a0.info) {
         char name[96];
-        snprintf(name, sizeof(name), "%s<v%d, policy=%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
-                 pol.key_mode ? "goal" : "ball", rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T, rec.every);
+        snprintf(name, sizeof(name), "%s<v%d, %s=%s%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant, form,
+                 tab.key_mode ? "goal" : "ball", table_note, rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T, rec.every);
         describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
         return hipSuccess;
     }
     StepArgs a = a0;
     a.envs_per_block = p.epb;
-    const PolicyTable tab{pol.table, pol.actions_t, pol.key_t, pol.key_mode, pol.epsilon};
     RolloutArgs plain{nullptr, reward_t, done_t, T};
-    RolloutPolicyArgs ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
-    RolloutPolicy8Args ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
+    Args ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
+    Args8 ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
     void* args[] = {&a, u8 ? (void*)&ro8 : (void*)&ro};
-    using K = void (*)(const StepArgs, const RolloutPolicyArgs);
-    using K8 = void (*)(const StepArgs, const RolloutPolicy8Args);
+    using K = void (*)(const StepArgs, const Args);
+    using K8 = void (*)(const StepArgs, const Args8);
     constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
     const void* kernel = p.family == RO_U8       ? kernel_of<K8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
                          : p.family == RO_PERENV ? kernel_of<K>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
@@ -1852,37 +1841,22 @@ hipError_t launch_rollout_policy(int variant, const StepArgs& a0, int layout_mod
     return hipGetLastError();
 }
 
-// The sampling closed-loop rollout (lmaze_rollout_sample / _u8): launch_rollout_policy with the threshold table.  The
-// table is staged in LDS by rule -- ball-keyed and G <= 32, i.e. at most 16 KiB -- and read from global memory otherwise.
-hipError_t launch_rollout_sample(int variant, const StepArgs& a0, int layout_mode, const RolloutSample& smp, int32_t T,
-                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
-    if (T <= 0 || a0.n == 0) return hipSuccess;
-    const bool staged = smp.key_mode == 0 && a0.grid <= 32;
-    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, staged ? PLAN_SAMPLE_LDS : PLAN_SAMPLE_GLOBAL);
-    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
-    if (a0.info) {
-        char name[96];
-        snprintf(name, sizeof(name), "%s<v%d, sample=%s, table=%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
-                 smp.key_mode ? "goal" : "ball", staged ? "lds" : "global", rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T,
-                 rec.every);
-        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
-        return hipSuccess;
-    }
-    StepArgs a = a0;
-    a.envs_per_block = p.epb;
-    const SampleTable tab{reinterpret_cast<const sample_row_t*>(smp.thresholds), smp.actions_t, smp.key_t, smp.key_mode, staged ? 1 : 0};
-    RolloutArgs plain{nullptr, reward_t, done_t, T};
-    RolloutSampleArgs ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
-    RolloutSample8Args ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
-    void* args[] = {&a, u8 ? (void*)&ro8 : (void*)&ro};
-    using K = void (*)(const StepArgs, const RolloutSampleArgs);
-    using K8 = void (*)(const StepArgs, const RolloutSample8Args);
-    constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
-    const void* kernel = p.family == RO_U8       ? kernel_of<K8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
-                         : p.family == RO_PERENV ? kernel_of<K>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
-                                                 : kernel_of<K>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
-    return hipGetLastError();
+// lmaze_rollout_policy / _u8: the epsilon-greedy table, always staged
+hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T, float* reward_t,
+                                 uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+    return launch_closed<RolloutPolicyArgs, RolloutPolicy8Args>(variant, a, layout_mode, tab, PLAN_POLICY, "policy", "", T, reward_t,
+                                                                done_t, s, rec, u8);
+}
+
+// lmaze_rollout_sample / _u8: the threshold table is staged in LDS by rule -- ball-keyed and G <= 32, i.e. at most 16 KiB --
+// and read from global memory otherwise
+hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const SampleTable& tab0, int32_t T, float* reward_t,
+                                 uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+    SampleTable tab = tab0;
+    tab.staged = tab.key_mode == 0 && a.grid <= 32 ? 1 : 0;
+    return launch_closed<RolloutSampleArgs, RolloutSample8Args>(variant, a, layout_mode, tab, tab.staged ? PLAN_SAMPLE_LDS : PLAN_SAMPLE_GLOBAL,
+                                                                "sample", tab.staged ? ", table=lds" : ", table=global", T, reward_t, done_t,
+                                                                s, rec, u8);
 }
 
 hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s) {

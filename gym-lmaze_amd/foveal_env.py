@@ -257,55 +257,26 @@ class LmazeFovealVecEnv(VecEnvBase):
         stream capture: the host's epoch would be frozen into the graph)."""
         if self._two_level:
             raise ValueError("rollout_policy() is not available for v5/v6: their two-level step needs two tables")
-        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
-            raise ValueError("T must be an int >= 0")
-        T, N = int(T), self.num_envs
+        T = self._steps(T)
         if (policy is None) == (q is None):
             raise ValueError("rollout_policy() wants exactly one of policy= and q=")
         eps = _abi.epsilon_u32(epsilon)
         if torch.cuda.is_current_stream_capturing():
             raise ValueError("rollout_policy() is not available with a device-resident epoch (under stream capture)")
-        entries = self.n_layouts * self.grid * self.grid
-        if q is not None:
-            if not isinstance(q, torch.Tensor) or q.device != self.device:
-                raise ValueError("q must be a float tensor [S, A] on %s" % self.device)
-            policy = self.greedy_table(q)
-        if not (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.device == self.device
-                and policy.is_contiguous() and policy.numel() == entries):
-            raise ValueError("policy must be a contiguous uint8 tensor of %d entries on %s (L=%d, G=%d)"
-                             % (entries, self.device, self.n_layouts, self.grid))
-        self._check_rows("rollout_policy()", actions_t, key_t)
-        for name, t in (("actions_t", actions_t), ("key_t", key_t)):
-            if t is not None and t.shape[0] != T:
-                raise ValueError("%s must have T = %d rows" % (name, T))
+        policy = self._greedy_policy(policy, q, self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid))
         k = 0
         if obs_every is not None:
             k = self._obs_slots(T, obs_every, obs_t, self.obs)
         elif obs_t is not None:
             raise ValueError("obs_t needs obs_every")
-        rows = self._traj_rows(T, 2 if self.variant == "v1" else 1) if trajectory else None
-        if trajectory:
-            actions_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
-            key_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if key_t is None else key_t
-        ptrs = [r.data_ptr() for r in rows] if rows else []
-        ptrs += [None] * (4 - len(ptrs))
-        slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
-        with self._guard():
-            rc = _abi.lib.lmaze_foveal_rollout_policy(
-                self._pp, self._p_layouts, policy.data_ptr(), eps, T, self._pb, N, 1 if auto_reset else 0,
-                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *ptrs,
-                None if actions_t is None else actions_t.data_ptr(), None if key_t is None else key_t.data_ptr(), slots, k,
-                self._stream())
-        _abi.check("lmaze_foveal_rollout_policy", rc)
-        self._epoch += T
-        out = self._rollout_result(rows)
-        return out + (actions_t, key_t) if trajectory else out
 
-    @staticmethod
-    def greedy_table(q):
-        """LmazeVecEnv.greedy_table: the first maximum of every row of q[S, A] as uint8[S]."""
-        from .vec_env import LmazeVecEnv
-        return LmazeVecEnv.greedy_table(q)
+        def call(rows, p_actions, p_key, slots):
+            return _abi.lib.lmaze_foveal_rollout_policy(
+                self._pp, self._p_layouts, policy.data_ptr(), eps, T, self._pb, self.num_envs, 1 if auto_reset else 0,
+                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key, slots, k,
+                self._stream())
+        return self._closed_loop("rollout_policy()", "lmaze_foveal_rollout_policy", call, T, k, obs_t, trajectory, actions_t, key_t,
+                                 streams=2 if self.variant == "v1" else 1)
 
     def state_keys(self):
         """int32[N]: the key of every env's CURRENT state, by the rule the key_t rows of rollout_policy() are written with --

@@ -337,18 +337,6 @@ class LmazeVecEnv(VecEnvBase):
                 self._launch_step(base + t * stride, self._p_obs, auto_reset, t if device_epoch else None)
         return self.obs, self.reward, self.done
 
-    @staticmethod
-    def greedy_table(q):
-        """The greedy action table uint8[S] of a float tensor q[S, A] (A <= 255), on q's device: the FIRST maximum of every
-        row, spelled out (the lowest index whose value equals the row's maximum) and not left to argmax's tie behaviour.
-        A row that holds a NaN equals its maximum nowhere and gets the id A, which every step treats as no move."""
-        if not (isinstance(q, torch.Tensor) and q.dim() == 2 and q.is_floating_point() and 1 <= q.shape[1] <= 255):
-            raise ValueError("q must be a float tensor [S, A] with 1 <= A <= 255")
-        A = q.shape[1]
-        idx = torch.arange(A, device=q.device, dtype=torch.int32).expand_as(q)
-        first = torch.where(q == q.max(dim=1, keepdim=True).values, idx, torch.full_like(idx, A)).min(dim=1).values
-        return first.to(torch.uint8)
-
     def rollout_policy(self, T, policy=None, q=None, epsilon=0.0, key="ball", auto_reset=True, trajectory=False,
                        actions_t=None, key_t=None, obs_t=None, obs_every=0):
         """T steps in ONE launch with a tabular epsilon-greedy policy inside the kernel (include/lmaze.h
@@ -363,50 +351,12 @@ class LmazeVecEnv(VecEnvBase):
         obs_every=k >= 1 records into obs_t as rollout() does; the default 0 stores the final planes only.  The epoch
         advances by T whether or not auto_reset is set: exploration consumes epochs too.  Not with a device-resident epoch
         (under stream capture: the host's epoch would be frozen into the graph), nor while the online tuner runs."""
-        if self._tuner is not None or torch.cuda.is_current_stream_capturing():
-            raise ValueError("rollout(obs_every=...) is not available with a device-resident epoch or while the online tuner runs")
-        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
-            raise ValueError("T must be an int >= 0")
-        T, N, G = int(T), self.num_envs, self.grid
+        T, entries = self._closed_loop_key("rollout_policy()", T, key)
         if (policy is None) == (q is None):
             raise ValueError("rollout_policy() wants exactly one of policy= and q=")
-        if key not in _abi.KEY_MODES:
-            raise ValueError("key must be 'ball' or 'goal'")
-        if key == "goal" and not self._is_v3:
-            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
-        entries = G ** 4 if key == "goal" else G * G
-        if q is not None:
-            if not isinstance(q, torch.Tensor) or q.device != self.device:
-                raise ValueError("q must be a float tensor [S, A] on %s" % self.device)
-            policy = self.greedy_table(q)
-        if not (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.device == self.device
-                and policy.is_contiguous() and policy.numel() == entries):
-            raise ValueError("policy must be a contiguous uint8 tensor of %d entries on %s (key=%r, G=%d)"
-                             % (entries, self.device, key, G))
-        eps = _abi.epsilon_u32(epsilon)
-        self._check_rows("rollout_policy()", actions_t, key_t)
-        for name, t in (("actions_t", actions_t), ("key_t", key_t)):
-            if t is not None and t.shape[0] != T:
-                raise ValueError("%s must have T = %d rows" % (name, T))
-        k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
-        rows = self._traj_rows(T) if trajectory else None
-        if trajectory:
-            actions_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
-            key_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if key_t is None else key_t
-        name = "lmaze_rollout_policy" + ("_u8" if self._u8 else "")
-        slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
-        with self._guard():
-            rc = getattr(_abi.lib, name)(
-                self._pp, self._p_layout, policy.data_ptr(), _abi.KEY_MODES[key], eps, T, self._p_ball,
-                self._p_goal if self._is_v3 else None, self._p_step, self._p_reward, self._p_done,
-                None if self._is_v3 else self._p_gc, self._p_obs, rows[0].data_ptr() if rows else None,
-                rows[1].data_ptr() if rows else None, None if actions_t is None else actions_t.data_ptr(),
-                None if key_t is None else key_t.data_ptr(), N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch,
-                self.env_base, slots, k, self._stream())
-        _abi.check(name, rc)
-        self._epoch += T
-        out = self._rollout_result(rows)
-        return out + (actions_t, key_t) if trajectory else out
+        policy = self._greedy_policy(policy, q, entries, "key=%r, G=%d" % (key, self.grid))
+        return self._rollout_table("rollout_policy", (policy.data_ptr(), _abi.KEY_MODES[key], _abi.epsilon_u32(epsilon)), T,
+                                   auto_reset, trajectory, actions_t, key_t, obs_t, obs_every)
 
     def rollout_sample(self, T, probs=None, logits=None, temperature=1.0, thresholds=None, key="ball", auto_reset=True,
                        trajectory=False, actions_t=None, key_t=None, obs_t=None, obs_every=0):
@@ -422,18 +372,10 @@ class LmazeVecEnv(VecEnvBase):
         (r >= c0) + (r >= c1) + (r >= c2) for one Philox value r per (seed, env, epoch); a cumulative probability of 1 is
         stored as 1 - 2**-32, so deterministic policies belong to rollout_policy().  Returns what rollout_policy() returns;
         obs_t / obs_every, the rows and the restrictions are its own too.  The epoch advances by T."""
-        if self._tuner is not None or torch.cuda.is_current_stream_capturing():
-            raise ValueError("rollout_sample() is not available with a device-resident epoch or while the online tuner runs")
-        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
-            raise ValueError("T must be an int >= 0")
-        T, N, G = int(T), self.num_envs, self.grid
+        T, entries = self._closed_loop_key("rollout_sample()", T, key)
+        G = self.grid
         if sum(x is not None for x in (probs, logits, thresholds)) != 1:
             raise ValueError("rollout_sample() wants exactly one of probs=, logits= and thresholds=")
-        if key not in _abi.KEY_MODES:
-            raise ValueError("key must be 'ball' or 'goal'")
-        if key == "goal" and not self._is_v3:
-            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
-        entries = G ** 4 if key == "goal" else G * G
         if thresholds is None:
             src, name = (probs, "probs") if logits is None else (logits, "logits")
             if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
@@ -449,29 +391,34 @@ class LmazeVecEnv(VecEnvBase):
                 and thresholds.data_ptr() % 16 == 0):
             raise ValueError("thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, 4] on %s (key=%r, G=%d)"
                              % (entries, self.device, key, G))
-        self._check_rows("rollout_sample()", actions_t, key_t)
-        for name, t in (("actions_t", actions_t), ("key_t", key_t)):
-            if t is not None and t.shape[0] != T:
-                raise ValueError("%s must have T = %d rows" % (name, T))
+        return self._rollout_table("rollout_sample", (thresholds.data_ptr(), _abi.KEY_MODES[key]), T, auto_reset, trajectory,
+                                   actions_t, key_t, obs_t, obs_every)
+
+    def _closed_loop_key(self, who, T, key):
+        """What rollout_policy() and rollout_sample() refuse before they look at their table; returns T as an int and the
+        number of keys, i.e. of table rows."""
+        if self._tuner is not None or torch.cuda.is_current_stream_capturing():
+            raise ValueError("%s is not available with a device-resident epoch or while the online tuner runs" % who)
+        T = self._steps(T)
+        if key not in _abi.KEY_MODES:
+            raise ValueError("key must be 'ball' or 'goal'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        return T, self.grid ** 4 if key == "goal" else self.grid ** 2
+
+    def _rollout_table(self, method, table_args, T, auto_reset, trajectory, actions_t, key_t, obs_t, obs_every):
+        """The launch of rollout_policy() / rollout_sample(): lmaze_<method> or, for the u8 env, lmaze_<method>_u8, which
+        differ in table_args alone -- (table, key_mode, epsilon_u32) or (table, key_mode)."""
+        name = "lmaze_" + method + ("_u8" if self._u8 else "")
         k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
-        rows = self._traj_rows(T) if trajectory else None
-        if trajectory:
-            actions_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
-            key_t = torch.empty((T, N), dtype=torch.int32, device=self.device) if key_t is None else key_t
-        name = "lmaze_rollout_sample" + ("_u8" if self._u8 else "")
-        slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
-        with self._guard():
-            rc = getattr(_abi.lib, name)(
-                self._pp, self._p_layout, thresholds.data_ptr(), _abi.KEY_MODES[key], T, self._p_ball,
-                self._p_goal if self._is_v3 else None, self._p_step, self._p_reward, self._p_done,
-                None if self._is_v3 else self._p_gc, self._p_obs, rows[0].data_ptr() if rows else None,
-                rows[1].data_ptr() if rows else None, None if actions_t is None else actions_t.data_ptr(),
-                None if key_t is None else key_t.data_ptr(), N, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch,
-                self.env_base, slots, k, self._stream())
-        _abi.check(name, rc)
-        self._epoch += T
-        out = self._rollout_result(rows)
-        return out + (actions_t, key_t) if trajectory else out
+
+        def call(rows, p_actions, p_key, slots):
+            return getattr(_abi.lib, name)(
+                self._pp, self._p_layout, *table_args, T, self._p_ball, self._p_goal if self._is_v3 else None, self._p_step,
+                self._p_reward, self._p_done, None if self._is_v3 else self._p_gc, self._p_obs, *(rows or (None, None)),
+                p_actions, p_key, self.num_envs, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base,
+                slots, k, self._stream())
+        return self._closed_loop(method + "()", name, call, T, k, obs_t, trajectory, actions_t, key_t)
 
     def observe(self, mask_ptr=None):
         """Re-render the compact planes of the current state (no transition)."""

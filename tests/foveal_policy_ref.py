@@ -12,8 +12,8 @@ import numpy as np
 
 import foveal_launch_matrix as M
 import oracle_lib as O
+from closed_loop_ref import explore_draw
 
-M32 = np.uint64(0xFFFFFFFF)
 SEED = 21
 ENV_BASE = (1 << 33) + 1000          # both words of the global env index and of the epoch enter the draws
 EPOCH = (1 << 35) + 77
@@ -27,26 +27,6 @@ Shape = namedtuple("Shape", "variant G L table")
 SHAPES = (Shape("v1", 14, 0, "lds"), Shape("v2", 18, 0, "lds"), Shape("v4", 18, 0, "lds"),
           Shape("v2", 12, 2, "lds"), Shape("v4", 12, 2, "lds"),       # the generic-grid kernels, padded random layouts
           Shape("v4", 24, 16, "global"))                               # 16 x 576 = 9216 bytes of table: past the 8192 of the rule
-
-
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on uint64 arrays holding 32-bit words (Salmon et al., SC'11); checked against the oracle's in the CPU
-    suite (test_foveal_rollout_policy_cpu.py)."""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in (c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0) & M32, np.uint64(k1) & M32
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M32, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
-def explore_draw(seed, ep, env_global):
-    """The closed loop's draw of (env, epoch): the reset draw's counter with the top bit of its last word flipped."""
-    e = np.asarray(env_global, dtype=np.uint64)
-    ep = np.uint64(ep)
-    return philox(e & M32, e >> np.uint64(32), ep & M32, ((ep >> np.uint64(32)) & M32) ^ np.uint64(0x80000000),
-                  np.uint64(seed) & M32, np.uint64(seed) >> np.uint64(32))
 
 
 def epsilon_u32(eps):

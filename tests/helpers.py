@@ -1,10 +1,41 @@
 """Shared helpers for the parity tests (fixture replay, hashing, layouts)."""
+import atexit
+import functools
 import hashlib
 import os
+import re
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gym-lmaze_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_usage(src):
+    """What every kernel of csrc/<src> needs per wave, by mangled name: {"VGPRs", "SGPRs", "ScratchSize", "Occupancy",
+    "LDS"} as hipcc -Rpass-analysis=kernel-resource-usage reports them for gfx950 (cross-compiled: no GPU).  One compile
+    of each source per process, into a directory that goes with the process; the result is shared, so read it only."""
+    tmp = tempfile.mkdtemp(prefix="lmaze_usage_")
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only",
+                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src),
+                          "-o", os.path.join(tmp, src + ".co")], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    kernels, cur = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+(VGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    return kernels
 
 
 def load_golden(name):

@@ -4,15 +4,15 @@ import ctypes as C
 import importlib
 import os
 import re
-import shutil
 import subprocess
 import sys
 
 import pytest
 
+from helpers import HIPCC, kernel_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-lmaze_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_NULL, E_COUNT, E_VARIANT, E_ALIGN = -1, -5, -3, -6
 
 
@@ -101,26 +101,9 @@ def test_describe_names_the_rollout_kernel(abi, variant, auto_reset, two_level, 
     assert abi.describe_foveal_rollout(p, 0, 8, auto_reset, two_level) == ""
 
 
-def _usage(tmp):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "lmaze_foveal.hip"),
-                          "-o", os.path.join(tmp, "lmaze_foveal.o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return kernels
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_rollout_kernels_no_scratch_and_occupancy_floors(tmp_path):
-    kernels = _usage(str(tmp_path))
+def test_rollout_kernels_no_scratch_and_occupancy_floors():
+    kernels = kernel_usage("lmaze_foveal.hip")
     floors = {1: 6, 2: 6, 4: 4, 5: 4}
     seen = set()
     for name, v in kernels.items():

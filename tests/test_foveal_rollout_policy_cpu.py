@@ -14,11 +14,13 @@ import numpy as np
 import pytest
 
 import foveal_policy_ref as R
+from closed_loop_ref import fields as _fields
+from closed_loop_ref import test_numpy_philox_is_the_oracles  # noqa: F401  (collected here: the restatement draws with philox)
+from helpers import HIPCC, kernel_usage
 import oracle_lib as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-lmaze_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_NULL, E_GRID, E_VARIANT, E_LAYOUT, E_COUNT, E_ALIGN = -1, -2, -3, -4, -5, -6
 NAMES = ("lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy")
 MAX_ENVS = 1 << 30
@@ -125,10 +127,6 @@ def test_refusals_in_their_documented_order(abi, variant):
     assert _call(abi, obs=4096 + 4, **kw) == E_ALIGN
 
 
-def _fields(line):
-    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", line)}
-
-
 def _foveal_lds(variant, G, L, epb):
     """lmaze_foveal.hip foveal_lds: per-env strings and flags, row masks, layout characters, v4's visit samples"""
     L = 1 if variant == "v1" else L
@@ -215,16 +213,6 @@ def test_python_argument_errors_that_need_no_device(abi):
 
 
 # ------------------------------------------------------------- the numpy restatement's own parts
-def test_numpy_philox_is_the_oracles():
-    rs = np.random.RandomState(5)
-    w = rs.randint(0, 1 << 32, (64, 6), dtype=np.uint64)
-    w[0] = 0
-    w[1] = (1 << 32) - 1
-    got = np.stack(R.philox(w[:, 0], w[:, 1], w[:, 2], w[:, 3], w[0, 4], w[0, 5]), axis=1)
-    for i in range(64):
-        assert [int(x) for x in got[i]] == O.philox4x32_10([int(x) for x in w[i, :4]], [int(w[0, 4]), int(w[0, 5])]), i
-
-
 def test_every_case_takes_the_paths_its_parameters_allow():
     """The GPU module's coverage conditions, here where the seeds were chosen: with the oracle alone."""
     for shape in R.SHAPES:
@@ -300,31 +288,14 @@ def test_host_selection_rule_is_the_numpy_one(select_host, variant, G, L, eps):
 
 
 # ------------------------------------------------------------- what the kernels need per wave
-def _usage(src, tmp):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                          "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, src), "-o", os.path.join(tmp, src + ".s")],
-                         capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return kernels
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_new_kernels_no_scratch_and_within_one_wave_of_their_twins(tmp_path):
+def test_new_kernels_no_scratch_and_within_one_wave_of_their_twins():
     """72 new kernels (v1 / v2 / v4 x 32 / 64 / 128 envs x specialised / generic grid x plain / fused x recording or not), none
     with scratch, none below 4 waves per SIMD, each at most one wave below its open-loop twin <variant, EPB, G, AR, REC> of
     lmaze_foveal.hip compiled here from the same tree.  v1's recording form at a generic grid has no twin (the open-loop
     one is refused there): it only has to hold the floor."""
-    new = _usage("lmaze_foveal_policy.hip", str(tmp_path))
-    old = _usage("lmaze_foveal.hip", str(tmp_path))
+    new = kernel_usage("lmaze_foveal_policy.hip")
+    old = kernel_usage("lmaze_foveal.hip")
     pat = re.compile(r"_ZN5lmaze28foveal_rollout_policy_kernelI(Li\dELi\d+ELi\d+ELb[01]E)EEvNS_10FovealArgsENS_(13FovealRollPol|16FovealRollObsPol)E")
     mine = {k: v for k, v in new.items() if "foveal_rollout_policy_kernel" in k}
     assert len(mine) == 72 and len(new) == 72, sorted(new)

@@ -1,5 +1,5 @@
 """GPU: the sampling closed-loop one-launch rollouts (lmaze_rollout_sample / lmaze_rollout_sample_u8) against the C oracle,
-step by step, with the sampling rule of include/lmaze.h restated here in numpy -- never against the library's own
+step by step, with the sampling rule of include/lmaze.h restated in numpy (closed_loop_ref.py) -- never against the library's own
 rollouts.  Bit-exact: keys, actions, float32 bit patterns of reward, done, every recorded slot, the final state, planes and
 goal counts.  And lmaze_returns against a float32 numpy loop, bit for bit."""
 import functools
@@ -9,83 +9,19 @@ import numpy as np
 import pytest
 import torch
 
-import oracle_lib as O
-from helpers import bordered_random_layouts, f32_bits
+from closed_loop_ref import DEV, EPOCH, TOP, explore_draw, make_env as _env, replay, sample_action, to_numpy as _np
+from closed_loop_ref import test_numpy_philox_is_the_oracles  # noqa: F401  (collected here: the replay draws with philox)
+from helpers import f32_bits
 
 pytestmark = pytest.mark.gpu
 
 PKG = importlib.import_module("gym-lmaze_amd")
 ABI = importlib.import_module("gym-lmaze_amd._abi")
-DEV = torch.device("cuda", 0)
-M32 = np.uint64(0xFFFFFFFF)
-TOP = 0xFFFFFFFF
-ENV_BASE = (1 << 33) + 1000          # both words of the global env index and of the epoch enter the draws
-EPOCH = (1 << 35) + 77
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on uint64 arrays holding 32-bit words (Salmon et al., SC'11); checked against the oracle's below."""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in (c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0) & M32, np.uint64(k1) & M32
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M32, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
-def test_numpy_philox_is_the_oracles():
-    rs = np.random.RandomState(5)
-    w = rs.randint(0, 1 << 32, (64, 6), dtype=np.uint64)
-    w[0] = 0
-    w[1] = (1 << 32) - 1
-    got = np.stack(philox(w[:, 0], w[:, 1], w[:, 2], w[:, 3], w[0, 4], w[0, 5]), axis=1)
-    for i in range(64):
-        assert [int(x) for x in got[i]] == O.philox4x32_10([int(x) for x in w[i, :4]], [int(w[0, 4]), int(w[0, 5])]), i
 
 
 def sample_draw(seed, ep, env_global):
-    """r of (env, epoch): the .x word of the closed loop's draw -- the reset draw's counter with the top bit of its last
-    word flipped."""
-    e = np.asarray(env_global, dtype=np.uint64)
-    ep = np.uint64(ep)
-    return philox(e & M32, e >> np.uint64(32), ep & M32, ((ep >> np.uint64(32)) & M32) ^ np.uint64(0x80000000),
-                  np.uint64(seed) & M32, np.uint64(seed) >> np.uint64(32))[0]
-
-
-def sample_action(rows, r):
-    """(r >= c0) + (r >= c1) + (r >= c2), unsigned, whatever the row holds."""
-    c = rows.astype(np.uint64)
-    return ((r >= c[:, 0]).astype(np.int32) + (r >= c[:, 1]) + (r >= c[:, 2])).astype(np.int32)
-
-
-@functools.lru_cache(maxsize=None)
-def _layouts(kind, G, N):
-    if kind == "per_env":
-        if N > 8192:                                        # a streaming batch: 4 099 mazes, tiled
-            return np.ascontiguousarray(np.resize(bordered_random_layouts(4099, G, 300 + G), (N, G, G)))
-        return bordered_random_layouts(N, G, 300 + G)
-    return bordered_random_layouts(1, G, 300 + G)[0]
-
-
-def _env(kind, variant, G, N, seed=21, step_limit=7, env_base=ENV_BASE, epoch=EPOCH, hint=0):
-    lay = _layouts(kind, G, N)
-    kw = dict(variant=variant, seed=seed, step_limit=step_limit, env_base=env_base)
-    if kind == "per_env":
-        env = PKG.LmazeVecEnv(N, per_env_layouts=lay, **kw)
-    else:
-        env = PKG.LmazeVecEnv(N, layout=lay, obs_dtype="u8" if kind == "u8" else "int32", **kw)
-    env._epoch = epoch
-    env.params.launch_hint = hint
-    # a spread of episode phases: some envs already done, some about to run into the step limit
-    rs = np.random.RandomState(G + N)
-    env.set_state(step_count=rs.randint(0, step_limit, N).astype(np.int32), done=(rs.rand(N) < 0.2).astype(np.uint8),
-                  reward=np.where(rs.rand(N) < 0.5, -0.01, -1.0).astype(np.float32))
-    return env, lay
+    """r of (env, epoch): the .x word of the closed loop's draw."""
+    return explore_draw(seed, ep, env_global)[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -114,64 +50,20 @@ def _dev_table(tab):
 
 def _replay(kind, variant, G, N, T, auto_reset, k, key, hint=0, seed=21, step_limit=7, table=None, env=None, lay=None, window=None,
             **how):
-    """One rollout_sample() call against the oracle stepped T times from the env's host_state(); window = (first env,
-    count): the oracle replays that contiguous range of the batch only (streaming sizes).  Returns the oracle's sequences
-    and the call's outputs.  how: probs= / logits= instead of the explicit thresholds (table is then what they must become)."""
+    """One rollout_sample() call against the oracle stepped T times from the env's host_state() (closed_loop_ref.replay);
+    window = (first env, count): the oracle replays that contiguous range of the batch only (streaming sizes).  Returns the
+    oracle's sequences and the call's outputs.  how: probs= / logits= instead of the explicit thresholds (table is then what
+    they must become)."""
     if env is None:
         env, lay = _env(kind, variant, G, N, seed=seed, step_limit=step_limit, hint=hint)
-    v3 = variant == "v3"
     tab = _thresholds(G, key, G * 7 + N % 1000) if table is None else table
-    lo, cnt = window if window else (0, N)
-    sl = slice(lo, lo + cnt)
-    st = {name: np.array(v[sl], copy=True) for name, v in env.host_state().items()}
-    p = O.params(O.VARIANT_V3 if v3 else O.VARIANT_V0, G, O.LAYOUT_PER_ENV if kind == "per_env" else O.LAYOUT_SHARED,
-                 env.step_limit, *env.rewards)
-    lay_c = np.ascontiguousarray(lay[sl] if kind == "per_env" else lay)
     epoch0 = env._epoch
-    S = T // k if k else 0
-    obs_t = torch.full((S, N, G, G), 113, dtype=env.obs.dtype, device=DEV) if k else None
-    env.obs.fill_(113)
     if not how:
         how = dict(thresholds=_dev_table(tab))
-    out = env.rollout_sample(T, key=key, auto_reset=auto_reset, trajectory=True, obs_t=obs_t, obs_every=k, **how)
-    assert len(out) == 7 and env._epoch == epoch0 + T
-    reward_t, done_t, actions_t, key_t = (np.ascontiguousarray(_np(x[:, sl])) for x in out[3:])
-    slots = np.ascontiguousarray(_np(obs_t[:, sl])) if k else None
-    obs_ref = np.zeros((cnt, G, G), np.int32)
-    seq = {name: np.zeros((T, cnt), dt) for name, dt in (("key", np.int32), ("act", np.int32), ("reward", np.float32),
-                                                         ("done", np.uint8))}
-    eg = np.arange(cnt, dtype=np.uint64) + np.uint64(env.env_base + lo)
-    n_reset = 0
-    for t in range(T):
-        if auto_reset and st["done"].any():                # reset(mask = done) with the library's draw rule
-            n_reset += int(st["done"].sum())
-            O.reset(p, lay_c, st["done"].copy(), env.seed, epoch0 + t, st["ball_xy"], st["goal_xy"], st["step_count"],
-                    st["reward"], st["done"], env_base=env.env_base + lo)
-        key_ref = st["ball_xy"][:, 0] * G + st["ball_xy"][:, 1]
-        if key == "goal":
-            key_ref = (st["goal_xy"][:, 0] * G + st["goal_xy"][:, 1]) * G * G + key_ref
-        act = sample_action(tab[key_ref], sample_draw(env.seed, epoch0 + t, eg))
-        seq["key"][t], seq["act"][t] = key_ref, act
-        if v3:
-            O.step_v3(p, lay_c, act, st["ball_xy"], st["goal_xy"], st["step_count"], st["reward"], st["done"], obs_ref)
-        else:
-            O.step_v0(p, lay_c, act, st["ball_xy"], st["step_count"], st["reward"], st["done"], st["goal_count"], obs_ref)
-        seq["reward"][t], seq["done"][t] = st["reward"], st["done"]
-        assert (key_t[t] == key_ref).all(), ("key", t)
-        assert (actions_t[t] == act).all(), ("action", t)
-        assert (f32_bits(reward_t[t]) == f32_bits(st["reward"])).all(), ("reward", t)
-        assert (done_t[t].view(np.uint8) == st["done"]).all(), ("done", t)
-        if k and (t + 1) % k == 0:
-            assert (slots[(t + 1) // k - 1] == obs_ref.astype(slots.dtype)).all(), ("slot", t)
-    if T:
-        h = env.host_state()
-        for name in h:
-            assert (np.ascontiguousarray(h[name][sl]).view(np.uint8) == np.ascontiguousarray(st[name]).view(np.uint8)).all(), name
-        got = _np(env.obs[sl])
-        assert (got == obs_ref.astype(got.dtype)).all(), "final planes"
-    if k and T % k:                                        # the steps past the last slot store no planes
-        assert slots.shape[0] == T // k
-    return dict(seq=seq, out=out, final=st, resets=n_reset, actions=np.bincount(seq["act"].reshape(-1), minlength=4), env=env)
+    r = replay(env, lay, kind, T, auto_reset, k, key,
+               lambda obs_t: env.rollout_sample(T, key=key, auto_reset=auto_reset, trajectory=True, obs_t=obs_t, obs_every=k, **how),
+               lambda key_ref, t, eg: sample_action(tab[key_ref], sample_draw(env.seed, epoch0 + t, eg)), window=window)
+    return dict(r, actions=np.bincount(r["seq"]["act"].reshape(-1), minlength=4))
 
 
 KINDS = ["shared", "u8", "per_env"]

@@ -4,14 +4,14 @@ import ctypes as C
 import importlib
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from helpers import HIPCC, kernel_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-lmaze_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_NULL, E_COUNT, E_VARIANT, E_ALIGN = -1, -5, -3, -6
 
 
@@ -83,31 +83,14 @@ def test_foveal_refusals_need_no_device(abi):
     assert _foveal(abi, v2, 2, None, None, 3) == E_NULL         # T < k: no slot, but no buffers either
 
 
-def _usage(src, tmp):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src),
-                          "-o", os.path.join(tmp, src + ".o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return kernels
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("src,plain_arg,rec_arg,n_rec", [("lmaze_step.hip", "11RolloutArgs", "14RolloutObsArgs", 6),
                                                          ("lmaze_foveal.hip", "10FovealRoll", "13FovealRollObs", 33)])
-def test_recording_kernels_no_scratch_and_occupancy(tmp_path, src, plain_arg, rec_arg, n_rec):
+def test_recording_kernels_no_scratch_and_occupancy(src, plain_arg, rec_arg, n_rec):
     """No scratch anywhere.  The v0/v3 recording kernels and the v5/v6 two-level one keep their plain twin's waves per
     SIMD; v1 / v2 / v4 keep the floors of the plain foveal rollouts (6 / 6 / 4) -- their slot stores cost a wave against
     some twins (lmaze_foveal.hip, the recording overload of foveal_rollout_kernel)."""
-    kernels = _usage(src, str(tmp_path))
+    kernels = kernel_usage(src)
     recs = [k for k in kernels if rec_arg in k]
     assert len(recs) == n_rec, recs
     floors = {1: 6, 2: 6, 4: 4}

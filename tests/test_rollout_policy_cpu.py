@@ -5,14 +5,16 @@ import ctypes as C
 import importlib
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from closed_loop_ref import (fields as _fields, grid_params as _params, perenv_lds as _perenv_lds, shared_lds as _shared_lds,
+                             u8_lds as _u8_lds)
+from helpers import HIPCC, kernel_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-lmaze_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_NULL, E_GRID, E_VARIANT, E_LAYOUT, E_COUNT, E_ALIGN = -1, -2, -3, -4, -5, -6
 NAMES = ("lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy")
 
@@ -97,33 +99,8 @@ def test_nothing_to_do_reads_no_pointer(abi, u8, variant, key_mode, T, n):
     assert fn(C.byref(p), None, None, key_mode, 123, -1, *none, n, 1, 1, 0, 0, None, 0, None) == E_COUNT
 
 
-def _fields(line):
-    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", line)}
-
-
-def _shared_lds(G, epb):
-    c = G * G
-    return c * 4 + 2 * epb * 4 + ((c + 15) & ~15) + ((2 * c + 15) & ~15)
-
-
-def _u8_lds(G, epb):
-    c = G * G
-    pw = (2 * c + 16 + 3) >> 2
-    return (4 * pw * 4 + 2 * (epb + 1) * 4 + ((c + 1) & ~1) * 2 + c + 15) & ~15
-
-
-def _perenv_lds(G, epb):
-    return 2 * epb * 4 + ((epb * G * G + 15) & ~15)
-
-
 def _table(G):
     return (G * G + 15) & ~15
-
-
-def _params(abi, variant, G, mode, hint=0):
-    p = abi.make_params(abi.VARIANT_V3 if variant == "v3" else abi.VARIANT_V0, G, mode, 100, -1.0, -0.01, 100.0)
-    p.launch_hint = hint
-    return p
 
 
 @pytest.mark.parametrize("variant,key", [("v0", "ball"), ("v3", "ball"), ("v3", "goal")])
@@ -210,30 +187,13 @@ def test_epsilon_conversion(abi):
             f(bad)
 
 
-def _usage(src, tmp):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src),
-                          "-o", os.path.join(tmp, src + ".o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return kernels
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_closed_loop_kernels_no_scratch_and_occupancy(tmp_path):
+def test_closed_loop_kernels_no_scratch_and_occupancy():
     """Six new instantiations (three kernels x v0 / v3), none with scratch.  A closed-loop form is its recording twin with the
     action load replaced by a table lookup and a Philox draw, and these kernels are latency-bound, so the shared and per-env
     forms keep the twin's waves per SIMD (8 / 7).  The u8 forms keep 5, the v3 twin's: at the v0 twin's 6 the v0 form
     spills 12 bytes per lane (lmaze_step.hip)."""
-    kernels = _usage("lmaze_step.hip", str(tmp_path))
+    kernels = kernel_usage("lmaze_step.hip")
     new = {k: v for k, v in kernels.items() if "RolloutPolicyArgs" in k or "RolloutPolicy8Args" in k}
     assert len(new) == 6, sorted(new)
     for name, v in new.items():

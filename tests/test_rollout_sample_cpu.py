@@ -7,19 +7,21 @@ import ctypes as C
 import importlib
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from closed_loop_ref import (explore_draw, fields as _fields, grid_params as _params, perenv_lds as _perenv_lds,
+                             shared_lds as _shared_lds, u8_lds as _u8_lds)
+from closed_loop_ref import test_numpy_philox_known_answers  # noqa: F401  (collected here: the draws below are philox's)
+from helpers import HIPCC, kernel_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-lmaze_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_NULL, E_GRID, E_VARIANT, E_LAYOUT, E_COUNT, E_ALIGN = -1, -2, -3, -4, -5, -6
 NAMES = ("lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns")
-M32 = np.uint64(0xFFFFFFFF)
 TOP = 2 ** 32 - 1
 
 
@@ -134,27 +136,8 @@ def test_returns_refusals_and_nothing_to_do(abi):
         assert f(68, 65, 66, 0.99, 72, T, n, None) == 0
 
 
-def _fields(line):
-    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", line)}
-
-
-def _up16(x):
+def _up16(x):                                               # the thresholds start on a 16-byte boundary
     return (x + 15) & ~15
-
-
-def _shared_lds(G, epb):
-    c = G * G
-    return _up16(c * 4 + 2 * epb * 4 + ((c + 15) & ~15) + ((2 * c + 15) & ~15))
-
-
-def _u8_lds(G, epb):
-    c = G * G
-    pw = (2 * c + 16 + 3) >> 2
-    return (4 * pw * 4 + 2 * (epb + 1) * 4 + ((c + 1) & ~1) * 2 + c + 15) & ~15
-
-
-def _perenv_lds(G, epb):
-    return _up16(2 * epb * 4 + ((epb * G * G + 15) & ~15))
 
 
 def _staged(G, key):
@@ -164,12 +147,6 @@ def _staged(G, key):
 
 def _where(G, key):
     return "lds" if _staged(G, key) else "global"
-
-
-def _params(abi, variant, G, mode, hint=0):
-    p = abi.make_params(abi.VARIANT_V3 if variant == "v3" else abi.VARIANT_V0, G, mode, 100, -1.0, -0.01, 100.0)
-    p.launch_hint = hint
-    return p
 
 
 @pytest.mark.parametrize("variant,key", [("v0", "ball"), ("v3", "ball"), ("v3", "goal")])
@@ -186,12 +163,12 @@ def test_describe_shared(abi, variant, key):
         assert line.startswith(head), line
         f = _fields(line)
         assert f["envs_per_workgroup"] == epb and f["grid"] == -(-n // epb) and f["block"] == 256, line
-        assert f["lds"] == _shared_lds(G, epb) + _staged(G, key), line
+        assert f["lds"] == _up16(_shared_lds(G, epb)) + _staged(G, key), line
     assert _where(11, "ball") == _where(32, "ball") == "lds" and _where(33, "ball") == _where(64, "ball") == "global"
     # launch_hint bits 12-14: every value; bit 15: the slots' other store policy
     for k in range(1, 8):
         f = _fields(abi.describe_rollout_sample(_params(abi, variant, 11, S, k << 12), 4099, 8, key=key))
-        assert f["envs_per_workgroup"] == 4 << (k - 1) and f["lds"] == _shared_lds(11, 4 << (k - 1)) + _staged(11, key)
+        assert f["envs_per_workgroup"] == 4 << (k - 1) and f["lds"] == _up16(_shared_lds(11, 4 << (k - 1))) + _staged(11, key)
     line = abi.describe_rollout_sample(_params(abi, variant, 11, S, 1 << 15), 4099, 8, obs_every=2, key=key)
     assert ", obs_t, nt> " in line
 
@@ -223,7 +200,7 @@ def test_describe_per_env_and_the_lds_clamp(abi, variant, key):
         assert line.startswith("rollout_perenv_kernel<v%s, sample=%s, table=%s, obs_t> T=16 every=4 " % (variant[1], key, _where(G, key))), line
         f = _fields(line)
         assert f["envs_per_workgroup"] == epb and f["grid"] == -(-n // epb), line
-        assert f["lds"] == _perenv_lds(G, epb) + _staged(G, key) <= 160 << 10, line
+        assert f["lds"] == _up16(_perenv_lds(G, epb)) + _staged(G, key) <= 160 << 10, line
     for k in range(1, 8):                                   # every value of bits 12-14; at most 64 (every lane in wave 0)
         f = _fields(abi.describe_rollout_sample(_params(abi, variant, 11, PE, k << 12), 4099, 8, key=key))
         assert f["envs_per_workgroup"] == min(4 << (k - 1), 64)
@@ -306,35 +283,13 @@ def test_sampling_thresholds_refusals(abi):
 
 
 # ------------------------------------------------------------- the rule, restated
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on uint64 arrays holding 32-bit words (Salmon et al., SC'11)."""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M32 for c in (c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0) & M32, np.uint64(k1) & M32
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M32, p0 & M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
-
-
-def test_numpy_philox_known_answers():
-    """The Random123 known-answer vectors of philox4x32-10."""
-    for ctr, key, want in (((0, 0, 0, 0), (0, 0), (0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8)),
-                           ((TOP, TOP, TOP, TOP), (TOP, TOP), (0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD)),
-                           ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0),
-                            (0xD16CFE09, 0x94FDCCEB, 0x5001E420, 0x24126EA1))):
-        got = philox(*([c] for c in ctr), *key)
-        assert tuple(int(x[0]) for x in got) == want
-
-
 def test_the_sampling_rule_reproduces_its_probabilities(abi):
     """action = (r >= c0) + (r >= c1) + (r >= c2) with r the .x word of the closed loop's draw (the reset draw's counter
     with the top bit of its last word flipped), on 2^20 draws -- consecutive envs of one epoch, both words of the env index
     and of the epoch in use.  Each action's count is binomial(n, p): within 5 sigma; a probability of 0 never fires."""
     n, seed, base, ep = 1 << 20, 21, (1 << 33) + 1000, (1 << 35) + 77
     e = np.arange(n, dtype=np.uint64) + np.uint64(base)
-    r = philox(e & M32, e >> np.uint64(32), np.uint64(ep) & M32, ((np.uint64(ep) >> np.uint64(32)) & M32) ^ np.uint64(0x80000000),
-               seed & 0xFFFFFFFF, seed >> 32)[0]
+    r = explore_draw(seed, ep, e)[0]
     rows = [[0.7, 0.1, 0.15, 0.05], [0.25, 0.25, 0.25, 0.25], [1, 0, 0, 0], [0, 0, 0, 1], [0, 0.5, 0, 0.5], [0.3, 0, 0.7, 0]]
     thr = abi.sampling_thresholds(torch.tensor(rows, dtype=torch.float64)).numpy().astype(np.uint64)
     for p, c in zip(rows, thr):
@@ -356,28 +311,11 @@ def test_the_sampling_rule_reproduces_its_probabilities(abi):
 
 
 # ------------------------------------------------------------- what the kernels need per wave
-def _usage(src, tmp):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src),
-                          "-o", os.path.join(tmp, src + ".o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return kernels
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_sampling_kernels_no_scratch_and_occupancy(tmp_path):
+def test_sampling_kernels_no_scratch_and_occupancy():
     """Six new rollout instantiations (three kernels x v0 / v3), none with scratch, none at fewer waves per SIMD than the
     epsilon-greedy closed-loop sibling of the same kernel and variant."""
-    kernels = _usage("lmaze_step.hip", str(tmp_path))
+    kernels = kernel_usage("lmaze_step.hip")
     new = {k: v for k, v in kernels.items() if "RolloutSampleArgs" in k or "RolloutSample8Args" in k}
     assert len(new) == 6, sorted(new)
     for name, v in new.items():
@@ -390,8 +328,8 @@ def test_sampling_kernels_no_scratch_and_occupancy(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_returns_kernel_no_scratch(tmp_path):
-    kernels = _usage("lmaze_aux.hip", str(tmp_path))
+def test_returns_kernel_no_scratch():
+    kernels = kernel_usage("lmaze_aux.hip")
     mine = {k: v for k, v in kernels.items() if "returns_kernel" in k}
     assert len(mine) == 1, sorted(kernels)
     (v,) = mine.values()

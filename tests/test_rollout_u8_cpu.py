@@ -5,14 +5,14 @@ import ctypes as C
 import importlib
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from helpers import HIPCC, kernel_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-lmaze_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_NULL, E_GRID, E_VARIANT, E_LAYOUT, E_COUNT, E_ALIGN = -1, -2, -3, -4, -5, -6
 
 
@@ -192,20 +192,8 @@ U8_FLOORS = {("0", "11RolloutArgs"): 7, ("3", "11RolloutArgs"): 5, ("0", "15Roll
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_u8_rollout_kernels_no_scratch_and_occupancy(tmp_path):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "lmaze_step.hip"),
-                          "-o", os.path.join(str(tmp_path), "lmaze_step.co")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+def test_u8_rollout_kernels_no_scratch_and_occupancy():
+    kernels = kernel_usage("lmaze_step.hip")
     found = {}
     for name, v in kernels.items():
         m = re.search(r"rollout_shared_u8_kernelILi(\d)EEEvNS_8StepArgsENS_(\w+)E$", name)
