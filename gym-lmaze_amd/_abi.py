@@ -37,7 +37,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy",
            "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns",
            "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
-           "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy")
+           "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy",
+           "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample")
 
 
 class LmazeParams(C.Structure):
@@ -195,6 +196,10 @@ def _load():
                                                 i32, vp]
     lib.lmaze_describe_foveal_rollout_policy.restype = C.c_int
     lib.lmaze_describe_foveal_rollout_policy.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_foveal_rollout_sample.restype = C.c_int
+    lib.lmaze_foveal_rollout_sample.argtypes = [FP, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.lmaze_describe_foveal_rollout_sample.restype = C.c_int
+    lib.lmaze_describe_foveal_rollout_sample.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -282,26 +287,31 @@ def describe_table_stats(m, keys, actions=4):
     return _describe("lmaze_describe_table_stats", int(m), int(keys), int(actions))
 
 
-def sampling_thresholds(probs):
+def sampling_thresholds(probs, actions=4):
     """The threshold table lmaze_rollout_sample takes, uint32[S, 4] on probs' device, of a float tensor probs[S, 4] of
     non-negative weights (a row need not sum to 1).  In float64, with this association:
         a0 = p0; a1 = a0 + p1; a2 = a1 + p2; s = a2 + p3;   c_k = min(floor(a_k / s * 2**32 + 0.5), 2**32 - 1)
     and word 3, reserved, is 0.  Action k is then taken with probability (c_k - c_(k-1)) / 2**32, c_(-1) = 0, c_3 = 2**32.
     A cumulative probability of exactly 1 is stored as 1 - 2**-32 (2**32 does not fit the word): a one-hot row lets one
     draw in 2**32 through to action 3 -- deterministic policies belong to rollout_policy().  Refuses negative or
-    non-finite entries and rows whose sum is not positive."""
-    if not (isinstance(probs, torch.Tensor) and probs.dim() == 2 and probs.shape[1] == 4 and probs.is_floating_point()):
-        raise ValueError("probs must be a float tensor [S, 4]")
+    non-finite entries and rows whose sum is not positive.
+    actions=A other than 4 (25: the table lmaze_foveal_rollout_sample takes for v2/v4): probs[S, A], the same definition --
+    the running sums a_k = a_(k-1) + p_k by sequential adds, s = a_(A-1) -- and uint32[S, A - 1], no reserved word."""
+    A = int(actions)
+    if A < 2:
+        raise ValueError("actions must be >= 2")
+    if not (isinstance(probs, torch.Tensor) and probs.dim() == 2 and probs.shape[1] == A and probs.is_floating_point()):
+        raise ValueError("probs must be a float tensor [S, %d]" % A)
     p = probs.detach().to(torch.float64)
     if not bool(torch.isfinite(p).all()) or bool((p < 0).any()):
         raise ValueError("probs must be finite and non-negative")
-    a0 = p[:, 0]
-    a1 = a0 + p[:, 1]
-    a2 = a1 + p[:, 2]
-    s = a2 + p[:, 3]
+    sums = [p[:, 0]]
+    for k in range(1, A):                          # explicit sequential adds: cumsum's association is not specified
+        sums.append(sums[-1] + p[:, k])
+    s = sums[-1]
     if not bool(torch.isfinite(s).all()) or bool((s <= 0).any()):
         raise ValueError("every row of probs must have a positive, finite sum")
-    c = torch.stack([torch.floor(a / s * 4294967296.0 + 0.5) for a in (a0, a1, a2)] + [torch.zeros_like(s)], dim=1)
+    c = torch.stack([torch.floor(a / s * 4294967296.0 + 0.5) for a in sums[:-1]] + ([torch.zeros_like(s)] if A == 4 else []), dim=1)
     c = c.clamp_(max=4294967295.0).to(torch.int64)
     return torch.where(c >= 2147483648, c - 4294967296, c).to(torch.int32).view(torch.uint32)   # the same 32 bits
 
@@ -319,6 +329,12 @@ def describe_foveal_rollout_policy(params, n, T, auto_reset=False, obs_every=0):
     """The kernel / grid / launch policy lmaze_foveal_rollout_policy would queue for n envs and T steps (obs_every=0: no
     recording), and where its table lives: "... table=lds ..." or "... table=global ..."."""
     return _describe("lmaze_describe_foveal_rollout_policy", C.byref(params), int(n), int(T), 1 if auto_reset else 0, int(obs_every))
+
+
+def describe_foveal_rollout_sample(params, n, T, auto_reset=False, obs_every=0):
+    """As describe_foveal_rollout_policy, for lmaze_foveal_rollout_sample: "foveal_rollout_sample_kernel<...> table=lds ..." or
+    "... table=global ..."."""
+    return _describe("lmaze_describe_foveal_rollout_sample", C.byref(params), int(n), int(T), 1 if auto_reset else 0, int(obs_every))
 
 
 def make_params(variant, grid, layout_mode, step_limit, reward_wall, reward_move, reward_goal):

@@ -474,6 +474,75 @@ int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_
     return format_launch(info, text_host, len, T);
 }
 
+// The sampling closed-loop foveal rollout (lmaze_foveal_sample.hip): foveal_rollout_policy's refusals in its order, with
+// `thresholds` in the place of `policy` and its 16-byte alignment last among the alignment refusals.
+static int foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* thresholds, int32_t T,
+                                 const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                                 int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, LaunchInfo* info, void* stream) {
+    int rc = check_recording(T, obs_t, obs_every);                     // 1. the recording request
+    if (rc) return rc;
+    if (!params) return LMAZE_E_NULL;                                  // 2. the params' own refusals
+    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
+        return LMAZE_E_VARIANT;
+    if (params->grid < LMAZE_FOVEA || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
+    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
+    if (params->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
+    if (v56) return LMAZE_E_VARIANT;                                   // 3. no closed loop for the two-level variants
+    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;    // 4.
+    if (T == 0 || n == 0) return 0;                                    // 5. nothing to do, nothing read
+    LmazeFovealBuffers none;
+    memset(&none, 0, sizeof(none));
+    if (!info) {                                                       // 6. the pointers, then the alignments
+        if (!thresholds) return LMAZE_E_NULL;
+        rc = check_foveal(params, layouts, bufs, n);
+        if (rc) return rc;
+        if ((uintptr_t)thresholds & 15) return LMAZE_E_ALIGN;
+    }
+    FovealArgs a = make_foveal_args(params, layouts, info ? &none : bufs, n);
+    a.auto_reset = auto_reset ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
+    a.info = info;
+    const bool rec = obs_every > 0;
+    FovealRollObsSmp ro;
+    memset(&ro, 0, sizeof(ro));
+    ro.T = T;
+    ro.reward_t = reward_t;
+    ro.done_t = done_t;
+    ro.freward_t = foveal_reward_t;
+    ro.fdone_t = foveal_done_t;
+    ro.obs_t = rec && T / obs_every > 0 ? obs_t : nullptr;
+    ro.obs_local_t = nullptr;
+    ro.every = rec ? obs_every : 1;
+    ro.smp = FovealSmp{thresholds, 0, actions_t, key_t};
+    return (int)launch_foveal_rollout_sample(a, ro, rec, (hipStream_t)stream);
+}
+
+int lmaze_foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* thresholds, int32_t T,
+                                const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                                int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                                int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream) {
+    return foveal_rollout_sample(params, layouts, thresholds, T, bufs, n, auto_reset, seed, epoch, env_base, reward_t, done_t,
+                                 foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
+}
+
+int lmaze_describe_foveal_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                         int32_t obs_every, char* text_host, int32_t len) {
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    // nothing is dereferenced: a fabricated, aligned address stands for the slots whose presence decides
+    const int rc = foveal_rollout_sample(params, nullptr, nullptr, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, obs_every, &info,
+                                         nullptr);
+    if (rc || n == 0 || T == 0) return rc;
+    return format_launch(info, text_host, len, T);
+}
+
 int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
                          int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count,
                          int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t, int64_t n,

@@ -5,11 +5,14 @@
 // closed-loop rollout of v1/v2/v4, lmaze_foveal_policy.hip: phase 1 takes the action from a table keyed by the env's state,
 // mixed with an exploration draw, instead of from the action tensor, and stores the action and key rows).  POL is the
 // include site's LMAZE_FOVEAL_POLICY_SITE: what it adds stands under the preprocessor, so that every other kernel compiles
-// from the text it always had.  Not a header of its own.
+// from the text it always had.  LMAZE_FOVEAL_SAMPLE_SITE (lmaze_foveal_sample.hip, POL = 2) is the sampling closed loop: the
+// table holds one row of cumulative thresholds per key and one draw word is compared against them.  Not a header of its own.
 #ifndef LMAZE_FOVEAL_BODY_SITE
-#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip and lmaze_foveal_policy.hip"
+#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip, lmaze_foveal_policy.hip and lmaze_foveal_sample.hip"
 #endif
-#ifdef LMAZE_FOVEAL_POLICY_SITE
+#if defined(LMAZE_FOVEAL_SAMPLE_SITE)
+#define LMAZE_POL 2
+#elif defined(LMAZE_FOVEAL_POLICY_SITE)
 #define LMAZE_POL 1
 #else
 #define LMAZE_POL 0
@@ -42,10 +45,17 @@
     uint64_t* rowwall = rowball + L * G;                                   // [G] v1: 'W'
     uint64_t* rowx = rowwall + G;                                          // [G] v1: 'X'
     uint8_t* lays = reinterpret_cast<uint8_t*>(rowx + G);                  // [L*CELLS]
-#if LMAZE_POL
+#if LMAZE_POL == 1
     uint8_t* ptab = lays + ((L * CELLS + 15) & ~15);                       // [L*CELLS] the policy table, when it is staged
     const FovealPol pol = ro.pol;
     const bool pstage = pol.in_lds != 0;
+#elif LMAZE_POL == 2
+    // [L*CELLS] rows of thresholds, when the table is staged: on the next 16-byte boundary of the allocation (the row masks
+    // leave the characters on a multiple of 8 only), read with 128-bit LDS reads
+    constexpr int SROW = V1 ? 4 : 24;                                      // words per key
+    uint32_t* stab = reinterpret_cast<uint32_t*>(lds4) + ((((lays - reinterpret_cast<uint8_t*>(lds4)) + L * CELLS + 15) & ~15) >> 2);
+    const FovealSmp smp = ro.smp;
+    const bool pstage = smp.in_lds != 0;
 #endif
     static_assert(PERENV <= 8 * 32 - 32 && 4 * W25 <= 4 * 32 - 4, "bit strings fit the 32 B / 16 B per env reserved for them");
     __shared__ int any_skip, ndense;
@@ -101,7 +111,7 @@
             for (int j = 0; j < 2; ++j)
                 if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) cw[j] = reinterpret_cast<const uint32_t*>(a.layouts)[tid + j * LMAZE_BLOCK];
         }
-#if LMAZE_POL
+#if LMAZE_POL == 1
         // the table is as large as the characters and indexed like them; its dwords are requested with theirs
         const bool pdwords = pstage && ((reinterpret_cast<uintptr_t>(pol.table) | (uintptr_t)(L * CELLS)) & 3) == 0;
         uint32_t pw[2] = {0u, 0u};
@@ -151,7 +161,7 @@
         } else {
             for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
         }
-#if LMAZE_POL
+#if LMAZE_POL == 1
         if (pdwords) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -161,11 +171,15 @@
         } else if (pstage) {
             for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) ptab[i] = pol.table[i];
         }
+#elif LMAZE_POL == 2
+        if (pstage) stage_thresholds(stab, smp.table, L * CELLS * (SROW / 4), tid);
 #endif
     } else {
     for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
-#if LMAZE_POL
+#if LMAZE_POL == 1
     if (pstage) for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) ptab[i] = pol.table[i];
+#elif LMAZE_POL == 2
+    if (pstage) stage_thresholds(stab, smp.table, L * CELLS * (SROW / 4), tid);
 #endif
     __syncthreads();
     for (int i = tid; i < L * G; i += LMAZE_BLOCK) {
@@ -220,7 +234,11 @@
         const int goal2_in = (MODE == FM_STEP && AR && V5) ? a.goal2[ROLL_ROW(e)] : 0;
         const int vword = (V4 && !(V5 && MODE == FM_PLANNER)) ? a.b.visit_clock[e] : 0;
         const int vclock = vword & 0xff;
-#if LMAZE_POL
+#if LMAZE_POL == 2
+        // the sampling draw, on every env-step: one word of it is live across the fused reset.  It depends on nothing loaded,
+        // so it stands in front of the placement chain and runs under the loads above.
+        const uint32_t prx = policy_draw(a.seed, ROLL_EP, a.env_base + e).x;
+#elif LMAZE_POL
         // the exploration draw, only when there is exploration (uniform over the launch).  It depends on nothing loaded, so
         // it stands in front of the fused reset's placement chain and runs under the loads above.
         uint4 pr = make_uint4(0u, 0u, 0u, 0u);
@@ -238,7 +256,9 @@
                         if (lays[c] == 'S') { bx = c / G; by = c % G; break; }
                     sc_in = 0;
                 }
-#if LMAZE_POL
+#if LMAZE_POL == 2
+                const int act = foveal_smp_action<true>(smp, pstage, stab, 0, bx, by, G, 1, prx, ROLL_ROW(e));   // the key is the placed ball's
+#elif LMAZE_POL
                 const int act = foveal_pol_action(pol, pstage, ptab, 0, bx, by, G, 1, 4, pr, ROLL_ROW(e));   // the key is the placed ball's
 #else
                 const int act = act_in;
@@ -468,7 +488,9 @@
                 sc_in = sc_ld;
             }
             if (MODE == FM_STEP) {
-#if LMAZE_POL
+#if LMAZE_POL == 2
+                const int act = foveal_smp_action<false>(smp, pstage, stab, lid, bx, by, G, L, prx, ROLL_ROW(e));   // the row the step uses
+#elif LMAZE_POL
                 const int act = foveal_pol_action(pol, pstage, ptab, lid, bx, by, G, L, W25, pr, ROLL_ROW(e));   // the row the step uses
 #else
                 const int act = act_in;
@@ -659,7 +681,11 @@
         // map, Appendix B-7 -- are left in vwin for phase 3.
         {
             // SUB envs at a time (one barrier each): the loads of a pass are held in registers, 9 per row
-#if LMAZE_POL
+#if LMAZE_POL == 2
+            // as the epsilon-greedy form below; the fused recording form at a generic grid has no registers for it either
+            constexpr int WSUB = (REC && (!AR || GT == 0)) ? 32 : LMAZE_WIN_SUB;
+            constexpr int IPE = 2 * FOV, SUB = EPB < WSUB ? EPB : WSUB, NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
+#elif LMAZE_POL
             // the plain recording form of the closed loop has no registers for a third window row per lane
             constexpr int IPE = 2 * FOV, SUB = EPB < ((REC && !AR) ? 32 : LMAZE_WIN_SUB) ? EPB : ((REC && !AR) ? 32 : LMAZE_WIN_SUB);
             constexpr int NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;

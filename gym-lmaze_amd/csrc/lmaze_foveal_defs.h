@@ -1,5 +1,5 @@
 // lmaze_foveal_defs.h -- what the translation units of the foveal kernels share (lmaze_foveal.hip: the step, reset and
-// open-loop rollout kernels; lmaze_foveal_policy.hip: the closed-loop rollout): the kernel arguments, the device helpers
+// open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip: the closed-loop rollouts): the kernel arguments, the device helpers
 // of lmaze_foveal_body.h, and the host-side checks and LDS sizing of their launchers.  Not part of the C ABI.
 #ifndef LMAZE_FOVEAL_DEFS_H_
 #define LMAZE_FOVEAL_DEFS_H_
@@ -7,6 +7,7 @@
 #include "lmaze_common.h"
 #include "lmaze_visit.h"
 #include "lmaze_foveal_select.h"
+#include "lmaze_foveal_sample.h"
 
 // Timing decomposition (tools/foveal_decompose.py): a build with -DLMAZE_EXPERIMENT -- never the shipped
 // one -- reads bits 16-23 of launch_hint as switches that turn phases off (results are garbage then; only the time
@@ -110,6 +111,56 @@ __device__ __forceinline__ int foveal_pol_action(const FovealPol& pol, bool stag
 }
 constexpr int kFovealPolicyLds = 8192;   // bytes of table up to which it is staged in LDS (a rule, not a measurement)
 hipError_t launch_foveal_rollout_policy(const FovealArgs& a, const FovealRollObsPol& ro, bool rec, hipStream_t s);
+
+// The sampling closed-loop rollout (lmaze_foveal_rollout_sample, lmaze_foveal_sample.hip): a categorical table policy, one
+// row of cumulative thresholds per key -- uint32[4] for v1 (c0, c1, c2, reserved: the grid envs' format), uint32[24] for
+// v2/v4 -- and one draw word per env-step compared against them (lmaze_foveal_sample.h).  The body is compiled with POL = 2
+// for the two types below and reads ro.smp.
+struct FovealSmp {
+    const uint32_t* table;  // uint32[L*G*G, 4 or 24], 16-byte aligned
+    int32_t in_lds;         // the table is staged in LDS behind the layout characters (at most kFovealSampleLds bytes), else read from global memory
+    int32_t* actions_t;     // [T,N] or null: the action every env took
+    int32_t* key_t;         // [T,N] or null: the key its row was looked up with
+};
+struct FovealRollSmp : FovealRoll { FovealSmp smp; };
+struct FovealRollObsSmp : FovealRollObs { FovealSmp smp; };
+typedef uint32_t foveal_row4_t __attribute__((ext_vector_type(4)));
+// The whole table into LDS, 16 bytes per lane and turn (n16 pieces); the caller's barrier follows.
+__device__ __forceinline__ void stage_thresholds(uint32_t* lds_table, const uint32_t* table, int n16, int tid) {
+    typedef __attribute__((address_space(3))) foveal_row4_t* lds_rows;
+    typedef const __attribute__((address_space(1))) foveal_row4_t* global_rows;
+    for (int i = tid; i < n16; i += LMAZE_BLOCK) ((lds_rows)lds_table)[i] = ((global_rows)table)[i];
+}
+// The action of an env in state (lid, bx, by) from the draw word r: key -> the key's row, one (v1) or six 128-bit reads
+// requested together, none depending on another -> the sum of compares, and element `row` of the action and key rows.  The
+// staged and the global table are read through pointers of their own address spaces (foveal_pol_action).  v1 reads its
+// reserved word with the rest and keeps it to the end, so that the row stays one 128-bit read.
+template <bool V1>
+__device__ __forceinline__ int foveal_smp_action(const FovealSmp& smp, bool staged, const uint32_t* lds_table, int lid, int bx, int by,
+                                                 int G, int L, uint32_t r, int64_t row) {
+    typedef const __attribute__((address_space(3))) foveal_row4_t* lds_rows;
+    typedef const __attribute__((address_space(1))) foveal_row4_t* global_rows;
+    constexpr int Q = V1 ? 1 : 6, NC = V1 ? 3 : 24;
+    const int key = lmaze_foveal_key(lid, bx, by, G, L);
+    foveal_row4_t q[Q];
+    if (staged) {
+#pragma unroll
+        for (int j = 0; j < Q; ++j) q[j] = ((lds_rows)lds_table)[key * Q + j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < Q; ++j) q[j] = ((global_rows)smp.table)[(size_t)key * Q + j];
+    }
+    uint32_t c[Q * 4];
+#pragma unroll
+    for (int j = 0; j < Q; ++j) { c[4 * j] = q[j].x; c[4 * j + 1] = q[j].y; c[4 * j + 2] = q[j].z; c[4 * j + 3] = q[j].w; }
+    const int act = lmaze_foveal_sample_action(c, NC, r);
+    if (V1) asm volatile("" ::"v"(c[3]));
+    if (smp.actions_t) smp.actions_t[row] = act;
+    if (smp.key_t) smp.key_t[row] = key;
+    return act;
+}
+constexpr int kFovealSampleLds = 16384;   // bytes of thresholds up to which they are staged in LDS: lmaze_rollout_sample's figure
+hipError_t launch_foveal_rollout_sample(const FovealArgs& a, const FovealRollObsSmp& ro, bool rec, hipStream_t s);
 
 struct EnvRec {           // one env after its transition (registers only; phase 1 turns it into plane masks)
     int16_t cx, cy;       // centre of the current window (ball after the move)

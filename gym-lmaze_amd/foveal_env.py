@@ -278,6 +278,59 @@ class LmazeFovealVecEnv(VecEnvBase):
         return self._closed_loop("rollout_policy()", "lmaze_foveal_rollout_policy", call, T, k, obs_t, trajectory, actions_t, key_t,
                                  streams=2 if self.variant == "v1" else 1)
 
+    def rollout_sample(self, T, probs=None, logits=None, temperature=1.0, thresholds=None, auto_reset=True, trajectory=False,
+                       actions_t=None, key_t=None, obs_t=None, obs_every=None):
+        """T steps in ONE launch with a categorical table policy inside the kernel (include/lmaze.h
+        lmaze_foveal_rollout_sample; v1, v2, v4): every env-step draws its action from the distribution of its key = layout
+        row * G*G + ball_x * G + ball_y (state_keys()).  With S = L*G*G keys and A = 4 (v1) or 25 (v2/v4) actions, exactly one of
+        probs       float device tensor [S, A] of non-negative weights, converted by _abi.sampling_thresholds(probs, actions=A);
+        logits      float device tensor [S, A]: sampling_thresholds(softmax(logits.double() / temperature)), temperature > 0
+                    (a Boltzmann policy);
+        thresholds  the table itself, uint32 (or int32, the same bits) device tensor, contiguous and 16-byte aligned: [S, 4]
+                    for v1 (c0 <= c1 <= c2 and a reserved word, the grid envs' format), [S, 24] for v2/v4.
+        The action is the number of the row's thresholds that one Philox value r per (seed, env, epoch) has reached; a
+        cumulative probability of 1 is stored as 1 - 2**-32, so deterministic policies belong to rollout_policy().  Returns
+        what rollout_policy() returns; obs_t / obs_every, the rows and the restrictions (not for v5/v6, not under stream
+        capture) are its own too.  The epoch advances by T whether or not auto_reset is set."""
+        if self._two_level:
+            raise ValueError("rollout_sample() is not available for v5/v6: their two-level step needs two tables")
+        T = self._steps(T)
+        if sum(x is not None for x in (probs, logits, thresholds)) != 1:
+            raise ValueError("rollout_sample() wants exactly one of probs=, logits= and thresholds=")
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("rollout_sample() is not available with a device-resident epoch (under stream capture)")
+        A = 4 if self.variant == "v1" else _abi.FOVEA * _abi.FOVEA
+        W = 4 if A == 4 else A - 1
+        entries, what = self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid)
+        if thresholds is None:
+            src, name = (probs, "probs") if logits is None else (logits, "logits")
+            if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
+                    and tuple(src.shape) == (entries, A)):
+                raise ValueError("%s must be a float tensor [%d, %d] on %s (%s)" % (name, entries, A, self.device, what))
+            if logits is not None:
+                if not float(temperature) > 0.0:
+                    raise ValueError("temperature must be > 0")
+                src = torch.softmax(logits.double() / float(temperature), -1)
+            thresholds = _abi.sampling_thresholds(src, actions=A)
+        if not (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
+                and thresholds.device == self.device and thresholds.is_contiguous() and tuple(thresholds.shape) == (entries, W)
+                and thresholds.data_ptr() % 16 == 0):
+            raise ValueError("thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, %d] on %s (%s)"
+                             % (entries, W, self.device, what))
+        k = 0
+        if obs_every is not None:
+            k = self._obs_slots(T, obs_every, obs_t, self.obs)
+        elif obs_t is not None:
+            raise ValueError("obs_t needs obs_every")
+
+        def call(rows, p_actions, p_key, slots):
+            return _abi.lib.lmaze_foveal_rollout_sample(
+                self._pp, self._p_layouts, thresholds.data_ptr(), T, self._pb, self.num_envs, 1 if auto_reset else 0,
+                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key, slots, k,
+                self._stream())
+        return self._closed_loop("rollout_sample()", "lmaze_foveal_rollout_sample", call, T, k, obs_t, trajectory, actions_t, key_t,
+                                 streams=2 if self.variant == "v1" else 1)
+
     def state_keys(self):
         """int32[N]: the key of every env's CURRENT state, by the rule the key_t rows of rollout_policy() are written with --
         layout row (clamped to 0..L-1; 0 for v1) * G*G + ball_x * G + ball_y, coordinates clamped onto the grid.  Right after

@@ -823,6 +823,50 @@ int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_
                                          int32_t obs_every, char* text_host, int32_t len);
 
 /*
+ * SAMPLING closed-loop foveal rollout (v1, v2, v4): lmaze_foveal_rollout_policy with a categorical table policy instead of the
+ * epsilon-greedy one -- every env-step draws its action from the distribution of its key, the form that produces REINFORCE,
+ * actor-critic and Boltzmann data in one launch.  Replaces the user loop of T x (gather the key's row, compare a draw,
+ * lmaze_foveal_step / lmaze_foveal_step_autoreset).  The arguments of lmaze_foveal_rollout_policy with `policy, epsilon_u32`
+ * replaced by
+ *   thresholds   const uint32_t*, 16-byte aligned, one row of cumulative thresholds per key:
+ *                v1     uint32[G*G, 4], the grid format of lmaze_rollout_sample: words 0-2 are c0 <= c1 <= c2, word 3 is
+ *                       reserved -- it is loaded with the rest and ignored;
+ *                v2/v4  uint32[L*G*G, 24], 96 bytes per key, c0 <= ... <= c23, six 128-bit reads.
+ * Env i (global index e = env_base + i) at step t, ep = epoch + t:
+ *   1. the fused reset exactly as in lmaze_foveal_rollout_policy (same draw, same epoch);
+ *   2. the key exactly as there: lid * G^2 + bx * G + by after the reset, each part clamped;
+ *   3. r = the .x word of the closed loop's exploration draw -- Philox4x32-10(counter (e_lo, e_hi, ep_lo, ep_hi ^ 0x80000000),
+ *      key (seed_lo, seed_hi)), the reset draw's counter with the top bit of its last word flipped -- and
+ *      action = sum over k of (r >= c_k), unsigned compares, over the 3 (v1) or 24 (v2/v4) thresholds of the key's row.  The
+ *      action is drawn on every env-step and is always in 0..A-1 (A = 4 or 25), so no env is ever skipped.  The table is not
+ *      validated: a row that is not monotone still yields the action this formula gives (an implementation by binary
+ *      search is not equivalent);
+ *   4. the transition, visit-map update (v4) and observation of lmaze_foveal_step with that action;
+ *   5. actions_t[t,i] and key_t[t,i] are written for every env; the reward and done rows (both streams for v1) and
+ *      obs_t / obs_every are as in lmaze_foveal_rollout_policy.
+ * Action k is taken with probability (c_k - c_(k-1)) / 2^32, c_(-1) = 0, c_(A-1) = 2^32.
+ * The caller advances its epoch by T whether or not auto_reset is set.
+ * The table is staged in LDS once per workgroup, behind the layout characters, when its size in bytes is at most 16 384
+ * (lmaze_rollout_sample's figure): v1 at 14 x 14 (3 136 B) and a single v2/v4 layout up to 13 x 13 (16 224 B).  Above that --
+ * the five 18 x 18 layouts of v2/v4 are 155 520 B -- it is read from global memory, the key's six reads requested together.
+ * A rule, not a measurement; lmaze_describe_foveal_rollout_sample reports it as table=lds / table=global.
+ * v5/v6 are refused with LMAZE_E_VARIANT.  No grid size is refused: every form exists for any G.
+ * Refused before anything is queued: the refusals of lmaze_foveal_rollout_policy, in its order, with `thresholds` in the
+ * place of `policy`; a table that is not 16-byte aligned is LMAZE_E_ALIGN, after the alignment refusals of
+ * lmaze_foveal_step.  launch_hint bits 0-3, 4-7 and 8-9 as in lmaze_foveal_rollout; they never change results.
+ */
+int lmaze_foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* thresholds, int32_t T,
+                                const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                                int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                                int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream);
+
+/* As lmaze_describe_foveal_rollout_policy, for lmaze_foveal_rollout_sample:
+ * "foveal_rollout_sample_kernel<v2, 32, 18, fused-reset, obs_t> table=global T=24 grid=...".  The same refusals and empty
+ * lines.  Nothing is queued or dereferenced. */
+int lmaze_describe_foveal_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
+                                         int32_t obs_every, char* text_host, int32_t len);
+
+/*
  * v6 safeFovealGoal() (v6:505-523): for every env one window cell index 0..24 drawn uniformly from the
  * cells of the 5x5 window around the ball that are not 'W' (the reference rejects on np.random; here
  * Philox keyed by (seed, env_base + i, epoch), index (r*count)>>32 among the accepted cells in
