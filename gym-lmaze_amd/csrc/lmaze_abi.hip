@@ -193,6 +193,87 @@ static int describe_rollout_closed(const LmazeParams* params, int64_t n, int32_t
     return format_launch(info, text_host, len);
 }
 
+// The tables of the closed-loop foveal rollouts: the pointer, the alignment it needs (1: none) and its place in the
+// recording struct its launcher takes (lmaze_foveal_defs.h).
+struct FovealPolicyTable {
+    typedef FovealRollObsPol Roll;
+    static constexpr uintptr_t kAlign = 1;
+    const uint8_t* table;
+    uint32_t epsilon;
+    void put(Roll& ro, int32_t* actions_t, int32_t* key_t) const { ro.pol = FovealPol{table, epsilon, 0, actions_t, key_t}; }
+};
+struct FovealSampleTable {
+    typedef FovealRollObsSmp Roll;
+    static constexpr uintptr_t kAlign = 16;
+    const uint32_t* table;
+    void put(Roll& ro, int32_t* actions_t, int32_t* key_t) const { ro.smp = FovealSmp{table, 0, actions_t, key_t}; }
+};
+
+// lmaze_foveal_rollout_policy / lmaze_foveal_rollout_sample (lmaze_foveal_policy.hip, lmaze_foveal_sample.hip).  info != null:
+// describe instead of launching -- then nothing past the params is looked at.  The refusals stand in the order
+// include/lmaze.h documents.
+template <class Table>
+static int foveal_rollout_closed(const LmazeFovealParams* params, const uint8_t* layouts, const Table& tab, int32_t T,
+                                 const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                                 int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
+                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, LaunchInfo* info, void* stream) {
+    int rc = check_recording(T, obs_t, obs_every);                     // 1. the recording request
+    if (rc) return rc;
+    if (!params) return LMAZE_E_NULL;                                  // 2. the params' own refusals
+    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
+    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
+        return LMAZE_E_VARIANT;
+    if (params->grid < LMAZE_FOVEA || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
+    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
+    if (params->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
+    if (v56) return LMAZE_E_VARIANT;                                   // 3. no closed loop for the two-level variants
+    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;    // 4.
+    if (T == 0 || n == 0) return 0;                                    // 5. nothing to do, nothing read
+    LmazeFovealBuffers none;
+    memset(&none, 0, sizeof(none));
+    if (!info) {                                                       // 6. the pointers, then the alignments
+        if (!tab.table) return LMAZE_E_NULL;                           // with the other pointers, before any alignment
+        rc = check_foveal(params, layouts, bufs, n);
+        if (rc) return rc;
+        if (misaligned(tab.table, Table::kAlign)) return LMAZE_E_ALIGN;   // the table's own alignment last
+    }
+    FovealArgs a = make_foveal_args(params, layouts, info ? &none : bufs, n);
+    a.auto_reset = auto_reset ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
+    a.info = info;
+    const bool rec = obs_every > 0;
+    typename Table::Roll ro;
+    memset(&ro, 0, sizeof(ro));
+    ro.T = T;
+    ro.reward_t = reward_t;
+    ro.done_t = done_t;
+    ro.freward_t = foveal_reward_t;
+    ro.fdone_t = foveal_done_t;
+    ro.obs_t = rec && T / obs_every > 0 ? obs_t : nullptr;
+    ro.obs_local_t = nullptr;
+    ro.every = rec ? obs_every : 1;
+    tab.put(ro, actions_t, key_t);
+    return (int)launch_foveal_rollout_closed(a, ro, rec, (hipStream_t)stream);
+}
+
+// lmaze_describe_foveal_rollout_policy / lmaze_describe_foveal_rollout_sample
+template <class Table>
+static int describe_foveal_rollout_closed(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t obs_every,
+                                          char* text_host, int32_t len) {
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    // nothing is dereferenced: a fabricated, aligned address stands for the slots whose presence decides
+    const int rc = foveal_rollout_closed(params, nullptr, Table{}, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, obs_every, &info,
+                                         nullptr);
+    if (rc || n == 0 || T == 0) return rc;
+    return format_launch(info, text_host, len, T);
+}
+
 extern "C" {
 
 int lmaze_abi_version(void) { return LMAZE_ABI_VERSION; }
@@ -405,142 +486,31 @@ int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t 
     return describe_rollout_closed<PolicyTable>(params, n, T, auto_reset, with_obs, obs_every, key_mode, text_host, len);
 }
 
-// The closed-loop foveal rollout (lmaze_foveal_policy.hip).  info != null: describe instead of launching -- then nothing
-// past the params is looked at.  The refusals stand in the order include/lmaze.h documents.
-static int foveal_rollout_policy(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* policy, uint32_t epsilon_u32,
-                                 int32_t T, const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
-                                 int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
-                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, LaunchInfo* info, void* stream) {
-    int rc = check_recording(T, obs_t, obs_every);                     // 1. the recording request
-    if (rc) return rc;
-    if (!params) return LMAZE_E_NULL;                                  // 2. the params' own refusals
-    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
-    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
-        return LMAZE_E_VARIANT;
-    if (params->grid < LMAZE_FOVEA || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
-    if (params->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
-    if (v56) return LMAZE_E_VARIANT;                                   // 3. no closed loop for the two-level variants
-    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;    // 4.
-    if (T == 0 || n == 0) return 0;                                    // 5. nothing to do, nothing read
-    LmazeFovealBuffers none;
-    memset(&none, 0, sizeof(none));
-    if (!info) {                                                       // 6. the pointers
-        if (!policy) return LMAZE_E_NULL;                              // with the other pointers, before any alignment
-        rc = check_foveal(params, layouts, bufs, n);
-        if (rc) return rc;
-    }
-    FovealArgs a = make_foveal_args(params, layouts, info ? &none : bufs, n);
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.info = info;
-    const bool rec = obs_every > 0;
-    FovealRollObsPol ro;
-    memset(&ro, 0, sizeof(ro));
-    ro.T = T;
-    ro.reward_t = reward_t;
-    ro.done_t = done_t;
-    ro.freward_t = foveal_reward_t;
-    ro.fdone_t = foveal_done_t;
-    ro.obs_t = rec && T / obs_every > 0 ? obs_t : nullptr;
-    ro.obs_local_t = nullptr;
-    ro.every = rec ? obs_every : 1;
-    ro.pol = FovealPol{policy, epsilon_u32, 0, actions_t, key_t};
-    return (int)launch_foveal_rollout_policy(a, ro, rec, (hipStream_t)stream);
-}
-
 int lmaze_foveal_rollout_policy(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* policy,
                                 uint32_t epsilon_u32, int32_t T, const LmazeFovealBuffers* bufs, int64_t n,
                                 int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
                                 float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream) {
-    return foveal_rollout_policy(params, layouts, policy, epsilon_u32, T, bufs, n, auto_reset, seed, epoch, env_base, reward_t, done_t,
-                                 foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
+    return foveal_rollout_closed(params, layouts, FovealPolicyTable{policy, epsilon_u32}, T, bufs, n, auto_reset, seed, epoch, env_base,
+                                 reward_t, done_t, foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
                                          int32_t obs_every, char* text_host, int32_t len) {
-    if (!text_host || len < 1) return LMAZE_E_NULL;
-    text_host[0] = 0;
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    // nothing is dereferenced: a fabricated, aligned address stands for the slots whose presence decides
-    const int rc = foveal_rollout_policy(params, nullptr, nullptr, 0, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, obs_every, &info,
-                                         nullptr);
-    if (rc || n == 0 || T == 0) return rc;
-    return format_launch(info, text_host, len, T);
-}
-
-// The sampling closed-loop foveal rollout (lmaze_foveal_sample.hip): foveal_rollout_policy's refusals in its order, with
-// `thresholds` in the place of `policy` and its 16-byte alignment last among the alignment refusals.
-static int foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* thresholds, int32_t T,
-                                 const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
-                                 int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
-                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, LaunchInfo* info, void* stream) {
-    int rc = check_recording(T, obs_t, obs_every);                     // 1. the recording request
-    if (rc) return rc;
-    if (!params) return LMAZE_E_NULL;                                  // 2. the params' own refusals
-    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
-    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
-        return LMAZE_E_VARIANT;
-    if (params->grid < LMAZE_FOVEA || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
-    if (params->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
-    if (v56) return LMAZE_E_VARIANT;                                   // 3. no closed loop for the two-level variants
-    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;    // 4.
-    if (T == 0 || n == 0) return 0;                                    // 5. nothing to do, nothing read
-    LmazeFovealBuffers none;
-    memset(&none, 0, sizeof(none));
-    if (!info) {                                                       // 6. the pointers, then the alignments
-        if (!thresholds) return LMAZE_E_NULL;
-        rc = check_foveal(params, layouts, bufs, n);
-        if (rc) return rc;
-        if ((uintptr_t)thresholds & 15) return LMAZE_E_ALIGN;
-    }
-    FovealArgs a = make_foveal_args(params, layouts, info ? &none : bufs, n);
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.info = info;
-    const bool rec = obs_every > 0;
-    FovealRollObsSmp ro;
-    memset(&ro, 0, sizeof(ro));
-    ro.T = T;
-    ro.reward_t = reward_t;
-    ro.done_t = done_t;
-    ro.freward_t = foveal_reward_t;
-    ro.fdone_t = foveal_done_t;
-    ro.obs_t = rec && T / obs_every > 0 ? obs_t : nullptr;
-    ro.obs_local_t = nullptr;
-    ro.every = rec ? obs_every : 1;
-    ro.smp = FovealSmp{thresholds, 0, actions_t, key_t};
-    return (int)launch_foveal_rollout_sample(a, ro, rec, (hipStream_t)stream);
+    return describe_foveal_rollout_closed<FovealPolicyTable>(params, n, T, auto_reset, obs_every, text_host, len);
 }
 
 int lmaze_foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* thresholds, int32_t T,
                                 const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                                 int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream) {
-    return foveal_rollout_sample(params, layouts, thresholds, T, bufs, n, auto_reset, seed, epoch, env_base, reward_t, done_t,
-                                 foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
+    return foveal_rollout_closed(params, layouts, FovealSampleTable{thresholds}, T, bufs, n, auto_reset, seed, epoch, env_base,
+                                 reward_t, done_t, foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_describe_foveal_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
                                          int32_t obs_every, char* text_host, int32_t len) {
-    if (!text_host || len < 1) return LMAZE_E_NULL;
-    text_host[0] = 0;
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    // nothing is dereferenced: a fabricated, aligned address stands for the slots whose presence decides
-    const int rc = foveal_rollout_sample(params, nullptr, nullptr, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, obs_every, &info,
-                                         nullptr);
-    if (rc || n == 0 || T == 0) return rc;
-    return format_launch(info, text_host, len, T);
+    return describe_foveal_rollout_closed<FovealSampleTable>(params, n, T, auto_reset, obs_every, text_host, len);
 }
 
 int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,

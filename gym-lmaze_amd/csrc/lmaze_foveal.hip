@@ -13,11 +13,11 @@
 // reference halves the whole G x G plane on every update (v4:211-214, v5:313-318); here that is `clock += 1` and a
 // step only gathers the 2 x 2 tiles (4 x 4 cells, 64 B each) under the window it shows, adds, and writes them back.
 // HBM bytes per env-step: v1 454, v2 545, v4 about 1 000 instead of round 2's 3 337.
+// The step and reset launchers are here; the one-launch rollout is launched by lmaze_foveal_launch.h (FovealOpen below).
 #include <cstdio>
 #include <cstring>
-#include <type_traits>
 
-#include "lmaze_foveal_defs.h"
+#include "lmaze_foveal_launch.h"
 
 namespace lmaze {
 
@@ -332,90 +332,26 @@ static hipError_t launch_foveal_mode(const FovealArgs& a0, hipStream_t s) {
     }
 }
 
-// ---- the one-launch rollout (lmaze_foveal_rollout) ----
-// Instantiations: envs per workgroup 32 / 64 / 128 (launch_hint bits 4-7 = 2 / 3 / 4; any other code takes the default
-// below), GT 14 (v1) or 18 (v2, v4, v5/v6) or 0, AR plain / fused.  The policy bits never change results.
-// RO = FovealRollObs: the recording form, the same instantiations of its overload.
-template <int VARIANT, int EPB, class RO>
-static hipError_t launch_rollout_one(const FovealArgs& a, const RO& ro, hipStream_t s) {
-    constexpr bool REC = std::is_same<RO, FovealRollObs>::value;
-    size_t lds = foveal_lds<VARIANT>(a.p, EPB);
-    if constexpr (EPB > 32) {
-        if (lds > lds_limit()) return launch_rollout_one<VARIANT, EPB / 2>(a, ro, s);
-    }
-    const int64_t nchunks = (a.n + EPB - 1) / EPB;
-    const int m = ((a.p.launch_hint >> 8) & 3) + 1;            // bits 8-9: chunks per workgroup - 1
-    const int64_t blocks = (nchunks + m - 1) / m;
-    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-    const int per_cu = a.p.launch_hint & 15;
-    lds = lds_for_cap(lds, per_cu);
-    FovealArgs b = a;
-    b.nt = 0;                 // plain stores: a chunk's observation is rewritten every step, the lines stay in L2
-    constexpr int GN = VARIANT == LMAZE_VARIANT_V1 ? 14 : 18;
-    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
-    if (a.info) {
-        char name[96];
-        snprintf(name, sizeof(name), "foveal_rollout_kernel<v%d, %d, %d, %s%s>", VARIANT, EPB, a.p.grid == GN ? GN : 0,
-                 a.auto_reset ? (VARIANT == LMAZE_VARIANT_V5 ? "two-level" : "fused-reset") : "plain", REC ? ", obs_t" : "");
-        describe_launch(a.info, name, EPB, lds > foveal_lds<VARIANT>(a.p, EPB) ? per_cu : 0, m, false, blocks, LMAZE_BLOCK, lds);
-        return hipSuccess;
-    }
-    if constexpr (VARIANT == LMAZE_VARIANT_V5) {
-        // the two-level step only (the plain v5/v6 step spills at 4 waves per SIMD: lmaze_foveal_rollout refuses it), and
-        // for grids other than 18 only at 32 envs per workgroup (64: 8 bytes of scratch) -- launch_rollout_variant
-        // The recording form only at G = 18: at G = 0 it needs 12 bytes of scratch at 4 waves per SIMD, so
-        // lmaze_foveal_rollout_obs refuses other grids for v5/v6 (LMAZE_E_GRID)
-        if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
-        else if constexpr (EPB == 32 && !REC) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, 32, 0, true>), grid, block, lds, s, b, ro);
-        else return hipErrorInvalidConfiguration;
-    } else if constexpr (REC && VARIANT == LMAZE_VARIANT_V1) {
+// ---- the one-launch rollout (lmaze_foveal_rollout): the open-loop family of lmaze_foveal_launch.h ----
+struct FovealOpen {
+    static constexpr const char* kKernel = "foveal_rollout_kernel";
+    static constexpr int kTableLds = 0;
+    template <int VARIANT, int EPB, int GT, bool AR, bool REC>
+    static constexpr bool exists() {
+        // v5/v6: the two-level step only (the plain v5/v6 step spills at 4 waves per SIMD: lmaze_foveal_rollout refuses it), and
+        // for grids other than 18 only at 32 envs per workgroup (64: 8 bytes of scratch) and not recording (at G = 0 that
+        // needs 12 bytes of scratch at 4 waves per SIMD, so lmaze_foveal_rollout_obs refuses other grids for v5/v6: LMAZE_E_GRID)
+        if (VARIANT == LMAZE_VARIANT_V5) return AR && (GT == 18 || (EPB == 32 && !REC));
         // v1's recording form only at G = 14: at G = 0 it spills (12 bytes) at the 6 waves per SIMD of v1's rollouts, so
         // lmaze_foveal_rollout_obs refuses other grids for v1 (LMAZE_E_GRID)
-        if (a.p.grid != GN) return hipErrorInvalidConfiguration;
-        if (a.auto_reset) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
-        else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, false>), grid, block, lds, s, b, ro);
-    } else if (a.auto_reset) {
-        if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, true>), grid, block, lds, s, b, ro);
-        else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, 0, true>), grid, block, lds, s, b, ro);
-    } else {
-        if (a.p.grid == GN) hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GN, false>), grid, block, lds, s, b, ro);
-        else hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, 0, false>), grid, block, lds, s, b, ro);
+        if (VARIANT == LMAZE_VARIANT_V1 && REC) return GT == 14;
+        return true;
     }
-    return hipGetLastError();
-}
-
-template <int VARIANT, class RO>
-static hipError_t launch_rollout_variant(const FovealArgs& a, const RO& ro, hipStream_t s) {
-    if (VARIANT == LMAZE_VARIANT_V5 && a.p.grid != 18) return launch_rollout_one<VARIANT, 32>(a, ro, s);
-    switch ((a.p.launch_hint >> 4) & 15) {
-        case 2: return launch_rollout_one<VARIANT, 32>(a, ro, s);
-        case 3: return launch_rollout_one<VARIANT, 64>(a, ro, s);
-        case 4: return launch_rollout_one<VARIANT, 128>(a, ro, s);
-        default: break;
+    template <int VARIANT, int EPB, int GT, bool AR, class RO>
+    static void launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const FovealArgs& a, const RO& ro) {
+        hipLaunchKernelGGL((foveal_rollout_kernel<VARIANT, EPB, GT, AR>), grid, block, lds, s, a, ro);
     }
-    // Default: the workgroup runs T steps of its chunk, so a launch is as many rounds of set-up + T steps as it has
-    // chunks per CU; small batches want many small chunks to cover the CUs, large ones the step's sizes
-    // (tools/bench_foveal_rollout.py: 4 096-65 536 envs 2.0-4.4 us per step for v1/v2 against 7.0-9.5 as T launches).  v1
-    // in the streaming regime: 128 envs per workgroup, 60.6 / 61.4 us (plain / fused, 1M envs, T = 64) against 79.8 / 77.6
-    // at 64 envs, 68.1 / 76.0 at 32 and 72.9 / 74.3 as T step launches; v2 fused 70.3 us (T = 256) against 97.6 at 64 envs
-    // and 109.9 as T launches, 72.1 / 95.8 / 101.7 at T = 64; v4 fused 299-315 us at 64 or 128 alike, 342-346 as T launches
-    // (three interleaved rounds each)
-    if (a.n <= (int64_t)32 * 1024) return launch_rollout_one<VARIANT, 32>(a, ro, s);
-    const int C = VARIANT == LMAZE_VARIANT_V1 ? 4 : (VARIANT == LMAZE_VARIANT_V2 ? 5 : 7);
-    if (VARIANT != LMAZE_VARIANT_V5 && (size_t)a.n * C * W25 * 4 > kFovealStreamBytes) return launch_rollout_one<VARIANT, 128>(a, ro, s);
-    return launch_rollout_one<VARIANT, 64>(a, ro, s);
-}
-
-template <class RO>
-static hipError_t launch_foveal_rollout(const FovealArgs& a, const RO& ro, hipStream_t s) {
-    switch (a.p.variant) {
-        case LMAZE_VARIANT_V1: return launch_rollout_variant<LMAZE_VARIANT_V1>(a, ro, s);
-        case LMAZE_VARIANT_V2: return launch_rollout_variant<LMAZE_VARIANT_V2>(a, ro, s);
-        case LMAZE_VARIANT_V4: return launch_rollout_variant<LMAZE_VARIANT_V4>(a, ro, s);
-        default: return launch_rollout_variant<LMAZE_VARIANT_V5>(a, ro, s);
-    }
-}
-
+};
 
 // The reference's float[N,G,G] out of / into the clock-relative tiles (include/lmaze.h): one thread per cell.
 __global__ __launch_bounds__(LMAZE_BLOCK) void visit_materialise_kernel(const uint32_t* tiles, const int32_t* clock, float* out,
@@ -543,9 +479,9 @@ static int foveal_rollout(const LmazeFovealParams* params, const uint8_t* layout
     a.epoch = epoch;
     a.env_base = env_base;
     const FovealRoll ro{T, reward_t, done_t, foveal_reward_t, foveal_done_t};
-    if (!rec) return (int)launch_foveal_rollout(a, ro, (hipStream_t)stream);
+    if (!rec) return (int)launch_foveal_rollout<FovealOpen>(a, ro, (hipStream_t)stream);
     const FovealRollObs rr{ro, slots > 0 ? rec->obs_t : nullptr, slots > 0 ? rec->obs_local_t : nullptr, rec->every};
-    return (int)launch_foveal_rollout(a, rr, (hipStream_t)stream);
+    return (int)launch_foveal_rollout<FovealOpen>(a, rr, (hipStream_t)stream);
 }
 
 int lmaze_foveal_rollout(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* actions,
@@ -595,8 +531,8 @@ static int describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, i
     memset(&rr, 0, sizeof(rr));
     rr.T = T;
     rr.every = obs_every ? *obs_every : 1;
-    const int rc = obs_every ? (int)launch_foveal_rollout(a, rr, nullptr)
-                             : (int)launch_foveal_rollout(a, static_cast<const FovealRoll&>(rr), nullptr);
+    const int rc = obs_every ? (int)launch_foveal_rollout<FovealOpen>(a, rr, nullptr)
+                             : (int)launch_foveal_rollout<FovealOpen>(a, static_cast<const FovealRoll&>(rr), nullptr);
     return rc ? rc : format_launch(info, text_host, len, T);
 }
 

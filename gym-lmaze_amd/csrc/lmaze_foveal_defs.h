@@ -1,6 +1,7 @@
 // lmaze_foveal_defs.h -- what the translation units of the foveal kernels share (lmaze_foveal.hip: the step, reset and
 // open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip: the closed-loop rollouts): the kernel arguments, the device helpers
-// of lmaze_foveal_body.h, and the host-side checks and LDS sizing of their launchers.  Not part of the C ABI.
+// of lmaze_foveal_body.h, and the host-side checks and LDS sizing of their launchers (the rollouts' one launcher:
+// lmaze_foveal_launch.h).  Not part of the C ABI.
 #ifndef LMAZE_FOVEAL_DEFS_H_
 #define LMAZE_FOVEAL_DEFS_H_
 
@@ -110,7 +111,8 @@ __device__ __forceinline__ int foveal_pol_action(const FovealPol& pol, bool stag
     return act;
 }
 constexpr int kFovealPolicyLds = 8192;   // bytes of table up to which it is staged in LDS (a rule, not a measurement)
-hipError_t launch_foveal_rollout_policy(const FovealArgs& a, const FovealRollObsPol& ro, bool rec, hipStream_t s);
+// rec false: the plain form, the recording members of ro unread (lmaze_foveal_launch.h launch_foveal_rollout_sliced)
+hipError_t launch_foveal_rollout_closed(const FovealArgs& a, const FovealRollObsPol& ro, bool rec, hipStream_t s);
 
 // The sampling closed-loop rollout (lmaze_foveal_rollout_sample, lmaze_foveal_sample.hip): a categorical table policy, one
 // row of cumulative thresholds per key -- uint32[4] for v1 (c0, c1, c2, reserved: the grid envs' format), uint32[24] for
@@ -160,7 +162,7 @@ __device__ __forceinline__ int foveal_smp_action(const FovealSmp& smp, bool stag
     return act;
 }
 constexpr int kFovealSampleLds = 16384;   // bytes of thresholds up to which they are staged in LDS: lmaze_rollout_sample's figure
-hipError_t launch_foveal_rollout_sample(const FovealArgs& a, const FovealRollObsSmp& ro, bool rec, hipStream_t s);
+hipError_t launch_foveal_rollout_closed(const FovealArgs& a, const FovealRollObsSmp& ro, bool rec, hipStream_t s);
 
 struct EnvRec {           // one env after its transition (registers only; phase 1 turns it into plane masks)
     int16_t cx, cy;       // centre of the current window (ball after the move)

@@ -28,7 +28,7 @@ CHANNELS = {"v1": 4, "v2": 5, "v4": 7, "v5": 7, "v6": 7}
 # obs_every: None for the entry points that do not record
 Row = namedtuple("Row", "entry variant G n_layouts N T obs_every hint")
 
-STREAM_BYTES = 192 << 20            # observations beyond this are streamed ("nt": kFovealStreamBytes, lmaze_foveal.hip)
+STREAM_BYTES = 192 << 20            # observations beyond this are streamed ("nt": kFovealStreamBytes, lmaze_foveal_defs.h)
 LDS_PER_WORKGROUP = 160 << 10       # gfx950
 LDS_WITHOUT_DEVICE = 64 << 10       # what the launcher assumes when it cannot ask a device
 MAX_LAYOUTS = 16

@@ -212,3 +212,30 @@ def test_the_table_holds_every_axis_value_the_launcher_branches_on():
                 assert {r.hint >> 8 for r in rows} == {0, 1, 2, 3}, (entry, v)
                 assert {r.hint & 15 for r in rows} >= {0, 2, 5} and any(r.hint & 15 > 8 for r in rows), (entry, v)
             assert any(r.hint & 15 == 8 for r in M.ROWS if r.entry == entry), entry
+
+
+@pytest.mark.parametrize("variant", ["v2", "v4"])
+def test_the_three_rollout_families_describe_one_launch_where_no_table_is_staged(abi, variant):
+    """The open loop, the epsilon-greedy and the sampling closed loop share one launcher (lmaze_foveal_launch.h): where the
+    closed loops stage no table they plan the open loop's launch, and their lines differ from its line in the kernel's name
+    and the " table=global" suffix alone.  G = 24 with 16 layouts: 9 216 B of greedy actions (rule: 8 192) and 884 736 B of
+    thresholds (rule: 16 384), and v4's 18 816 + 272 envs = 53 632 B at 128 envs per workgroup is within the 64 KiB the
+    launcher assumes without a device, so no size is halved."""
+    G, L, T = 24, 16, 24
+    assert L * G * G == 9216 > 8192 and L * G * G * 96 == 884736 > 16384
+    fields = ("envs_per_workgroup", "chunks", "grid", "block", "lds", "workgroups_per_cu")
+    sizes = set()
+    for n in (333, 40000, 1 << 20):
+        for h in (0, 0x20, 0x30, 0x40, 0x120, 0x25):
+            for ar in (False, True):
+                for every in (0, 3):
+                    p = M.params(abi, variant, G, L, h)
+                    o = abi.describe_foveal_rollout(p, n, T, ar, False, every or None)
+                    assert o.startswith("foveal_rollout_kernel<"), o
+                    lines = {"policy": abi.describe_foveal_rollout_policy(p, n, T, ar, every),
+                             "sample": abi.describe_foveal_rollout_sample(p, n, T, ar, every)}
+                    for family, c in lines.items():
+                        assert [M.field(c, f) for f in fields] == [M.field(o, f) for f in fields], (o, c)
+                        assert c.replace("foveal_rollout_%s_kernel<" % family, "foveal_rollout_kernel<").replace("> table=global ", "> ") == o, (o, c)
+                    sizes.add(M.field(o, "envs_per_workgroup"))
+    assert sizes == {32, 64, 128}

@@ -128,7 +128,7 @@ def test_refusals_in_their_documented_order(abi, variant):
 
 
 def _foveal_lds(variant, G, L, epb):
-    """lmaze_foveal.hip foveal_lds: per-env strings and flags, row masks, layout characters, v4's visit samples"""
+    """lmaze_foveal_defs.h foveal_lds: per-env strings and flags, row masks, layout characters, v4's visit samples"""
     L = 1 if variant == "v1" else L
     lds = epb * 64 + (3 * L * G + 2 * G) * 8 + ((L * G * G + 15) & ~15)
     return lds + (epb * (2 * 25 * 4 + 8) if variant == "v4" else 0)
