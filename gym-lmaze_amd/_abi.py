@@ -38,7 +38,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns",
            "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
            "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy",
-           "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample")
+           "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
+           "lmaze_describe_v5_rollout_policy")
 
 
 class LmazeParams(C.Structure):
@@ -200,6 +201,11 @@ def _load():
     lib.lmaze_foveal_rollout_sample.argtypes = [FP, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.lmaze_describe_foveal_rollout_sample.restype = C.c_int
     lib.lmaze_describe_foveal_rollout_sample.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_v5_rollout_policy.restype = C.c_int
+    lib.lmaze_v5_rollout_policy.argtypes = [FP, vp, vp, i32, C.c_uint32, vp, C.c_uint32, i32, FB, i64, u64, u64, i64, vp, vp, vp, vp, vp,
+                                            vp, vp, vp, vp, vp, i32, vp]
+    lib.lmaze_describe_v5_rollout_policy.restype = C.c_int
+    lib.lmaze_describe_v5_rollout_policy.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -329,6 +335,25 @@ def describe_foveal_rollout_policy(params, n, T, auto_reset=False, obs_every=0):
     """The kernel / grid / launch policy lmaze_foveal_rollout_policy would queue for n envs and T steps (obs_every=0: no
     recording), and where its table lives: "... table=lds ..." or "... table=global ..."."""
     return _describe("lmaze_describe_foveal_rollout_policy", C.byref(params), int(n), int(T), 1 if auto_reset else 0, int(obs_every))
+
+
+def describe_v5_rollout_policy(params, n, T, controller_key=0, obs_every=0):
+    """As describe_foveal_rollout_policy, for lmaze_v5_rollout_policy (v5/v6): "foveal_hier_policy_kernel<v5, 32, 18, obs_t>
+    controller=lds planner=lds T=...".  controller_key: 0 / "offset" or 1 / "cell"."""
+    return _describe("lmaze_describe_v5_rollout_policy", C.byref(params), int(n), int(T), controller_key_id(controller_key),
+                     int(obs_every))
+
+
+CONTROLLER_KEYS = {"offset": 0, "cell": 1}
+
+
+def controller_key_id(controller_key):
+    """0 / 1 of "offset" / "cell" (the ids themselves pass through)"""
+    if isinstance(controller_key, str):
+        if controller_key not in CONTROLLER_KEYS:
+            raise ValueError("controller_key must be 'offset' or 'cell'")
+        return CONTROLLER_KEYS[controller_key]
+    return int(controller_key)
 
 
 def describe_foveal_rollout_sample(params, n, T, auto_reset=False, obs_every=0):

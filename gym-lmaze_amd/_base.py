@@ -169,27 +169,30 @@ class VecEnvBase(object):
             raise ValueError("policy must be a contiguous uint8 tensor of %d entries on %s (%s)" % (entries, self.device, shape))
         return policy
 
-    def _closed_loop(self, who, name, call, T, k, obs_t, trajectory, actions_t, key_t, streams=1):
+    def _closed_loop(self, who, name, call, T, k, obs_t, trajectory, actions_t, key_t, streams=1, more=None):
         """What every closed-loop rollout does around its ABI call `name`, once its table and its recording request (k =
         _obs_slots()) are checked: the actions_t / key_t rows (checked; allocated under trajectory=True), the trajectory
         rows of `streams` streams, the launch -- call(row addresses, actions_t's, key_t's, the slots') returns the ABI's
-        code -- the epoch, which advances by T, and the result: rollout()'s, then under trajectory=True actions_t, key_t."""
-        self._check_rows(who, actions_t, key_t)
-        for label, t in (("actions_t", actions_t), ("key_t", key_t)):
+        code -- the epoch, which advances by T, and the result: rollout()'s, then under trajectory=True actions_t, key_t.
+        more: further int32[T,N] rows as (label, tensor or None) pairs (the two-level loop's goals_t, goal_key_t), treated as
+        actions_t / key_t are; their addresses are call's fifth argument and they follow key_t in the result."""
+        named = [("actions_t", actions_t), ("key_t", key_t)] + list(more or ())
+        self._check_rows(who, *(t for _, t in named))
+        for label, t in named:
             if t is not None and t.shape[0] != T:
                 raise ValueError("%s must have T = %d rows" % (label, T))
         rows = self._traj_rows(T, streams) if trajectory else None
         if trajectory:
-            actions_t = torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device) if actions_t is None else actions_t
-            key_t = torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device) if key_t is None else key_t
+            named = [(label, torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device) if t is None else t)
+                     for label, t in named]
+        ptrs = [None if t is None else t.data_ptr() for _, t in named]
         slots = obs_t.data_ptr() if k > 0 and obs_t.shape[0] > 0 else None
         with self._guard():
-            rc = call([r.data_ptr() for r in rows or ()], None if actions_t is None else actions_t.data_ptr(),
-                      None if key_t is None else key_t.data_ptr(), slots)
+            rc = call([r.data_ptr() for r in rows or ()], ptrs[0], ptrs[1], slots, *([ptrs[2:]] if more is not None else []))
         _abi.check(name, rc)
         self._epoch += T
         out = self._rollout_result(rows)
-        return out + (actions_t, key_t) if trajectory else out
+        return out + tuple(t for _, t in named) if trajectory else out
 
     def host_state(self, raw=None):
         """Every per-env scalar on the host: numpy views of ONE device->host copy of the state block.  raw: bytes of

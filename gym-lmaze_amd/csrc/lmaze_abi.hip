@@ -193,32 +193,62 @@ static int describe_rollout_closed(const LmazeParams* params, int64_t n, int32_t
     return format_launch(info, text_host, len);
 }
 
-// The tables of the closed-loop foveal rollouts: the pointer, the alignment it needs (1: none) and its place in the
-// recording struct its launcher takes (lmaze_foveal_defs.h).
+// The tables of the closed-loop foveal rollouts: the pointer(s), the alignment they need (1: none), the variants the family
+// takes (kTwoLevel: v5/v6 and nothing else; otherwise v1/v2/v4), a refusal of their own that stands with the counts, and
+// their place in the recording struct the launcher takes (lmaze_foveal_defs.h).
 struct FovealPolicyTable {
     typedef FovealRollObsPol Roll;
     static constexpr uintptr_t kAlign = 1;
+    static constexpr bool kTwoLevel = false;
     const uint8_t* table;
     uint32_t epsilon;
+    int refused() const { return 0; }
+    bool missing() const { return !table; }
+    bool unaligned() const { return false; }
     void put(Roll& ro, int32_t* actions_t, int32_t* key_t) const { ro.pol = FovealPol{table, epsilon, 0, actions_t, key_t}; }
 };
 struct FovealSampleTable {
     typedef FovealRollObsSmp Roll;
     static constexpr uintptr_t kAlign = 16;
+    static constexpr bool kTwoLevel = false;
     const uint32_t* table;
+    int refused() const { return 0; }
+    bool missing() const { return !table; }
+    bool unaligned() const { return misaligned(table, kAlign); }
     void put(Roll& ro, int32_t* actions_t, int32_t* key_t) const { ro.smp = FovealSmp{table, 0, actions_t, key_t}; }
 };
+struct FovealHierTables {
+    typedef FovealRollObsHier Roll;
+    static constexpr uintptr_t kAlign = 1;
+    static constexpr bool kTwoLevel = true;
+    const uint8_t* controller;
+    const uint8_t* planner;
+    uint32_t epsilon, planner_epsilon;
+    int32_t controller_key;
+    int32_t* goals_t;
+    int32_t* goal_key_t;
+    int refused() const { return controller_key != 0 && controller_key != 1 ? LMAZE_E_COUNT : 0; }
+    bool missing() const { return !controller || !planner; }
+    bool unaligned() const { return false; }
+    void put(Roll& ro, int32_t* actions_t, int32_t* key_t) const {
+        ro.hier = FovealHier{controller, planner, epsilon, planner_epsilon, controller_key, 0, actions_t, key_t, goals_t, goal_key_t};
+    }
+};
 
-// lmaze_foveal_rollout_policy / lmaze_foveal_rollout_sample (lmaze_foveal_policy.hip, lmaze_foveal_sample.hip).  info != null:
-// describe instead of launching -- then nothing past the params is looked at.  The refusals stand in the order
-// include/lmaze.h documents.
+// lmaze_foveal_rollout_policy / lmaze_foveal_rollout_sample / lmaze_v5_rollout_policy (lmaze_foveal_policy.hip,
+// lmaze_foveal_sample.hip, lmaze_hier_policy.hip).  info != null: describe instead of launching -- then nothing past the params
+// and the table's own refusal is looked at.  The refusals stand in the order include/lmaze.h documents.  obs_local_t: the
+// two-level family's second recording (nullable; 16-byte aligned, refused with the recording request).
 template <class Table>
 static int foveal_rollout_closed(const LmazeFovealParams* params, const uint8_t* layouts, const Table& tab, int32_t T,
                                  const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                                  int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
-                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, LaunchInfo* info, void* stream) {
+                                 int32_t* actions_t, int32_t* key_t, float* obs_t, float* obs_local_t, int32_t obs_every,
+                                 LaunchInfo* info, void* stream) {
     int rc = check_recording(T, obs_t, obs_every);                     // 1. the recording request
     if (rc) return rc;
+    if (obs_local_t && obs_every == 0) return LMAZE_E_COUNT;
+    if (misaligned(obs_local_t, 16)) return LMAZE_E_ALIGN;
     if (!params) return LMAZE_E_NULL;                                  // 2. the params' own refusals
     const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
     if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
@@ -226,19 +256,21 @@ static int foveal_rollout_closed(const LmazeFovealParams* params, const uint8_t*
     if (params->grid < LMAZE_FOVEA || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
     if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
     if (params->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
-    if (v56) return LMAZE_E_VARIANT;                                   // 3. no closed loop for the two-level variants
+    if (v56 != Table::kTwoLevel) return LMAZE_E_VARIANT;               // 3. the two-level variants have a closed loop of their own
     if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;    // 4.
+    rc = tab.refused();
+    if (rc) return rc;
     if (T == 0 || n == 0) return 0;                                    // 5. nothing to do, nothing read
     LmazeFovealBuffers none;
     memset(&none, 0, sizeof(none));
     if (!info) {                                                       // 6. the pointers, then the alignments
-        if (!tab.table) return LMAZE_E_NULL;                           // with the other pointers, before any alignment
+        if (tab.missing()) return LMAZE_E_NULL;                        // with the other pointers, before any alignment
         rc = check_foveal(params, layouts, bufs, n);
         if (rc) return rc;
-        if (misaligned(tab.table, Table::kAlign)) return LMAZE_E_ALIGN;   // the table's own alignment last
+        if (tab.unaligned()) return LMAZE_E_ALIGN;                     // the table's own alignment last
     }
     FovealArgs a = make_foveal_args(params, layouts, info ? &none : bufs, n);
-    a.auto_reset = auto_reset ? 1 : 0;
+    a.auto_reset = auto_reset || Table::kTwoLevel ? 1 : 0;             // the two-level step resets and plans by itself
     a.seed = seed;
     a.epoch = epoch;
     a.env_base = env_base;
@@ -252,24 +284,24 @@ static int foveal_rollout_closed(const LmazeFovealParams* params, const uint8_t*
     ro.freward_t = foveal_reward_t;
     ro.fdone_t = foveal_done_t;
     ro.obs_t = rec && T / obs_every > 0 ? obs_t : nullptr;
-    ro.obs_local_t = nullptr;
+    ro.obs_local_t = rec && T / obs_every > 0 ? obs_local_t : nullptr;
     ro.every = rec ? obs_every : 1;
     tab.put(ro, actions_t, key_t);
     return (int)launch_foveal_rollout_closed(a, ro, rec, (hipStream_t)stream);
 }
 
-// lmaze_describe_foveal_rollout_policy / lmaze_describe_foveal_rollout_sample
+// lmaze_describe_foveal_rollout_policy / lmaze_describe_foveal_rollout_sample / lmaze_describe_v5_rollout_policy
 template <class Table>
 static int describe_foveal_rollout_closed(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t obs_every,
-                                          char* text_host, int32_t len) {
+                                          char* text_host, int32_t len, const Table& tab = Table{}) {
     if (!text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
     LaunchInfo info;
     memset(&info, 0, sizeof(info));
     // nothing is dereferenced: a fabricated, aligned address stands for the slots whose presence decides
-    const int rc = foveal_rollout_closed(params, nullptr, Table{}, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, obs_every, &info,
-                                         nullptr);
+    const int rc = foveal_rollout_closed(params, nullptr, tab, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, nullptr, obs_every,
+                                         &info, nullptr);
     if (rc || n == 0 || T == 0) return rc;
     return format_launch(info, text_host, len, T);
 }
@@ -492,7 +524,8 @@ int lmaze_foveal_rollout_policy(const LmazeFovealParams* params, const uint8_t* 
                                 float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream) {
     return foveal_rollout_closed(params, layouts, FovealPolicyTable{policy, epsilon_u32}, T, bufs, n, auto_reset, seed, epoch, env_base,
-                                 reward_t, done_t, foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
+                                 reward_t, done_t, foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, nullptr, obs_every, nullptr,
+                                 stream);
 }
 
 int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
@@ -500,12 +533,29 @@ int lmaze_describe_foveal_rollout_policy(const LmazeFovealParams* params, int64_
     return describe_foveal_rollout_closed<FovealPolicyTable>(params, n, T, auto_reset, obs_every, text_host, len);
 }
 
+int lmaze_v5_rollout_policy(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* controller, int32_t controller_key,
+                            uint32_t epsilon_u32, const uint8_t* planner, uint32_t planner_epsilon_u32, int32_t T,
+                            const LmazeFovealBuffers* bufs, int64_t n, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t,
+                            uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t, int32_t* actions_t, int32_t* key_t,
+                            int32_t* goals_t, int32_t* goal_key_t, float* obs_t, float* obs_local_t, int32_t obs_every, void* stream) {
+    const FovealHierTables tab{controller, planner, epsilon_u32, planner_epsilon_u32, controller_key, goals_t, goal_key_t};
+    return foveal_rollout_closed(params, layouts, tab, T, bufs, n, 1, seed, epoch, env_base, reward_t, done_t, foveal_reward_t,
+                                 foveal_done_t, actions_t, key_t, obs_t, obs_local_t, obs_every, nullptr, stream);
+}
+
+int lmaze_describe_v5_rollout_policy(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t controller_key, int32_t obs_every,
+                                     char* text_host, int32_t len) {
+    const FovealHierTables tab{nullptr, nullptr, 0, 0, controller_key, nullptr, nullptr};
+    return describe_foveal_rollout_closed(params, n, T, 1, obs_every, text_host, len, tab);
+}
+
 int lmaze_foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* thresholds, int32_t T,
                                 const LmazeFovealBuffers* bufs, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                                 int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t, uint8_t* foveal_done_t,
                                 int32_t* actions_t, int32_t* key_t, float* obs_t, int32_t obs_every, void* stream) {
     return foveal_rollout_closed(params, layouts, FovealSampleTable{thresholds}, T, bufs, n, auto_reset, seed, epoch, env_base,
-                                 reward_t, done_t, foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, obs_every, nullptr, stream);
+                                 reward_t, done_t, foveal_reward_t, foveal_done_t, actions_t, key_t, obs_t, nullptr, obs_every, nullptr,
+                                 stream);
 }
 
 int lmaze_describe_foveal_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,

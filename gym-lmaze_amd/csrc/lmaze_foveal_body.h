@@ -6,11 +6,16 @@
 // mixed with an exploration draw, instead of from the action tensor, and stores the action and key rows).  POL is the
 // include site's LMAZE_FOVEAL_POLICY_SITE: what it adds stands under the preprocessor, so that every other kernel compiles
 // from the text it always had.  LMAZE_FOVEAL_SAMPLE_SITE (lmaze_foveal_sample.hip, POL = 2) is the sampling closed loop: the
-// table holds one row of cumulative thresholds per key and one draw word is compared against them.  Not a header of its own.
+// table holds one row of cumulative thresholds per key and one draw word is compared against them.
+// LMAZE_FOVEAL_HIER_SITE (lmaze_hier_policy.hip, POL = 3) is the closed loop of the two-level step of v5/v6: the V5 FM_STEP / AR
+// branch of phase 1 loads neither a.action nor a.goal2; the planner's goal and the controller's action come from two tables
+// (ro.hier) mixed with one draw, and their rows are stored where they are produced.  Not a header of its own.
 #ifndef LMAZE_FOVEAL_BODY_SITE
-#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip, lmaze_foveal_policy.hip and lmaze_foveal_sample.hip"
+#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip, lmaze_foveal_policy.hip, lmaze_foveal_sample.hip and lmaze_hier_policy.hip"
 #endif
-#if defined(LMAZE_FOVEAL_SAMPLE_SITE)
+#if defined(LMAZE_FOVEAL_HIER_SITE)
+#define LMAZE_POL 3
+#elif defined(LMAZE_FOVEAL_SAMPLE_SITE)
 #define LMAZE_POL 2
 #elif defined(LMAZE_FOVEAL_POLICY_SITE)
 #define LMAZE_POL 1
@@ -56,6 +61,13 @@
     uint32_t* stab = reinterpret_cast<uint32_t*>(lds4) + ((((lays - reinterpret_cast<uint8_t*>(lds4)) + L * CELLS + 15) & ~15) >> 2);
     const FovealSmp smp = ro.smp;
     const bool pstage = smp.in_lds != 0;
+#elif LMAZE_POL == 3
+    // the controller table behind the characters and the planner table behind it, each only when it is staged
+    const FovealHier hier = ro.hier;
+    const int cbytes = hier_controller_bytes(hier.controller_key, L, G), pbytes = L * CELLS;
+    const bool cstage = (hier.in_lds & kHierControllerStaged) != 0, pstage = (hier.in_lds & kHierPlannerStaged) != 0;
+    uint8_t* ctab = lays + ((L * CELLS + 15) & ~15);
+    uint8_t* ptab = ctab + (cstage ? (cbytes + 15) & ~15 : 0);
 #endif
     static_assert(PERENV <= 8 * 32 - 32 && 4 * W25 <= 4 * 32 - 4, "bit strings fit the 32 B / 16 B per env reserved for them");
     __shared__ int any_skip, ndense;
@@ -120,6 +132,13 @@
             for (int j = 0; j < 2; ++j)
                 if (tid + j * LMAZE_BLOCK < (L * CELLS) >> 2) pw[j] = reinterpret_cast<const uint32_t*>(pol.table)[tid + j * LMAZE_BLOCK];
         }
+#elif LMAZE_POL == 3
+        // the staged tables' dwords are requested with the characters'
+        const bool cdwords = cstage && ((reinterpret_cast<uintptr_t>(hier.controller) | (uintptr_t)cbytes) & 3) == 0;
+        const bool pdwords = pstage && ((reinterpret_cast<uintptr_t>(hier.planner) | (uintptr_t)pbytes) & 3) == 0;
+        uint32_t hcw[2], hpw[2];
+        hier_request(hier.controller, cbytes, cdwords, tid, hcw);
+        hier_request(hier.planner, pbytes, pdwords, tid, hpw);
 #endif
         for (int r00 = 0; r00 < rows; r00 += UNR * 4 * RPW) {
             uint8_t cc[UNR];
@@ -173,6 +192,9 @@
         }
 #elif LMAZE_POL == 2
         if (pstage) stage_thresholds(stab, smp.table, L * CELLS * (SROW / 4), tid);
+#elif LMAZE_POL == 3
+        if (cstage) hier_stage(ctab, hier.controller, cbytes, cdwords, tid, hcw);
+        if (pstage) hier_stage(ptab, hier.planner, pbytes, pdwords, tid, hpw);
 #endif
     } else {
     for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
@@ -180,6 +202,9 @@
     if (pstage) for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) ptab[i] = pol.table[i];
 #elif LMAZE_POL == 2
     if (pstage) stage_thresholds(stab, smp.table, L * CELLS * (SROW / 4), tid);
+#elif LMAZE_POL == 3
+    if (cstage) for (int i = tid; i < cbytes; i += LMAZE_BLOCK) ctab[i] = hier.controller[i];
+    if (pstage) for (int i = tid; i < pbytes; i += LMAZE_BLOCK) ptab[i] = hier.planner[i];
 #endif
     __syncthreads();
     for (int i = tid; i < L * G; i += LMAZE_BLOCK) {
@@ -231,13 +256,19 @@
 #endif
         const int sc_ld = (MODE == FM_STEP) ? a.b.step_count[e] : 0;
         const int done_in = (MODE == FM_STEP && AR) ? a.b.done[e] : 0;
+#if LMAZE_POL != 3
         const int goal2_in = (MODE == FM_STEP && AR && V5) ? a.goal2[ROLL_ROW(e)] : 0;
+#endif
         const int vword = (V4 && !(V5 && MODE == FM_PLANNER)) ? a.b.visit_clock[e] : 0;
         const int vclock = vword & 0xff;
 #if LMAZE_POL == 2
         // the sampling draw, on every env-step: one word of it is live across the fused reset.  It depends on nothing loaded,
         // so it stands in front of the placement chain and runs under the loads above.
         const uint32_t prx = policy_draw(a.seed, ROLL_EP, a.env_base + e).x;
+#elif LMAZE_POL == 3
+        // one draw for both levels, only when either explores (uniform over the launch): in front of the placement chain
+        uint4 pr = make_uint4(0u, 0u, 0u, 0u);
+        if ((hier.epsilon | hier.planner_epsilon) != 0u) pr = policy_draw(a.seed, ROLL_EP, a.env_base + e);
 #elif LMAZE_POL
         // the exploration draw, only when there is exploration (uniform over the launch).  It depends on nothing loaded, so
         // it stands in front of the fused reset's placement chain and runs under the loads above.
@@ -258,7 +289,7 @@
                 }
 #if LMAZE_POL == 2
                 const int act = foveal_smp_action<true>(smp, pstage, stab, 0, bx, by, G, 1, prx, ROLL_ROW(e));   // the key is the placed ball's
-#elif LMAZE_POL
+#elif LMAZE_POL == 1
                 const int act = foveal_pol_action(pol, pstage, ptab, 0, bx, by, G, 1, 4, pr, ROLL_ROW(e));   // the key is the placed ball's
 #else
                 const int act = act_in;
@@ -322,7 +353,11 @@
             int b1x = a.b.ball1_xy[2 * e], b1y = a.b.ball1_xy[2 * e + 1];
             int lx = a.b.last_xy[2 * e], ly = a.b.last_xy[2 * e + 1];
             if (MODE == FM_STEP) {                                     // v5:187-292
+#if LMAZE_POL == 3
+                int act = act_in;                                      // the controller's, once the planner has stepped
+#else
                 const int act = act_in;
+#endif
                 int fgx = a.b.fgoal_xy[2 * e], fgy = a.b.fgoal_xy[2 * e + 1];
                 int fsc = a.b.foveal_step_count[e];
                 int sc_in = sc_ld;
@@ -347,7 +382,11 @@
                         fresh = true;
                     }
                     if (plan) {                                        // plannerStep(goal): v5:158-182, as FM_PLANNER below
+#if LMAZE_POL == 3
+                        const int g = hier_plan_goal(hier, ptab, lid, bx, by, G, L, pr.z, pr.w, ROLL_ROW(e));   // the state after the reset
+#else
                         const int g = goal2_in;
+#endif
                         if (g >= 0 && g < W25) {
                             fg = g;
                             sc_in = 0;                                 // v5:160
@@ -358,6 +397,9 @@
                             planned = true;
                         }
                     }
+#if LMAZE_POL == 3
+                    else hier_no_goal(hier, ROLL_ROW(e));
+#endif
                     if (fresh || planned) {
                         a.b.foveal_goal[e] = fg;
                         a.b.fgoal_xy[2 * e] = fgx; a.b.fgoal_xy[2 * e + 1] = fgy;
@@ -365,6 +407,9 @@
                         a.b.foveal_step_count[e] = fsc;
                     }
                 }
+#if LMAZE_POL == 3
+                act = hier_act(hier, ctab, lid, bx, by, fgx, fgy, G, L, pr.x, pr.y, ROLL_ROW(e));   // the state after the plannerStep
+#endif
                 const uint8_t* lay = lays + lid * CELLS;
                 b1x = bx; b1y = by;                                    // v5:193-194
                 float lr = -0.0f, gr;                                  // v5:196
@@ -490,7 +535,7 @@
             if (MODE == FM_STEP) {
 #if LMAZE_POL == 2
                 const int act = foveal_smp_action<false>(smp, pstage, stab, lid, bx, by, G, L, prx, ROLL_ROW(e));   // the row the step uses
-#elif LMAZE_POL
+#elif LMAZE_POL == 1
                 const int act = foveal_pol_action(pol, pstage, ptab, lid, bx, by, G, L, W25, pr, ROLL_ROW(e));   // the row the step uses
 #else
                 const int act = act_in;
@@ -685,7 +730,7 @@
             // as the epsilon-greedy form below; the fused recording form at a generic grid has no registers for it either
             constexpr int WSUB = (REC && (!AR || GT == 0)) ? 32 : LMAZE_WIN_SUB;
             constexpr int IPE = 2 * FOV, SUB = EPB < WSUB ? EPB : WSUB, NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;
-#elif LMAZE_POL
+#elif LMAZE_POL == 1
             // the plain recording form of the closed loop has no registers for a third window row per lane
             constexpr int IPE = 2 * FOV, SUB = EPB < ((REC && !AR) ? 32 : LMAZE_WIN_SUB) ? EPB : ((REC && !AR) ? 32 : LMAZE_WIN_SUB);
             constexpr int NIT = (SUB * IPE + LMAZE_BLOCK - 1) / LMAZE_BLOCK;

@@ -1,5 +1,5 @@
 // lmaze_foveal_defs.h -- what the translation units of the foveal kernels share (lmaze_foveal.hip: the step, reset and
-// open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip: the closed-loop rollouts): the kernel arguments, the device helpers
+// open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip, lmaze_hier_policy.hip: the closed-loop rollouts): the kernel arguments, the device helpers
 // of lmaze_foveal_body.h, and the host-side checks and LDS sizing of their launchers (the rollouts' one launcher:
 // lmaze_foveal_launch.h).  Not part of the C ABI.
 #ifndef LMAZE_FOVEAL_DEFS_H_
@@ -9,6 +9,7 @@
 #include "lmaze_visit.h"
 #include "lmaze_foveal_select.h"
 #include "lmaze_foveal_sample.h"
+#include "lmaze_hier_select.h"
 
 // Timing decomposition (tools/foveal_decompose.py): a build with -DLMAZE_EXPERIMENT -- never the shipped
 // one -- reads bits 16-23 of launch_hint as switches that turn phases off (results are garbage then; only the time
@@ -163,6 +164,85 @@ __device__ __forceinline__ int foveal_smp_action(const FovealSmp& smp, bool stag
 }
 constexpr int kFovealSampleLds = 16384;   // bytes of thresholds up to which they are staged in LDS: lmaze_rollout_sample's figure
 hipError_t launch_foveal_rollout_closed(const FovealArgs& a, const FovealRollObsSmp& ro, bool rec, hipStream_t s);
+
+// The closed-loop TWO-LEVEL rollout of v5/v6 (lmaze_v5_rollout_policy, lmaze_hier_policy.hip): two uint8 tables, the planner's
+// keyed by (layout row, ball) and the controller's by the foveal goal's offset from the ball (and, controller_key 1, the
+// planner key as well), each mixed with two words of one exploration draw (lmaze_hier_select.h).  The body is compiled with
+// POL = 3 for the two types below and reads ro.hier.
+struct FovealHier {
+    const uint8_t* controller;   // uint8[100] or uint8[100*L*G*G]: the greedy action id of every controller key
+    const uint8_t* planner;      // uint8[L*G*G]: the greedy goal id of every planner key
+    uint32_t epsilon;            // controller: min(floor(eps * 2^32), 2^32 - 1)
+    uint32_t planner_epsilon;    // planner: likewise; nothing is drawn when both are 0
+    int32_t controller_key;      // 0 offset, 1 cell
+    int32_t in_lds;              // bit 0: the controller table is staged in LDS behind the layout characters, bit 1: the planner table, behind it
+    int32_t* actions_t;          // [T,N] or null: the action every env took
+    int32_t* key_t;              // [T,N] or null: the controller key it was looked up with
+    int32_t* goals_t;            // [T,N] or null: the goal of every env that planned, -1 elsewhere
+    int32_t* goal_key_t;         // [T,N] or null: the planner key it was looked up with, -1 elsewhere
+};
+struct FovealRollHier : FovealRoll { FovealHier hier; };
+struct FovealRollObsHier : FovealRollObs { FovealHier hier; };
+constexpr int kHierControllerStaged = 1, kHierPlannerStaged = 2;
+__host__ __device__ __forceinline__ int hier_controller_bytes(int controller_key, int L, int G) {
+    return controller_key ? LMAZE_HIER_OFFSETS * L * G * G : LMAZE_HIER_OFFSETS;
+}
+// Staging a table of `bytes` bytes: its first two dwords per lane are requested here (beside the layout loads, before the
+// row masks are built) ...
+__device__ __forceinline__ void hier_request(const uint8_t* table, int bytes, bool dwords, int tid, uint32_t (&w)[2]) {
+    w[0] = w[1] = 0u;
+    if (!dwords) return;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (tid + j * LMAZE_BLOCK < bytes >> 2) w[j] = reinterpret_cast<const uint32_t*>(table)[tid + j * LMAZE_BLOCK];
+}
+// ... and stored here, with whatever lies past 2 KiB; a table that is not whole aligned dwords goes byte by byte.  The
+// caller's barrier follows.
+__device__ __forceinline__ void hier_stage(uint8_t* lds_table, const uint8_t* table, int bytes, bool dwords, int tid, const uint32_t (&w)[2]) {
+    if (dwords) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (tid + j * LMAZE_BLOCK < bytes >> 2) reinterpret_cast<uint32_t*>(lds_table)[tid + j * LMAZE_BLOCK] = w[j];
+        for (int i = tid + 2 * LMAZE_BLOCK; i < bytes >> 2; i += LMAZE_BLOCK)
+            reinterpret_cast<uint32_t*>(lds_table)[i] = reinterpret_cast<const uint32_t*>(table)[i];
+    } else {
+        for (int i = tid; i < bytes; i += LMAZE_BLOCK) lds_table[i] = table[i];
+    }
+}
+// One byte of a table: the staged and the global side are read through pointers of their own address spaces (foveal_pol_action).
+__device__ __forceinline__ int hier_table_byte(bool staged, const uint8_t* lds_table, const uint8_t* table, int key) {
+    typedef const __attribute__((address_space(3))) uint8_t* lds_bytes;
+    typedef const __attribute__((address_space(1))) uint8_t* global_bytes;
+    return staged ? (int)((lds_bytes)lds_table)[key] : (int)((global_bytes)table)[key];
+}
+// The goal of an env that plans in state (lid, bx, by): planner key -> table -> mix with the draw words r.z / r.w, and element
+// `row` of the goal and goal-key rows, stored here where they are produced.
+__device__ __forceinline__ int hier_plan_goal(const FovealHier& h, const uint8_t* lds_table, int lid, int bx, int by, int G, int L,
+                                              uint32_t rz, uint32_t rw, int64_t row) {
+    const int kp = lmaze_hier_planner_key(lid, bx, by, G, L);
+    const int g = lmaze_hier_goal(hier_table_byte((h.in_lds & kHierPlannerStaged) != 0, lds_table, h.planner, kp), rz, rw, h.planner_epsilon);
+    if (h.goals_t) h.goals_t[row] = g;
+    if (h.goal_key_t) h.goal_key_t[row] = kp;
+    return g;
+}
+// ... and of an env that does not: both rows are -1.
+__device__ __forceinline__ void hier_no_goal(const FovealHier& h, int64_t row) {
+    if (h.goals_t) h.goals_t[row] = -1;
+    if (h.goal_key_t) h.goal_key_t[row] = -1;
+}
+// The action of an env whose state after the plannerStep is (lid, bx, by, fgx, fgy): controller key -> table -> mix with the
+// draw words r.x / r.y, and element `row` of the action and key rows.
+__device__ __forceinline__ int hier_act(const FovealHier& h, const uint8_t* lds_table, int lid, int bx, int by, int fgx, int fgy, int G,
+                                        int L, uint32_t rx, uint32_t ry, int64_t row) {
+    const int d = lmaze_hier_offset(fgx, fgy, bx, by);
+    const int kc = lmaze_hier_controller_key(h.controller_key, h.controller_key ? lmaze_hier_planner_key(lid, bx, by, G, L) : 0, d);
+    const int act = lmaze_hier_action(hier_table_byte((h.in_lds & kHierControllerStaged) != 0, lds_table, h.controller, kc), rx, ry, h.epsilon);
+    if (h.actions_t) h.actions_t[row] = act;
+    if (h.key_t) h.key_t[row] = kc;
+    return act;
+}
+// rec false: the row form, the recording members of ro unread (lmaze_foveal_launch.h launch_foveal_rollout_sliced)
+hipError_t launch_foveal_rollout_closed(const FovealArgs& a, const FovealRollObsHier& ro, bool rec, hipStream_t s);
 
 struct EnvRec {           // one env after its transition (registers only; phase 1 turns it into plane masks)
     int16_t cx, cy;       // centre of the current window (ball after the move)

@@ -1,5 +1,6 @@
 // lmaze_foveal_launch.h -- the one launcher of the foveal one-launch rollouts (host only).  lmaze_foveal.hip (open loop),
-// lmaze_foveal_policy.hip (epsilon-greedy closed loop) and lmaze_foveal_sample.hip (sampling closed loop) keep their kernels
+// lmaze_foveal_policy.hip (epsilon-greedy closed loop), lmaze_foveal_sample.hip (sampling closed loop) and
+// lmaze_hier_policy.hip (the two-level closed loop of v5/v6) keep their kernels
 // and describe themselves as a family F; everything a launch decides -- the LDS sum, the launch_hint bits, the default envs per
 // workgroup, the describe line -- is decided here, once.  A family is a struct of statics:
 //   kKernel            the kernel's name as the describe line prints it
@@ -8,7 +9,11 @@
 // and, where there is a table,
 //   table_bytes<VARIANT>(p), staged_lds(base, table)
 //                      the table's size, and foveal_lds with a staged table added the way the family's kernels lay it out
-//   table(ro)          the FovealPol / FovealSmp of a family's RO, whose in_lds the launcher sets
+//   table(ro)          the FovealPol / FovealSmp / FovealHier of a family's RO, whose in_lds the launcher sets
+// or, a family of two tables (kTables == 2; its kernel has one mode, which the describe line does not name),
+//   place<VARIANT>(p, ro, lds), suffix(staged)
+//                      which of its tables are staged (the bits of in_lds), their bytes added to lds the way the family's
+//                      kernels lay them out; and the describe line's suffix for those bits
 // and in every family
 //   exists<VARIANT, EPB, GT, AR, REC>()
 //                      the instantiations the family has; no other kernel is instantiated, and a call for one that does not
@@ -24,6 +29,14 @@
 #include "lmaze_foveal_defs.h"
 
 namespace lmaze {
+
+// tables a family stages by a placement of its own: 2 where it says so (kTables), else its one table or none
+template <class F, class = void>
+struct family_tables_of { static constexpr int value = F::kTableLds > 0 ? 1 : 0; };
+template <class F>
+struct family_tables_of<F, std::void_t<decltype(F::kTables)>> { static constexpr int value = F::kTables; };
+template <class F>
+constexpr int family_tables() { return family_tables_of<F>::value; }
 
 template <class F, int VARIANT, int EPB, int GT, bool AR, class RO>
 static hipError_t queue_foveal_rollout(dim3 grid, dim3 block, size_t lds, hipStream_t s, const FovealArgs& a, const RO& ro) {
@@ -42,10 +55,12 @@ template <class F, int VARIANT, int EPB, class RO>
 static hipError_t launch_foveal_rollout_one(const FovealArgs& a, const RO& ro0, hipStream_t s) {
     constexpr bool REC = std::is_base_of<FovealRollObs, RO>::value;
     size_t lds0 = foveal_lds<VARIANT>(a.p, EPB);
-    bool staged = false;
-    if constexpr (F::kTableLds > 0) {
+    int staged = 0;
+    if constexpr (family_tables<F>() == 2) {
+        staged = F::template place<VARIANT>(a.p, ro0, lds0);   // a rule, not a measurement
+    } else if constexpr (F::kTableLds > 0) {
         const size_t table = F::template table_bytes<VARIANT>(a.p);
-        staged = table <= (size_t)F::kTableLds;                // a rule, not a measurement
+        staged = table <= (size_t)F::kTableLds ? 1 : 0;        // a rule, not a measurement
         if (staged) lds0 = F::staged_lds(lds0, table);
     }
     // envs per workgroup is a performance knob: a size whose LDS (the staged table included) does not fit the device falls
@@ -62,14 +77,18 @@ static hipError_t launch_foveal_rollout_one(const FovealArgs& a, const RO& ro0, 
     FovealArgs b = a;
     b.nt = 0;                 // plain stores: a chunk's observation is rewritten every step, the lines stay in L2
     RO ro = ro0;
-    if constexpr (F::kTableLds > 0) F::table(ro).in_lds = staged ? 1 : 0;
+    if constexpr (F::kTableLds > 0) F::table(ro).in_lds = staged;
     constexpr int GN = VARIANT == LMAZE_VARIANT_V1 ? 14 : 18;
     const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
     if (a.info) {
         char name[96];
-        snprintf(name, sizeof(name), "%s<v%d, %d, %d, %s%s>%s", F::kKernel, VARIANT, EPB, a.p.grid == GN ? GN : 0,
-                 a.auto_reset ? (VARIANT == LMAZE_VARIANT_V5 ? "two-level" : "fused-reset") : "plain", REC ? ", obs_t" : "",
-                 F::kTableLds > 0 ? (staged ? " table=lds" : " table=global") : "");
+        if constexpr (family_tables<F>() == 2)
+            snprintf(name, sizeof(name), "%s<v%d, %d, %d%s>%s", F::kKernel, VARIANT, EPB, a.p.grid == GN ? GN : 0, REC ? ", obs_t" : "",
+                     F::suffix(staged));
+        else
+            snprintf(name, sizeof(name), "%s<v%d, %d, %d, %s%s>%s", F::kKernel, VARIANT, EPB, a.p.grid == GN ? GN : 0,
+                     a.auto_reset ? (VARIANT == LMAZE_VARIANT_V5 ? "two-level" : "fused-reset") : "plain", REC ? ", obs_t" : "",
+                     F::kTableLds > 0 ? (staged ? " table=lds" : " table=global") : "");
         describe_launch(a.info, name, EPB, lds > lds0 ? per_cu : 0, m, false, blocks, LMAZE_BLOCK, lds);
         return hipSuccess;
     }
@@ -84,8 +103,10 @@ static hipError_t launch_foveal_rollout_one(const FovealArgs& a, const RO& ro0, 
 // launch_hint bits 4-7: envs per workgroup, 2: 32, 3: 64, 4: 128; any other code takes the default below
 template <class F, int VARIANT, class RO>
 static hipError_t launch_foveal_rollout_variant(const FovealArgs& a, const RO& ro, hipStream_t s) {
-    // v5/v6 at grids other than 18 exist at 32 envs per workgroup only (lmaze_foveal.hip FovealOpen::exists)
-    if (VARIANT == LMAZE_VARIANT_V5 && a.p.grid != 18) return launch_foveal_rollout_one<F, VARIANT, 32>(a, ro, s);
+    // v5/v6 at grids other than 18 exist at 32 envs per workgroup only (lmaze_foveal.hip FovealOpen::exists), in a family
+    // that has no larger form there
+    if (VARIANT == LMAZE_VARIANT_V5 && a.p.grid != 18 && !F::template exists<LMAZE_VARIANT_V5, 64, 0, true, false>())
+        return launch_foveal_rollout_one<F, VARIANT, 32>(a, ro, s);
     switch ((a.p.launch_hint >> 4) & 15) {
         case 2: return launch_foveal_rollout_one<F, VARIANT, 32>(a, ro, s);
         case 3: return launch_foveal_rollout_one<F, VARIANT, 64>(a, ro, s);
@@ -112,7 +133,8 @@ static hipError_t launch_foveal_rollout(const FovealArgs& a, const RO& ro, hipSt
         case LMAZE_VARIANT_V2: return launch_foveal_rollout_variant<F, LMAZE_VARIANT_V2>(a, ro, s);
         case LMAZE_VARIANT_V4: return launch_foveal_rollout_variant<F, LMAZE_VARIANT_V4>(a, ro, s);
         default:
-            // v5/v6: the open loop's two-level step; the closed loops have none, and their entry refuses the variants
+            // v5/v6: the two-level step of the open loop and of lmaze_hier_policy.hip; the other closed loops have none, and
+            // their entry refuses the variants
             if constexpr (F::template exists<LMAZE_VARIANT_V5, 32, 18, true, false>()) return launch_foveal_rollout_variant<F, LMAZE_VARIANT_V5>(a, ro, s);
             else return hipErrorInvalidValue;
     }

@@ -331,6 +331,75 @@ class LmazeFovealVecEnv(VecEnvBase):
         return self._closed_loop("rollout_sample()", "lmaze_foveal_rollout_sample", call, T, k, obs_t, trajectory, actions_t, key_t,
                                  streams=2 if self.variant == "v1" else 1)
 
+    def rollout_hier_policy(self, T, controller=None, controller_q=None, planner=None, planner_q=None, epsilon=0.0,
+                            planner_epsilon=0.0, controller_key="offset", trajectory=False, actions_t=None, key_t=None,
+                            goals_t=None, goal_key_t=None, obs_t=None, obs_local_t=None, obs_every=None):
+        """v5/v6: T two-level steps (hier_step) in ONE launch with BOTH policies inside the kernel (include/lmaze.h
+        lmaze_v5_rollout_policy): a planner table picks the foveal goal of the envs that enter a step done or locally done,
+        a controller table the action of every env; no action or goal tensors, no per-step launches.
+        planner         uint8 device tensor of L*G*G entries: the goal id (0..24; above: the plannerStep is skipped) of every
+                        planner key = state_keys();  planner_q instead: a float tensor [L*G*G, 25], reduced by greedy_table()
+        controller      uint8 device tensor, the action id (0..3; above: no move) of every controller key = controller_keys():
+                        100 entries for controller_key="offset" (the foveal goal's offset from the ball), 100*L*G*G for "cell"
+                        (planner key * 100 + offset);  controller_q instead: a float tensor [keys, 4]
+        epsilon, planner_epsilon   exploration rates in [0, 1] of the controller (a uniform action 0..3) and of the planner
+                        (a uniform goal 0..24), both from one Philox draw per (seed, env, epoch); nothing is drawn when both are 0
+        Returns what rollout(actions, goals=) returns -- the final (obs, reward, done), with trajectory=True also reward,
+        done, foveal_reward, foveal_done rows -- and then, with trajectory=True, actions_t, key_t, goals_t, goal_key_t
+        int32[T,N] (the caller's, or allocated); goals_t / goal_key_t hold -1 where an env did not plan, which
+        table_stats() skips.  obs_every=k >= 1 records into obs_t and, optionally, obs_local_t as rollout() does.  The epoch
+        advances by T.  Not for v1/v2/v4 (rollout_policy() is theirs), nor under stream capture."""
+        if not self._two_level:
+            raise ValueError("rollout_hier_policy() is the two-level closed loop of v5/v6; v1/v2/v4 have rollout_policy()")
+        T = self._steps(T)
+        if (controller is None) == (controller_q is None):
+            raise ValueError("rollout_hier_policy() wants exactly one of controller= and controller_q=")
+        if (planner is None) == (planner_q is None):
+            raise ValueError("rollout_hier_policy() wants exactly one of planner= and planner_q=")
+        eps, peps = _abi.epsilon_u32(epsilon), _abi.epsilon_u32(planner_epsilon)
+        ck = _abi.controller_key_id(controller_key)
+        if ck not in (0, 1):
+            raise ValueError("controller_key must be 'offset' or 'cell'")
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("rollout_hier_policy() is not available with a device-resident epoch (under stream capture)")
+        cells, what = self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid)
+        for q, A, name in ((controller_q, 4, "controller_q"), (planner_q, _abi.FOVEA * _abi.FOVEA, "planner_q")):
+            if q is not None and not (isinstance(q, torch.Tensor) and q.dim() == 2 and q.shape[1] == A):
+                raise ValueError("%s must be a float tensor [keys, %d]" % (name, A))
+        controller = self._greedy_policy(controller, controller_q, 100 * cells if ck else 100, "controller_key=%r, %s" % (controller_key, what))
+        planner = self._greedy_policy(planner, planner_q, cells, what)
+        k = 0
+        if obs_every is not None:
+            k = self._obs_slots(T, obs_every, obs_t, self.obs)
+            if obs_local_t is not None:
+                self._obs_slots(T, obs_every, obs_local_t, self.obs_local, name="obs_local_t")
+        elif obs_t is not None or obs_local_t is not None:
+            raise ValueError("obs_t / obs_local_t need obs_every")
+
+        def call(rows, p_actions, p_key, slots, goal_rows):
+            return _abi.lib.lmaze_v5_rollout_policy(
+                self._pp, self._p_layouts, controller.data_ptr(), ck, eps, planner.data_ptr(), peps, T, self._pb, self.num_envs,
+                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key,
+                *goal_rows, slots, obs_local_t.data_ptr() if slots is not None and obs_local_t is not None else None, k,
+                self._stream())
+        return self._closed_loop("rollout_hier_policy()", "lmaze_v5_rollout_policy", call, T, k, obs_t, trajectory, actions_t, key_t,
+                                 streams=2, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
+
+    def controller_keys(self, controller_key="offset"):
+        """v5/v6, int32[N]: the controller key of every env's CURRENT state, by the rule the key_t rows of
+        rollout_hier_policy() are written with -- d = clamp(fgoal_x - ball_x + 4, 0, 9) * 10 + clamp(fgoal_y - ball_y + 4, 0, 9),
+        and for "cell" state_keys() * 100 + d.  Plain torch ops; state_keys() is the planner key."""
+        if not self._two_level:
+            raise ValueError("controller_keys() is the two-level controller's key: v5/v6 only")
+        ck = _abi.controller_key_id(controller_key)
+        if ck not in (0, 1):
+            raise ValueError("controller_key must be 'offset' or 'cell'")
+        o = (self.fgoal_xy.to(torch.int64) - self.ball_xy.to(torch.int64) + 4).clamp(0, 9)
+        d = o[:, 0] * 10 + o[:, 1]
+        if ck:
+            d = d + self.state_keys().to(torch.int64) * 100
+        return d.to(torch.int32).contiguous()
+
     def state_keys(self):
         """int32[N]: the key of every env's CURRENT state, by the rule the key_t rows of rollout_policy() are written with --
         layout row (clamped to 0..L-1; 0 for v1) * G*G + ball_x * G + ball_y, coordinates clamped onto the grid.  Right after

@@ -796,7 +796,7 @@ int lmaze_describe_foveal_rollout_obs(const LmazeFovealParams* params, int64_t n
  * 1 620 B for the five 18 x 18 layouts of v2/v4); above that it is read from global memory, one byte per env-step.  This is
  * a rule, not a measurement; lmaze_describe_foveal_rollout_policy reports it as table=lds / table=global.
  * v5/v6 are refused: their two-level step sits at 128 VGPRs and a closed loop there needs two tables (action and planner
- * goal).  No grid size is refused: every form exists for any G (v1's recording form at G != 14 runs at 4 waves per SIMD).
+ * goal) -- lmaze_v5_rollout_policy is that loop.  No grid size is refused: every form exists for any G (v1's recording form at G != 14 runs at 4 waves per SIMD).
  * Refused before anything is queued, in this order:
  *   1. the recording request: LMAZE_E_COUNT obs_every < 0, or obs_t given with obs_every == 0; LMAZE_E_NULL obs_t missing
  *      while T / obs_every > 0; LMAZE_E_ALIGN obs_t not 16-byte aligned;
@@ -865,6 +865,77 @@ int lmaze_foveal_rollout_sample(const LmazeFovealParams* params, const uint8_t* 
  * lines.  Nothing is queued or dereferenced. */
 int lmaze_describe_foveal_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset,
                                          int32_t obs_every, char* text_host, int32_t len);
+
+/*
+ * CLOSED-LOOP TWO-LEVEL rollout (v5, v6): lmaze_foveal_rollout / lmaze_foveal_rollout_obs over the two-level step
+ * (lmaze_v5_hier_step, v5:104-292) with BOTH policies inside the kernel -- a tabular epsilon-greedy planner that picks the
+ * foveal goal and a tabular epsilon-greedy controller that walks to it -- instead of pre-generated action and planner-goal
+ * tensors.  Replaces the user loop of T x (two gathers, two epsilon mixes, lmaze_v5_hier_step) by ONE launch; the selections
+ * themselves have no reference counterpart.  The arguments of lmaze_foveal_rollout_obs with `actions`, `planner_goals` and
+ * `auto_reset` replaced by
+ *   controller           uint8[100] (controller_key 0) or uint8[100 L G G] (controller_key 1): the greedy action id of every
+ *                        controller key, passed through unchanged; 0..3 as lmaze_foveal_step reads them, anything above 3 is
+ *                        no move
+ *   controller_key       0 "offset": the key is the foveal goal's offset from the ball; 1 "cell": planner key * 100 + offset,
+ *                        the controller's full Markov state.  A run-time argument, uniform over the launch
+ *   epsilon_u32          the controller's exploration rate, as in lmaze_rollout_policy
+ *   planner              uint8[L G G]: the greedy goal id of every planner key, passed through unchanged; 0..24 = 5 row + col
+ *                        of the goal in the window, anything above 24 skips the plannerStep (lmaze_v5_planner_step)
+ *   planner_epsilon_u32  the planner's exploration rate, likewise
+ * and, beside reward_t / done_t / foveal_reward_t / foveal_done_t (all nullable),
+ *   actions_t, key_t        int32[T,N], nullable: the action step t took and the controller key it was looked up with
+ *   goals_t, goal_key_t     int32[T,N], nullable: the goal and the planner key of the envs that took a plannerStep at step t,
+ *                           -1 in both where none was due -- table_stats skips those entries by construction
+ *   obs_t, obs_local_t, obs_every   obs_every == 0: no recording, both must be NULL; obs_every = k >= 1: the slots exactly
+ *                           as in lmaze_foveal_rollout_obs (obs_local_t nullable)
+ * Env i (global index e = env_base + i) at step t, ep = epoch + t, gd / ld its done / foveal_done ON ENTRY:
+ *   1. if epsilon_u32 | planner_epsilon_u32 is non-zero, r = the exploration draw of lmaze_rollout_policy, drawn once --
+ *      Philox4x32-10(counter (e_lo, e_hi, ep_lo, ep_hi ^ 0x80000000), key (seed_lo, seed_hi)); nothing is drawn when both
+ *      are 0;
+ *   2. gd: the reset of lmaze_v5_hier_step, same draw, epoch ep (v5:104-150);
+ *   3. gd | ld: the planner steps.  kp = lid * G^2 + bx * G + by of the state after that reset, lid clamped to 0..L-1, bx and
+ *      by to 0..G-1; g = planner[kp]; if planner_epsilon_u32 != 0 and r.z < planner_epsilon_u32, g = (r.w * 25) >> 32; then
+ *      plannerStep(g) as lmaze_v5_hier_step does it (v5:158-182) -- g > 24 skips it and the env goes on with its old goal.
+ *      goals_t[t,i] = g, goal_key_t[t,i] = kp; where no plannerStep was due both are -1;
+ *   4. the controller key, from the state after 3.: ox = clamp(fgoal_x - ball_x + 4, 0, 9), oy likewise, d = ox * 10 + oy (an
+ *      undisturbed env has the offset in -4..5; the clamp only matters after a skipped plannerStep or for a loaded state);
+ *      kc = d for controller_key 0 and kp' * 100 + d for controller_key 1, kp' the formula of 3. on the current state;
+ *   5. a = controller[kc]; if epsilon_u32 != 0 and r.x < epsilon_u32, a = r.y >> 30; then step(a) as lmaze_v5_hier_step does it
+ *      (v5:187-292), a > 3 is no move.  actions_t[t,i] = a, key_t[t,i] = kc, for every env;
+ *   6. reward and done rows of both streams, visit map, obs, obs_local and the recorded slots as in lmaze_foveal_rollout_obs.
+ * The caller advances its epoch by T.
+ * Each table of at most 8192 bytes is staged in LDS once per workgroup, behind the layout characters (the controller's first,
+ * then the planner's), its dwords requested beside the layout loads: the 100-byte offset table always, the planner table of
+ * the five 18 x 18 layouts (1 620 B) too; a larger one -- a cell-mode controller of those layouts is 162 000 B, a planner table
+ * of 16 layouts of 24 x 24 is 9 216 B -- is read from global memory, one byte per use.  This is a rule, not a measurement;
+ * lmaze_describe_v5_rollout_policy reports it as controller=lds|global planner=lds|global.
+ * No grid size is refused: the row and the recording form exist for any G, at 32, 64 and 128 envs per workgroup.
+ * Refused before anything is queued, in the order of lmaze_foveal_rollout_policy:
+ *   1. the recording request: LMAZE_E_COUNT obs_every < 0, or obs_t / obs_local_t given with obs_every == 0; LMAZE_E_NULL obs_t
+ *      missing while T / obs_every > 0; LMAZE_E_ALIGN obs_t or obs_local_t not 16-byte aligned;
+ *   2. the params' own: LMAZE_E_NULL params; LMAZE_E_VARIANT an unknown variant; LMAZE_E_GRID; LMAZE_E_LAYOUT n_layouts or
+ *      launch_hint;
+ *   3. LMAZE_E_VARIANT anything but v5/v6;
+ *   4. LMAZE_E_COUNT T < 0 or n outside [0, LMAZE_MAX_ENVS], then controller_key outside {0, 1};
+ *   5. T == 0 or n == 0 returns 0 with nothing read;
+ *   6. LMAZE_E_NULL a required pointer (layouts, bufs and its members as for lmaze_v5_hier_step, controller, planner), then
+ *      LMAZE_E_ALIGN as lmaze_foveal_step.
+ * lmaze_foveal_rollout_policy and lmaze_foveal_rollout_sample keep refusing v5/v6.
+ * launch_hint bits 0-3, 4-7 and 8-9 as in lmaze_foveal_rollout; they never change results.
+ */
+int lmaze_v5_rollout_policy(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* controller,
+                            int32_t controller_key, uint32_t epsilon_u32, const uint8_t* planner,
+                            uint32_t planner_epsilon_u32, int32_t T, const LmazeFovealBuffers* bufs, int64_t n, uint64_t seed,
+                            uint64_t epoch, int64_t env_base, float* reward_t, uint8_t* done_t, float* foveal_reward_t,
+                            uint8_t* foveal_done_t, int32_t* actions_t, int32_t* key_t, int32_t* goals_t, int32_t* goal_key_t,
+                            float* obs_t, float* obs_local_t, int32_t obs_every, void* stream);
+
+/* As lmaze_describe_foveal_rollout_policy, for lmaze_v5_rollout_policy with this controller_key and obs_every (0: no recording):
+ * "foveal_hier_policy_kernel<v5, 32, 18, obs_t> controller=lds planner=lds T=24 grid=...".  LMAZE_E_NULL text_host NULL or
+ * len < 1, then the entry point's refusals 1-4 in their order (obs_every > 0 stands for a given obs_t); an empty line for
+ * T == 0 or n == 0.  Nothing is queued or dereferenced. */
+int lmaze_describe_v5_rollout_policy(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t controller_key,
+                                     int32_t obs_every, char* text_host, int32_t len);
 
 /*
  * v6 safeFovealGoal() (v6:505-523): for every env one window cell index 0..24 drawn uniformly from the
