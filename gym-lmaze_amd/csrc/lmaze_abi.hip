@@ -20,20 +20,55 @@ static int check_params(const LmazeParams* p, int64_t n) {
 
 static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
-static StepArgs make_args(const LmazeParams* p, const uint8_t* layout, const int32_t* action, int32_t* ball_xy,
-                          const int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
-                          int32_t* goal_count, int32_t* obs, int64_t n) {
+// The variants a grid entry takes
+enum { TAKES_V0 = 1, TAKES_V3 = 2, TAKES_BOTH = 3 };
+
+// The narrow (uint8) planes: shared layouts and G >= 4 only
+static int check_narrow(const LmazeParams* p) {
+    if (p->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
+    if (p->grid < 4) return LMAZE_E_GRID;                  // a 16-byte store must not span more than two envs
+    return 0;
+}
+
+// What every grid step and rollout entry judges first, in this order: the params, the variant against what the entry takes
+// and, with u8, the narrow planes' own refusals
+static int check_grid_params(const LmazeParams* p, int64_t n, int takes, bool u8) {
+    const int rc = check_params(p, n);
+    if (rc) return rc;
+    if (!(p->variant == LMAZE_VARIANT_V0 && (takes & TAKES_V0)) && !(p->variant == LMAZE_VARIANT_V3 && (takes & TAKES_V3)))
+        return LMAZE_E_VARIANT;
+    return u8 ? check_narrow(p) : 0;
+}
+
+// ... and last, the buffers: LMAZE_E_NULL for the layout, ball_xy, goal_xy under v3's rules and the others the entry needs
+// (`others`: false if one of them is missing), then LMAZE_E_ALIGN -- ball_xy / goal_xy 8 bytes, the planes 16, the layout 16
+// unless the planes are narrow (those kernels read it by bytes), and a closed-loop rollout's table as it says
+static int check_buffers(const LmazeParams* p, bool u8, const void* layout, const void* ball_xy, const void* goal_xy, const void* obs,
+                         bool others, const void* table = nullptr, uintptr_t table_align = 1) {
+    if (!layout || !ball_xy || !others || (p->variant == LMAZE_VARIANT_V3 && !goal_xy)) return LMAZE_E_NULL;
+    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16)) ||
+        misaligned(table, table_align))
+        return LMAZE_E_ALIGN;
+    return 0;
+}
+
+// The StepArgs of a grid step or rollout: obs the int32 planes, or with u8 the narrow ones (a.obs8).  v0 keeps no goal_xy,
+// v3 no goal_count.
+static StepArgs grid_args(const LmazeParams* p, const uint8_t* layout, const int32_t* action, int32_t* ball_xy, int32_t* goal_xy,
+                          int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8, int64_t n,
+                          int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base) {
+    const bool v3 = p->variant == LMAZE_VARIANT_V3;
     StepArgs a;
     a.layout = layout;
     a.action = action;
     a.ball = reinterpret_cast<int2*>(ball_xy);
-    a.goal = reinterpret_cast<const int2*>(goal_xy);
+    a.goal = v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr;
     a.step_count = step_count;
     a.reward = reward;
     a.done = done;
-    a.goal_count = goal_count;
-    a.obs = obs;
-    a.obs8 = nullptr;
+    a.goal_count = v3 ? nullptr : goal_count;
+    a.obs = u8 ? nullptr : static_cast<int32_t*>(obs);
+    a.obs8 = u8 ? static_cast<uint8_t*>(obs) : nullptr;
     a.n = n;
     a.grid = p->grid;
     a.step_limit = p->step_limit;
@@ -41,17 +76,49 @@ static StepArgs make_args(const LmazeParams* p, const uint8_t* layout, const int
     a.reward_move = p->reward_move;
     a.reward_goal = p->reward_goal;
     a.envs_per_block = 0;
-    a.auto_reset = 0;
-    a.seed = 0;
-    a.epoch = 0;
-    a.env_base = 0;
+    a.auto_reset = auto_reset ? 1 : 0;
+    a.seed = seed;
+    a.epoch = epoch;
+    a.env_base = env_base;
     a.epoch_in = nullptr;
     a.epoch_out = nullptr;
-    a.goal_rw = nullptr;
+    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
     a.mask = nullptr;
     a.launch_hint = p->launch_hint;
     a.info = nullptr;
     return a;
+}
+
+// The fused reset of the *_autoreset entries and lmaze_step_u8, and the device-resident epoch words
+struct FusedReset {
+    int32_t auto_reset;
+    uint64_t seed, epoch;
+    int64_t env_base;
+    const uint64_t* epoch_in;
+    uint64_t* epoch_out;
+};
+
+// Every grid step / observe entry and the render of lmaze_reset.  takes: the variants the entry accepts; do_step: a step
+// (action, step_count, reward and done required) or a render of the planes only (obs required, mask: just these envs); u8:
+// obs is the narrow planes; fr: the entry has a fused reset.  The refusals stand in this order: params, variant, the narrow
+// planes' own, LMAZE_E_NULL, LMAZE_E_ALIGN for the buffers and then the epoch words; n == 0 returns 0 after all of them.
+static int grid_step(const LmazeParams* params, int takes, bool do_step, bool u8, const uint8_t* layout, const int32_t* action,
+                     int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count,
+                     void* obs, const uint8_t* mask, const FusedReset* fr, int64_t n, void* stream) {
+    int rc = check_grid_params(params, n, takes, u8);
+    if (rc) return rc;
+    rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, do_step ? action && step_count && reward && done : obs != nullptr);
+    if (rc) return rc;
+    if (fr && bad_epoch_words(fr->epoch_in, fr->epoch_out)) return LMAZE_E_ALIGN;
+    const FusedReset none{0, 0, 0, 0, nullptr, nullptr};
+    const FusedReset& r = fr ? *fr : none;
+    StepArgs a = grid_args(params, layout, action, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, r.auto_reset,
+                           r.seed, r.epoch, r.env_base);
+    if (!fr) a.goal_rw = nullptr;                          // only a fused reset writes goals
+    a.epoch_in = r.epoch_in;
+    a.epoch_out = r.epoch_out;
+    a.mask = mask;
+    return (int)launch_step(params->variant, do_step, a, params->layout_mode, u8, (hipStream_t)stream);
 }
 
 namespace lmaze {
@@ -89,40 +156,20 @@ static RolloutRec recording(int32_t T, void* slots, int32_t every) {
     return RolloutRec{every > 0 && T / every > 0 ? slots : nullptr, every};
 }
 
-// The StepArgs of a grid rollout: obs the int32 planes, or with u8 the narrow ones (a.obs8)
-static StepArgs rollout_args(const LmazeParams* p, const uint8_t* layout, const int32_t* actions, int32_t* ball_xy, int32_t* goal_xy,
-                             int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8, int64_t n,
-                             int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base) {
-    const bool v3 = p->variant == LMAZE_VARIANT_V3;
-    StepArgs a = make_args(p, layout, actions, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count,
-                           u8 ? nullptr : static_cast<int32_t*>(obs), n);
-    a.obs8 = u8 ? static_cast<uint8_t*>(obs) : nullptr;
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
-    return a;
-}
-
 // lmaze_rollout and its three siblings after the recording request's own checks: T == 0 or n == 0 answered once the
 // params are valid, before any pointer is looked at; u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only
 static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                         int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8,
                         float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                         int64_t env_base, const RolloutRec* rec, void* stream) {
-    int rc = check_params(params, n);
+    int rc = check_grid_params(params, n, TAKES_BOTH, u8);
     if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-    if (u8 && params->grid < 4) return LMAZE_E_GRID;       // a 16-byte store must not span more than two envs
     if (T < 0) return LMAZE_E_COUNT;
     if (T == 0 || n == 0) return 0;                        // nothing to do, nothing read
-    if (!layout || !actions || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16))) return LMAZE_E_ALIGN;
-    const StepArgs a = rollout_args(params, layout, actions, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n,
-                                    auto_reset, seed, epoch, env_base);
+    rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, actions && step_count && reward && done);
+    if (rc) return rc;
+    const StepArgs a = grid_args(params, layout, actions, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n,
+                                 auto_reset, seed, epoch, env_base);
     return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
 }
 
@@ -134,21 +181,15 @@ static int check_closed_loop(const LmazeParams* params, const uint8_t* layout, c
                              int32_t key_mode, int32_t T, const int32_t* ball_xy, const int32_t* goal_xy, const int32_t* step_count,
                              const float* reward, const uint8_t* done, const void* obs, bool u8, int64_t n, bool describing, bool* go) {
     *go = false;
-    int rc = check_params(params, n);
+    int rc = check_grid_params(params, n, TAKES_BOTH, u8);
     if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-    if (u8 && params->grid < 4) return LMAZE_E_GRID;
     if (T < 0) return LMAZE_E_COUNT;
     if (key_mode != 0 && key_mode != 1) return LMAZE_E_COUNT;
-    if (key_mode == 1 && !v3) return LMAZE_E_VARIANT;              // v0 keeps no goal_xy
+    if (key_mode == 1 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;   // v0 keeps no goal_xy
     if (T == 0 || n == 0) return 0;                                // nothing to do, nothing read
     if (!describing) {
-        if (!layout || !table || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-        if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || (!u8 && misaligned(layout, 16)) ||
-            misaligned(table, table_align))
-            return LMAZE_E_ALIGN;
+        rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, table && step_count && reward && done, table, table_align);
+        if (rc) return rc;
     }
     *go = true;
     return 0;
@@ -168,8 +209,8 @@ static int grid_rollout_closed(const LmazeParams* params, const uint8_t* layout,
     rc = check_closed_loop(params, layout, tab.table, sizeof(*tab.table), tab.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs,
                            u8, n, info != nullptr, &go);
     if (!go) return rc;
-    StepArgs a = rollout_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
-                              seed, epoch, env_base);
+    StepArgs a = grid_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
+                           seed, epoch, env_base);
     a.info = info;
     return (int)launch_rollout_closed(params->variant, a, params->layout_mode, tab, T, reward_t, done_t, (hipStream_t)stream,
                                       recording(T, slots, every), u8);
@@ -343,29 +384,21 @@ int lmaze_device_info(int device, int32_t* cu_count_host, char* name_host, int32
 
 int lmaze_describe_step(const LmazeParams* params, int64_t n, int32_t auto_reset, int32_t with_obs, char* text_host,
                         int32_t len) {
-    int rc = check_params(params, n);
+    int rc = check_grid_params(params, n, TAKES_BOTH, false);
     if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V0 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
     if (!text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
     if (n == 0) return 0;
+    const bool u8 = with_obs == 2;   // the narrow-observation step (lmaze_step_u8)
+    if (u8 && (rc = check_narrow(params)) != 0) return rc;
     LaunchInfo info;
     memset(&info, 0, sizeof(info));
-    // nothing is dereferenced: the launcher fills `info` where it would have queued the kernel
-    StepArgs a = make_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           with_obs ? reinterpret_cast<int32_t*>(16) : nullptr, n);
-    a.auto_reset = auto_reset ? 1 : 0;
+    // nothing is dereferenced: the launcher fills `info` where it would have queued the kernel (a fabricated, aligned
+    // address stands for the planes, whose presence decides)
+    StepArgs a = grid_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           with_obs ? reinterpret_cast<void*>(16) : nullptr, u8, n, auto_reset, 0, 0, 0);
     a.info = &info;
-    if (with_obs == 2) {             // the narrow-observation step (lmaze_step_u8)
-        if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-        if (params->grid < 4) return LMAZE_E_GRID;
-        a.obs = nullptr;
-        a.obs8 = reinterpret_cast<uint8_t*>(16);
-        rc = (int)launch_step_u8(params->variant, true, a, nullptr);
-        if (rc) return rc;
-        return format_launch(info, text_host, len);
-    }
-    rc = (int)launch_step(params->variant, true, a, params->layout_mode, nullptr);
+    rc = (int)launch_step(params->variant, true, a, params->layout_mode, u8, nullptr);
     if (rc) return rc;
     return format_launch(info, text_host, len);
 }
@@ -373,88 +406,54 @@ int lmaze_describe_step(const LmazeParams* params, int64_t n, int32_t auto_reset
 int lmaze_step_v0(const LmazeParams* params, const uint8_t* layout, const int32_t* action, int32_t* ball_xy,
                   int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
                   int64_t n, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V0) return LMAZE_E_VARIANT;
-    if (!layout || !action || !ball_xy || !step_count || !reward || !done) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, action, ball_xy, nullptr, step_count, reward, done, goal_count, obs, n);
-    return (int)launch_step(LMAZE_VARIANT_V0, true, a, params->layout_mode, (hipStream_t)stream);
+    return grid_step(params, TAKES_V0, true, false, layout, action, ball_xy, nullptr, step_count, reward, done, goal_count, obs, nullptr,
+                     nullptr, n, stream);
 }
 
 int lmaze_step_v3(const LmazeParams* params, const uint8_t* layout, const int32_t* action, int32_t* ball_xy,
                   const int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* obs,
                   int64_t n, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
-    if (!layout || !action || !ball_xy || !goal_xy || !step_count || !reward || !done) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16))
-        return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, action, ball_xy, goal_xy, step_count, reward, done, nullptr, obs, n);
-    return (int)launch_step(LMAZE_VARIANT_V3, true, a, params->layout_mode, (hipStream_t)stream);
+    return grid_step(params, TAKES_V3, true, false, layout, action, ball_xy, const_cast<int32_t*>(goal_xy), step_count, reward, done,
+                     nullptr, obs, nullptr, nullptr, n, stream);
 }
 
 int lmaze_step_v0_autoreset(const LmazeParams* params, const uint8_t* layout, const int32_t* action,
                             int32_t* ball_xy, int32_t* step_count, float* reward, uint8_t* done,
                             int32_t* goal_count, int32_t* obs, int64_t n, uint64_t seed, uint64_t epoch,
                             int64_t env_base, const uint64_t* epoch_in_dev, uint64_t* epoch_out_dev, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V0) return LMAZE_E_VARIANT;
-    if (!layout || !action || !ball_xy || !step_count || !reward || !done) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, action, ball_xy, nullptr, step_count, reward, done, goal_count, obs, n);
-    if (bad_epoch_words(epoch_in_dev, epoch_out_dev)) return LMAZE_E_ALIGN;
-    a.auto_reset = 1;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.epoch_in = epoch_in_dev;
-    a.epoch_out = epoch_out_dev;
-    return (int)launch_step(LMAZE_VARIANT_V0, true, a, params->layout_mode, (hipStream_t)stream);
+    const FusedReset fr{1, seed, epoch, env_base, epoch_in_dev, epoch_out_dev};
+    return grid_step(params, TAKES_V0, true, false, layout, action, ball_xy, nullptr, step_count, reward, done, goal_count, obs, nullptr,
+                     &fr, n, stream);
+}
+
+int lmaze_step_v3_autoreset(const LmazeParams* params, const uint8_t* layout, const int32_t* action,
+                            int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                            uint8_t* done, int32_t* obs, int64_t n, uint64_t seed, uint64_t epoch,
+                            int64_t env_base, const uint64_t* epoch_in_dev, uint64_t* epoch_out_dev, void* stream) {
+    const FusedReset fr{1, seed, epoch, env_base, epoch_in_dev, epoch_out_dev};
+    return grid_step(params, TAKES_V3, true, false, layout, action, ball_xy, goal_xy, step_count, reward, done, nullptr, obs, nullptr,
+                     &fr, n, stream);
 }
 
 int lmaze_step_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* action, int32_t* ball_xy, int32_t* goal_xy,
                   int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8, int64_t n,
                   int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, const uint64_t* epoch_in_dev,
                   uint64_t* epoch_out_dev, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-    if (params->grid < 4) return LMAZE_E_GRID;        // a 16-byte store must not span more than two envs
-    if (!layout || !action || !ball_xy || !step_count || !reward || !done || (v3 && !goal_xy)) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs8, 16)) return LMAZE_E_ALIGN;
-    if (bad_epoch_words(epoch_in_dev, epoch_out_dev)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, action, ball_xy, v3 ? goal_xy : nullptr, step_count, reward, done, v3 ? nullptr : goal_count, nullptr, n);
-    a.obs8 = obs8;
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.epoch_in = epoch_in_dev;
-    a.epoch_out = epoch_out_dev;
-    a.goal_rw = v3 ? reinterpret_cast<int2*>(goal_xy) : nullptr;
-    return (int)launch_step_u8(params->variant, true, a, (hipStream_t)stream);
+    const FusedReset fr{auto_reset, seed, epoch, env_base, epoch_in_dev, epoch_out_dev};
+    return grid_step(params, TAKES_BOTH, true, true, layout, action, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, nullptr,
+                     &fr, n, stream);
+}
+
+int lmaze_observe(const LmazeParams* params, const uint8_t* layout, const int32_t* ball_xy,
+                  const int32_t* goal_xy, int32_t* obs, int64_t n, void* stream) {
+    return grid_step(params, TAKES_BOTH, false, false, layout, nullptr, const_cast<int32_t*>(ball_xy), const_cast<int32_t*>(goal_xy),
+                     nullptr, nullptr, nullptr, nullptr, obs, nullptr, nullptr, n, stream);
 }
 
 int lmaze_observe_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* ball_xy, const int32_t* goal_xy,
                      const uint8_t* mask, uint8_t* obs8, int64_t n, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (params->variant != LMAZE_VARIANT_V0 && !v3) return LMAZE_E_VARIANT;
-    if (params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-    if (params->grid < 4) return LMAZE_E_GRID;
-    if (!layout || !ball_xy || !obs8 || (v3 && !goal_xy)) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs8, 16)) return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, nullptr, const_cast<int32_t*>(ball_xy), v3 ? goal_xy : nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, n);
-    a.obs8 = obs8;
-    a.mask = mask;
-    return (int)launch_step_u8(params->variant, false, a, (hipStream_t)stream);
+    return grid_step(params, TAKES_BOTH, false, true, layout, nullptr, const_cast<int32_t*>(ball_xy), const_cast<int32_t*>(goal_xy),
+                     nullptr, nullptr, nullptr, nullptr, obs8, mask, nullptr, n, stream);
 }
 
 int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
@@ -651,22 +650,20 @@ int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* t
 
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
                            char* text_host, int32_t len) {
-    int rc = check_params(params, n);
+    int rc = check_grid_params(params, n, TAKES_BOTH, false);
     if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V0 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
     if (T < 0) return LMAZE_E_COUNT;
     if (!text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
     if (n == 0 || T == 0) return 0;
     const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8)
-    if (u8 && params->layout_mode != LMAZE_LAYOUT_SHARED) return LMAZE_E_LAYOUT;
-    if (u8 && params->grid < 4) return LMAZE_E_GRID;
+    if (u8 && (rc = check_narrow(params)) != 0) return rc;
     LaunchInfo info;
     memset(&info, 0, sizeof(info));
     // nothing is dereferenced: the launcher fills `info` where it would have queued the rollout (fabricated, aligned
     // addresses stand for the buffers whose presence decides)
-    StepArgs a = rollout_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, n, auto_reset, 0, 0, 0);
+    StepArgs a = grid_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, n, auto_reset, 0, 0, 0);
     a.info = &info;
     const RolloutRec rec = recording(T, reinterpret_cast<void*>(32), obs_every);
     rc = (int)launch_rollout(params->variant, a, params->layout_mode, nullptr, T, nullptr, nullptr, nullptr,
@@ -675,52 +672,13 @@ int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int3
     return format_launch(info, text_host, len);
 }
 
-int lmaze_step_v3_autoreset(const LmazeParams* params, const uint8_t* layout, const int32_t* action,
-                            int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
-                            uint8_t* done, int32_t* obs, int64_t n, uint64_t seed, uint64_t epoch,
-                            int64_t env_base, const uint64_t* epoch_in_dev, uint64_t* epoch_out_dev, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
-    if (!layout || !action || !ball_xy || !goal_xy || !step_count || !reward || !done) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16))
-        return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, action, ball_xy, goal_xy, step_count, reward, done, nullptr, obs, n);
-    if (bad_epoch_words(epoch_in_dev, epoch_out_dev)) return LMAZE_E_ALIGN;
-    a.auto_reset = 1;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.epoch_in = epoch_in_dev;
-    a.epoch_out = epoch_out_dev;
-    a.goal_rw = reinterpret_cast<int2*>(goal_xy);
-    return (int)launch_step(LMAZE_VARIANT_V3, true, a, params->layout_mode, (hipStream_t)stream);
-}
-
-int lmaze_observe(const LmazeParams* params, const uint8_t* layout, const int32_t* ball_xy,
-                  const int32_t* goal_xy, int32_t* obs, int64_t n, void* stream) {
-    int rc = check_params(params, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V0 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
-    if (!layout || !ball_xy || !obs) return LMAZE_E_NULL;
-    if (params->variant == LMAZE_VARIANT_V3 && !goal_xy) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16))
-        return LMAZE_E_ALIGN;
-    StepArgs a = make_args(params, layout, nullptr, const_cast<int32_t*>(ball_xy), goal_xy, nullptr, nullptr,
-                           nullptr, nullptr, obs, n);
-    return (int)launch_step(params->variant, false, a, params->layout_mode, (hipStream_t)stream);
-}
-
 int lmaze_reset(const LmazeParams* params, const uint8_t* layout, const uint8_t* mask, uint64_t seed,
                 uint64_t epoch, int64_t env_base, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
                 uint8_t* done, int32_t* obs, int64_t n, void* stream) {
-    int rc = check_params(params, n);
+    int rc = check_grid_params(params, n, TAKES_BOTH, false);
     if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V0 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
-    if (!layout || !ball_xy || !step_count || !reward || !done) return LMAZE_E_NULL;
-    if (params->variant == LMAZE_VARIANT_V3 && !goal_xy) return LMAZE_E_NULL;
-    if (misaligned(ball_xy, 8) || misaligned(goal_xy, 8) || misaligned(obs, 16) || misaligned(layout, 16))
-        return LMAZE_E_ALIGN;
+    rc = check_buffers(params, false, layout, ball_xy, goal_xy, obs, step_count && reward && done);
+    if (rc) return rc;
     ResetArgs r;
     r.layout = layout;
     r.mask = mask;
@@ -736,9 +694,9 @@ int lmaze_reset(const LmazeParams* params, const uint8_t* layout, const uint8_t*
     r.grid = params->grid;
     hipError_t e = launch_reset(params->variant, r, params->layout_mode, (hipStream_t)stream);
     if (e != hipSuccess || !obs) return (int)e;
-    StepArgs a = make_args(params, layout, nullptr, ball_xy, goal_xy, nullptr, nullptr, nullptr, nullptr, obs, n);
-    a.mask = mask;  // only the envs that were reset are re-rendered
-    return (int)launch_step(params->variant, false, a, params->layout_mode, (hipStream_t)stream);
+    // only the envs that were reset are re-rendered
+    return grid_step(params, TAKES_BOTH, false, false, layout, nullptr, ball_xy, goal_xy, nullptr, nullptr, nullptr, nullptr, obs, mask,
+                     nullptr, n, stream);
 }
 
 int lmaze_episode_stats(const uint8_t* done, const float* reward, const int32_t* step_count,

@@ -106,8 +106,8 @@ inline bool bad_epoch_words(const uint64_t* in, const uint64_t* out) {
 // so an over-large env count is refused with hipErrorInvalidConfiguration instead of wrapping the grid.
 inline bool grid_ok(int64_t blocks) { return blocks >= 1 && blocks <= (int64_t)0xFFFFFF; }
 
-hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s);
-hipError_t launch_step_u8(int variant, bool do_step, const StepArgs& a, hipStream_t s);
+// One step (do_step) or one render of the planes only.  u8: the narrow planes in a.obs8 (shared layouts, G >= 4) instead of a.obs.
+hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, bool u8, hipStream_t s);
 // T steps of a grid rollout (lmaze_rollout and its siblings).  rec: the recording request (lmaze_rollout_obs /
 // lmaze_rollout_obs_u8) -- obs_t the slots, int32[T / every, N, G, G] (u8: uint8, slots that may start at any byte past
 // slot 0), null when every == 0 or T / every == 0; every = k >= 1, or 0 for the final planes only.  A null RolloutRec* is

@@ -226,7 +226,7 @@ static hipError_t launch_foveal_one(const FovealArgs& a, hipStream_t s) {
     b.nt = (size_t)a.n * C * W25 * 4 > kFovealStreamBytes;
     if (LMAZE_XP(a, 2)) b.nt = 0;
     // launch_hint bits 0-3: at most that many workgroups resident per CU, by padding the dynamic LDS (160 KiB per
-    // CU), as the step kernel does in its streaming regime (lmaze_step.hip launch_shared); 0 = no cap
+    // CU), as the step kernel does in its streaming regime (lmaze_step.hip step_plan); 0 = no cap
     const int per_cu = a.p.launch_hint & 15;
     if (MODE == FM_STEP) lds = lds_for_cap(lds, per_cu);
     const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);

@@ -1312,6 +1312,33 @@ static size_t lds_for_workgroups_per_cu(int k) {
     return ((cap / k + cap / (k + 1)) / 2) & ~(size_t)255;
 }
 
+// The instantiations of the shared-layout step kernel, X(grid side, selector, envs per workgroup): per grid side the kernel is
+// specialised for -- the reference's shipped sizes (12, 14, 18) and BASELINE.json's (8, 11, 32); any other G in [3, 64] takes the
+// generic instantiation, side 0 -- the workgroup sizes that launch_hint bits 10-11 = 1 / 2 / 3 name.  About 32 KiB of observation
+// per workgroup (8 sixteen-byte stores per lane) was the starting point: measured at G=11 on MI355X (tools/kbench.hip), 64 envs
+// (31 KiB) 90-91 us per 1M-env step, 128/256 envs 96-101 us, 32 envs 120 us; the smaller sizes are step_default_sel's.
+// The one list behind kSharedSizes (what step_plan chooses from), step_kernel (what is compiled; the per-env LDS kernel takes
+// its grid sides from here too) and specialised_grid.
+#define LMAZE_SHARED_SIZES(X)                      \
+    X(8, 1, 128) X(8, 2, 64)                       \
+    X(11, 1, 64) X(11, 2, 32) X(11, 3, 16)         \
+    X(12, 1, 64) X(12, 2, 32) X(12, 3, 16)         \
+    X(14, 1, 32) X(14, 2, 16)                      \
+    X(18, 1, 32) X(18, 2, 16)                      \
+    X(32, 1, 8) X(32, 2, 4)                        \
+    X(0, 1, 256) X(0, 2, 64) X(0, 3, 16) /* three sizes cover [3, 64] */
+static const struct { int gt, sel, epb; } kSharedSizes[] = {
+#define X(GT, SEL, EPB) {GT, SEL, EPB},
+    LMAZE_SHARED_SIZES(X)
+#undef X
+};
+
+static bool specialised_grid(int g) {
+#define X(GT, SEL, EPB) || (GT != 0 && g == GT)
+    return false LMAZE_SHARED_SIZES(X);
+#undef X
+}
+
 // Launch policy of the streaming (non-temporal) regime, measured on MI355X with
 // tools/kbench.hip (one process, interleaved rounds), workgroups per CU = 8 (no cap) / 4 / 3 / 2:
 //   1M x 11x11 (546 MB)   99-101 / 91-97 / 78-79 / 102 us     4M x 11x11   354 / 350 / 320 / 424 us
@@ -1326,8 +1353,6 @@ static size_t lds_for_workgroups_per_cu(int k) {
 // from sweeps recorded on MI355X boxes (profiles/rNN/shape_sweep_*.jsonl), looked up by grid side, rules, fused reset and
 // the nearest batch size in log2.  sel = the envs-per-workgroup selector of launch_hint bits 10-11 (0: the table's default
 // one).  tests/test_gpu_policy_guard.py checks the table's choice against a small sweep on the box it runs on.
-static bool specialised_grid(int g) { return g == 8 || g == 11 || g == 12 || g == 14 || g == 18 || g == 32; }
-
 static const StepPolicyRow* step_policy_lookup(int g, int variant, bool auto_reset, int64_t n, int sel) {
     const StepPolicyRow* best = nullptr;
     long best_cost = 0;
@@ -1345,268 +1370,224 @@ static const StepPolicyRow* step_policy_lookup(int g, int variant, bool auto_res
     return best;
 }
 
-// the selector (launch_hint bits 10-11) that names EPB envs per workgroup for this grid size; see launch_one
-template <int GT, int EPB>
-constexpr int sel_of() {
-    if (GT == 11 || GT == 12) return EPB == 64 ? 1 : (EPB == 32 ? 2 : 3);
-    if (GT == 14 || GT == 18) return EPB == 32 ? 1 : 2;
-    if (GT == 8) return EPB == 128 ? 1 : 2;
-    if (GT == 32) return EPB == 8 ? 1 : 2;
-    return EPB == 256 ? 1 : (EPB == 64 ? 2 : 3);
-}
-
-template <int GT, int VARIANT, bool DO_STEP, int EPB>
-static hipError_t launch_shared(const StepArgs& a, hipStream_t s) {
-    const int64_t blocks = (a.n + EPB - 1) / EPB;
-    size_t lds = shared_lds_bytes(a.grid, GT != 0, EPB, VARIANT == LMAZE_VARIANT_V3);
-    const bool nt = a.obs != nullptr && beyond_caches(a.n, a.grid * a.grid);
-    // default (workgroups per CU, chunks per workgroup) of the streaming regime: the generated table (round 2 kept them
-    // in a hand-edited if-chain here, retuned four times in its last hour; LAB_NOTES.md has that history)
-    int def_cu = 3, def_m = 2;
-    if (const StepPolicyRow* r = step_policy_lookup(a.grid, VARIANT, a.auto_reset != 0, a.n, sel_of<GT, EPB>())) {
-        def_cu = r->per_cu;
-        def_m = r->chunks;
-    }
-    int per_cu = a.launch_hint & 15;
-    if (per_cu == 0 && nt) per_cu = def_cu;
-    if (per_cu >= 1 && per_cu < 8) {
-        const size_t want = lds_for_workgroups_per_cu(per_cu);
-        if (want > lds) lds = want;
-    }
-    // chunks per workgroup (hint bits 4-7, 0 = default): the inputs of chunk k+1 are loaded while chunk k is
-    // stored, and the per-workgroup LDS set-up is shared.
-    int m = (a.launch_hint >> 4) & 15;
-    if (m == 0) m = nt ? def_m : 1;
-    const int64_t grid = (blocks + m - 1) / m;
-    if (!grid_ok(grid)) return hipErrorInvalidConfiguration;
-    if (a.info) {
-        char name[96];
-        snprintf(name, sizeof(name), "step_shared_kernel<%d, v%d, %s, %d, %s>", GT, VARIANT, DO_STEP ? "step" : "observe", EPB, nt ? "nt" : "plain");
-        describe_launch(a.info, name, EPB, per_cu >= 1 && per_cu < 8 ? per_cu : 0, m, nt, grid, LMAZE_BLOCK, lds);
-        return hipSuccess;
-    }
-    if (nt)
-        hipLaunchKernelGGL((step_shared_kernel<GT, VARIANT, DO_STEP, EPB, true>), dim3((unsigned)grid),
-                           dim3(LMAZE_BLOCK), lds, s, a);
-    else
-        hipLaunchKernelGGL((step_shared_kernel<GT, VARIANT, DO_STEP, EPB, false>), dim3((unsigned)grid),
-                           dim3(LMAZE_BLOCK), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int G, int VARIANT, bool DO_STEP>
-static hipError_t launch_perenv_wave(const StepArgs& a, hipStream_t s) {
-    // One env per wave measured best at 1M x 32x32 (bench.py --workload c5): 0.873 ms per step
-    // (0.775 of HBM peak, non-temporal stores) against 0.985 ms with four envs per wave and 0.96 ms
-    // for the LDS-tiled kernel -- short-lived waves, as with the one-store-per-thread fill.
-    StepArgs b = a;
-    b.envs_per_block = 1;
-    const int64_t per_block = (int64_t)b.envs_per_block * (LMAZE_BLOCK / 64);
-    const int64_t blocks = (a.n + per_block - 1) / per_block;
-    const bool nt = a.obs != nullptr && beyond_caches(a.n, G * G);
-    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-    if (a.info) {
-        char name[96];
-        snprintf(name, sizeof(name), "step_perenv_wave_kernel<%d, v%d, %s, %s>", G, VARIANT, DO_STEP ? "step" : "observe", nt ? "nt" : "plain");
-        describe_launch(a.info, name, (int)per_block, 0, 1, nt, blocks, LMAZE_BLOCK, 0);
-        return hipSuccess;
-    }
-    if (nt)
-        hipLaunchKernelGGL((step_perenv_wave_kernel<G, VARIANT, DO_STEP, true>), dim3((unsigned)blocks),
-                           dim3(LMAZE_BLOCK), 0, s, b);
-    else
-        hipLaunchKernelGGL((step_perenv_wave_kernel<G, VARIANT, DO_STEP, false>), dim3((unsigned)blocks),
-                           dim3(LMAZE_BLOCK), 0, s, b);
-    return hipGetLastError();
-}
-
-template <int GT, int VARIANT, bool DO_STEP>
-static hipError_t launch_perenv(const StepArgs& a, hipStream_t s) {
-    // G*G a multiple of 256: the register-tiled one-wave-per-env kernel
-    if constexpr (GT == 32) return launch_perenv_wave<32, VARIANT, DO_STEP>(a, s);
-    if constexpr (GT == 0) {
-        if (a.grid == 16) return launch_perenv_wave<16, VARIANT, DO_STEP>(a, s);
-        if (a.grid == 48) return launch_perenv_wave<48, VARIANT, DO_STEP>(a, s);
-        if (a.grid == 64) return launch_perenv_wave<64, VARIANT, DO_STEP>(a, s);
-    }
-    StepArgs b = a;
-    // about 8 KiB of layouts = 32 KiB of planes per workgroup (round 1: 16 KiB; 1M x 11x11 / 12x12, 512K x 18x18 with
-    // non-temporal stores: 107 / 125 / 134 us with 16 KiB, 102-103 / 120-122 / 133-140 with 8)
-    b.envs_per_block = perenv_envs_per_block(a.grid, 8192);
-    const int64_t blocks = (a.n + b.envs_per_block - 1) / b.envs_per_block;
-    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-    if (a.info) {
-        char name[96];
-        snprintf(name, sizeof(name), "step_perenv_kernel<%d, v%d, %s>", GT, VARIANT, DO_STEP ? "step" : "observe");
-        describe_launch(a.info, name, b.envs_per_block, 0, 1, false, blocks, LMAZE_BLOCK, perenv_lds_bytes(a.grid, b.envs_per_block));
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL((step_perenv_kernel<GT, VARIANT, DO_STEP>), dim3((unsigned)blocks), dim3(LMAZE_BLOCK),
-                       perenv_lds_bytes(a.grid, b.envs_per_block), s, b);
-    return hipGetLastError();
-}
-
 // the table's default envs-per-workgroup selector for this launch (streaming regime), or `fallback`
-template <int VARIANT>
-static int table_sel(const StepArgs& a, int fallback) {
-    const StepPolicyRow* r = step_policy_lookup(a.grid, VARIANT, a.auto_reset != 0, a.n, 0);
+static int table_sel(const StepArgs& a, int variant, int fallback) {
+    const StepPolicyRow* r = step_policy_lookup(a.grid, variant, a.auto_reset != 0, a.n, 0);
     return r ? r->sel : fallback;
 }
 
-// Envs per workgroup for the shared-layout kernel: about 32 KiB of observation per workgroup
-// (8 sixteen-byte stores per lane).  Measured at G=11 on MI355X (tools/kbench.hip): 64 envs
-// (31 KiB) 90-91 us per 1M-env step, 128/256 envs 96-101 us, 32 envs 120 us.
-template <int GT, int VARIANT, bool DO_STEP>
-static hipError_t launch_one(const StepArgs& a, int layout_mode, hipStream_t s) {
+// The shared-layout kernel's selector where launch_hint bits 10-11 leave it to the library.  gt: the grid side of the
+// instantiation; streaming: the planes go beyond the caches.
+static int step_default_sel(const StepArgs& a, int variant, int gt, bool streaming) {
+    const bool v3 = variant == LMAZE_VARIANT_V3;
+    switch (gt) {
+        case 8:
+            // large 8x8 batches: 1: 128 envs per workgroup, 2: 64 (16 KiB of planes).  2M envs: 64 envs at
+            // 4 / 5 / 6 / 8 per CU 89.0 / 91.7 / 91.8 / 91.7 us, 128 envs at (2, 1) 92.6, at 3-8 per CU 102-105.
+            return table_sel(a, variant, a.obs != nullptr ? 2 : 1);
+        case 11:
+            // envs per workgroup, 1: 64, 2: 32.  Round 2, once the set-up was one global
+            // round trip: v0 11x11 1M, 32 envs (15 KiB of planes) per workgroup, uncapped, one chunk 76.1-76.6 us on every
+            // placement of the observation buffer tried, against 78.6-80.9 for 64 envs at (3, 2) / (3, 1) (16 envs: 90+);
+            // with the fused reset (after its set-up lost the compacted spawn list and the early wait) 32 envs uncapped 78.8-83.5
+            // on two boxes, 64 envs at (3, 2) 81 / 95-97, at (3, 1) 81-84.
+            return streaming ? table_sel(a, variant, 2) : 1;     // the render-only launches (lmaze_observe) write the same stream
+        case 12:
+            // 12x12 (1M envs, 643 MB): 16 envs (9 KiB) per workgroup, uncapped 97.1-97.4 us, (5, 2) 96.0, against 104-105 for 64
+            // envs at (2, 1) and 111-119 for nearly everything else; with the fused reset 103-104 against 109.  (3: 16 envs.)
+            return streaming ? table_sel(a, variant, 3) : 1;
+        case 14:
+        case 18:
+            // envs per workgroup, 1: 32, 2: 16.  1M x 14x14 v0 (861 MB): 16 envs (12 KiB
+            // of planes) at 5 workgroups per CU 120.5 us, at 4 / 6 / uncapped 134 / 142 / 142, against 150-161 for every
+            // policy of 32 envs but (2, 2) (132.5); 512K x 18x18 v3: 16 envs at (4, 1) or (3, 2) 104.3-104.5 against 109.5
+            // for 32 at (2, 1) -- but 118-134 one step to either side, so there it stays a tuner candidate.
+            // v3 18x18 since its render went to bit strings: 16 envs at 4-5 per CU 109 us (with the fused reset 5-8 per CU
+            // 103-107) against 112-120
+            return streaming ? table_sel(a, variant, gt == 14 || v3 ? 2 : 1) : 1;
+        case 32:
+            // 1: 8 envs per workgroup (32 KiB of planes), 2: 4 envs (16 KiB).  128K / 512K envs, us per
+            // step: 4 envs at (5, 1) 84.0 / 337 and at (4, 1) 85.0 / 323 against 96 / 363 for 8 envs at (2, 1); with the fused
+            // reset 4 envs at (5, 1) 88.6 / 342, at (6, 1) 81.8 / 313, against 102 / 403.
+            return streaming ? table_sel(a, variant, 2) : 1;
+        default: {
+            // unspecialised G: 1: 256, 2: 64, 3: 16 envs per workgroup.
+            // Round 2 (1M envs at G = 9, 10, 13; 512K at 16, 20; 256K at 27; us per step, old -> new default): 64.9 -> 56.4,
+            // 88.0 -> 76.2, 120.7 (unchanged), 118.9 -> 90.0 (16 envs at (5, 2): 81.7), 169.7 -> 148.1, 155.3 -> 152.
+            const int sel = a.grid >= 15 ? 3 : (a.grid >= 5 ? 2 : 1);
+            return streaming && a.grid >= 5 ? table_sel(a, variant, sel) : sel;
+        }
+    }
+}
+
+// What a step / observe launch queues (step_plan): everything the description and the launch need
+enum StepFamily { ST_SHARED, ST_WAVE8, ST_PERENV, ST_PERENV_WAVE, ST_U8 };
+struct StepPlan {
+    StepFamily family;
+    int gt;                   // the instantiation's grid side (0: the generic one; wave8 and u8 have none)
+    int epb;                  // ... and its envs per workgroup (wave8: per wave; the per-env kernels have none)
+    bool nt;                  // the instantiation with non-temporal stores
+    int envs;                 // reported: envs per workgroup
+    int per_cu;               // reported: the workgroups per CU the LDS request asks for, 0 without a cap
+    int chunks;
+    int64_t grid;
+    int block;
+    size_t lds;
+    int32_t envs_per_block;   // what the kernel receives as StepArgs::envs_per_block (the per-env kernels') ...
+    int32_t launch_hint;      // ... and as launch_hint (the u8 kernel's bit 8: streaming stores)
+};
+
+// narrow (uint8) observation: envs per workgroup 256 and two chunks of them unless the hint says otherwise
+static const int kU8DefaultSel = 1, kU8DefaultChunks = 2;
+
+static StepPlan step_plan(const StepArgs& a, int variant, int layout_mode, bool u8) {
+    const int cells = a.grid * a.grid;
+    const int hint_sel = (a.launch_hint >> 10) & 3, hint_lo = a.launch_hint & 15, hint_hi = (a.launch_hint >> 4) & 15;
+    const bool streaming = a.obs != nullptr && beyond_caches(a.n, cells);
+    StepPlan p{ST_SHARED, 0, 0, false, 0, 0, 1, 0, LMAZE_BLOCK, 0, a.envs_per_block, a.launch_hint};
+    if (u8) {
+        // shared layout.  launch_hint bits 10-11: envs per workgroup, 1: 256, 2: 128, 3: 64 (0 = default)
+        p.family = ST_U8;
+        p.envs = p.epb = 512 >> (hint_sel ? hint_sel : kU8DefaultSel);
+        const int pw = (2 * cells + 16 + 3) >> 2;
+        p.lds = ((size_t)4 * pw * 4 + 3 * (size_t)(p.epb + 1) * 4 + (size_t)((cells + 1) & ~1) * 2 + (size_t)cells + 15) & ~(size_t)15;
+        // launch_hint bits 4-7: chunks of epb envs per workgroup (0 = default)
+        p.chunks = hint_hi ? hint_hi : kU8DefaultChunks;
+        p.grid = ((a.n + p.epb - 1) / p.epb + p.chunks - 1) / p.chunks;
+        // more than 64 MiB of planes: streamed (1M x 11x11, 127 MB: 31.2 us per step against 33.3 with plain stores)
+        p.launch_hint = (a.launch_hint & ~0x100) | ((size_t)a.n * cells > ((size_t)64 << 20) ? 0x100 : 0);
+    } else if (layout_mode != LMAZE_LAYOUT_SHARED && cells % 256 == 0) {
+        // G*G a multiple of 256 (16, 32, 48, 64): the register-tiled one-wave-per-env kernel.
+        // One env per wave measured best at 1M x 32x32 (bench.py --workload c5): 0.873 ms per step
+        // (0.775 of HBM peak, non-temporal stores) against 0.985 ms with four envs per wave and 0.96 ms
+        // for the LDS-tiled kernel -- short-lived waves, as with the one-store-per-thread fill.
+        p.family = ST_PERENV_WAVE;
+        p.gt = a.grid;
+        p.nt = streaming;
+        p.envs_per_block = 1;
+        p.envs = p.envs_per_block * (LMAZE_BLOCK / 64);
+        p.grid = (a.n + p.envs - 1) / p.envs;
+    } else if (layout_mode != LMAZE_LAYOUT_SHARED) {
+        p.family = ST_PERENV;
+        p.gt = specialised_grid(a.grid) ? a.grid : 0;
+        // about 8 KiB of layouts = 32 KiB of planes per workgroup (round 1: 16 KiB; 1M x 11x11 / 12x12, 512K x 18x18 with
+        // non-temporal stores: 107 / 125 / 134 us with 16 KiB, 102-103 / 120-122 / 133-140 with 8)
+        p.envs = p.envs_per_block = perenv_envs_per_block(a.grid, 8192);
+        p.grid = (a.n + p.envs - 1) / p.envs;
+        p.lds = perenv_lds_bytes(a.grid, p.envs);
+    } else if (a.grid == 8 && !streaming && a.mask == nullptr && (a.launch_hint & 0x100) == 0) {
+        // small 8x8 batches (the planes stay on-die): the wave-autonomous kernel, no LDS, no barrier
+        // envs per wave: launch_hint bits 4-7 = 1: 64, 2: 32, 3: 16 (0 = default)
+        // Defaults, measured at 65 536 envs under hipGraph (us per step, two boxes): 64 envs per wave x 4 waves per
+        // workgroup -- one 256-thread workgroup per CU -- 5.35-5.53; 64 x 1 5.6-5.9; 32 x 1 / 2 / 4 5.72 / 5.72-5.87 /
+        // 5.89; 64 x 2 5.9-6.1.  Smaller batches keep single-wave workgroups so that they spread over the CUs.
+        p.family = ST_WAVE8;
+        p.epb = 128 >> (hint_hi >= 1 && hint_hi <= 3 ? hint_hi : a.n >= 65536 ? 1 : 2);
+        // bits 0-3: waves per workgroup, 1 / 2 / 4 (0 = default)
+        const int wpb = hint_lo == 1 || hint_lo == 2 || hint_lo == 4 ? hint_lo : a.n >= 65536 ? 4 : 1;
+        p.envs = p.epb * wpb;
+        p.block = 64 * wpb;
+        p.grid = ((a.n + p.epb - 1) / p.epb + wpb - 1) / wpb;
+    } else {
+        // launch_hint bits 10-11 name the envs per workgroup (0 = default); a selector the grid side has no size for takes
+        // selector 1's
+        p.gt = specialised_grid(a.grid) ? a.grid : 0;
+        auto size_of = [&](int sel) {
+            for (const auto& size : kSharedSizes)
+                if (size.gt == p.gt && size.sel == sel) return size.epb;
+            return 0;
+        };
+        int sel = hint_sel ? hint_sel : step_default_sel(a, variant, p.gt, streaming);
+        if (!size_of(sel)) sel = 1;
+        p.envs = p.epb = size_of(sel);
+        p.nt = streaming;
+        p.lds = shared_lds_bytes(a.grid, p.gt != 0, p.epb, variant == LMAZE_VARIANT_V3);
+        // default (workgroups per CU, chunks per workgroup) of the streaming regime: the generated table's row for the chosen
+        // size (round 2 kept them in a hand-edited if-chain here, retuned four times in its last hour; LAB_NOTES.md has that
+        // history).  Inside the caches neither default is read.
+        int def_cu = 3, def_m = 2;
+        const StepPolicyRow* r = p.nt ? step_policy_lookup(a.grid, variant, a.auto_reset != 0, a.n, sel) : nullptr;
+        if (r) {
+            def_cu = r->per_cu;
+            def_m = r->chunks;
+        }
+        const int per_cu = hint_lo == 0 && p.nt ? def_cu : hint_lo;
+        if (per_cu >= 1 && per_cu < 8) {
+            p.per_cu = per_cu;
+            const size_t want = lds_for_workgroups_per_cu(per_cu);
+            if (want > p.lds) p.lds = want;
+        }
+        // chunks per workgroup (hint bits 4-7, 0 = default): the inputs of chunk k+1 are loaded while chunk k is
+        // stored, and the per-workgroup LDS set-up is shared.
+        p.chunks = hint_hi ? hint_hi : p.nt ? def_m : 1;
+        p.grid = ((a.n + p.epb - 1) / p.epb + p.chunks - 1) / p.chunks;
+    }
+    return p;
+}
+
+// The kernel of a planned step: every instantiation the code object holds is named here and nowhere else
+using StepKernel = void (*)(const StepArgs);
+template <int V, bool S>
+static StepKernel step_kernel(const StepPlan& p) {
+    switch (p.family) {
+        case ST_SHARED:
+#define X(GT, SEL, EPB) \
+    if (p.gt == GT && p.epb == EPB) return p.nt ? step_shared_kernel<GT, V, S, EPB, true> : step_shared_kernel<GT, V, S, EPB, false>;
+            LMAZE_SHARED_SIZES(X)
+#undef X
+            break;
+        case ST_PERENV:   // side 32 always takes the wave kernel; its instantiation stays in the code object
+#define X(GT, SEL, EPB) \
+    if (SEL == 1 && p.gt == GT) return step_perenv_kernel<GT, V, S>;
+            LMAZE_SHARED_SIZES(X)
+#undef X
+            break;
+        case ST_PERENV_WAVE:
+#define X(G) \
+    if (p.gt == G) return p.nt ? step_perenv_wave_kernel<G, V, S, true> : step_perenv_wave_kernel<G, V, S, false>;
+            X(16) X(32) X(48) X(64)
+#undef X
+            break;
+        case ST_WAVE8:
+            return p.epb == 64 ? step_shared_wave8_kernel<V, S, 64> : p.epb == 32 ? step_shared_wave8_kernel<V, S, 32> : step_shared_wave8_kernel<V, S, 16>;
+        case ST_U8:
+            return p.epb == 256 ? step_shared_u8_kernel<V, S, 256> : p.epb == 128 ? step_shared_u8_kernel<V, S, 128> : step_shared_u8_kernel<V, S, 64>;
+    }
+    return nullptr;
+}
+
+static const void* step_kernel(const StepPlan& p, bool v3, bool do_step) {
+    constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
+    return (const void*)(v3 ? (do_step ? step_kernel<V3, true>(p) : step_kernel<V3, false>(p))
+                            : (do_step ? step_kernel<V0, true>(p) : step_kernel<V0, false>(p)));
+}
+
+// One step (do_step) or one render (observe) of a.n envs as step_plan decides; u8: the narrow planes in a.obs8 (shared layouts,
+// G >= 4).  a.info != null: the plan is described instead of queued.
+hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, bool u8, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
-    if (layout_mode != LMAZE_LAYOUT_SHARED) return launch_perenv<GT, VARIANT, DO_STEP>(a, s);
-    if constexpr (GT == 8) {
-        // small batches (the planes stay on-die): the wave-autonomous kernel, no LDS, no barrier
-        const bool small = a.obs == nullptr || !beyond_caches(a.n, 64);
-        if (small && a.mask == nullptr && (a.launch_hint & 0x100) == 0) {
-            // envs per wave: launch_hint bits 4-7 = 1: 64, 2: 32, 3: 16 (0 = default)
-            // Defaults, measured at 65 536 envs under hipGraph (us per step, two boxes): 64 envs per wave x 4 waves per
-            // workgroup -- one 256-thread workgroup per CU -- 5.35-5.53; 64 x 1 5.6-5.9; 32 x 1 / 2 / 4 5.72 / 5.72-5.87 /
-            // 5.89; 64 x 2 5.9-6.1.  Smaller batches keep single-wave workgroups so that they spread over the CUs.
-            int code = (a.launch_hint >> 4) & 15;
-            if (code < 1 || code > 3) code = a.n >= 65536 ? 1 : 2;
-            const int epw = 128 >> code;
-            int wpb = a.launch_hint & 15;                   // bits 0-3: waves per workgroup, 1 / 2 / 4 (0 = default)
-            if (wpb != 1 && wpb != 2 && wpb != 4) wpb = a.n >= 65536 ? 4 : 1;
-            const int64_t waves = (a.n + epw - 1) / epw;
-            const int64_t blocks = (waves + wpb - 1) / wpb;
-            if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-            const dim3 grid((unsigned)blocks), block(64 * wpb);
-            if (a.info) {
-                char name[96];
-                snprintf(name, sizeof(name), "step_shared_wave8_kernel<v%d, %s, %d>", VARIANT, DO_STEP ? "step" : "observe", epw);
-                describe_launch(a.info, name, epw * wpb, 0, 1, false, blocks, 64 * wpb, 0);
-                return hipSuccess;
-            }
-            if (code == 1) hipLaunchKernelGGL((step_shared_wave8_kernel<VARIANT, DO_STEP, 64>), grid, block, 0, s, a);
-            else if (code == 2) hipLaunchKernelGGL((step_shared_wave8_kernel<VARIANT, DO_STEP, 32>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((step_shared_wave8_kernel<VARIANT, DO_STEP, 16>), grid, block, 0, s, a);
-            return hipGetLastError();
-        }
-        // large 8x8 batches: launch_hint bits 10-11: 1: 128 envs per workgroup, 2: 64 (16 KiB of planes).  2M envs: 64 envs at
-        // 4 / 5 / 6 / 8 per CU 89.0 / 91.7 / 91.8 / 91.7 us, 128 envs at (2, 1) 92.6, at 3-8 per CU 102-105.
-        int sel = (a.launch_hint >> 10) & 3;
-        if (sel == 0) sel = table_sel<VARIANT>(a, a.obs != nullptr ? 2 : 1);
-        if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 64>(a, s);
-        return launch_shared<GT, VARIANT, DO_STEP, 128>(a, s);
-    } else if constexpr (GT == 11 || GT == 12) {
-        // launch_hint bits 10-11: envs per workgroup, 1: 64, 2: 32 (0 = default).  Round 2, once the set-up was one global
-        // round trip: v0 11x11 1M, 32 envs (15 KiB of planes) per workgroup, uncapped, one chunk 76.1-76.6 us on every
-        // placement of the observation buffer tried, against 78.6-80.9 for 64 envs at (3, 2) / (3, 1) (16 envs: 90+);
-        // with the fused reset (after its set-up lost the compacted spawn list and the early wait) 32 envs uncapped 78.8-83.5
-        // on two boxes, 64 envs at (3, 2) 81 / 95-97, at (3, 1) 81-84.
-        int sel = (a.launch_hint >> 10) & 3;
-        const bool streaming = a.obs != nullptr && beyond_caches(a.n, GT * GT);
-        // 12x12 (1M envs, 643 MB): 16 envs (9 KiB) per workgroup, uncapped 97.1-97.4 us, (5, 2) 96.0, against 104-105 for 64
-        // envs at (2, 1) and 111-119 for nearly everything else; with the fused reset 103-104 against 109.  (3: 16 envs.)
-        if (sel == 0) {
-            if (GT == 11) sel = streaming ? 2 : 1;      // the render-only launches (lmaze_observe) write the same stream
-            else sel = streaming ? 3 : 1;
-            if (streaming) sel = table_sel<VARIANT>(a, sel);
-        }
-        if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 32>(a, s);
-        if (sel == 3) return launch_shared<GT, VARIANT, DO_STEP, 16>(a, s);
-        return launch_shared<GT, VARIANT, DO_STEP, 64>(a, s);
-    } else if constexpr (GT == 14 || GT == 18) {
-        // launch_hint bits 10-11: envs per workgroup, 1: 32, 2: 16 (0 = default).  1M x 14x14 v0 (861 MB): 16 envs (12 KiB
-        // of planes) at 5 workgroups per CU 120.5 us, at 4 / 6 / uncapped 134 / 142 / 142, against 150-161 for every
-        // policy of 32 envs but (2, 2) (132.5); 512K x 18x18 v3: 16 envs at (4, 1) or (3, 2) 104.3-104.5 against 109.5
-        // for 32 at (2, 1) -- but 118-134 one step to either side, so there it stays a tuner candidate.
-        int sel = (a.launch_hint >> 10) & 3;
-        const bool streaming = a.obs != nullptr && beyond_caches(a.n, GT * GT);
-        if (sel == 0) sel = ((GT == 14 || VARIANT == LMAZE_VARIANT_V3) && streaming) ? 2 : 1;
-        if (((a.launch_hint >> 10) & 3) == 0 && streaming) sel = table_sel<VARIANT>(a, sel);   // v3 18x18 since its render went to bit strings: 16 envs at 4-5 per CU 109 us (with the fused reset 5-8 per CU 103-107) against 112-120
-        if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 16>(a, s);
-        return launch_shared<GT, VARIANT, DO_STEP, 32>(a, s);
-    } else if constexpr (GT == 32) {
-        // launch_hint bits 10-11: 1: 8 envs per workgroup (32 KiB of planes), 2: 4 envs (16 KiB).  128K / 512K envs, us per
-        // step: 4 envs at (5, 1) 84.0 / 337 and at (4, 1) 85.0 / 323 against 96 / 363 for 8 envs at (2, 1); with the fused
-        // reset 4 envs at (5, 1) 88.6 / 342, at (6, 1) 81.8 / 313, against 102 / 403.
-        int sel = (a.launch_hint >> 10) & 3;
-        const bool streaming = a.obs != nullptr && beyond_caches(a.n, GT * GT);
-        if (sel == 0) sel = streaming ? table_sel<VARIANT>(a, 2) : 1;
-        if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 4>(a, s);
-        return launch_shared<GT, VARIANT, DO_STEP, 8>(a, s);
-    } else {  // unspecialised G: three sizes cover [3, 64]; launch_hint bits 10-11: 1: 256, 2: 64, 3: 16 envs per workgroup
-        // Round 2 (1M envs at G = 9, 10, 13; 512K at 16, 20; 256K at 27; us per step, old -> new default): 64.9 -> 56.4,
-        // 88.0 -> 76.2, 120.7 (unchanged), 118.9 -> 90.0 (16 envs at (5, 2): 81.7), 169.7 -> 148.1, 155.3 -> 152.
-        int sel = (a.launch_hint >> 10) & 3;
-        if (sel == 0) {
-            sel = a.grid >= 15 ? 3 : (a.grid >= 5 ? 2 : 1);
-            if (a.obs != nullptr && beyond_caches(a.n, a.grid * a.grid) && a.grid >= 5) sel = table_sel<VARIANT>(a, sel);
-        }
-        if (sel == 3) return launch_shared<GT, VARIANT, DO_STEP, 16>(a, s);
-        if (sel == 2) return launch_shared<GT, VARIANT, DO_STEP, 64>(a, s);
-        return launch_shared<GT, VARIANT, DO_STEP, 256>(a, s);
-    }
-}
-
-// Grid sizes the kernels are specialised for: the reference's shipped sizes (12, 14, 18)
-// and BASELINE.json's (8, 11, 32); any other G in [3, 64] takes the GT = 0 instantiation.
-template <int VARIANT, bool DO_STEP>
-static hipError_t dispatch_grid(const StepArgs& a, int layout_mode, hipStream_t s) {
-    switch (a.grid) {
-        case 8:  return launch_one<8, VARIANT, DO_STEP>(a, layout_mode, s);
-        case 11: return launch_one<11, VARIANT, DO_STEP>(a, layout_mode, s);
-        case 12: return launch_one<12, VARIANT, DO_STEP>(a, layout_mode, s);
-        case 14: return launch_one<14, VARIANT, DO_STEP>(a, layout_mode, s);
-        case 18: return launch_one<18, VARIANT, DO_STEP>(a, layout_mode, s);
-        case 32: return launch_one<32, VARIANT, DO_STEP>(a, layout_mode, s);
-        default: return launch_one<0, VARIANT, DO_STEP>(a, layout_mode, s);
-    }
-}
-
-hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s);
-
-#ifndef LMAZE_U8_DEFAULT_SEL
-#define LMAZE_U8_DEFAULT_SEL 1
-#endif
-#ifndef LMAZE_U8_DEFAULT_CHUNKS
-#define LMAZE_U8_DEFAULT_CHUNKS 2
-#endif
-// narrow (uint8) observation, shared layout.  launch_hint bits 10-11: envs per workgroup, 1: 256, 2: 128, 3: 64 (0 = default)
-template <int EPB>
-static hipError_t launch_step_u8_epb(int variant, bool do_step, const StepArgs& a, hipStream_t s) {
-    const int cells = a.grid * a.grid, pw = (2 * cells + 16 + 3) >> 2;
-    const size_t lds = ((size_t)4 * pw * 4 + 3 * (size_t)(EPB + 1) * 4 + (size_t)((cells + 1) & ~1) * 2 + (size_t)cells + 15) & ~(size_t)15;
-    // launch_hint bits 4-7: chunks of EPB envs per workgroup (0 = default)
-    int m = (a.launch_hint >> 4) & 15;
-    if (m == 0) m = LMAZE_U8_DEFAULT_CHUNKS;
-    const int64_t nchunks = (a.n + EPB - 1) / EPB;
-    const int64_t blocks = (nchunks + m - 1) / m;
-    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
+    const bool v3 = variant == LMAZE_VARIANT_V3;
+    const StepPlan p = step_plan(a, v3 ? LMAZE_VARIANT_V3 : LMAZE_VARIANT_V0, layout_mode, u8);
+    if (!grid_ok(p.grid)) return hipErrorInvalidConfiguration;
     if (a.info) {
         char name[96];
-        snprintf(name, sizeof(name), "step_shared_u8_kernel<v%d, %s, %d>", variant, do_step ? "step" : "observe", EPB);
-        describe_launch(a.info, name, EPB, 0, m, false, blocks, LMAZE_BLOCK, lds);
+        const char *v = v3 ? "v3" : "v0", *form = do_step ? "step" : "observe", *stores = p.nt ? "nt" : "plain";
+        switch (p.family) {
+            case ST_SHARED: snprintf(name, sizeof(name), "step_shared_kernel<%d, %s, %s, %d, %s>", p.gt, v, form, p.epb, stores); break;
+            case ST_PERENV: snprintf(name, sizeof(name), "step_perenv_kernel<%d, %s, %s>", p.gt, v, form); break;
+            case ST_PERENV_WAVE: snprintf(name, sizeof(name), "step_perenv_wave_kernel<%d, %s, %s, %s>", p.gt, v, form, stores); break;
+            case ST_WAVE8: snprintf(name, sizeof(name), "step_shared_wave8_kernel<%s, %s, %d>", v, form, p.epb); break;
+            case ST_U8: snprintf(name, sizeof(name), "step_shared_u8_kernel<%s, %s, %d>", v, form, p.epb); break;
+        }
+        describe_launch(a.info, name, p.envs, p.per_cu, p.chunks, p.nt, p.grid, p.block, p.lds);
         return hipSuccess;
     }
-    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
     StepArgs b = a;
-    // more than 64 MiB of planes: streamed (1M x 11x11, 127 MB: 31.2 us per step against 33.3 with plain stores)
-    b.launch_hint = (a.launch_hint & ~0x100) | ((size_t)a.n * cells > ((size_t)64 << 20) ? 0x100 : 0);
-    if (variant == LMAZE_VARIANT_V3) {
-        if (do_step) hipLaunchKernelGGL((step_shared_u8_kernel<LMAZE_VARIANT_V3, true, EPB>), grid, block, lds, s, b);
-        else hipLaunchKernelGGL((step_shared_u8_kernel<LMAZE_VARIANT_V3, false, EPB>), grid, block, lds, s, b);
-    } else {
-        if (do_step) hipLaunchKernelGGL((step_shared_u8_kernel<LMAZE_VARIANT_V0, true, EPB>), grid, block, lds, s, b);
-        else hipLaunchKernelGGL((step_shared_u8_kernel<LMAZE_VARIANT_V0, false, EPB>), grid, block, lds, s, b);
-    }
+    b.envs_per_block = p.envs_per_block;
+    b.launch_hint = p.launch_hint;
+    void* args[] = {&b};
+    (void)hipLaunchKernel(step_kernel(p, v3, do_step), dim3((unsigned)p.grid), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
     return hipGetLastError();
-}
-
-hipError_t launch_step_u8(int variant, bool do_step, const StepArgs& a, hipStream_t s) {
-    if (a.n == 0) return hipSuccess;
-    int sel = (a.launch_hint >> 10) & 3;
-    if (sel == 0) sel = LMAZE_U8_DEFAULT_SEL;
-    if (sel == 1) return launch_step_u8_epb<256>(variant, do_step, a, s);
-    if (sel == 2) return launch_step_u8_epb<128>(variant, do_step, a, s);
-    return launch_step_u8_epb<64>(variant, do_step, a, s);
 }
 
 // Store policy of the recording form's slots: plain.  Measured (tools/bench_rollout_obs.py --sweep, two runs, T = 16,
@@ -1779,7 +1760,7 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
             if (obs_t && rec->every > 0 && (t + 1) % rec->every == 0)
                 slot = obs_t + (size_t)((t + 1) / rec->every - 1) * plane;
             if (rec) a.obs = t == T - 1 && a0.obs ? a0.obs : slot;                     // the caller's obs after the last step
-            hipError_t rc = launch_step(variant, true, a, layout_mode, s);
+            hipError_t rc = launch_step(variant, true, a, layout_mode, u8, s);
             if (rc != hipSuccess || a0.info) return rc;
             if (slot && a.obs != slot && (rc = hipMemcpyAsync(slot, a.obs, (size_t)plane * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess)
                 return rc;
@@ -1857,14 +1838,6 @@ hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode
     return launch_closed<RolloutSampleArgs, RolloutSample8Args>(variant, a, layout_mode, tab, tab.staged ? PLAN_SAMPLE_LDS : PLAN_SAMPLE_GLOBAL,
                                                                 "sample", tab.staged ? ", table=lds" : ", table=global", T, reward_t, done_t,
                                                                 s, rec, u8);
-}
-
-hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, hipStream_t s) {
-    if (variant == LMAZE_VARIANT_V3)
-        return do_step ? dispatch_grid<LMAZE_VARIANT_V3, true>(a, layout_mode, s)
-                       : dispatch_grid<LMAZE_VARIANT_V3, false>(a, layout_mode, s);
-    return do_step ? dispatch_grid<LMAZE_VARIANT_V0, true>(a, layout_mode, s)
-                   : dispatch_grid<LMAZE_VARIANT_V0, false>(a, layout_mode, s);
 }
 
 }  // namespace lmaze

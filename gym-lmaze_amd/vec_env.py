@@ -226,7 +226,7 @@ class LmazeVecEnv(VecEnvBase):
         self._p_obs = ptr
 
     # launch policies autotune() tries: (workgroups per CU, chunks per workgroup) -> LmazeParams.launch_hint
-    DEFAULT_POLICY = (0, 0)       # launch_hint = 0: the library's per-shape default (lmaze_step.hip launch_shared)
+    DEFAULT_POLICY = (0, 0)       # launch_hint = 0: the library's per-shape default (lmaze_step.hip step_plan)
     # a third element selects the envs per workgroup where the kernel offers a choice (11x11, 12x12: 1 = 64, 2 = 32, 3 = 16;
     # 14x14, 18x18: 1 = 32, 2 = 16; large 8x8 batches: 1 = 128, 2 = 64; 32x32: 1 = 8, 2 = 4; any other G: 1 = 256, 2 = 64,
     # 3 = 16 -- include/lmaze.h)
@@ -251,7 +251,7 @@ class LmazeVecEnv(VecEnvBase):
         restored, so results are unaffected.  The optimum is narrow and depends on shape, device and -- most of all -- on
         WHERE THE INPUTS COME FROM: the policy that wins when actions and state sit in the Infinity Cache (3 workgroups
         per CU) loses a third of its rate when the actions are a fresh row from HBM every step (lmaze_step.hip
-        launch_shared).  So pass the action tensor the rollout will use (`actions`: int32[T,N] on the
+        step_plan).  So pass the action tensor the rollout will use (`actions`: int32[T,N] on the
         device; the rows are cycled exactly as rollout() would); without one, a private ring of rows larger
         than the cache is generated, the conservative assumption.  `between`: a callable that enqueues, on the
         current stream, whatever runs between two steps in the real loop (the policy's forward pass): back to

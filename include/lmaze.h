@@ -78,7 +78,7 @@ typedef struct LmazeParams {
     float reward_move;   /* positiveNominal  -0.01  (v0:22)                                  */
     float reward_goal;   /* positiveFull    100.0   (v0:23)                                  */
     int32_t launch_hint; /* 0 = library default launch policy.  Performance only, never results
-                            (lmaze_step.hip launch_shared / launch_one); bits not listed are 0.
+                            (lmaze_step.hip step_plan); bits not listed are 0.              
                               bits 0-3   workgroups resident per CU (1..8; 0 = default)
                               bits 4-7   chunks of envs a workgroup takes one after the other, loading
                                          the next chunk's inputs while it stores the current one

@@ -65,7 +65,7 @@ void run_grid(int64_t N, int rounds, int iters, hipStream_t s) {
         snprintf(nm, sizeof nm, "step G=%d EPB=%d NT=%d wg/CU=%d rot=%d autoreset=%d", G, EPB, (int)nt, per_cu, rot, ar);
         vs.push_back({nm, [=](hipStream_t st) {
             StepArgs b = a; (void)rot; b.auto_reset = ar; b.seed = 1; b.epoch = 5;
-            size_t lds = shared_lds_bytes(G, true, EPB);
+            size_t lds = shared_lds_bytes(G, true, EPB, false);
             if (per_cu < 8) lds = std::max(lds, lds_for_workgroups_per_cu(per_cu));
             const unsigned blocks = (unsigned)((N + EPB - 1) / EPB);
             if (nt) hipLaunchKernelGGL((step_shared_kernel<G, LMAZE_VARIANT_V0, true, EPB, true>), dim3(blocks), dim3(256), lds, st, b);

@@ -3,7 +3,7 @@
 10-11) x workgroups per CU x chunks per workgroup, plain and with the fused reset, a fresh action row per step from a ring
 larger than the Infinity Cache.  The median of three interleaved passes counts.  One JSON line per (shape, mode):
     python tools/shape_sweep.py 11:v0:1048576 14:v0:1048576 18:v3:524288 32:v0:131072        (G:variant:envs)
-This is the sweep behind the per-shape defaults of lmaze_step.hip launch_one / launch_shared."""
+This is the sweep behind the per-shape defaults of lmaze_step.hip step_default_sel / step_plan."""
 import importlib
 import json
 import os
