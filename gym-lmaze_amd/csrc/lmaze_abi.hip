@@ -290,43 +290,29 @@ static int foveal_rollout_closed(const LmazeFovealParams* params, const uint8_t*
     if (rc) return rc;
     if (obs_local_t && obs_every == 0) return LMAZE_E_COUNT;
     if (misaligned(obs_local_t, 16)) return LMAZE_E_ALIGN;
-    if (!params) return LMAZE_E_NULL;                                  // 2. the params' own refusals
+    rc = check_foveal_params(params);                                  // 2. the params' own refusals, the hint before the counts
+    if (!rc) rc = check_foveal_hint(params);
+    if (rc) return rc;
     const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
-    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
-        return LMAZE_E_VARIANT;
-    if (params->grid < LMAZE_FOVEA || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
-    if (params->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
     if (v56 != Table::kTwoLevel) return LMAZE_E_VARIANT;               // 3. the two-level variants have a closed loop of their own
-    if (T < 0 || n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;    // 4.
-    rc = tab.refused();
+    rc = T < 0 ? LMAZE_E_COUNT : check_foveal_count(n);                // 4.
+    if (!rc) rc = tab.refused();
     if (rc) return rc;
     if (T == 0 || n == 0) return 0;                                    // 5. nothing to do, nothing read
-    LmazeFovealBuffers none;
-    memset(&none, 0, sizeof(none));
     if (!info) {                                                       // 6. the pointers, then the alignments
         if (tab.missing()) return LMAZE_E_NULL;                        // with the other pointers, before any alignment
         rc = check_foveal(params, layouts, bufs, n);
         if (rc) return rc;
         if (tab.unaligned()) return LMAZE_E_ALIGN;                     // the table's own alignment last
     }
-    FovealArgs a = make_foveal_args(params, layouts, info ? &none : bufs, n);
-    a.auto_reset = auto_reset || Table::kTwoLevel ? 1 : 0;             // the two-level step resets and plans by itself
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
+    // the two-level step resets and plans by itself
+    FovealArgs a = make_foveal_args(params, layouts, info ? nullptr : bufs, n,
+                                    FovealReset{auto_reset || Table::kTwoLevel, seed, epoch, env_base, nullptr, nullptr});
     a.info = info;
-    const bool rec = obs_every > 0;
-    typename Table::Roll ro;
-    memset(&ro, 0, sizeof(ro));
-    ro.T = T;
-    ro.reward_t = reward_t;
-    ro.done_t = done_t;
-    ro.freward_t = foveal_reward_t;
-    ro.fdone_t = foveal_done_t;
-    ro.obs_t = rec && T / obs_every > 0 ? obs_t : nullptr;
-    ro.obs_local_t = rec && T / obs_every > 0 ? obs_local_t : nullptr;
-    ro.every = rec ? obs_every : 1;
+    const bool rec = obs_every > 0, slots = rec && T / obs_every > 0;
+    typename Table::Roll ro{FovealRollObs{FovealRoll{T, reward_t, done_t, foveal_reward_t, foveal_done_t}, slots ? obs_t : nullptr,
+                                          slots ? obs_local_t : nullptr, rec ? obs_every : 1},
+                            {}};
     tab.put(ro, actions_t, key_t);
     return (int)launch_foveal_rollout_closed(a, ro, rec, (hipStream_t)stream);
 }
@@ -337,8 +323,7 @@ static int describe_foveal_rollout_closed(const LmazeFovealParams* params, int64
                                           char* text_host, int32_t len, const Table& tab = Table{}) {
     if (!text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
+    LaunchInfo info{};
     // nothing is dereferenced: a fabricated, aligned address stands for the slots whose presence decides
     const int rc = foveal_rollout_closed(params, nullptr, tab, T, nullptr, n, auto_reset, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
                                          nullptr, nullptr, obs_every > 0 ? reinterpret_cast<float*>(32) : nullptr, nullptr, obs_every,

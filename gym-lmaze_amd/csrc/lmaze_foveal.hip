@@ -208,128 +208,62 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void expand_planes_stream_kernel(const
 // host side
 // ------------------------------------------------------------------------------------
 
+// The instantiations of foveal_kernel, X(variant, mode, envs per workgroup): the step at the four sizes launch_hint bits 4-7
+// name, the other modes at their one size and its LDS fallback; each at GT 18 / 14 / 0 and, the step, plain and with the
+// fused reset (v5: the two-level step).  v6 runs v5's.  No plan names the planner mode of v1 / v2 / v4, the 32-env fallback
+// of the other modes on a device with 160 KiB of LDS, or the last line's sizes of v2; the code object has always held them.
+#define LMAZE_FOVEAL_VARIANTS(X, MODE, EPB) \
+    X(LMAZE_VARIANT_V1, MODE, EPB) X(LMAZE_VARIANT_V2, MODE, EPB) X(LMAZE_VARIANT_V4, MODE, EPB) X(LMAZE_VARIANT_V5, MODE, EPB)
+#define LMAZE_FOVEAL_KERNELS(X)                                                             \
+    LMAZE_FOVEAL_VARIANTS(X, FM_STEP, 32) LMAZE_FOVEAL_VARIANTS(X, FM_STEP, 64)             \
+    LMAZE_FOVEAL_VARIANTS(X, FM_STEP, 128) LMAZE_FOVEAL_VARIANTS(X, FM_STEP, 256)           \
+    LMAZE_FOVEAL_VARIANTS(X, FM_RESET, 32) LMAZE_FOVEAL_VARIANTS(X, FM_RESET, 64)           \
+    X(LMAZE_VARIANT_V1, FM_SETGOAL, 32) X(LMAZE_VARIANT_V1, FM_SETGOAL, 64)                 \
+    LMAZE_FOVEAL_VARIANTS(X, FM_PLANNER, 32) LMAZE_FOVEAL_VARIANTS(X, FM_PLANNER, 64)       \
+    X(LMAZE_VARIANT_V2, FM_RESET, 128) X(LMAZE_VARIANT_V2, FM_RESET, 256)                   \
+    X(LMAZE_VARIANT_V2, FM_PLANNER, 128) X(LMAZE_VARIANT_V2, FM_PLANNER, 256)
+
+// The kernel of a planned launch: every instantiation of foveal_kernel is named here and nowhere else
+using FovealKernel = void (*)(const FovealArgs);
 template <int VARIANT, int MODE, int EPB>
-static hipError_t launch_foveal_one(const FovealArgs& a, hipStream_t s) {
-    size_t lds = foveal_lds<VARIANT>(a.p, EPB);
-    // envs per workgroup is a performance knob (launch_hint bits 4-7): a size whose LDS does not fit the device falls
-    // back to the next smaller one instead of failing the launch (v4-v6 at 256 envs: 164 KiB)
-    if constexpr (EPB > 32) {
-        if (lds > lds_limit()) return launch_foveal_one<VARIANT, MODE, EPB / 2>(a, s);
+static FovealKernel foveal_kernel_of(int gt, bool ar) {
+    if constexpr (MODE == FM_STEP) {
+        if (ar) return gt == 18 ? foveal_kernel<VARIANT, MODE, EPB, 18, true> : gt == 14 ? foveal_kernel<VARIANT, MODE, EPB, 14, true>
+                                                                                         : foveal_kernel<VARIANT, MODE, EPB, 0, true>;
     }
-    // launch_hint bits 8-9 (plain and fused step): chunks of EPB envs per workgroup - 1 (more than 4, or 16-env chunks: slower)
-    const int64_t nchunks = (a.n + EPB - 1) / EPB;
-    const int m = MODE == FM_STEP ? ((a.p.launch_hint >> 8) & 3) + 1 : 1;
-    const int64_t blocks = (nchunks + m - 1) / m;
-    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
-    FovealArgs b = a;
-    const int C = VARIANT == LMAZE_VARIANT_V1 ? 4 : (VARIANT == LMAZE_VARIANT_V2 ? 5 : 7);
-    b.nt = (size_t)a.n * C * W25 * 4 > kFovealStreamBytes;
-    if (LMAZE_XP(a, 2)) b.nt = 0;
-    // launch_hint bits 0-3: at most that many workgroups resident per CU, by padding the dynamic LDS (160 KiB per
-    // CU), as the step kernel does in its streaming regime (lmaze_step.hip step_plan); 0 = no cap
-    const int per_cu = a.p.launch_hint & 15;
-    if (MODE == FM_STEP) lds = lds_for_cap(lds, per_cu);
-    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
+    return gt == 18 ? foveal_kernel<VARIANT, MODE, EPB, 18, false> : gt == 14 ? foveal_kernel<VARIANT, MODE, EPB, 14, false>
+                                                                              : foveal_kernel<VARIANT, MODE, EPB, 0, false>;
+}
+
+static const void* foveal_kernel_of(const FovealPlan& p) {
+#define X(VARIANT, MODE, EPB) \
+    if (p.variant == VARIANT && p.mode == MODE && p.epb == EPB) return (const void*)foveal_kernel_of<VARIANT, MODE, EPB>(p.gt, p.ar);
+    LMAZE_FOVEAL_KERNELS(X)
+#undef X
+    return nullptr;
+}
+
+// One launch of foveal_kernel in `mode` over a.n envs as foveal_plan decides (lmaze_foveal_launch.h).  a.info != null: the
+// plan is described instead of queued.
+static hipError_t launch_foveal(const FovealArgs& a, int mode, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    FovealPlan p;
+    if (!foveal_plan(a, FovealForm{mode, false, false, 0}, p)) return hipErrorInvalidConfiguration;
     if (a.info) {
+        static const char* const modes[] = {"step", "reset", "setgoal", "planner"};
         char name[96];
-        snprintf(name, sizeof(name), "foveal_kernel<v%d, %s, %d, %d, %s>", VARIANT,
-                 MODE == FM_STEP ? "step" : (MODE == FM_RESET ? "reset" : (MODE == FM_SETGOAL ? "setgoal" : "planner")), EPB,
-                 (a.p.grid == 18 || a.p.grid == 14) ? a.p.grid : 0, a.auto_reset ? "fused-reset" : "plain");
-        describe_launch(a.info, name, EPB, (MODE == FM_STEP && per_cu >= 1 && per_cu <= 8 && lds > (size_t)EPB * 64) ? per_cu : 0, m, b.nt != 0,
-                        blocks, LMAZE_BLOCK, lds);
+        snprintf(name, sizeof(name), "foveal_kernel<v%d, %s, %d, %d, %s>", p.variant, modes[mode], p.epb, p.gt, p.ar ? "fused-reset" : "plain");
+        describe_launch(a.info, name, p.epb, p.per_cu, p.chunks, p.nt != 0, p.blocks, p.block, p.lds);
         return hipSuccess;
     }
-    if constexpr (MODE == FM_STEP) {
-        if (a.auto_reset) {
-            if (a.p.grid == 18) hipLaunchKernelGGL((foveal_kernel<VARIANT, MODE, EPB, 18, true>), grid, block, lds, s, b);
-            else if (a.p.grid == 14) hipLaunchKernelGGL((foveal_kernel<VARIANT, MODE, EPB, 14, true>), grid, block, lds, s, b);
-            else hipLaunchKernelGGL((foveal_kernel<VARIANT, MODE, EPB, 0, true>), grid, block, lds, s, b);
-            return hipGetLastError();
-        }
-    }
-    if (a.p.grid == 18) hipLaunchKernelGGL((foveal_kernel<VARIANT, MODE, EPB, 18, false>), grid, block, lds, s, b);
-    else if (a.p.grid == 14) hipLaunchKernelGGL((foveal_kernel<VARIANT, MODE, EPB, 14, false>), grid, block, lds, s, b);
-    else hipLaunchKernelGGL((foveal_kernel<VARIANT, MODE, EPB, 0, false>), grid, block, lds, s, b);
+    const void* kernel = foveal_kernel_of(p);
+    if (!kernel) return hipErrorInvalidConfiguration;
+    FovealArgs b = a;
+    b.nt = p.nt;
+    b.p.launch_hint = p.launch_hint;
+    void* args[] = {&b};
+    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
     return hipGetLastError();
-}
-
-// launch_hint bits 4-7 (plain step only): envs per workgroup, 2: 32 ... 5: 256; anything else = the default below
-template <int VARIANT>
-static bool launch_step_hinted(const FovealArgs& a, hipStream_t s, hipError_t& rc) {
-    switch ((a.p.launch_hint >> 4) & 15) {
-        case 2: rc = launch_foveal_one<VARIANT, FM_STEP, 32>(a, s); return true;
-        case 3: rc = launch_foveal_one<VARIANT, FM_STEP, 64>(a, s); return true;
-        case 4: rc = launch_foveal_one<VARIANT, FM_STEP, 128>(a, s); return true;
-        case 5: rc = launch_foveal_one<VARIANT, FM_STEP, 256>(a, s); return true;
-        default: return false;
-    }
-}
-
-template <int MODE>
-static hipError_t launch_foveal_mode(const FovealArgs& a0, hipStream_t s) {
-    if (a0.n == 0) return hipSuccess;
-    FovealArgs a = a0;
-    if (MODE == FM_STEP && a.p.launch_hint == 0 && (!a.auto_reset || a.p.variant == LMAZE_VARIANT_V5 || a.p.variant == LMAZE_VARIANT_V6)) {
-        // Default policy of the plain step in the streaming regime (observation larger than the Infinity Cache), as a
-        // hint.  Round 2, after workgroups learnt to take several chunks: on a box where every uncapped one-chunk launch of
-        // v1 sat at 78.5 us whatever the envs per workgroup (on other boxes 32 envs: 66.8-67.4), 32 envs x 3 chunks ran
-        // at 68.0 and x 2 at 68.7; v4 32 x 2 595 against 611; v2 64 envs at 5 workgroups per CU 88.7-89.1 on two
-        // boxes against 92-96 uncapped (32 x 2-3: 93-94).
-        const int C = a.p.variant == LMAZE_VARIANT_V1 ? 4 : (a.p.variant == LMAZE_VARIANT_V2 ? 5 : 7);
-        if ((size_t)a.n * C * W25 * 4 > kFovealStreamBytes) {
-            if (a.p.variant == LMAZE_VARIANT_V1) a.p.launch_hint = 0x220;
-            else if (a.p.variant == LMAZE_VARIANT_V2) a.p.launch_hint = 0x35;
-            // round 3 (window-only visit map): v4 128 envs per workgroup 305.8 us, 64 envs 311.2 (x 2 chunks 321, at 5 per
-            // CU 308.7), 32 envs 406; v5/v6 128 envs 446-449 (x 2 chunks 446), 64 envs 503-511
-            // (profiles/r03/foveal_sweep_{a,b}.jsonl, two boxes: v4 128 envs x 2 chunks 296.0 / 297.9 us, x 1 304-307, 64 x 2
-            // 299.7 / 301.3; v5/v6 128 envs 422.0 / 434.7, x 2 chunks 438.7 / 453.0, 64 envs 503-511)
-            else if (a.p.variant == LMAZE_VARIANT_V4) a.p.launch_hint = 0x140;
-            else a.p.launch_hint = 0x40;
-        }
-    }
-    if (MODE == FM_STEP && a.p.launch_hint == 0 && a.auto_reset && (size_t)a.n * W25 * 4 * 4 > kFovealStreamBytes) {
-        // fused reset (v1, v2, v4; one measured size each, below), same sweeps: v1 at 5 workgroups per CU 74.0 / 74.0 us
-        // against 74.2 / 76.8 uncapped; v2 two chunks 97.3 / 99.2 against 102.9 / 100.2; v4 two chunks 402-406 against 426-430
-        // (foveal_sweep_ar_a.jsonl, once the envs-per-workgroup hints applied to the fused reset too: v4 128 envs 377-378 us
-        // against 417 at 64 envs x 2 chunks; v2 128 x 2 97.3 against 99.3; v1 64 envs at 4-5 per CU 72.9-73.0 against 74.0)
-        if (a.p.variant == LMAZE_VARIANT_V1) a.p.launch_hint = 0x35;
-        else if (a.p.variant == LMAZE_VARIANT_V2 || a.p.variant == LMAZE_VARIANT_V4) a.p.launch_hint = 0x140;
-    }
-    if (MODE == FM_STEP) {
-        hipError_t rc = hipSuccess;
-        switch (a.p.variant) {
-            case LMAZE_VARIANT_V1: if (launch_step_hinted<LMAZE_VARIANT_V1>(a, s, rc)) return rc; break;
-            case LMAZE_VARIANT_V2: if (launch_step_hinted<LMAZE_VARIANT_V2>(a, s, rc)) return rc; break;
-            case LMAZE_VARIANT_V4: if (launch_step_hinted<LMAZE_VARIANT_V4>(a, s, rc)) return rc; break;
-            default: if (launch_step_hinted<LMAZE_VARIANT_V5>(a, s, rc)) return rc; break;
-        }
-    }
-    // Defaults, measured at 1M envs with a fresh action row per step (tools/foveal_hint_study.py, tools/foveal_decompose.py;
-    // us per step, envs per workgroup 32 / 64 / 128 / 256, round 2, after the render went to bit strings):
-    //   v1 (400 B of observation per env)  83 / 78-79 / 84 / 87;  64 envs at 5 workgroups per CU: 73.6-73.7 on three boxes
-    //   v2 (500 B)                        119 / 94-96 / 98-104 / 100-106; the cap is flat or worse
-    // The bare store loop of these kernels (no set-up, no phase 1) takes 88-93 us on v2 and 72-77 us on v1 whatever
-    // the chunk size and the cap: the kernels sit within 3-5 % of what their write pattern -- every workgroup streaming
-    // a private, env-aligned chunk -- reaches on this memory system (tools/wbench.hip: 6.1 TB/s for 32-KiB private
-    // chunks against 6.9 for a fill in which consecutive workgroups write consecutive 4-KiB pieces).
-    // After the set-up went to one barrier with ballot-built row masks (cheap enough for small workgroups), re-measured on
-    // two boxes: v1 32 envs per workgroup, uncapped 66.8-67.2 us (0.89 of peak; 64 x 4-5 per CU 71-73, 16 envs 105);
-    // v4 32 envs 589-652 against 600-675 with 64 on the same boxes; v2 and v5 stay at 64 (32: 102 / 487 against 88-92 / 441).
-    switch (a.p.variant) {
-        case LMAZE_VARIANT_V1:
-            if (MODE == FM_STEP && !a.auto_reset) return launch_foveal_one<LMAZE_VARIANT_V1, MODE, 32>(a, s);
-            return launch_foveal_one<LMAZE_VARIANT_V1, MODE, 64>(a, s);
-        case LMAZE_VARIANT_V2:
-            if (MODE == FM_STEP && a.auto_reset) return launch_foveal_one<LMAZE_VARIANT_V2, MODE, 256>(a, s);
-            return launch_foveal_one<LMAZE_VARIANT_V2, MODE, 64>(a, s);
-        case LMAZE_VARIANT_V5:
-        case LMAZE_VARIANT_V6:
-            return launch_foveal_one<LMAZE_VARIANT_V5, MODE, 64>(a, s);
-        default:
-            // 32 envs per workgroup: 41 KiB of visit maps streamed + 22 KiB of observation written
-            if (MODE == FM_STEP && !a.auto_reset) return launch_foveal_one<LMAZE_VARIANT_V4, MODE, 32>(a, s);
-            return launch_foveal_one<LMAZE_VARIANT_V4, MODE, 64>(a, s);
-    }
 }
 
 // ---- the one-launch rollout (lmaze_foveal_rollout): the open-loop family of lmaze_foveal_launch.h ----
@@ -382,57 +316,59 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void visit_load_kernel(uint32_t* tiles
 
 using namespace lmaze;
 
+// The variants a foveal entry takes
+enum { TAKES_V1 = 1, TAKES_V2_V4 = 2, TAKES_V5_V6 = 4, TAKES_ALL = 7 };
+static bool takes_variant(int takes, int variant) {
+    const bool v56 = variant == LMAZE_VARIANT_V5 || variant == LMAZE_VARIANT_V6;
+    return (takes & (variant == LMAZE_VARIANT_V1 ? TAKES_V1 : (v56 ? TAKES_V5_V6 : TAKES_V2_V4))) != 0;
+}
+
+// Every entry that queues foveal_kernel -- the plain, the fused and the two-level step, reset, setFovealGoal, plannerStep --
+// and, info != null, the step's describe (which has judged the params itself: nothing is refused here then, and bufs is
+// null).  mode: the FovealMode; takes: the variants the entry accepts; action: the mode's int32 input (action ids, ij,
+// goals); own: false if one of the entry's own pointers is missing; fr: its draws, fused reset and epoch words.  The
+// refusals stand in this order: check_foveal's, the entry's variant, its own pointers (LMAZE_E_NULL), the epoch words
+// (LMAZE_E_ALIGN); n == 0 returns 0 after all of them.
+static int foveal_entry(const LmazeFovealParams* params, int mode, int takes, const uint8_t* layouts, const int32_t* action,
+                        const int32_t* goal2, bool own, const uint8_t* mask, int32_t place, const FovealReset& fr,
+                        const LmazeFovealBuffers* bufs, int64_t n, LaunchInfo* info, void* stream) {
+    if (!info) {
+        const int rc = check_foveal(params, layouts, bufs, n);
+        if (rc) return rc;
+        if (!takes_variant(takes, params->variant)) return LMAZE_E_VARIANT;
+        if (!own) return LMAZE_E_NULL;
+        if (bad_epoch_words(fr.epoch_in, fr.epoch_out)) return LMAZE_E_ALIGN;
+    }
+    FovealArgs a = make_foveal_args(params, layouts, bufs, n, fr);
+    a.action = action;
+    a.goal2 = goal2;
+    a.mask = mask;
+    a.place = place;
+    a.info = info;
+    return (int)launch_foveal(a, mode, (hipStream_t)stream);
+}
+
 extern "C" {
 
 int lmaze_foveal_step(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* action,
                       const LmazeFovealBuffers* bufs, int64_t n, void* stream) {
-    int rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    if (!action) return LMAZE_E_NULL;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.action = action;
-    return (int)launch_foveal_mode<FM_STEP>(a, (hipStream_t)stream);
+    return foveal_entry(params, FM_STEP, TAKES_ALL, layouts, action, nullptr, action != nullptr, nullptr, 0,
+                        kNoFovealReset, bufs, n, nullptr, stream);
 }
 
 int lmaze_foveal_step_autoreset(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* action,
                                 const LmazeFovealBuffers* bufs, int64_t n, uint64_t seed, uint64_t epoch,
                                 int64_t env_base, const uint64_t* epoch_in_dev, uint64_t* epoch_out_dev, void* stream) {
-    int rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4)
-        return LMAZE_E_VARIANT;
-    if (!action) return LMAZE_E_NULL;
-    if (bad_epoch_words(epoch_in_dev, epoch_out_dev)) return LMAZE_E_ALIGN;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.action = action;
-    a.auto_reset = 1;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.epoch_in = epoch_in_dev;
-    a.epoch_out = epoch_out_dev;
-    return (int)launch_foveal_mode<FM_STEP>(a, (hipStream_t)stream);
+    return foveal_entry(params, FM_STEP, TAKES_V1 | TAKES_V2_V4, layouts, action, nullptr, action != nullptr, nullptr, 0,
+                        FovealReset{1, seed, epoch, env_base, epoch_in_dev, epoch_out_dev}, bufs, n, nullptr, stream);
 }
 
 int lmaze_v5_hier_step(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* action,
                        const int32_t* planner_goal, const LmazeFovealBuffers* bufs, int64_t n, uint64_t seed,
                        uint64_t epoch, int64_t env_base, const uint64_t* epoch_in_dev, uint64_t* epoch_out_dev,
                        void* stream) {
-    int rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V5 && params->variant != LMAZE_VARIANT_V6) return LMAZE_E_VARIANT;
-    if (!action || !planner_goal) return LMAZE_E_NULL;
-    if (bad_epoch_words(epoch_in_dev, epoch_out_dev)) return LMAZE_E_ALIGN;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.action = action;
-    a.goal2 = planner_goal;
-    a.auto_reset = 1;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    a.epoch_in = epoch_in_dev;
-    a.epoch_out = epoch_out_dev;
-    return (int)launch_foveal_mode<FM_STEP>(a, (hipStream_t)stream);
+    return foveal_entry(params, FM_STEP, TAKES_V5_V6, layouts, action, planner_goal, action && planner_goal, nullptr, 0,
+                        FovealReset{1, seed, epoch, env_base, epoch_in_dev, epoch_out_dev}, bufs, n, nullptr, stream);
 }
 
 // the argument checks of lmaze_foveal_rollout that need no buffers (answered before anything else is looked at)
@@ -471,13 +407,10 @@ static int foveal_rollout(const LmazeFovealParams* params, const uint8_t* layout
         if (v56 && params->grid != 18) return LMAZE_E_GRID;            // their recording form exists at G = 18 only
         if (params->variant == LMAZE_VARIANT_V1 && params->grid != 14) return LMAZE_E_GRID;   // v1's at G = 14 only
     }
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
+    FovealArgs a = make_foveal_args(params, layouts, bufs, n,
+                                    FovealReset{planner_goals || (!v56 && auto_reset), seed, epoch, env_base, nullptr, nullptr});
     a.action = actions;
     a.goal2 = planner_goals;
-    a.auto_reset = (planner_goals || (!v56 && auto_reset)) ? 1 : 0;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
     const FovealRoll ro{T, reward_t, done_t, foveal_reward_t, foveal_done_t};
     if (!rec) return (int)launch_foveal_rollout<FovealOpen>(a, ro, (hipStream_t)stream);
     const FovealRollObs rr{ro, slots > 0 ? rec->obs_t : nullptr, slots > 0 ? rec->obs_local_t : nullptr, rec->every};
@@ -508,31 +441,24 @@ static int describe_foveal_rollout(const LmazeFovealParams* params, int64_t n, i
     if (!params || !text_host || len < 1) return LMAZE_E_NULL;
     if (obs_every && *obs_every < 1) return LMAZE_E_COUNT;                 // the recording request first, as the entry point
     const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
-    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
-        return LMAZE_E_VARIANT;
-    if ((two_level != 0) != v56) return LMAZE_E_VARIANT;                   // v5/v6: the two-level step only
-    if (params->grid < FOV || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
-    if (n < 0 || n > LMAZE_MAX_ENVS || T < 0) return LMAZE_E_COUNT;
+    // v5/v6: the two-level step only.  The same code as an unknown variant's, which is judged next: their order does not show
+    if ((two_level != 0) != v56) return LMAZE_E_VARIANT;
+    int rc = check_foveal_params(params);
+    if (!rc) rc = T < 0 ? LMAZE_E_COUNT : check_foveal_count(n);
+    if (rc) return rc;
     text_host[0] = 0;
     if (n == 0 || T == 0) return 0;
     if (obs_every) {
         if (v56 && params->grid != 18) return LMAZE_E_GRID;                // their recording form exists at G = 18 only
         if (params->variant == LMAZE_VARIANT_V1 && params->grid != 14) return LMAZE_E_GRID;   // v1's at G = 14 only
     }
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    LmazeFovealBuffers none;
-    memset(&none, 0, sizeof(none));
-    FovealArgs a = make_foveal_args(params, nullptr, &none, n);     // nothing is dereferenced: the launcher fills `info`
-    a.auto_reset = (two_level || (!v56 && auto_reset)) ? 1 : 0;
+    LaunchInfo info{};
+    // nothing is dereferenced: the launcher fills `info`
+    FovealArgs a = make_foveal_args(params, nullptr, nullptr, n, FovealReset{two_level || (!v56 && auto_reset), 0, 0, 0, nullptr, nullptr});
     a.info = &info;
-    FovealRollObs rr;
-    memset(&rr, 0, sizeof(rr));
-    rr.T = T;
-    rr.every = obs_every ? *obs_every : 1;
-    const int rc = obs_every ? (int)launch_foveal_rollout<FovealOpen>(a, rr, nullptr)
-                             : (int)launch_foveal_rollout<FovealOpen>(a, static_cast<const FovealRoll&>(rr), nullptr);
+    const FovealRollObs rr{{T, nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, obs_every ? *obs_every : 1};
+    rc = obs_every ? (int)launch_foveal_rollout<FovealOpen>(a, rr, nullptr)
+                   : (int)launch_foveal_rollout<FovealOpen>(a, static_cast<const FovealRoll&>(rr), nullptr);
     return rc ? rc : format_launch(info, text_host, len, T);
 }
 
@@ -549,40 +475,20 @@ int lmaze_describe_foveal_rollout_obs(const LmazeFovealParams* params, int64_t n
 int lmaze_foveal_reset(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* mask, int32_t place,
                        uint64_t seed, uint64_t epoch, int64_t env_base, const LmazeFovealBuffers* bufs, int64_t n,
                        void* stream) {
-    int rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.mask = mask;
-    a.place = place;
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
-    return (int)launch_foveal_mode<FM_RESET>(a, (hipStream_t)stream);
+    return foveal_entry(params, FM_RESET, TAKES_ALL, layouts, nullptr, nullptr, true, mask, place,
+                        FovealReset{0, seed, epoch, env_base, nullptr, nullptr}, bufs, n, nullptr, stream);
 }
 
 int lmaze_v1_set_foveal_goal(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* ij,
                              const uint8_t* mask, const LmazeFovealBuffers* bufs, int64_t n, void* stream) {
-    int rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V1) return LMAZE_E_VARIANT;
-    if (!ij) return LMAZE_E_NULL;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.action = ij;
-    a.mask = mask;
-    if (n == 0) return 0;
-    return (int)launch_foveal_one<LMAZE_VARIANT_V1, FM_SETGOAL, 64>(a, (hipStream_t)stream);
+    return foveal_entry(params, FM_SETGOAL, TAKES_V1, layouts, ij, nullptr, ij != nullptr, mask, 0,
+                        kNoFovealReset, bufs, n, nullptr, stream);
 }
 
 int lmaze_v5_planner_step(const LmazeFovealParams* params, const uint8_t* layouts, const int32_t* goal,
                           const uint8_t* mask, const LmazeFovealBuffers* bufs, int64_t n, void* stream) {
-    int rc = check_foveal(params, layouts, bufs, n);
-    if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V5 && params->variant != LMAZE_VARIANT_V6) return LMAZE_E_VARIANT;
-    if (!goal) return LMAZE_E_NULL;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.action = goal;
-    a.mask = mask;
-    return (int)launch_foveal_mode<FM_PLANNER>(a, (hipStream_t)stream);
+    return foveal_entry(params, FM_PLANNER, TAKES_V5_V6, layouts, goal, nullptr, goal != nullptr, mask, 0,
+                        kNoFovealReset, bufs, n, nullptr, stream);
 }
 
 int lmaze_v6_safe_foveal_goal(const LmazeFovealParams* params, const uint8_t* layouts, uint64_t seed, uint64_t epoch,
@@ -590,13 +496,10 @@ int lmaze_v6_safe_foveal_goal(const LmazeFovealParams* params, const uint8_t* la
                               void* stream) {
     int rc = check_foveal(params, layouts, bufs, n);
     if (rc) return rc;
-    if (params->variant != LMAZE_VARIANT_V5 && params->variant != LMAZE_VARIANT_V6) return LMAZE_E_VARIANT;
+    if (!takes_variant(TAKES_V5_V6, params->variant)) return LMAZE_E_VARIANT;
     if (!out_goal) return LMAZE_E_NULL;
     if (n == 0) return 0;
-    FovealArgs a = make_foveal_args(params, layouts, bufs, n);
-    a.seed = seed;
-    a.epoch = epoch;
-    a.env_base = env_base;
+    const FovealArgs a = make_foveal_args(params, layouts, bufs, n, FovealReset{0, seed, epoch, env_base, nullptr, nullptr});
     if (!grid_ok((n + LMAZE_BLOCK - 1) / LMAZE_BLOCK)) return (int)hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(safe_goal_kernel, dim3((unsigned)((n + LMAZE_BLOCK - 1) / LMAZE_BLOCK)), dim3(LMAZE_BLOCK), 0,
                        (hipStream_t)stream, a, out_goal);
@@ -605,22 +508,15 @@ int lmaze_v6_safe_foveal_goal(const LmazeFovealParams* params, const uint8_t* la
 
 int lmaze_describe_foveal_step(const LmazeFovealParams* params, int64_t n, int32_t auto_reset, char* text_host, int32_t len) {
     if (!params || !text_host || len < 1) return LMAZE_E_NULL;
-    const bool v56 = params->variant == LMAZE_VARIANT_V5 || params->variant == LMAZE_VARIANT_V6;
-    if (params->variant != LMAZE_VARIANT_V1 && params->variant != LMAZE_VARIANT_V2 && params->variant != LMAZE_VARIANT_V4 && !v56)
-        return LMAZE_E_VARIANT;
-    if (params->grid < FOV || params->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (params->n_layouts < 1 || params->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
-    if (n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    int rc = check_foveal_params(params);
+    if (!rc) rc = check_foveal_count(n);
+    if (rc) return rc;
     text_host[0] = 0;
     if (n == 0) return 0;
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    LmazeFovealBuffers none;
-    memset(&none, 0, sizeof(none));
-    FovealArgs a = make_foveal_args(params, nullptr, &none, n);     // nothing is dereferenced: the launcher fills `info`
-    a.auto_reset = auto_reset ? 1 : 0;
-    a.info = &info;
-    const int rc = (int)launch_foveal_mode<FM_STEP>(a, nullptr);
+    LaunchInfo info{};
+    // nothing is dereferenced: the launcher fills `info`
+    rc = foveal_entry(params, FM_STEP, TAKES_ALL, nullptr, nullptr, nullptr, true, nullptr, 0, FovealReset{auto_reset, 0, 0, 0, nullptr, nullptr},
+                      nullptr, n, &info, nullptr);
     return rc ? rc : format_launch(info, text_host, len);
 }
 
@@ -632,8 +528,8 @@ int64_t lmaze_foveal_visit_bytes(int32_t grid, int64_t n) {
 
 static int check_visit(const LmazeFovealParams* p, const LmazeFovealBuffers* b, const void* other, int64_t n) {
     if (!p || !b || !other || !b->visit || !b->visit_clock) return LMAZE_E_NULL;
-    if (p->grid < FOV || p->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    if (!foveal_grid_ok(p->grid)) return LMAZE_E_GRID;
+    if (check_foveal_count(n)) return LMAZE_E_COUNT;
     if (((uintptr_t)b->visit & 63) || ((uintptr_t)other & 3)) return LMAZE_E_ALIGN;
     return 0;
 }

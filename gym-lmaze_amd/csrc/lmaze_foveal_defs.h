@@ -1,6 +1,6 @@
 // lmaze_foveal_defs.h -- what the translation units of the foveal kernels share (lmaze_foveal.hip: the step, reset and
 // open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip, lmaze_hier_policy.hip: the closed-loop rollouts): the kernel arguments, the device helpers
-// of lmaze_foveal_body.h, and the host-side checks and LDS sizing of their launchers (the rollouts' one launcher:
+// of lmaze_foveal_body.h, and the host-side checks and LDS sizing their launchers use (the one plan of every foveal launch:
 // lmaze_foveal_launch.h).  Not part of the C ABI.
 #ifndef LMAZE_FOVEAL_DEFS_H_
 #define LMAZE_FOVEAL_DEFS_H_
@@ -407,14 +407,16 @@ static inline size_t lds_limit() {
     return limit;
 }
 
-// dynamic LDS of foveal_body for EPB envs per workgroup
-template <int VARIANT>
-static size_t foveal_lds(const LmazeFovealParams& p, int epb) {
+// planes of a variant's observation
+static inline int foveal_channels(int variant) { return variant == LMAZE_VARIANT_V1 ? 4 : (variant == LMAZE_VARIANT_V2 ? 5 : 7); }
+
+// dynamic LDS of foveal_body for epb envs per workgroup; variant: the kernels' (v5 for v6)
+static inline size_t foveal_lds(int variant, const LmazeFovealParams& p, int epb) {
     const int cells = p.grid * p.grid;
-    const int L = VARIANT == LMAZE_VARIANT_V1 ? 1 : p.n_layouts;
+    const int L = variant == LMAZE_VARIANT_V1 ? 1 : p.n_layouts;
     // obs bit string 32 B + obs_local bit string 16 B + centres 8 B + flags 4 B + reset centre 4 B per env, row masks, layout characters, visit samples
     size_t lds = (size_t)epb * 64 + (3 * (size_t)L * p.grid + 2 * (size_t)p.grid) * 8 + (size_t)((L * cells + 15) & ~15);
-    if (VARIANT == LMAZE_VARIANT_V4 || VARIANT == LMAZE_VARIANT_V5)
+    if (variant == LMAZE_VARIANT_V4 || variant == LMAZE_VARIANT_V5)
         lds += (size_t)epb * (2 * W25 * 4 + 8);   // + visit samples, clock, whole-map list
     return lds;
 }
@@ -429,17 +431,32 @@ static inline size_t lds_for_cap(size_t lds, int per_cu) {
     return lds;
 }
 
+static inline bool foveal_grid_ok(int g) { return g >= FOV && g <= LMAZE_MAX_GRID; }
+
+// The refusals that need only the params, in this order: the variant, the grid side, the number of layouts.  The env count
+// and launch_hint's range are calls of their own, because the entry points order them differently (the step family answers
+// the count first, the closed-loop rollouts the hint; the describes do not look at the hint).
+static inline int check_foveal_params(const LmazeFovealParams* p) {
+    if (!p) return LMAZE_E_NULL;
+    if (p->variant != LMAZE_VARIANT_V1 && p->variant != LMAZE_VARIANT_V2 && p->variant != LMAZE_VARIANT_V4 &&
+        p->variant != LMAZE_VARIANT_V5 && p->variant != LMAZE_VARIANT_V6)
+        return LMAZE_E_VARIANT;
+    if (!foveal_grid_ok(p->grid)) return LMAZE_E_GRID;
+    if (p->n_layouts < 1 || p->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
+    return 0;
+}
+static inline int check_foveal_count(int64_t n) { return n < 0 || n > LMAZE_MAX_ENVS ? LMAZE_E_COUNT : 0; }
+static inline int check_foveal_hint(const LmazeFovealParams* p) { return (p->launch_hint & ~0x3ff) ? LMAZE_E_LAYOUT : 0; }
+
 static inline int check_foveal(const LmazeFovealParams* p, const uint8_t* layouts, const LmazeFovealBuffers* b, int64_t n) {
     if (!p || !layouts || !b) return LMAZE_E_NULL;
-    const bool v56 = p->variant == LMAZE_VARIANT_V5 || p->variant == LMAZE_VARIANT_V6;
-    if (p->variant != LMAZE_VARIANT_V1 && p->variant != LMAZE_VARIANT_V2 && p->variant != LMAZE_VARIANT_V4 && !v56)
-        return LMAZE_E_VARIANT;
-    if (p->grid < FOV || p->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
-    if (p->n_layouts < 1 || p->n_layouts > LMAZE_MAX_LAYOUTS) return LMAZE_E_LAYOUT;
-    if (n < 0 || n > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    int rc = check_foveal_params(p);
+    if (!rc) rc = check_foveal_count(n);
 #ifndef LMAZE_EXPERIMENT
-    if (p->launch_hint & ~0x3ff) return LMAZE_E_LAYOUT;
+    if (!rc) rc = check_foveal_hint(p);
 #endif
+    if (rc) return rc;
+    const bool v56 = p->variant == LMAZE_VARIANT_V5 || p->variant == LMAZE_VARIANT_V6;
     if (v56) {
         if (!b->fgoal_xy || !b->foveal_step_count || !b->foveal_reward || !b->foveal_done || !b->visit || !b->ball1_xy ||
             !b->fovea_xy || !b->last_xy || !b->foveal_goal || !b->obs_local)
@@ -455,25 +472,23 @@ static inline int check_foveal(const LmazeFovealParams* p, const uint8_t* layout
     return 0;
 }
 
-static inline FovealArgs make_foveal_args(const LmazeFovealParams* p, const uint8_t* layouts, const LmazeFovealBuffers* b, int64_t n) {
-    FovealArgs a;
-    a.p = *p;
-    a.b = *b;
-    a.layouts = layouts;
-    a.action = nullptr;
-    a.goal2 = nullptr;
-    a.mask = nullptr;
-    a.n = n;
-    a.place = 0;
-    a.seed = 0;
-    a.epoch = 0;
-    a.env_base = 0;
-    a.epoch_in = nullptr;
-    a.epoch_out = nullptr;
-    a.nt = 0;
-    a.auto_reset = 0;
-    a.info = nullptr;
-    return a;
+// The draws of an entry that resets or places (seed, epoch, env_base), its fused reset or two-level step (auto_reset) and the
+// device-resident epoch words (lmaze_common.h)
+struct FovealReset {
+    int32_t auto_reset;
+    uint64_t seed, epoch;
+    int64_t env_base;
+    const uint64_t* epoch_in;
+    uint64_t* epoch_out;
+};
+constexpr FovealReset kNoFovealReset{0, 0, 0, 0, nullptr, nullptr};
+
+// b null: a describe, which dereferences nothing -- the launcher fills a.info where it would have queued the kernel
+static inline FovealArgs make_foveal_args(const LmazeFovealParams* p, const uint8_t* layouts, const LmazeFovealBuffers* b, int64_t n,
+                                          const FovealReset& r = kNoFovealReset) {
+    // in FovealArgs' order: action, goal2, mask null, place 0, ..., nt 0, ..., info null
+    return FovealArgs{*p, b ? *b : LmazeFovealBuffers{}, layouts, nullptr, nullptr, nullptr, n, 0, r.seed, r.epoch, r.env_base,
+                      r.epoch_in, r.epoch_out, 0, r.auto_reset ? 1 : 0, nullptr};
 }
 
 }  // namespace lmaze

@@ -52,9 +52,8 @@ void foveal_rollout_policy_kernel(const FovealArgs a, const FovealRollObsPol ro)
 struct FovealPolicy {
     static constexpr const char* kKernel = "foveal_rollout_policy_kernel";
     static constexpr int kTableLds = kFovealPolicyLds;
-    template <int VARIANT>
     static size_t table_bytes(const LmazeFovealParams& p) {
-        return (size_t)(VARIANT == LMAZE_VARIANT_V1 ? 1 : p.n_layouts) * p.grid * p.grid;                   // one byte per key
+        return (size_t)(p.variant == LMAZE_VARIANT_V1 ? 1 : p.n_layouts) * p.grid * p.grid;                 // one byte per key
     }
     // the staged bytes follow the layout characters at once, rounded up to 16
     static size_t staged_lds(size_t base, size_t table) { return base + ((table + 15) & ~(size_t)15); }

@@ -52,9 +52,9 @@ void foveal_rollout_sample_kernel(const FovealArgs a, const FovealRollObsSmp ro)
 struct FovealSample {
     static constexpr const char* kKernel = "foveal_rollout_sample_kernel";
     static constexpr int kTableLds = kFovealSampleLds;
-    template <int VARIANT>
     static size_t table_bytes(const LmazeFovealParams& p) {
-        return (size_t)(VARIANT == LMAZE_VARIANT_V1 ? 1 : p.n_layouts) * p.grid * p.grid * (VARIANT == LMAZE_VARIANT_V1 ? 16 : 96);   // a multiple of 16
+        const bool v1 = p.variant == LMAZE_VARIANT_V1;
+        return (size_t)(v1 ? 1 : p.n_layouts) * p.grid * p.grid * (v1 ? 16 : 96);   // a multiple of 16
     }
     // the staged rows start on the next 16-byte boundary behind the layout characters
     static size_t staged_lds(size_t base, size_t table) { return ((base + 15) & ~(size_t)15) + table; }

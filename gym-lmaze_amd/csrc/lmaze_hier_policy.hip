@@ -56,7 +56,7 @@ struct FovealHierPolicy {
     static constexpr int kTableLds = kFovealPolicyLds;
     static constexpr int kTables = 2;
     // which tables are staged (FovealHier::in_lds) and the LDS sum with them
-    template <int VARIANT, class RO>
+    template <class RO>
     static int place(const LmazeFovealParams& p, const RO& ro, size_t& lds) {
         const size_t cbytes = (size_t)hier_controller_bytes(ro.hier.controller_key, p.n_layouts, p.grid);
         const size_t pbytes = (size_t)p.n_layouts * p.grid * p.grid;

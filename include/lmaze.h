@@ -565,7 +565,7 @@ typedef struct LmazeFovealParams {
                                    (1..8, 0 = no cap), bits 4-7 = envs per workgroup, 2: 32, 3: 64, 4: 128,
                                    5: 256 (anything else = default), bits 8-9 = chunks of that many envs a
                                    workgroup takes, minus one.  Performance only, never results
-                                   (lmaze_foveal.hip launch_foveal_mode); other bits 0.                  */
+                                   (lmaze_foveal_launch.h foveal_plan); other bits 0.                    */
 } LmazeFovealParams;
 
 /* Device pointers, one element per env; entries a variant does not use may be NULL. */

@@ -870,6 +870,68 @@ def test_visit_map_on_other_grid_sizes(variant, G):
             _same56(env, st, t)
 
 
+@pytest.mark.parametrize("variant", ["v1", "v6"])
+def test_reset_goal_and_planner_modes_on_a_generic_grid(variant):
+    """G = 13, neither 14 nor 18: the unspecialised instantiations of the modes beside the step -- reset, v1's setFovealGoal,
+    v5 / v6's plannerStep, and safeFovealGoal -- every call against the oracle.  70 envs: one full chunk of 64 and a ragged
+    one of 6."""
+    N, G, seed = 70, 13, 61
+    lays = _padded_layouts(G, 1 if variant == "v1" else 3, seed)
+    env = PKG.LmazeFovealVecEnv(N, variant=variant, layouts=lays, seed=seed, env_base=3)
+    assert env.grid == G
+    lay = _np(env.layouts)
+    rs = np.random.RandomState(seed)
+    epoch = 1
+    if variant == "v1":
+        p = O.foveal_params(O.VARIANT_V1, G, 1)
+        st = O.FovealState(O.VARIANT_V1, N, G)
+        O.foveal_reset(p, lay, None, 1, seed, 0, st, env_base=3)
+        _assert_same(env, st, "v1", "reset")
+        for t in range(4):
+            ij = rs.randint(0, 5, (N, 2)).astype(np.int32)
+            m = (rs.rand(N) < 0.6).astype(np.uint8)
+            env.set_foveal_goal(ij, mask=torch.from_numpy(m))
+            O.v1_set_foveal_goal(p, lay, ij, m, st)
+            _assert_same(env, st, "v1", ("setgoal", t))
+            a = rs.randint(0, 4, N).astype(np.int32)
+            env.step(torch.from_numpy(a))
+            O.foveal_step(p, lay, a, st)
+            _assert_same(env, st, "v1", ("step", t))
+            m = (rs.rand(N) < 0.5).astype(np.uint8)
+            env.reset(mask=torch.from_numpy(m))
+            O.foveal_reset(p, lay, m, 1, seed, epoch, st, env_base=3)
+            epoch += 1
+            _assert_same(env, st, "v1", ("reset", t))
+        return
+    p = O.foveal_params(O.VARIANT_V6, G, 3)
+    st = O.FovealState(O.VARIANT_V6, N, G)
+    O.v5_reset(p, lay, None, 1, seed, 0, st, env_base=3)
+    st.obs_local[...] = _np(env.obs_local)
+    _same56(env, st, "reset")
+    for t in range(6):
+        m = np.ones(N, np.uint8) if t == 0 else (st.foveal_done.astype(bool) | (rs.rand(N) < 0.3)).astype(np.uint8)
+        if t % 2 == 0:
+            goal = _np(env.safe_foveal_goal())
+            ref = O.v6_safe_foveal_goal(p, lay, seed, epoch, st, env_base=3)
+            epoch += 1
+            assert (goal == ref).all(), t
+        else:
+            goal = rs.randint(0, 25, N).astype(np.int32)
+        env.planner_step(goal, mask=torch.from_numpy(m))
+        O.v5_planner_step(p, lay, goal, m, st)
+        _same56(env, st, ("planner", t))
+        a = rs.randint(0, 4, N).astype(np.int32)
+        env.step(torch.from_numpy(a))
+        O.v5_step(p, lay, a, st)
+        _same56(env, st, ("step", t))
+        if t % 2 == 1:
+            m = (st.done.astype(bool) | (rs.rand(N) < 0.3)).astype(np.uint8)
+            env.reset(mask=torch.from_numpy(m))
+            O.v5_reset(p, lay, m, 1, seed, epoch, st, env_base=3)
+            epoch += 1
+            _same56(env, st, ("reset", t))
+
+
 def test_load_visit_takes_the_references_plane_mid_rollout():
     """lmaze_foveal_load_visit: the reference's own state[2] (v4_deepdecay fixture, cells below 2^-126 included) injected in
     the middle of the walk; the steps that follow match the recording, whole plane included."""
