@@ -151,85 +151,53 @@ static int check_recording(int32_t T, const void* slots, int32_t every) {
     return 0;
 }
 
-// ... and the request the launcher gets: the slots only where T / every > 0 of them are filled
-static RolloutRec recording(int32_t T, void* slots, int32_t every) {
-    return RolloutRec{every > 0 && T / every > 0 ? slots : nullptr, every};
-}
+// What the entry path judges of a rollout's action source: the pointer it needs, that pointer's alignment (1: none; 16: the
+// rows of the sampling thresholds), its key mode (the action rows have none) and whether a recording request comes with it
+struct SourceChecks { const void* rows; uintptr_t align; int32_t key_mode; bool recording; };
+static SourceChecks checks_of(const ActionRows& s) { return {s.actions, 1, 0, s.recording}; }
+static SourceChecks checks_of(const PolicyTable& t) { return {t.table, 1, t.key_mode, true}; }
+static SourceChecks checks_of(const SampleTable& t) { return {t.table, 16, t.key_mode, true}; }
 
-// lmaze_rollout and its three siblings after the recording request's own checks: T == 0 or n == 0 answered once the
-// params are valid, before any pointer is looked at; u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only
-static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
+// Every grid rollout entry and, with info != null, its describe (then neither the recording request nor any pointer is
+// judged).  slots / every: the recording request as the caller gave it.  The refusals stand in this order: the recording
+// request; the params, the variant and with u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only; T; the key mode -- a
+// bad argument is refused whether or not there is anything to do --; T == 0 or n == 0 answered before any pointer is looked
+// at; LMAZE_E_NULL with the source among the pointers; LMAZE_E_ALIGN with the source's alignment among the others.
+template <class Source>
+static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const Source& src, int32_t T, int32_t* ball_xy,
                         int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8,
                         float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
-                        int64_t env_base, const RolloutRec* rec, void* stream) {
-    int rc = check_grid_params(params, n, TAKES_BOTH, u8);
+                        int64_t env_base, void* slots, int32_t every, LaunchInfo* info, void* stream) {
+    const SourceChecks c = checks_of(src);
+    int rc = info || !c.recording ? 0 : check_recording(T, slots, every);
+    if (!rc) rc = check_grid_params(params, n, TAKES_BOTH, u8);
     if (rc) return rc;
     if (T < 0) return LMAZE_E_COUNT;
-    if (T == 0 || n == 0) return 0;                        // nothing to do, nothing read
-    rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, actions && step_count && reward && done);
-    if (rc) return rc;
-    const StepArgs a = grid_args(params, layout, actions, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n,
-                                 auto_reset, seed, epoch, env_base);
-    return (int)launch_rollout(params->variant, a, params->layout_mode, actions, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
-}
-
-// The refusals of the closed-loop rollouts (lmaze_rollout_policy / lmaze_rollout_sample and their _u8 forms) after the
-// recording request's own checks: grid_rollout's in its order, the key mode where T is judged (a bad argument is refused
-// whether or not there is anything to do), the table among the pointers and, where it has an alignment (the 16-byte rows
-// of the sampling thresholds), among the alignment refusals.  *go: something is left to queue or describe.
-static int check_closed_loop(const LmazeParams* params, const uint8_t* layout, const void* table, uintptr_t table_align,
-                             int32_t key_mode, int32_t T, const int32_t* ball_xy, const int32_t* goal_xy, const int32_t* step_count,
-                             const float* reward, const uint8_t* done, const void* obs, bool u8, int64_t n, bool describing, bool* go) {
-    *go = false;
-    int rc = check_grid_params(params, n, TAKES_BOTH, u8);
-    if (rc) return rc;
-    if (T < 0) return LMAZE_E_COUNT;
-    if (key_mode != 0 && key_mode != 1) return LMAZE_E_COUNT;
-    if (key_mode == 1 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;   // v0 keeps no goal_xy
+    if (c.key_mode != 0 && c.key_mode != 1) return LMAZE_E_COUNT;
+    if (c.key_mode == 1 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;   // v0 keeps no goal_xy
     if (T == 0 || n == 0) return 0;                                // nothing to do, nothing read
-    if (!describing) {
-        rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, table && step_count && reward && done, table, table_align);
-        if (rc) return rc;
-    }
-    *go = true;
-    return 0;
-}
-
-// lmaze_rollout_policy / lmaze_rollout_sample and their _u8 forms, and with info != null their describes (then only the
-// params, the counts and key_mode are judged).  tab: a PolicyTable or a SampleTable; an entry's size is the alignment the
-// table needs (1 or 16).  slots / every: the recording request as the caller gave it, refused first.
-template <class Table>
-static int grid_rollout_closed(const LmazeParams* params, const uint8_t* layout, const Table& tab, int32_t T, int32_t* ball_xy,
-                               int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs,
-                               bool u8, float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed,
-                               uint64_t epoch, int64_t env_base, void* slots, int32_t every, LaunchInfo* info, void* stream) {
-    int rc = info ? 0 : check_recording(T, slots, every);
-    if (rc) return rc;
-    bool go;
-    rc = check_closed_loop(params, layout, tab.table, sizeof(*tab.table), tab.key_mode, T, ball_xy, goal_xy, step_count, reward, done, obs,
-                           u8, n, info != nullptr, &go);
-    if (!go) return rc;
+    if (!info && (rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, c.rows && step_count && reward && done, c.rows, c.align)) != 0)
+        return rc;
     StepArgs a = grid_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
                            seed, epoch, env_base);
     a.info = info;
-    return (int)launch_rollout_closed(params->variant, a, params->layout_mode, tab, T, reward_t, done_t, (hipStream_t)stream,
-                                      recording(T, slots, every), u8);
+    const RolloutRec rec{every > 0 && T / every > 0 ? slots : nullptr, every};   // the slots only where some are filled
+    return (int)launch_rollout(params->variant, a, params->layout_mode, src, T, reward_t, done_t, (hipStream_t)stream, rec, u8);
 }
 
-// lmaze_describe_rollout_policy / lmaze_describe_rollout_sample
-template <class Table>
-static int describe_rollout_closed(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
-                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
-    if (obs_every < 0) return LMAZE_E_COUNT;
+// lmaze_describe_rollout and its closed-loop kin from the text buffer on: the line of what grid_rollout would queue, or an
+// empty one.  with_obs 2: the narrow planes (the _u8 entry points).
+template <class Source>
+static int describe_rollout(const LmazeParams* params, const Source& src, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                            int32_t obs_every, char* text_host, int32_t len) {
     if (!text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
-    const bool u8 = with_obs == 2;   // the narrow planes (the _u8 entry points)
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
+    const bool u8 = with_obs == 2;
+    LaunchInfo info{};
     // nothing is dereferenced: fabricated, aligned addresses stand for the buffers whose presence decides
-    const int rc = grid_rollout_closed(params, nullptr, Table{nullptr, nullptr, nullptr, key_mode, 0}, T, nullptr, nullptr, nullptr,
-                                       nullptr, nullptr, nullptr, with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8,
-                                       nullptr, nullptr, n, auto_reset, 0, 0, 0, reinterpret_cast<void*>(32), obs_every, &info, nullptr);
+    const int rc = grid_rollout(params, nullptr, src, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, nullptr, nullptr, n, auto_reset, 0, 0, 0,
+                                reinterpret_cast<void*>(32), obs_every, &info, nullptr);
     if (rc || n == 0 || T == 0) return rc;
     return format_launch(info, text_host, len);
 }
@@ -445,36 +413,32 @@ int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_
                   int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
                   float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                   int64_t env_base, void* stream) {
-    return grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t,
-                        done_t, n, auto_reset, seed, epoch, env_base, nullptr, stream);
+    return grid_rollout(params, layout, ActionRows{actions, false}, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
+                        reward_t, done_t, n, auto_reset, seed, epoch, env_base, nullptr, 0, nullptr, stream);
 }
 
 int lmaze_rollout_obs(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                       int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, int32_t* obs,
                       float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                       int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream) {
-    const int rc = check_recording(T, obs_t, obs_every);
-    const RolloutRec rec = recording(T, obs_t, obs_every);
-    return rc ? rc : grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
-                                  reward_t, done_t, n, auto_reset, seed, epoch, env_base, &rec, stream);
+    return grid_rollout(params, layout, ActionRows{actions, true}, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false,
+                        reward_t, done_t, n, auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_rollout_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
                      float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                      int64_t env_base, void* stream) {
-    return grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t,
-                        done_t, n, auto_reset, seed, epoch, env_base, nullptr, stream);
+    return grid_rollout(params, layout, ActionRows{actions, false}, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
+                        reward_t, done_t, n, auto_reset, seed, epoch, env_base, nullptr, 0, nullptr, stream);
 }
 
 int lmaze_rollout_obs_u8(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,
                          int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, uint8_t* obs8,
                          float* reward_t, uint8_t* done_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
                          int64_t env_base, uint8_t* obs_t8, int32_t obs_every, void* stream) {
-    const int rc = check_recording(T, obs_t8, obs_every);
-    const RolloutRec rec = recording(T, obs_t8, obs_every);
-    return rc ? rc : grid_rollout(params, layout, actions, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
-                                  reward_t, done_t, n, auto_reset, seed, epoch, env_base, &rec, stream);
+    return grid_rollout(params, layout, ActionRows{actions, true}, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true,
+                        reward_t, done_t, n, auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
 }
 
 int lmaze_rollout_policy(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
@@ -483,8 +447,8 @@ int lmaze_rollout_policy(const LmazeParams* params, const uint8_t* layout, const
                          int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
                          int32_t* obs_t, int32_t obs_every, void* stream) {
     const PolicyTable tab{policy, actions_t, key_t, key_mode, epsilon_u32};
-    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t,
-                               n, auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_rollout_policy_u8(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, int32_t key_mode,
@@ -493,13 +457,14 @@ int lmaze_rollout_policy_u8(const LmazeParams* params, const uint8_t* layout, co
                             int32_t* key_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base,
                             uint8_t* obs_t8, int32_t obs_every, void* stream) {
     const PolicyTable tab{policy, actions_t, key_t, key_mode, epsilon_u32};
-    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t, done_t,
-                               n, auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
 }
 
 int lmaze_describe_rollout_policy(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
-    return describe_rollout_closed<PolicyTable>(params, n, T, auto_reset, with_obs, obs_every, key_mode, text_host, len);
+    const PolicyTable tab{nullptr, nullptr, nullptr, key_mode, 0};   // obs_every and the text buffer before the params
+    return obs_every < 0 ? LMAZE_E_COUNT : describe_rollout(params, tab, n, T, auto_reset, with_obs, obs_every, text_host, len);
 }
 
 int lmaze_foveal_rollout_policy(const LmazeFovealParams* params, const uint8_t* layouts, const uint8_t* policy,
@@ -553,8 +518,8 @@ int lmaze_rollout_sample(const LmazeParams* params, const uint8_t* layout, const
                          int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t, int32_t obs_every,
                          void* stream) {
     const SampleTable tab{reinterpret_cast<const sample_row_t*>(thresholds), actions_t, key_t, key_mode, 0};
-    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t,
-                               n, auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
 }
 
 int lmaze_rollout_sample_u8(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t key_mode, int32_t T,
@@ -563,13 +528,14 @@ int lmaze_rollout_sample_u8(const LmazeParams* params, const uint8_t* layout, co
                             int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, uint8_t* obs_t8,
                             int32_t obs_every, void* stream) {
     const SampleTable tab{reinterpret_cast<const sample_row_t*>(thresholds), actions_t, key_t, key_mode, 0};
-    return grid_rollout_closed(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t, done_t,
-                               n, auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs8, true, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t8, obs_every, nullptr, stream);
 }
 
 int lmaze_describe_rollout_sample(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
-    return describe_rollout_closed<SampleTable>(params, n, T, auto_reset, with_obs, obs_every, key_mode, text_host, len);
+    const SampleTable tab{nullptr, nullptr, nullptr, key_mode, 0};
+    return obs_every < 0 ? LMAZE_E_COUNT : describe_rollout(params, tab, n, T, auto_reset, with_obs, obs_every, text_host, len);
 }
 
 int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t, int32_t T,
@@ -635,26 +601,14 @@ int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* t
 
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
                            char* text_host, int32_t len) {
+    // this describe's own order: the params, the variant and T before the text buffer, and the narrow planes' refusals
+    // (grid_rollout's) only when there is something to do
     int rc = check_grid_params(params, n, TAKES_BOTH, false);
-    if (rc) return rc;
-    if (T < 0) return LMAZE_E_COUNT;
-    if (!text_host || len < 1) return LMAZE_E_NULL;
+    if (!rc && T < 0) rc = LMAZE_E_COUNT;
+    if (rc || !text_host || len < 1) return rc ? rc : LMAZE_E_NULL;
     text_host[0] = 0;
     if (n == 0 || T == 0) return 0;
-    const bool u8 = with_obs == 2;   // the narrow planes (lmaze_rollout_u8 / lmaze_rollout_obs_u8)
-    if (u8 && (rc = check_narrow(params)) != 0) return rc;
-    LaunchInfo info;
-    memset(&info, 0, sizeof(info));
-    // nothing is dereferenced: the launcher fills `info` where it would have queued the rollout (fabricated, aligned
-    // addresses stand for the buffers whose presence decides)
-    StepArgs a = grid_args(params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           with_obs == 1 || u8 ? reinterpret_cast<void*>(16) : nullptr, u8, n, auto_reset, 0, 0, 0);
-    a.info = &info;
-    const RolloutRec rec = recording(T, reinterpret_cast<void*>(32), obs_every);
-    rc = (int)launch_rollout(params->variant, a, params->layout_mode, nullptr, T, nullptr, nullptr, nullptr,
-                             obs_every >= 0 ? &rec : nullptr, u8);
-    if (rc) return rc;
-    return format_launch(info, text_host, len);
+    return describe_rollout(params, ActionRows{nullptr, obs_every >= 0}, n, T, auto_reset, with_obs, obs_every, text_host, len);
 }
 
 int lmaze_reset(const LmazeParams* params, const uint8_t* layout, const uint8_t* mask, uint64_t seed,

@@ -108,20 +108,19 @@ inline bool grid_ok(int64_t blocks) { return blocks >= 1 && blocks <= (int64_t)0
 
 // One step (do_step) or one render of the planes only.  u8: the narrow planes in a.obs8 (shared layouts, G >= 4) instead of a.obs.
 hipError_t launch_step(int variant, bool do_step, const StepArgs& a, int layout_mode, bool u8, hipStream_t s);
-// T steps of a grid rollout (lmaze_rollout and its siblings).  rec: the recording request (lmaze_rollout_obs /
-// lmaze_rollout_obs_u8) -- obs_t the slots, int32[T / every, N, G, G] (u8: uint8, slots that may start at any byte past
-// slot 0), null when every == 0 or T / every == 0; every = k >= 1, or 0 for the final planes only.  A null RolloutRec* is
-// the plain rollout.  u8: the narrow planes in a.obs8 (shared layouts, G >= 4) instead of a.obs.
+// T steps of a grid rollout, by where its actions come from: launch_rollout(..., source, ...) with ActionRows (the open
+// loop: lmaze_rollout and its siblings), a PolicyTable or a SampleTable.  rec: the recording request -- obs_t the slots,
+// int32[T / every, N, G, G] (u8: uint8, slots that may start at any byte past slot 0), null when every == 0 or T / every == 0;
+// every = k >= 1, or 0 for the final planes only.  u8: the narrow planes in a.obs8 (shared layouts, G >= 4) instead of a.obs.
 struct RolloutRec {
     void* obs_t;
     int32_t every;
 };
-hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
-                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec, bool u8);
+struct ActionRows { const int32_t* actions; bool recording; };   // int32[T, N]; recording false: the plain rollout, rec is not read
 // The closed-loop grid rollouts: a table policy stands where the action tensor stood, and the optional rows int32[T,N] of
 // the actions taken and their keys.  The table structs are what the kernels take (members of their argument structs): the
-// ABI fills them, the launcher sets what it decides itself (SampleTable::staged).  rec is never null: these rollouts store
-// planes on recorded steps and after the last one only.  Always one launch.
+// ABI fills them, the launcher sets what it decides itself (SampleTable::staged).  These rollouts store planes on recorded
+// steps and after the last one only.  Always one launch.
 // lmaze_rollout_policy / lmaze_rollout_policy_u8: the tabular epsilon-greedy policy
 struct PolicyTable {
     const uint8_t* table;     // uint8[G^2] (key_mode 0) or uint8[G^4] (key_mode 1): the greedy action id of each key
@@ -140,10 +139,12 @@ struct SampleTable {
     int32_t key_mode;            // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
     int32_t staged;              // != 0: the workgroup copies the ball-keyed table into LDS and reads it there
 };
-hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T,
-                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
-hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const SampleTable& tab, int32_t T,
-                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const ActionRows& src, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const SampleTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
 // Discounted returns-to-go over trajectory rows (lmaze_returns, lmaze_aux.hip)
 hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t,
                           int32_t T, int64_t n, hipStream_t s);

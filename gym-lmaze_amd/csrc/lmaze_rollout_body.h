@@ -7,8 +7,9 @@
 // (RolloutPolicyArgs, u8: RolloutPolicy8Args; REC true): no action row is read -- after the fused reset the lane that owns
 // the env looks its action up by the env's key (policy_act) -- and the ball-keyed table sits in LDS behind the body's other
 // arrays.  The lines of the open-loop forms are the #else branches, untouched.  LMAZE_ROLLOUT_POLICY == 2: the sampling
-// forms (RolloutSampleArgs, u8: RolloutSample8Args) -- the same lines, but the table holds one sample_row_t of thresholds per key
-// and sits, when staged, on the first 16-byte boundary behind the other arrays.  Not a header of its own.
+// forms (RolloutSampleArgs, u8: RolloutSample8Args) -- the same lines, but the table holds one sample_row_t of thresholds per key.
+// Where each array of bodies 2-4 lies in LDS is lmaze_rollout_lds.h's to say, the text the host sizes the launch from (L; the
+// table by the form's kind, which moves no other array).  Not a header of its own.
 #ifndef LMAZE_ROLLOUT_BODY
 #error "lmaze_rollout_body.h is the body of the rollout kernels: it is included only inside them, in lmaze_step.hip"
 #endif
@@ -86,12 +87,13 @@
 #elif LMAZE_ROLLOUT_BODY == 2
     constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
     const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
-    extern __shared__ int4 lds4[];
-    int* pat = reinterpret_cast<int*>(lds4);                                  // [CELLS] plane bits without ball / goal
-    int* ballflat = pat + CELLS;                                              // [EPB]
-    int* goalflat = ballflat + EPB;                                           // [EPB]
-    uint8_t* lay = reinterpret_cast<uint8_t*>(goalflat + EPB);                // [CELLS]
-    uint16_t* spawn = reinterpret_cast<uint16_t*>(lay + ((CELLS + 15) & ~15));   // [CELLS] accepted spawn cells, row-major
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const LmazeRolloutLds L = lmaze_rollout_lds_shared(CELLS, EPB, LMAZE_TAB_NONE);
+    int* pat = reinterpret_cast<int*>(lds + L.pat);                           // [CELLS] plane bits without ball / goal
+    int* ballflat = reinterpret_cast<int*>(lds + L.ballflat);                 // [EPB]
+    int* goalflat = reinterpret_cast<int*>(lds + L.goalflat);                 // [EPB]
+    uint8_t* lay = reinterpret_cast<uint8_t*>(lds + L.lay);                   // [CELLS]
+    uint16_t* spawn = reinterpret_cast<uint16_t*>(lds + L.spawn);             // [CELLS] accepted spawn cells, row-major
     __shared__ int spawn_count_s;
 
     const int tid = threadIdx.x;
@@ -101,13 +103,13 @@
     const int64_t e = blockbase + tid;
 #ifdef LMAZE_ROLLOUT_POLICY
 #if LMAZE_ROLLOUT_POLICY == 2
-    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds4) + ((CELLS * 4 + EPB * 8 + ((CELLS + 15) & ~15) + ((CELLS * 2 + 15) & ~15) + 15) >> 4);   // [CELLS] staged thresholds
+    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds + lmaze_rollout_lds_shared(CELLS, EPB, LMAZE_TAB_ROWS).tab);   // [CELLS] staged thresholds
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
     int hits = 0;
     if (ro.pol.staged)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
 #else
-    uint8_t* tab = reinterpret_cast<uint8_t*>(spawn) + ((CELLS * 2 + 15) & ~15);   // [CELLS] the ball-keyed table
+    uint8_t* tab = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_shared(CELLS, EPB, LMAZE_TAB_BYTES).tab);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
     int hits = 0;
     if (ro.pol.key_mode == 0)
@@ -168,10 +170,11 @@
 #elif LMAZE_ROLLOUT_BODY == 3
     constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
     const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
-    extern __shared__ int4 lds4[];
-    int* ballflat = reinterpret_cast<int*>(lds4);                             // [EPB] cell of the ball
-    int* goalflat = ballflat + EPB;                                           // [EPB]
-    uint8_t* lays = reinterpret_cast<uint8_t*>(goalflat + EPB);               // [EPB * CELLS]
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const LmazeRolloutLds L = lmaze_rollout_lds_perenv(CELLS, EPB, LMAZE_TAB_NONE);
+    int* ballflat = reinterpret_cast<int*>(lds + L.ballflat);                 // [EPB] cell of the ball
+    int* goalflat = reinterpret_cast<int*>(lds + L.goalflat);                 // [EPB]
+    uint8_t* lays = reinterpret_cast<uint8_t*>(lds + L.lay);                  // [EPB * CELLS]
 
     const int tid = threadIdx.x;
     const int64_t blockbase = (int64_t)blockIdx.x * EPB;
@@ -180,13 +183,13 @@
     const int64_t e = blockbase + tid;
 #ifdef LMAZE_ROLLOUT_POLICY
 #if LMAZE_ROLLOUT_POLICY == 2
-    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds4) + ((EPB * 8 + ((EPB * CELLS + 15) & ~15) + 15) >> 4);   // [CELLS] staged thresholds
+    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds + lmaze_rollout_lds_perenv(CELLS, EPB, LMAZE_TAB_ROWS).tab);   // [CELLS] staged thresholds
     EnvState s = policy_load<VARIANT>(a, e, live);
     int hits = 0;
     if (ro.pol.staged)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
 #else
-    uint8_t* tab = lays + ((EPB * CELLS + 15) & ~15);                         // [CELLS] the ball-keyed table
+    uint8_t* tab = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_perenv(CELLS, EPB, LMAZE_TAB_BYTES).tab);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);
     int hits = 0;
     if (ro.pol.key_mode == 0)
@@ -254,13 +257,14 @@
     // spawn list), the same transition, and each step's render through rollout_render_u8
     constexpr bool V3 = VARIANT == LMAZE_VARIANT_V3;
     const int G = a.grid, CELLS = G * G, EPB = a.envs_per_block;
-    const int PW = (2 * CELLS + 16 + 3) >> 2;                                 // dwords of one shifted copy, as step_shared_u8_kernel
-    extern __shared__ int4 lds4[];
-    uint32_t* patw = reinterpret_cast<uint32_t*>(lds4);                       // [4][PW] copy s = the doubled pattern from byte s
-    int* ballflat = reinterpret_cast<int*>(patw + 4 * PW);                    // [EPB + 1]
-    int* goalflat = ballflat + EPB + 1;                                       // [EPB + 1]
-    uint16_t* spawn = reinterpret_cast<uint16_t*>(goalflat + EPB + 1);        // [CELLS] accepted spawn cells, row-major
-    uint8_t* lay = reinterpret_cast<uint8_t*>(spawn + ((CELLS + 1) & ~1));    // [CELLS]
+    const int PW = lmaze_rollout_u8_pw(CELLS);                                // dwords of one shifted copy, as step_shared_u8_kernel
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const LmazeRolloutLds L = lmaze_rollout_lds_u8(CELLS, EPB, LMAZE_TAB_NONE);
+    uint32_t* patw = reinterpret_cast<uint32_t*>(lds + L.pat);                // [4][PW] copy s = the doubled pattern from byte s
+    int* ballflat = reinterpret_cast<int*>(lds + L.ballflat);                 // [EPB + 1]
+    int* goalflat = reinterpret_cast<int*>(lds + L.goalflat);                 // [EPB + 1]
+    uint16_t* spawn = reinterpret_cast<uint16_t*>(lds + L.spawn);             // [CELLS] accepted spawn cells, row-major
+    uint8_t* lay = reinterpret_cast<uint8_t*>(lds + L.lay);                   // [CELLS]
     __shared__ int spawn_count_s;
 
     const int tid = threadIdx.x;
@@ -270,13 +274,13 @@
     const int64_t e = blockbase + tid;
 #ifdef LMAZE_ROLLOUT_POLICY
 #if LMAZE_ROLLOUT_POLICY == 2
-    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds4) + ((4 * PW * 4 + 2 * (EPB + 1) * 4 + ((CELLS + 1) & ~1) * 2 + CELLS + 15) >> 4);   // [CELLS] staged thresholds
+    sample_row_t* tab = reinterpret_cast<sample_row_t*>(lds + lmaze_rollout_lds_u8(CELLS, EPB, LMAZE_TAB_ROWS).tab);   // [CELLS] staged thresholds
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
     int hits = 0;
     if (ro.pol.staged)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
 #else
-    uint8_t* tab = lay + CELLS;                                               // [CELLS] the ball-keyed table
+    uint8_t* tab = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_u8(CELLS, EPB, LMAZE_TAB_BYTES).tab);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
     int hits = 0;
     if (ro.pol.key_mode == 0)

@@ -26,6 +26,7 @@
 
 #include "lmaze_common.h"
 #include "lmaze_policy_table.h"
+#include "lmaze_rollout_lds.h"
 
 namespace lmaze {
 
@@ -1615,30 +1616,16 @@ struct RolloutPlan {
     bool nt;                  // the recording form's slot stores: non-temporal
 };
 
-// LDS of rollout_shared_u8_kernel: the four shifted pattern copies, ballflat / goalflat, the spawn list and the layout
-static size_t rollout_u8_lds_bytes(int G, int epb) {
-    const int cells = G * G, pw = (2 * cells + 16 + 3) >> 2;
-    return ((size_t)4 * pw * 4 + 2 * (size_t)(epb + 1) * 4 + (size_t)((cells + 1) & ~1) * 2 + (size_t)cells + 15) & ~(size_t)15;
-}
-
-// LDS of a closed-loop form's ball-keyed table, behind its body's other arrays (kept for the goal-conditioned table too,
-// which is read from global memory: one size per shape)
-static size_t policy_table_lds_bytes(int G) { return (size_t)((G * G + 15) & ~15); }
-
 // T >= 1 steps of a.n >= 1 envs (rec != null: the recording form; u8: the narrow planes, shared layouts).  int32 planes: ONE
 // launch (shared layouts: rollout_shared_wave8_kernel for on-die 8x8, rollout_shared_kernel otherwise; per-env layouts:
 // rollout_perenv_kernel); T launches of the step kernel only for T = 1 or when launch_hint bit 8 forces streaming stores.
 // u8: ONE launch of rollout_shared_u8_kernel for any T and any batch size.
-// pol: the closed-loop forms (rec != null) -- always one launch of a workgroup kernel (no T-launch fallback, no wave8 form:
-// on-die 8x8 goes through rollout_shared_kernel), the recording form's envs per workgroup, and the ball-keyed table in
-// every LDS size, the fits and clamps below included.  PLAN_SAMPLE_LDS / PLAN_SAMPLE_GLOBAL: the sampling forms, planned
-// as the closed-loop ones; the staged threshold table (16 G^2 bytes, on a 16-byte boundary behind the other arrays) is
-// counted in the same places, a table read from global memory reserves nothing.
-enum { PLAN_OPEN = 0, PLAN_POLICY = 1, PLAN_SAMPLE_LDS = 2, PLAN_SAMPLE_GLOBAL = 3 };
-static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8, int pol = PLAN_OPEN) {
+// pol: the table kind of lmaze_rollout_lds.h, which says what each body keeps in LDS and where.  Not LMAZE_TAB_NONE: the
+// closed-loop forms (rec != null) -- always one launch of a workgroup kernel (no T-launch fallback, no wave8 form: on-die
+// 8x8 goes through rollout_shared_kernel), the recording form's envs per workgroup, and the table in every LDS size, the
+// fits and clamps below included.
+static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, const RolloutRec* rec, bool u8, int pol = LMAZE_TAB_NONE) {
     const int cells = a.grid * a.grid;
-    const bool sample = pol == PLAN_SAMPLE_LDS || pol == PLAN_SAMPLE_GLOBAL;
-    const size_t tab = pol == PLAN_POLICY ? policy_table_lds_bytes(a.grid) : pol == PLAN_SAMPLE_LDS ? (size_t)16 * cells : 0;
     const int hint_epb = (a.launch_hint >> 12) & 7;       // bits 12-14 = k > 0 ask for 4 << (k - 1) envs per workgroup
     // the recording form streams its slots wherever the batch sits; on-die means the batch's planes fit the caches
     const bool planes = a.obs != nullptr || (rec && rec->obs_t);
@@ -1662,10 +1649,10 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
         if (hint_epb) epb = 4 << (hint_epb - 1);
         if (epb < 16) epb = 16;
         if (epb > LMAZE_BLOCK) epb = LMAZE_BLOCK;
-        while (epb > 16 && rollout_u8_lds_bytes(a.grid, epb) + tab > ((size_t)64 << 10)) epb >>= 1;
+        while (epb > 16 && lmaze_rollout_lds_u8(cells, epb, pol).total > (64 << 10)) epb >>= 1;
         p.family = RO_U8;
         p.epb = epb;
-        p.lds = rollout_u8_lds_bytes(a.grid, epb) + tab;
+        p.lds = (size_t)lmaze_rollout_lds_u8(cells, epb, pol).total;
     } else if (!pol && layout_mode == LMAZE_LAYOUT_SHARED && a.grid == 8 && (!planes || !beyond_caches(a.n, 64)) &&
                (a.launch_hint & 0x100) == 0) {
         // on-die 8x8: 64 envs per wave, one wave per workgroup below 65 536 envs and 4 from there on
@@ -1703,58 +1690,80 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
         if (perenv && rec && epb == 32 && a.n < 65536) epb = 16;
         if (hint_epb) epb = 4 << (hint_epb - 1);
         if (perenv && epb > 64) epb = 64;                                               // every env's lane sits in wave 0
-        auto lds_of = [&](int k) {
-            const size_t own = perenv ? 2 * (size_t)k * 4 + (((size_t)k * cells + 15) & ~(size_t)15)
-                                      : (size_t)cells * 4 + 2 * (size_t)k * 4 + (size_t)((cells + 15) & ~15) + (size_t)((cells * 2 + 15) & ~15);
-            return tab + (sample ? (own + 15) & ~(size_t)15 : own);                     // the thresholds start on a 16-byte boundary
-        };
         // per-env layouts past G = 50 at 64 envs outgrow one workgroup's LDS (the hint is applied after the 32-KiB rule above):
         // halve to what fits, the device's 160 KiB as lds_for_workgroups_per_cu takes it, so that lmaze_describe_rollout
         // answers the same without a device.  Stays a multiple of 4 (body 3 copies the layouts as dwords).
         if (perenv)
-            while (epb > 4 && lds_of(epb) > (size_t)160 * 1024) epb >>= 1;
+            while (epb > 4 && lmaze_rollout_lds_perenv(cells, epb, pol).total > 160 * 1024) epb >>= 1;
         p.epb = epb;
-        p.lds = lds_of(epb);
+        p.lds = (size_t)(perenv ? lmaze_rollout_lds_perenv(cells, epb, pol) : lmaze_rollout_lds_shared(cells, epb, pol)).total;
         p.nt = slot_stores_nt(a, rec);
     }
     if (p.family != RO_STEPS) p.blocks = (a.n + p.epb - 1) / p.epb;
     return p;
 }
 
-// The kernel of a planned rollout: the plain form (RolloutArgs) or the recording one (RolloutObsArgs, u8:
-// RolloutObs8Args), overloads of one kernel template.  Named in the order the code object has always held them.
+// The kernel of a planned rollout, the only place that names a rollout instantiation: by family and variant, and by form an
+// overload on its argument struct -- plain RolloutArgs, recording RolloutObsArgs, epsilon-greedy RolloutPolicyArgs, sampling
+// RolloutSampleArgs; u8: RolloutArgs and the *8Args.  The wave-autonomous family is never planned for a closed-loop form.
+enum RolloutForm { RF_PLAIN, RF_REC, RF_POLICY, RF_SAMPLE };
+template <class Args>
+using RolloutFn = void (*)(const StepArgs, const Args);
 template <class F>
 static const void* kernel_of(int variant, F v3, F v0) { return (const void*)(variant == LMAZE_VARIANT_V3 ? v3 : v0); }
 
-static const void* rollout_kernel(RolloutFamily f, int variant, bool rec) {
-    using P = void (*)(const StepArgs, const RolloutArgs);
-    using R = void (*)(const StepArgs, const RolloutObsArgs);
-    using R8 = void (*)(const StepArgs, const RolloutObs8Args);
+static const void* rollout_kernel(RolloutFamily f, int variant, RolloutForm form) {
+    using P = RolloutFn<RolloutArgs>; using R = RolloutFn<RolloutObsArgs>; using R8 = RolloutFn<RolloutObs8Args>;
+    using E = RolloutFn<RolloutPolicyArgs>; using E8 = RolloutFn<RolloutPolicy8Args>;
+    using S = RolloutFn<RolloutSampleArgs>; using S8 = RolloutFn<RolloutSample8Args>;
     constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
     switch (f) {
-        case RO_WAVE8: return !rec ? kernel_of<P>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>)
-                                   : kernel_of<R>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>);
-        case RO_SHARED: return !rec ? kernel_of<P>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
-                                    : kernel_of<R>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
-        case RO_PERENV: return !rec ? kernel_of<P>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
-                                    : kernel_of<R>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
-        default: return rec ? kernel_of<R8>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
-                            : kernel_of<P>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>);
+        case RO_WAVE8: return form == RF_PLAIN ? kernel_of<P>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>)
+                                               : kernel_of<R>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>);
+        case RO_SHARED: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                               : form == RF_REC    ? kernel_of<R>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                               : form == RF_POLICY ? kernel_of<E>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                                                   : kernel_of<S>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
+        case RO_PERENV: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                               : form == RF_REC    ? kernel_of<R>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                               : form == RF_POLICY ? kernel_of<E>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                                                   : kernel_of<S>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
+        default: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
+                        : form == RF_REC    ? kernel_of<R8>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
+                        : form == RF_POLICY ? kernel_of<E8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
+                                            : kernel_of<S8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>);
     }
+}
+
+// The one launch site of the one-launch rollouts: plan p of form `form` with the kernel's second argument ro (the form's
+// struct), queued -- or, a0.info != null, described under `name`
+static hipError_t launch_planned(const RolloutPlan& p, int variant, RolloutForm form, const StepArgs& a0, void* ro, const char* name,
+                                 hipStream_t s) {
+    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
+    if (a0.info) {
+        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
+        return hipSuccess;
+    }
+    StepArgs a = a0;
+    a.envs_per_block = p.epb;
+    void* args[] = {&a, ro};
+    (void)hipLaunchKernel(rollout_kernel(p.family, variant, form), dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
+    return hipGetLastError();
 }
 
 // T steps as rollout_plan decides.  T launches: step t with the action row t, epoch + t and, when given, the per-step
 // reward / done rows copied out; recording, each step gets its slot, the caller's obs (last step) or nothing.
-hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, const int32_t* actions, int32_t T, float* reward_t,
-                          uint8_t* done_t, hipStream_t s, const RolloutRec* rec, bool u8) {
+hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, const ActionRows& src, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& request, bool u8) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
+    const RolloutRec* rec = src.recording ? &request : nullptr;
     const RolloutPlan p = rollout_plan(a0, layout_mode, T, rec, u8);
     if (p.family == RO_STEPS) {
         int32_t* obs_t = rec ? static_cast<int32_t*>(rec->obs_t) : nullptr;
         const int64_t plane = (int64_t)a0.n * a0.grid * a0.grid;                    // dwords of one step's planes
         for (int32_t t = 0; t < T; ++t) {
             StepArgs a = a0;
-            a.action = actions + (size_t)t * a0.n;
+            a.action = src.actions + (size_t)t * a0.n;
             a.epoch = a0.epoch + (uint64_t)t;
             int32_t* slot = nullptr;                                                 // recording: the slot step t fills
             if (obs_t && rec->every > 0 && (t + 1) % rec->every == 0)
@@ -1769,75 +1778,52 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
         }
         return hipSuccess;
     }
-    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
+    char name[96] = "", every[24] = "";
     if (a0.info) {
-        char name[96], every[24] = "";
         if (rec) snprintf(every, sizeof(every), " every=%d", rec->every);
         snprintf(name, sizeof(name), "%s<v%d%s%s%s> T=%d%s", kRolloutKernel[p.family], variant, p.family == RO_WAVE8 ? ", 64" : "",
                  rec ? ", obs_t" : "", p.nt ? ", nt" : "", T, every);
-        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
-        return hipSuccess;
     }
-    StepArgs a = a0;
-    a.envs_per_block = p.epb;
-    RolloutArgs plain{actions, reward_t, done_t, T};
+    RolloutArgs plain{src.actions, reward_t, done_t, T};
     RolloutObsArgs ro{plain, rec ? static_cast<int32_t*>(rec->obs_t) : nullptr, rec ? rec->every : 0, p.nt ? 1 : 0};
     RolloutObs8Args ro8{plain, rec ? static_cast<uint8_t*>(rec->obs_t) : nullptr, rec ? rec->every : 0};
-    void* args[] = {&a, !rec ? (void*)&plain : u8 ? (void*)&ro8 : (void*)&ro};
-    const void* kernel = rollout_kernel(p.family, variant, rec != nullptr);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
-    return hipGetLastError();
+    return launch_planned(p, variant, rec ? RF_REC : RF_PLAIN, a0, !rec ? (void*)&plain : u8 ? (void*)&ro8 : (void*)&ro, name, s);
 }
 
 // The closed-loop rollouts: ONE launch of the planned family's closed-loop form, whatever T and launch_hint bit 8 say.
-// Args / Args8: the kernel argument structs that carry `tab` (int32 / narrow planes); plan: a PLAN_* of the form; form and
-// table_note: what the describe name says of the policy, "<form>=<ball|goal><table_note>".
+// Args / Args8: the kernel argument structs that carry `tab` (int32 / narrow planes); kind: the LMAZE_TAB_* of the form,
+// which the describe name states as "<form>=<ball|goal>[, table=<lds|global>]".
 template <class Args, class Args8, class Table>
-static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode, const Table& tab, int plan, const char* form,
-                                const char* table_note, int32_t T, float* reward_t, uint8_t* done_t, hipStream_t s,
-                                const RolloutRec& rec, bool u8) {
+static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode, const Table& tab, int kind, RolloutForm form, int32_t T,
+                                float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
     if (T <= 0 || a0.n == 0) return hipSuccess;
-    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, plan);
-    if (!grid_ok(p.blocks)) return hipErrorInvalidConfiguration;
-    if (a0.info) {
-        char name[96];
-        snprintf(name, sizeof(name), "%s<v%d, %s=%s%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant, form,
-                 tab.key_mode ? "goal" : "ball", table_note, rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T, rec.every);
-        describe_launch(a0.info, name, p.epb, 0, 1, p.nt, p.blocks, p.block, p.lds);
-        return hipSuccess;
-    }
-    StepArgs a = a0;
-    a.envs_per_block = p.epb;
+    const RolloutPlan p = rollout_plan(a0, layout_mode, T, &rec, u8, kind);
+    char name[96] = "";
+    if (a0.info)
+        snprintf(name, sizeof(name), "%s<v%d, %s=%s%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
+                 form == RF_POLICY ? "policy" : "sample", tab.key_mode ? "goal" : "ball",
+                 kind == LMAZE_TAB_ROWS ? ", table=lds" : kind == LMAZE_TAB_GLOBAL ? ", table=global" : "", rec.obs_t ? ", obs_t" : "",
+                 p.nt ? ", nt" : "", T, rec.every);
     RolloutArgs plain{nullptr, reward_t, done_t, T};
     Args ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
     Args8 ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
-    void* args[] = {&a, u8 ? (void*)&ro8 : (void*)&ro};
-    using K = void (*)(const StepArgs, const Args);
-    using K8 = void (*)(const StepArgs, const Args8);
-    constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
-    const void* kernel = p.family == RO_U8       ? kernel_of<K8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
-                         : p.family == RO_PERENV ? kernel_of<K>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
-                                                 : kernel_of<K>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(p.block), args, p.lds, s);   // read back as after hipLaunchKernelGGL
-    return hipGetLastError();
+    return launch_planned(p, variant, form, a0, u8 ? (void*)&ro8 : (void*)&ro, name, s);
 }
 
 // lmaze_rollout_policy / _u8: the epsilon-greedy table, always staged
-hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T, float* reward_t,
-                                 uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
-    return launch_closed<RolloutPolicyArgs, RolloutPolicy8Args>(variant, a, layout_mode, tab, PLAN_POLICY, "policy", "", T, reward_t,
-                                                                done_t, s, rec, u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+    return launch_closed<RolloutPolicyArgs, RolloutPolicy8Args>(variant, a, layout_mode, tab, LMAZE_TAB_BYTES, RF_POLICY, T, reward_t, done_t, s, rec, u8);
 }
 
 // lmaze_rollout_sample / _u8: the threshold table is staged in LDS by rule -- ball-keyed and G <= 32, i.e. at most 16 KiB --
 // and read from global memory otherwise
-hipError_t launch_rollout_closed(int variant, const StepArgs& a, int layout_mode, const SampleTable& tab0, int32_t T, float* reward_t,
-                                 uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const SampleTable& tab0, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
     SampleTable tab = tab0;
     tab.staged = tab.key_mode == 0 && a.grid <= 32 ? 1 : 0;
-    return launch_closed<RolloutSampleArgs, RolloutSample8Args>(variant, a, layout_mode, tab, tab.staged ? PLAN_SAMPLE_LDS : PLAN_SAMPLE_GLOBAL,
-                                                                "sample", tab.staged ? ", table=lds" : ", table=global", T, reward_t, done_t,
-                                                                s, rec, u8);
+    const int kind = tab.staged ? LMAZE_TAB_ROWS : LMAZE_TAB_GLOBAL;
+    return launch_closed<RolloutSampleArgs, RolloutSample8Args>(variant, a, layout_mode, tab, kind, RF_SAMPLE, T, reward_t, done_t, s, rec, u8);
 }
 
 }  // namespace lmaze
