@@ -39,7 +39,7 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
            "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy",
            "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
-           "lmaze_describe_v5_rollout_policy")
+           "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample")
 
 
 class LmazeParams(C.Structure):
@@ -206,6 +206,11 @@ def _load():
                                             vp, vp, vp, vp, vp, i32, vp]
     lib.lmaze_describe_v5_rollout_policy.restype = C.c_int
     lib.lmaze_describe_v5_rollout_policy.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_v5_rollout_sample.restype = C.c_int
+    lib.lmaze_v5_rollout_sample.argtypes = [FP, vp, vp, i32, vp, i32, FB, i64, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            i32, vp]
+    lib.lmaze_describe_v5_rollout_sample.restype = C.c_int
+    lib.lmaze_describe_v5_rollout_sample.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -341,6 +346,13 @@ def describe_v5_rollout_policy(params, n, T, controller_key=0, obs_every=0):
     """As describe_foveal_rollout_policy, for lmaze_v5_rollout_policy (v5/v6): "foveal_hier_policy_kernel<v5, 32, 18, obs_t>
     controller=lds planner=lds T=...".  controller_key: 0 / "offset" or 1 / "cell"."""
     return _describe("lmaze_describe_v5_rollout_policy", C.byref(params), int(n), int(T), controller_key_id(controller_key),
+                     int(obs_every))
+
+
+def describe_v5_rollout_sample(params, n, T, controller_key=0, obs_every=0):
+    """As describe_v5_rollout_policy, for lmaze_v5_rollout_sample (v5/v6): "foveal_hier_sample_kernel<v5, 32, 18, obs_t>
+    controller=lds planner=global T=...".  controller_key: 0 / "offset" or 1 / "cell"."""
+    return _describe("lmaze_describe_v5_rollout_sample", C.byref(params), int(n), int(T), controller_key_id(controller_key),
                      int(obs_every))
 
 

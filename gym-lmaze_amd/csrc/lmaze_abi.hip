@@ -244,8 +244,25 @@ struct FovealHierTables {
     }
 };
 
-// lmaze_foveal_rollout_policy / lmaze_foveal_rollout_sample / lmaze_v5_rollout_policy (lmaze_foveal_policy.hip,
-// lmaze_foveal_sample.hip, lmaze_hier_policy.hip).  info != null: describe instead of launching -- then nothing past the params
+struct FovealHierSampleTables {
+    typedef FovealRollObsHierSmp Roll;
+    static constexpr uintptr_t kAlign = 16;
+    static constexpr bool kTwoLevel = true;
+    const uint32_t* controller;
+    const uint32_t* planner;
+    int32_t controller_key;
+    int32_t* goals_t;
+    int32_t* goal_key_t;
+    int refused() const { return controller_key != 0 && controller_key != 1 ? LMAZE_E_COUNT : 0; }
+    bool missing() const { return !controller || !planner; }
+    bool unaligned() const { return misaligned(controller, kAlign) || misaligned(planner, kAlign); }
+    void put(Roll& ro, int32_t* actions_t, int32_t* key_t) const {
+        ro.hsmp = FovealHierSmp{controller, planner, controller_key, 0, actions_t, key_t, goals_t, goal_key_t};
+    }
+};
+
+// lmaze_foveal_rollout_policy / lmaze_foveal_rollout_sample / lmaze_v5_rollout_policy / lmaze_v5_rollout_sample
+// (lmaze_foveal_policy.hip, lmaze_foveal_sample.hip, lmaze_hier_policy.hip, lmaze_hier_sample.hip).  info != null: describe instead of launching -- then nothing past the params
 // and the table's own refusal is looked at.  The refusals stand in the order include/lmaze.h documents.  obs_local_t: the
 // two-level family's second recording (nullable; 16-byte aligned, refused with the recording request).
 template <class Table>
@@ -285,7 +302,8 @@ static int foveal_rollout_closed(const LmazeFovealParams* params, const uint8_t*
     return (int)launch_foveal_rollout_closed(a, ro, rec, (hipStream_t)stream);
 }
 
-// lmaze_describe_foveal_rollout_policy / lmaze_describe_foveal_rollout_sample / lmaze_describe_v5_rollout_policy
+// lmaze_describe_foveal_rollout_policy / lmaze_describe_foveal_rollout_sample / lmaze_describe_v5_rollout_policy /
+// lmaze_describe_v5_rollout_sample
 template <class Table>
 static int describe_foveal_rollout_closed(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t obs_every,
                                           char* text_host, int32_t len, const Table& tab = Table{}) {
@@ -495,6 +513,22 @@ int lmaze_v5_rollout_policy(const LmazeFovealParams* params, const uint8_t* layo
 int lmaze_describe_v5_rollout_policy(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t controller_key, int32_t obs_every,
                                      char* text_host, int32_t len) {
     const FovealHierTables tab{nullptr, nullptr, 0, 0, controller_key, nullptr, nullptr};
+    return describe_foveal_rollout_closed(params, n, T, 1, obs_every, text_host, len, tab);
+}
+
+int lmaze_v5_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* controller_thresholds,
+                            int32_t controller_key, const uint32_t* planner_thresholds, int32_t T, const LmazeFovealBuffers* bufs,
+                            int64_t n, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t, uint8_t* done_t,
+                            float* foveal_reward_t, uint8_t* foveal_done_t, int32_t* actions_t, int32_t* key_t, int32_t* goals_t,
+                            int32_t* goal_key_t, float* obs_t, float* obs_local_t, int32_t obs_every, void* stream) {
+    const FovealHierSampleTables tab{controller_thresholds, planner_thresholds, controller_key, goals_t, goal_key_t};
+    return foveal_rollout_closed(params, layouts, tab, T, bufs, n, 1, seed, epoch, env_base, reward_t, done_t, foveal_reward_t,
+                                 foveal_done_t, actions_t, key_t, obs_t, obs_local_t, obs_every, nullptr, stream);
+}
+
+int lmaze_describe_v5_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t controller_key, int32_t obs_every,
+                                     char* text_host, int32_t len) {
+    const FovealHierSampleTables tab{nullptr, nullptr, controller_key, nullptr, nullptr};
     return describe_foveal_rollout_closed(params, n, T, 1, obs_every, text_host, len, tab);
 }
 

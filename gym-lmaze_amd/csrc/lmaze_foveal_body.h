@@ -9,11 +9,16 @@
 // table holds one row of cumulative thresholds per key and one draw word is compared against them.
 // LMAZE_FOVEAL_HIER_SITE (lmaze_hier_policy.hip, POL = 3) is the closed loop of the two-level step of v5/v6: the V5 FM_STEP / AR
 // branch of phase 1 loads neither a.action nor a.goal2; the planner's goal and the controller's action come from two tables
-// (ro.hier) mixed with one draw, and their rows are stored where they are produced.  Not a header of its own.
+// (ro.hier) mixed with one draw, and their rows are stored where they are produced.  LMAZE_FOVEAL_HIER_SAMPLE_SITE
+// (lmaze_hier_sample.hip, POL = 4) is that loop's sampling form: both tables hold rows of cumulative thresholds (ro.hsmp), staged
+// as POL 2 stages its one, and the words r.x and r.z of a draw taken on every env-step are compared against them.  Not a header
+// of its own.
 #ifndef LMAZE_FOVEAL_BODY_SITE
-#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip, lmaze_foveal_policy.hip, lmaze_foveal_sample.hip and lmaze_hier_policy.hip"
+#error "lmaze_foveal_body.h is the body of the foveal kernels: it is included only inside them, in lmaze_foveal.hip, lmaze_foveal_policy.hip, lmaze_foveal_sample.hip, lmaze_hier_policy.hip and lmaze_hier_sample.hip"
 #endif
-#if defined(LMAZE_FOVEAL_HIER_SITE)
+#if defined(LMAZE_FOVEAL_HIER_SAMPLE_SITE)
+#define LMAZE_POL 4
+#elif defined(LMAZE_FOVEAL_HIER_SITE)
 #define LMAZE_POL 3
 #elif defined(LMAZE_FOVEAL_SAMPLE_SITE)
 #define LMAZE_POL 2
@@ -68,6 +73,14 @@
     const bool cstage = (hier.in_lds & kHierControllerStaged) != 0, pstage = (hier.in_lds & kHierPlannerStaged) != 0;
     uint8_t* ctab = lays + ((L * CELLS + 15) & ~15);
     uint8_t* ptab = ctab + (cstage ? (cbytes + 15) & ~15 : 0);
+#elif LMAZE_POL == 4
+    // the controller's rows on the next 16-byte boundary of the allocation behind the characters (POL 2's place) and the
+    // planner's behind them, each only when it is staged; both sizes are multiples of 16
+    const FovealHierSmp hsmp = ro.hsmp;
+    const bool cstage = (hsmp.in_lds & kHierControllerStaged) != 0, pstage = (hsmp.in_lds & kHierPlannerStaged) != 0;
+    const int ckeys = lmaze_hier_sample_controller_keys(hsmp.controller_key, L, G);
+    uint32_t* ctab = reinterpret_cast<uint32_t*>(lds4) + ((((lays - reinterpret_cast<uint8_t*>(lds4)) + L * CELLS + 15) & ~15) >> 2);
+    uint32_t* ptab = ctab + (cstage ? ckeys * LMAZE_HIER_SAMPLE_CROW : 0);
 #endif
     static_assert(PERENV <= 8 * 32 - 32 && 4 * W25 <= 4 * 32 - 4, "bit strings fit the 32 B / 16 B per env reserved for them");
     __shared__ int any_skip, ndense;
@@ -195,6 +208,9 @@
 #elif LMAZE_POL == 3
         if (cstage) hier_stage(ctab, hier.controller, cbytes, cdwords, tid, hcw);
         if (pstage) hier_stage(ptab, hier.planner, pbytes, pdwords, tid, hpw);
+#elif LMAZE_POL == 4
+        if (cstage) stage_thresholds(ctab, hsmp.controller, ckeys * (LMAZE_HIER_SAMPLE_CROW / 4), tid);
+        if (pstage) stage_thresholds(ptab, hsmp.planner, L * CELLS * (LMAZE_HIER_SAMPLE_PROW / 4), tid);
 #endif
     } else {
     for (int i = tid; i < L * CELLS; i += LMAZE_BLOCK) lays[i] = a.layouts[i];
@@ -205,6 +221,9 @@
 #elif LMAZE_POL == 3
     if (cstage) for (int i = tid; i < cbytes; i += LMAZE_BLOCK) ctab[i] = hier.controller[i];
     if (pstage) for (int i = tid; i < pbytes; i += LMAZE_BLOCK) ptab[i] = hier.planner[i];
+#elif LMAZE_POL == 4
+    if (cstage) stage_thresholds(ctab, hsmp.controller, ckeys * (LMAZE_HIER_SAMPLE_CROW / 4), tid);
+    if (pstage) stage_thresholds(ptab, hsmp.planner, L * CELLS * (LMAZE_HIER_SAMPLE_PROW / 4), tid);
 #endif
     __syncthreads();
     for (int i = tid; i < L * G; i += LMAZE_BLOCK) {
@@ -256,7 +275,7 @@
 #endif
         const int sc_ld = (MODE == FM_STEP) ? a.b.step_count[e] : 0;
         const int done_in = (MODE == FM_STEP && AR) ? a.b.done[e] : 0;
-#if LMAZE_POL != 3
+#if LMAZE_POL != 3 && LMAZE_POL != 4
         const int goal2_in = (MODE == FM_STEP && AR && V5) ? a.goal2[ROLL_ROW(e)] : 0;
 #endif
         const int vword = (V4 && !(V5 && MODE == FM_PLANNER)) ? a.b.visit_clock[e] : 0;
@@ -269,6 +288,11 @@
         // one draw for both levels, only when either explores (uniform over the launch): in front of the placement chain
         uint4 pr = make_uint4(0u, 0u, 0u, 0u);
         if ((hier.epsilon | hier.planner_epsilon) != 0u) pr = policy_draw(a.seed, ROLL_EP, a.env_base + e);
+#elif LMAZE_POL == 4
+        // one draw for both levels, on every env-step: two words of it are live across the fused reset.  In front of the
+        // placement chain, under the loads above.
+        const uint4 pr4 = policy_draw(a.seed, ROLL_EP, a.env_base + e);
+        const uint32_t prx = pr4.x, prz = pr4.z;
 #elif LMAZE_POL
         // the exploration draw, only when there is exploration (uniform over the launch).  It depends on nothing loaded, so
         // it stands in front of the fused reset's placement chain and runs under the loads above.
@@ -353,7 +377,7 @@
             int b1x = a.b.ball1_xy[2 * e], b1y = a.b.ball1_xy[2 * e + 1];
             int lx = a.b.last_xy[2 * e], ly = a.b.last_xy[2 * e + 1];
             if (MODE == FM_STEP) {                                     // v5:187-292
-#if LMAZE_POL == 3
+#if LMAZE_POL == 3 || LMAZE_POL == 4
                 int act = act_in;                                      // the controller's, once the planner has stepped
 #else
                 const int act = act_in;
@@ -384,6 +408,8 @@
                     if (plan) {                                        // plannerStep(goal): v5:158-182, as FM_PLANNER below
 #if LMAZE_POL == 3
                         const int g = hier_plan_goal(hier, ptab, lid, bx, by, G, L, pr.z, pr.w, ROLL_ROW(e));   // the state after the reset
+#elif LMAZE_POL == 4
+                        const int g = hier_smp_goal(hsmp, ptab, lid, bx, by, G, L, prz, ROLL_ROW(e));   // the state after the reset; 0..24
 #else
                         const int g = goal2_in;
 #endif
@@ -399,6 +425,8 @@
                     }
 #if LMAZE_POL == 3
                     else hier_no_goal(hier, ROLL_ROW(e));
+#elif LMAZE_POL == 4
+                    else hier_smp_no_goal(hsmp, ROLL_ROW(e));
 #endif
                     if (fresh || planned) {
                         a.b.foveal_goal[e] = fg;
@@ -409,6 +437,8 @@
                 }
 #if LMAZE_POL == 3
                 act = hier_act(hier, ctab, lid, bx, by, fgx, fgy, G, L, pr.x, pr.y, ROLL_ROW(e));   // the state after the plannerStep
+#elif LMAZE_POL == 4
+                act = hier_smp_act(hsmp, ctab, lid, bx, by, fgx, fgy, G, L, prx, ROLL_ROW(e));   // the state after the plannerStep
 #endif
                 const uint8_t* lay = lays + lid * CELLS;
                 b1x = bx; b1y = by;                                    // v5:193-194

@@ -1,5 +1,5 @@
 // lmaze_foveal_defs.h -- what the translation units of the foveal kernels share (lmaze_foveal.hip: the step, reset and
-// open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip, lmaze_hier_policy.hip: the closed-loop rollouts): the kernel arguments, the device helpers
+// open-loop rollout kernels; lmaze_foveal_policy.hip, lmaze_foveal_sample.hip, lmaze_hier_policy.hip, lmaze_hier_sample.hip: the closed-loop rollouts): the kernel arguments, the device helpers
 // of lmaze_foveal_body.h, and the host-side checks and LDS sizing their launchers use (the one plan of every foveal launch:
 // lmaze_foveal_launch.h).  Not part of the C ABI.
 #ifndef LMAZE_FOVEAL_DEFS_H_
@@ -10,6 +10,7 @@
 #include "lmaze_foveal_select.h"
 #include "lmaze_foveal_sample.h"
 #include "lmaze_hier_select.h"
+#include "lmaze_hier_sample.h"
 
 // Timing decomposition (tools/foveal_decompose.py): a build with -DLMAZE_EXPERIMENT -- never the shipped
 // one -- reads bits 16-23 of launch_hint as switches that turn phases off (results are garbage then; only the time
@@ -243,6 +244,79 @@ __device__ __forceinline__ int hier_act(const FovealHier& h, const uint8_t* lds_
 }
 // rec false: the row form, the recording members of ro unread (lmaze_foveal_launch.h launch_foveal_rollout_sliced)
 hipError_t launch_foveal_rollout_closed(const FovealArgs& a, const FovealRollObsHier& ro, bool rec, hipStream_t s);
+
+// The SAMPLING closed-loop two-level rollout of v5/v6 (lmaze_v5_rollout_sample, lmaze_hier_sample.hip): both levels draw from
+// categorical tables -- the controller's one row uint32[4] per controller key (c0, c1, c2, reserved: the grid envs' and v1's
+// format), the planner's one row uint32[24] per planner key (the v2/v4 format) -- compared against the words r.x and r.z of
+// ONE draw per env-step (lmaze_hier_sample.h).  The body is compiled with POL = 4 for the two types below and reads ro.hsmp.
+struct FovealHierSmp {
+    const uint32_t* controller;  // uint32[100, 4] or uint32[100*L*G*G, 4], 16-byte aligned
+    const uint32_t* planner;     // uint32[L*G*G, 24], 16-byte aligned
+    int32_t controller_key;      // 0 offset, 1 cell
+    int32_t in_lds;              // kHierControllerStaged: the controller table is staged in LDS on the next 16-byte boundary behind the
+                                 // layout characters; kHierPlannerStaged: the planner table, behind it
+    int32_t* actions_t;          // [T,N] or null: the action every env took
+    int32_t* key_t;              // [T,N] or null: the controller key its row was looked up with
+    int32_t* goals_t;            // [T,N] or null: the goal of every env that planned, -1 elsewhere
+    int32_t* goal_key_t;         // [T,N] or null: the planner key its row was looked up with, -1 elsewhere
+};
+struct FovealRollHierSmp : FovealRoll { FovealHierSmp hsmp; };
+struct FovealRollObsHierSmp : FovealRollObs { FovealHierSmp hsmp; };
+__host__ __device__ __forceinline__ int64_t hier_sample_controller_bytes(int controller_key, int L, int G) {
+    return (int64_t)lmaze_hier_sample_controller_keys(controller_key, L, G) * (LMAZE_HIER_SAMPLE_CROW * 4);
+}
+__host__ __device__ __forceinline__ int64_t hier_sample_planner_bytes(int L, int G) { return (int64_t)L * G * G * (LMAZE_HIER_SAMPLE_PROW * 4); }
+// A key's row, Q 128-bit reads requested together, the staged and the global side through pointers of their own address
+// spaces (foveal_smp_action).
+template <int Q>
+__device__ __forceinline__ void hier_smp_row(bool staged, const uint32_t* lds_table, const uint32_t* table, int key, uint32_t (&c)[Q * 4]) {
+    typedef const __attribute__((address_space(3))) foveal_row4_t* lds_rows;
+    typedef const __attribute__((address_space(1))) foveal_row4_t* global_rows;
+    foveal_row4_t q[Q];
+    if (staged) {
+#pragma unroll
+        for (int j = 0; j < Q; ++j) q[j] = ((lds_rows)lds_table)[key * Q + j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < Q; ++j) q[j] = ((global_rows)table)[(size_t)key * Q + j];
+    }
+#pragma unroll
+    for (int j = 0; j < Q; ++j) { c[4 * j] = q[j].x; c[4 * j + 1] = q[j].y; c[4 * j + 2] = q[j].z; c[4 * j + 3] = q[j].w; }
+}
+// The goal of an env that plans in state (lid, bx, by): planner key -> the key's row, six 128-bit reads in one group -> the sum
+// of compares against r.z, and element `row` of the goal and goal-key rows, stored here where they are produced.
+__device__ __forceinline__ int hier_smp_goal(const FovealHierSmp& h, const uint32_t* lds_table, int lid, int bx, int by, int G, int L,
+                                             uint32_t rz, int64_t row) {
+    const int kp = lmaze_hier_planner_key(lid, bx, by, G, L);
+    uint32_t c[LMAZE_HIER_SAMPLE_PROW];
+    hier_smp_row<LMAZE_HIER_SAMPLE_PROW / 4>((h.in_lds & kHierPlannerStaged) != 0, lds_table, h.planner, kp, c);
+    const int g = lmaze_hier_sample_goal(c, rz);
+    if (h.goals_t) h.goals_t[row] = g;
+    if (h.goal_key_t) h.goal_key_t[row] = kp;
+    return g;
+}
+// ... and of an env that does not: both rows are -1.
+__device__ __forceinline__ void hier_smp_no_goal(const FovealHierSmp& h, int64_t row) {
+    if (h.goals_t) h.goals_t[row] = -1;
+    if (h.goal_key_t) h.goal_key_t[row] = -1;
+}
+// The action of an env whose state after the plannerStep is (lid, bx, by, fgx, fgy): controller key -> the key's row, one
+// 128-bit read (the reserved word is read with the rest and kept to the end, foveal_smp_action) -> the sum of compares against
+// r.x, and element `row` of the action and key rows.
+__device__ __forceinline__ int hier_smp_act(const FovealHierSmp& h, const uint32_t* lds_table, int lid, int bx, int by, int fgx, int fgy,
+                                            int G, int L, uint32_t rx, int64_t row) {
+    const int d = lmaze_hier_offset(fgx, fgy, bx, by);
+    const int kc = lmaze_hier_controller_key(h.controller_key, h.controller_key ? lmaze_hier_planner_key(lid, bx, by, G, L) : 0, d);
+    uint32_t c[LMAZE_HIER_SAMPLE_CROW];
+    hier_smp_row<1>((h.in_lds & kHierControllerStaged) != 0, lds_table, h.controller, kc, c);
+    const int act = lmaze_hier_sample_action(c, rx);
+    asm volatile("" ::"v"(c[3]));
+    if (h.actions_t) h.actions_t[row] = act;
+    if (h.key_t) h.key_t[row] = kc;
+    return act;
+}
+// rec false: the row form, the recording members of ro unread (lmaze_foveal_launch.h launch_foveal_rollout_sliced)
+hipError_t launch_foveal_rollout_closed(const FovealArgs& a, const FovealRollObsHierSmp& ro, bool rec, hipStream_t s);
 
 struct EnvRec {           // one env after its transition (registers only; phase 1 turns it into plane masks)
     int16_t cx, cy;       // centre of the current window (ball after the move)

@@ -3,7 +3,8 @@
 // envs per workgroup and their LDS fallback, the LDS sum and its pad, the block count -- for the step and its sibling modes
 // (foveal_kernel, queued by lmaze_foveal.hip) and for the rollouts alike; what sets a caller apart is a FovealForm.
 // lmaze_foveal.hip (open loop), lmaze_foveal_policy.hip (epsilon-greedy closed loop), lmaze_foveal_sample.hip (sampling
-// closed loop) and lmaze_hier_policy.hip (the two-level closed loop of v5/v6) keep their rollout kernels and describe
+// closed loop), lmaze_hier_policy.hip (the two-level closed loop of v5/v6) and lmaze_hier_sample.hip (its sampling form) keep
+// their rollout kernels and describe
 // themselves as a family F, a struct of statics:
 //   kKernel            the kernel's name as the describe line prints it
 //   kTableLds          bytes of table up to which it is staged in LDS behind the layout characters; 0: the family has no
@@ -11,7 +12,7 @@
 // and, where there is a table,
 //   table_bytes(p), staged_lds(base, table)
 //                      the table's size, and foveal_lds with a staged table added the way the family's kernels lay it out
-//   table(ro)          the FovealPol / FovealSmp / FovealHier of a family's RO, whose in_lds the launcher sets
+//   table(ro)          the FovealPol / FovealSmp / FovealHier / FovealHierSmp of a family's RO, whose in_lds the launcher sets
 // or, a family of two tables (kTables == 2; its kernel has one mode, which the describe line does not name),
 //   place(p, ro, lds), suffix(staged)
 //                      which of its tables are staged (the bits of in_lds), their bytes added to lds the way the family's
@@ -199,7 +200,7 @@ template <class F, class RO>
 static hipError_t launch_foveal_rollout(const FovealArgs& a, const RO& ro0, hipStream_t s) {
     constexpr bool REC = std::is_base_of<FovealRollObs, RO>::value;
     const bool v1 = a.p.variant == LMAZE_VARIANT_V1, v56 = !v1 && a.p.variant != LMAZE_VARIANT_V2 && a.p.variant != LMAZE_VARIANT_V4;
-    // v5/v6: the two-level step of the open loop and of lmaze_hier_policy.hip; the other closed loops have none, and
+    // v5/v6: the two-level step of the open loop, of lmaze_hier_policy.hip and of lmaze_hier_sample.hip; the other closed loops have none, and
     // their entry refuses the variants
     if (v56 && !F::template exists<LMAZE_VARIANT_V5, 32, 18, true, false>()) return hipErrorInvalidValue;
     // which tables are staged is a rule, not a measurement; their bytes by the family's own layout (the envs per workgroup

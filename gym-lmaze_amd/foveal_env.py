@@ -385,6 +385,82 @@ class LmazeFovealVecEnv(VecEnvBase):
         return self._closed_loop("rollout_hier_policy()", "lmaze_v5_rollout_policy", call, T, k, obs_t, trajectory, actions_t, key_t,
                                  streams=2, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
 
+    def rollout_hier_sample(self, T, controller_probs=None, controller_logits=None, controller_thresholds=None, planner_probs=None,
+                            planner_logits=None, planner_thresholds=None, temperature=1.0, planner_temperature=None,
+                            controller_key="offset", trajectory=False, actions_t=None, key_t=None, goals_t=None, goal_key_t=None,
+                            obs_t=None, obs_local_t=None, obs_every=None):
+        """v5/v6: T two-level steps (hier_step) in ONE launch with a categorical planner and a categorical controller inside
+        the kernel (include/lmaze.h lmaze_v5_rollout_sample): every env that enters a step done or locally done draws its
+        foveal goal from the distribution of its planner key = state_keys(), every env its action from the distribution of
+        its controller key = controller_keys(controller_key).  With K = 100 ("offset") or 100*L*G*G ("cell") controller keys
+        and S = L*G*G planner keys, exactly one per level of
+        controller_probs / planner_probs            float device tensors [K, 4] / [S, 25] of non-negative weights, converted by
+                                                    _abi.sampling_thresholds(probs, actions=4 | 25);
+        controller_logits / planner_logits          float device tensors [K, 4] / [S, 25]: sampling_thresholds(softmax(
+                                                    logits.double() / temperature)); the planner's temperature is
+                                                    planner_temperature, which defaults to temperature; both > 0;
+        controller_thresholds / planner_thresholds  the tables themselves, uint32 (or int32, the same bits) device tensors,
+                                                    contiguous and 16-byte aligned: [K, 4] (c0 <= c1 <= c2 and a reserved
+                                                    word, the grid envs' format) / [S, 24].
+        The goal and the action are the numbers of their row's thresholds that the words r.z and r.x of one Philox draw per
+        (seed, env, epoch) have reached: always 0..24 and 0..3, so no plannerStep is skipped and every step moves or hits a
+        wall.  Returns what rollout_hier_policy() returns; the rows, obs_t / obs_local_t / obs_every and the restrictions
+        (not for v1/v2/v4, not under stream capture) are its own too.  The epoch advances by T."""
+        if not self._two_level:
+            raise ValueError("rollout_hier_sample() is the two-level closed loop of v5/v6; v1/v2/v4 have rollout_sample()")
+        T = self._steps(T)
+        for level, given in (("controller", (controller_probs, controller_logits, controller_thresholds)),
+                             ("planner", (planner_probs, planner_logits, planner_thresholds))):
+            if sum(x is not None for x in given) != 1:
+                raise ValueError("rollout_hier_sample() wants exactly one of %s_probs=, %s_logits= and %s_thresholds=" % ((level,) * 3))
+        ck = _abi.controller_key_id(controller_key)
+        if ck not in (0, 1):
+            raise ValueError("controller_key must be 'offset' or 'cell'")
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("rollout_hier_sample() is not available with a device-resident epoch (under stream capture)")
+        cells, what = self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid)
+        if planner_temperature is None:
+            planner_temperature = temperature
+
+        def table(level, probs, logits, thresholds, temp, keys, A, what):
+            W = 4 if A == 4 else A - 1
+            if thresholds is None:
+                src, name = (probs, level + "_probs") if logits is None else (logits, level + "_logits")
+                if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
+                        and tuple(src.shape) == (keys, A)):
+                    raise ValueError("%s must be a float tensor [%d, %d] on %s (%s)" % (name, keys, A, self.device, what))
+                if logits is not None:
+                    if not float(temp) > 0.0:
+                        raise ValueError("temperature and planner_temperature must be > 0")
+                    src = torch.softmax(logits.double() / float(temp), -1)
+                thresholds = _abi.sampling_thresholds(src, actions=A)
+            if not (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
+                    and thresholds.device == self.device and thresholds.is_contiguous() and tuple(thresholds.shape) == (keys, W)
+                    and thresholds.data_ptr() % 16 == 0):
+                raise ValueError("%s_thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, %d] on %s (%s)"
+                                 % (level, keys, W, self.device, what))
+            return thresholds
+        controller = table("controller", controller_probs, controller_logits, controller_thresholds, temperature,
+                           100 * cells if ck else 100, 4, "controller_key=%r, %s" % (controller_key, what))
+        planner = table("planner", planner_probs, planner_logits, planner_thresholds, planner_temperature, cells,
+                        _abi.FOVEA * _abi.FOVEA, what)
+        k = 0
+        if obs_every is not None:
+            k = self._obs_slots(T, obs_every, obs_t, self.obs)
+            if obs_local_t is not None:
+                self._obs_slots(T, obs_every, obs_local_t, self.obs_local, name="obs_local_t")
+        elif obs_t is not None or obs_local_t is not None:
+            raise ValueError("obs_t / obs_local_t need obs_every")
+
+        def call(rows, p_actions, p_key, slots, goal_rows):
+            return _abi.lib.lmaze_v5_rollout_sample(
+                self._pp, self._p_layouts, controller.data_ptr(), ck, planner.data_ptr(), T, self._pb, self.num_envs,
+                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key,
+                *goal_rows, slots, obs_local_t.data_ptr() if slots is not None and obs_local_t is not None else None, k,
+                self._stream())
+        return self._closed_loop("rollout_hier_sample()", "lmaze_v5_rollout_sample", call, T, k, obs_t, trajectory, actions_t, key_t,
+                                 streams=2, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
+
     def controller_keys(self, controller_key="offset"):
         """v5/v6, int32[N]: the controller key of every env's CURRENT state, by the rule the key_t rows of
         rollout_hier_policy() are written with -- d = clamp(fgoal_x - ball_x + 4, 0, 9) * 10 + clamp(fgoal_y - ball_y + 4, 0, 9),

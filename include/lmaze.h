@@ -938,6 +938,55 @@ int lmaze_describe_v5_rollout_policy(const LmazeFovealParams* params, int64_t n,
                                      int32_t obs_every, char* text_host, int32_t len);
 
 /*
+ * SAMPLING closed-loop two-level rollout (v5, v6): lmaze_v5_rollout_policy with a categorical planner and a categorical
+ * controller instead of the epsilon-greedy ones -- the form that produces policy-gradient, actor-critic and Boltzmann data for
+ * both levels in one launch.  Replaces the user loop of T x (two row gathers, two compare-sums, lmaze_v5_hier_step).  The
+ * arguments of lmaze_v5_rollout_policy with `controller, epsilon_u32, planner, planner_epsilon_u32` replaced by
+ *   controller_thresholds   const uint32_t*, 16-byte aligned, uint32[keys, 4]: c0, c1, c2 and a reserved word per controller key
+ *                           (the grid envs' and v1's format; the reserved word is loaded with the rest and ignored); keys =
+ *                           100 for controller_key 0 "offset", 100 L G G for controller_key 1 "cell"
+ *   planner_thresholds      const uint32_t*, 16-byte aligned, uint32[L G G, 24]: c0 .. c23 per planner key (the v2/v4 format)
+ * Env i (global index e = env_base + i) at step t, ep = epoch + t, gd / ld its done / foveal_done ON ENTRY:
+ *   1. r = the exploration draw of lmaze_rollout_policy -- Philox4x32-10(counter (e_lo, e_hi, ep_lo, ep_hi ^ 0x80000000), key
+ *      (seed_lo, seed_hi)) -- drawn on every env-step; only r.x and r.z are used;
+ *   2. gd: the reset of lmaze_v5_hier_step, same draw, epoch ep (v5:104-150);
+ *   3. gd | ld: the planner steps.  kp = the planner key of lmaze_v5_rollout_policy (step 3 there) of the state after that
+ *      reset; g = sum over k < 24 of (r.z >= planner_thresholds[kp][k]), unsigned compares; then plannerStep(g) (v5:158-182).
+ *      g is always in 0..24, so no plannerStep is ever skipped.  goals_t[t,i] = g, goal_key_t[t,i] = kp; where no plannerStep
+ *      was due both are -1;
+ *   4. the controller key kc exactly as in lmaze_v5_rollout_policy, steps 4-5: d from the state after 3., kc = d or kp' 100 + d;
+ *   5. a = sum over k < 3 of (r.x >= controller_thresholds[kc][k]), unsigned compares; then step(a) (v5:187-292).  a is always
+ *      in 0..3.  actions_t[t,i] = a, key_t[t,i] = kc, for every env;
+ *   6. reward and done rows of both streams, visit map, obs, obs_local and the recorded slots as in lmaze_foveal_rollout_obs.
+ * The caller advances its epoch by T.
+ * Goal k is taken with probability (c_k - c_(k-1)) / 2^32, c_(-1) = 0, c_24 = 2^32; an action likewise.  Nothing is validated:
+ * a row that is not monotone still yields what the sums give (an implementation by binary search is not equivalent).
+ * Each table of at most 16 384 bytes (lmaze_rollout_sample's figure) is staged in LDS once per workgroup, on the next 16-byte
+ * boundary behind the layout characters, the controller's first: the 1 600-byte offset controller always, a cell-mode
+ * controller (1 600 L G G bytes) never, the planner table (96 L G G bytes) for one layout up to 13 x 13 (16 224 B).  A larger
+ * one -- the planner table from 14 x 14 on, 155 520 B for the five 18 x 18 layouts -- is read from global memory: the controller
+ * row is one 128-bit read, the planner row six, requested together and only by the envs that plan.  This is a rule, not a
+ * measurement; lmaze_describe_v5_rollout_sample reports it as controller=lds|global planner=lds|global.
+ * No grid size is refused: the row and the recording form exist for any G, at 32, 64 and 128 envs per workgroup.
+ * Refused before anything is queued: the refusals of lmaze_v5_rollout_policy, in its order, with the two threshold tables in
+ * the place of `controller` and `planner` (step 6: LMAZE_E_NULL a missing table, with the other pointers); a table that is not
+ * 16-byte aligned is LMAZE_E_ALIGN, after the alignment refusals of lmaze_foveal_step.
+ * lmaze_foveal_rollout_policy and lmaze_foveal_rollout_sample keep refusing v5/v6.
+ * launch_hint bits 0-3, 4-7 and 8-9 as in lmaze_foveal_rollout; they never change results.
+ */
+int lmaze_v5_rollout_sample(const LmazeFovealParams* params, const uint8_t* layouts, const uint32_t* controller_thresholds,
+                            int32_t controller_key, const uint32_t* planner_thresholds, int32_t T, const LmazeFovealBuffers* bufs,
+                            int64_t n, uint64_t seed, uint64_t epoch, int64_t env_base, float* reward_t, uint8_t* done_t,
+                            float* foveal_reward_t, uint8_t* foveal_done_t, int32_t* actions_t, int32_t* key_t, int32_t* goals_t,
+                            int32_t* goal_key_t, float* obs_t, float* obs_local_t, int32_t obs_every, void* stream);
+
+/* As lmaze_describe_v5_rollout_policy, for lmaze_v5_rollout_sample:
+ * "foveal_hier_sample_kernel<v5, 32, 18, obs_t> controller=lds planner=global T=24 grid=...".  The same refusals and empty
+ * lines.  Nothing is queued or dereferenced. */
+int lmaze_describe_v5_rollout_sample(const LmazeFovealParams* params, int64_t n, int32_t T, int32_t controller_key,
+                                     int32_t obs_every, char* text_host, int32_t len);
+
+/*
  * v6 safeFovealGoal() (v6:505-523): for every env one window cell index 0..24 drawn uniformly from the
  * cells of the 5x5 window around the ball that are not 'W' (the reference rejects on np.random; here
  * Philox keyed by (seed, env_base + i, epoch), index (r*count)>>32 among the accepted cells in
