@@ -39,7 +39,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
            "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy",
            "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
-           "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample")
+           "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
+           "lmaze_solve", "lmaze_describe_solve")
 
 
 class LmazeParams(C.Structure):
@@ -211,6 +212,10 @@ def _load():
                                             i32, vp]
     lib.lmaze_describe_v5_rollout_sample.restype = C.c_int
     lib.lmaze_describe_v5_rollout_sample.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_solve.restype = C.c_int
+    lib.lmaze_solve.argtypes = [P, vp, vp, i64, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.lmaze_describe_solve.restype = C.c_int
+    lib.lmaze_describe_solve.argtypes = [P, i64, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -296,6 +301,13 @@ def describe_table_stats(m, keys, actions=4):
     """The kernel / grid / LDS lmaze_table_stats would queue for m samples and a [keys, actions] table
     (lmaze_describe_table_stats): table_stats_kernel<lds> up to 4096 bins, <global> above; "" for m == 0."""
     return _describe("lmaze_describe_table_stats", int(m), int(keys), int(actions))
+
+
+def describe_solve(params, problems):
+    """The kernel form / grid / LDS / problems per workgroup lmaze_solve would queue for `problems` mazes with these LmazeParams
+    (lmaze_describe_solve): "solve_kernel<v0, wave, 2> ..." while G*G <= 256, "solve_kernel<v0, workgroup, 4> ..." above; "" for
+    no problem."""
+    return _describe("lmaze_describe_solve", C.byref(params), int(problems))
 
 
 def sampling_thresholds(probs, actions=4):

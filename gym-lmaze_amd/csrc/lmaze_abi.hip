@@ -633,6 +633,44 @@ int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* t
     return 0;
 }
 
+// What lmaze_solve and lmaze_describe_solve judge of the params, in the header's order (the variant before the layout mode)
+static int check_solve_params(const LmazeParams* p) {
+    if (p->grid < 3 || p->grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
+    if (p->variant != LMAZE_VARIANT_V0 && p->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;
+    if (p->layout_mode != LMAZE_LAYOUT_SHARED && p->layout_mode != LMAZE_LAYOUT_PER_ENV) return LMAZE_E_LAYOUT;
+    return 0;
+}
+
+int lmaze_solve(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, float gamma,
+                int32_t sweeps, const float* v_init, float* q, float* v, uint8_t* policy, int32_t* sweeps_run, float* delta,
+                void* stream) {
+    if (!params || !layouts) return LMAZE_E_NULL;
+    const int rc = check_solve_params(params);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (v3 && !goal_xy) return LMAZE_E_NULL;
+    if (!q && !v && !policy) return LMAZE_E_NULL;
+    if (problems < 0 || problems > LMAZE_MAX_ENVS || sweeps < 1) return LMAZE_E_COUNT;
+    if (misaligned(q, 16) || (v3 && misaligned(goal_xy, 8)) || misaligned(v_init, 4) || misaligned(v, 4) || misaligned(sweeps_run, 4) ||
+        misaligned(delta, 4))
+        return LMAZE_E_ALIGN;
+    if (problems == 0) return 0;
+    const SolveArgs a{layouts, v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr, v_init, reinterpret_cast<float4*>(q), v, policy,
+                      sweeps_run, delta, problems, params->grid, sweeps, params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0, gamma,
+                      params->reward_wall, params->reward_move, params->reward_goal};
+    return (int)launch_solve(params->variant, a, (hipStream_t)stream);
+}
+
+int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    if (!params || !text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const int rc = check_solve_params(params);
+    if (rc) return rc;
+    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    if (problems == 0) return 0;
+    return describe_solve(params->variant, plan_solve(params->grid, problems), text_host, len);
+}
+
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
                            char* text_host, int32_t len) {
     // this describe's own order: the params, the variant and T before the text buffer, and the narrow planes' refusals

@@ -184,6 +184,30 @@ struct TableStatsPlan {
 #define LMAZE_TABLE_LDS_BINS 4096   // 16 bytes per bin: at most 64 KiB
 TableStatsPlan plan_table_stats(int64_t m, int64_t keys, int32_t actions);
 hipError_t launch_table_stats(const TableStatsArgs& a, hipStream_t s);
+// Value iteration over the grid mazes (lmaze_solve, lmaze_solve.hip): one problem = one maze, solved in LDS in one launch.
+struct SolveArgs {
+    const uint8_t* layouts;   // [G*G] shared or [problems*G*G]
+    const int2* goal;         // v3: [problems]
+    const float* v_init;      // [problems, G*G] or null (0)
+    float4* q;                // [problems, G*G] or null: the four action values of a cell, one 16-byte store
+    float* v;                 // [problems, G*G] or null
+    uint8_t* policy;          // [problems, G*G] or null
+    int32_t* sweeps_run;      // [problems] or null
+    float* delta;             // [problems] or null
+    int64_t problems;
+    int32_t grid, sweeps, per_env;
+    float gamma, reward_wall, reward_move, reward_goal;
+};
+// What the launcher decides from G alone, and what lmaze_describe_solve prints: a wave per problem while G*G <= 256 (four
+// problems per workgroup, no workgroup barrier), a workgroup per problem above; cells_per_lane cells of a problem per lane.
+struct SolvePlan {
+    bool wave;
+    int32_t cells_per_lane, problems_per_workgroup;
+    int64_t grid, lds_bytes;
+};
+SolvePlan plan_solve(int32_t G, int64_t problems);
+int describe_solve(int variant, const SolvePlan& p, char* text, int32_t len);
+hipError_t launch_solve(int variant, const SolveArgs& a, hipStream_t s);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

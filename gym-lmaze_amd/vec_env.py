@@ -7,6 +7,7 @@ masked reset) runs in liblmaze_hip.so; there is no CPU implementation in this pa
 
 Reference semantics: gym_lmaze/envs/lmaze_env.py (v0) and lmaze_env_v3.py (v3).
 """
+import collections
 import ctypes as C
 import logging
 
@@ -490,6 +491,45 @@ class LmazeVecEnv(VecEnvBase):
             k = k + (g[:, 0] * G + g[:, 1]) * (G * G)
         return k.to(torch.int32).contiguous()
 
+    def solve(self, gamma=0.99, sweeps=4096, key="ball", rewards=None, v_init=None, goal=None):
+        """Value iteration on this env's own maze(s), in ONE launch (solve_tables(), include/lmaze.h lmaze_solve): the
+        tables rollout_policy(q=...), rollout_sample(logits=...) and gae(values=...) take.  It reads no planes, so the u8
+        env solves as well.  rewards defaults to the env's.
+        shared layout, key="ball"   one problem: q float32[G*G, 4], v float32[G*G], policy uint8[G*G], sweeps_run and delta
+                                    0-d.  v3 needs goal=(x, y): a shared-layout v3 env has no single goal.
+        shared layout, key="goal"   v3 only: G*G problems, one per goal cell in row-major order; q [G**4, 4], v [G**4],
+                                    policy [G**4], indexed by the key of state_keys("goal"); sweeps_run, delta [G*G].
+        per-env layouts             N problems, env i's layout and (v3) its current goal_xy: q [N, G*G, 4], ...
+        v_init: float32 [problems, G*G].  Returns SolvedTables(q, v, policy, sweeps_run, delta)."""
+        if key not in _abi.KEY_MODES:
+            raise ValueError("key must be 'ball' or 'goal'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        G, dev = self.grid, self.device
+        rewards = self.rewards if rewards is None else rewards
+        shared = self.layout_mode == _abi.LAYOUT_SHARED
+        if goal is not None and not (shared and key == "ball" and self._is_v3):
+            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
+        goals = None
+        if not shared:
+            if key == "goal":
+                raise ValueError("key='goal' solves one shared layout for every goal cell; per-env layouts solve each env's own goal")
+            goals = self.goal_xy if self._is_v3 else None
+        elif key == "goal":
+            cells = torch.arange(G * G, dtype=torch.int32, device=dev)
+            goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
+        elif self._is_v3:
+            if goal is None or len(goal) != 2:
+                raise ValueError("solve(key='ball') on a shared-layout v3 env needs goal=(x, y)")
+            goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
+        t = solve_tables(self.layout, self.variant, goals=goals, gamma=gamma, sweeps=sweeps, rewards=rewards, v_init=v_init,
+                         validate=False)
+        if not shared:
+            return t
+        if key == "goal":
+            return SolvedTables(t.q.reshape(G ** 4, 4), t.v.reshape(G ** 4), t.policy.reshape(G ** 4), t.sweeps_run, t.delta)
+        return SolvedTables(t.q[0], t.v[0], t.policy[0], t.sweeps_run[0], t.delta[0])
+
     def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
         """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
         observations (obs_t / obs_every) is not captured: ValueError."""
@@ -674,6 +714,82 @@ def table_means(count, total, fill=0.0):
     seen = count > 0
     mean = total.to(torch.float64) / 16777216.0 / count.clamp(min=1).to(torch.float64)
     return torch.where(seen, mean, torch.full_like(mean, float(fill)))
+
+
+class SolvedTables(collections.namedtuple("SolvedTables", "q v policy sweeps_run delta")):
+    """What solve_tables() returns: q float32[P, S, 4], v float32[P, S], policy uint8[P, S], sweeps_run int32[P], delta
+    float32[P]; an output that was not asked for is None."""
+    __slots__ = ()
+
+
+SOLVE_OUTPUTS = ("q", "v", "policy", "sweeps_run", "delta")
+
+
+def solve_tables(layouts, variant="v0", goals=None, gamma=0.99, sweeps=4096, rewards=None, v_init=None, outputs=SOLVE_OUTPUTS,
+                 validate=True):
+    """Value iteration on the GPU: the optimal action values of every maze, in ONE launch (include/lmaze.h lmaze_solve).
+    layouts  uint8 device tensor [G, G] (one layout for every problem) or [P, G, G] (problem p solves its own maze), the
+             reference's cell characters, validated like the env's own layouts (validate=False skips that).
+    variant  "v0" (the goal is the layout's 'X') or "v3" (the goal of problem p is goals[p]).
+    goals    v3: int32 [P, 2] (x, y) on layouts' device; with a [G, G] layout P is goals' length, for v0 it is 1.
+    gamma, sweeps   the discount and the most Jacobi sweeps to run; a problem stops at the first sweep that leaves every
+             value's bits unchanged (that sweep counts), and sweeps_run tells.
+    rewards  (wall, move, goal); default the variant's.
+    v_init   float32 [P, G*G] warm start; default 0.
+    outputs  the names of the outputs to compute, of "q", "v", "policy", "sweeps_run", "delta"; at least one of the first three.
+    State s = x * G + y is the key of LmazeVecEnv.state_keys().  What the solver is and is not: the grid variants only; the
+    infinite-horizon discounted problem, the step limit is not in the model; v0's sticky pairs (a move onto an 'S' cell, which
+    the step refuses while repeating the previous reward) have no reward of their own and are excluded, q = -inf; a state on a
+    'W' cell has q = v = 0.  float32 with every operation rounded on its own, so a float32 numpy loop reproduces every bit.
+    Returns SolvedTables(q, v, policy, sweeps_run, delta)."""
+    if variant not in VARIANTS:
+        raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
+    spec = VARIANTS[variant]
+    v3 = variant == "v3"
+    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
+            and layouts.shape[-1] == layouts.shape[-2]):
+        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
+    dev = layouts.device
+    G = int(layouts.shape[-1])
+    if not (3 <= G <= _abi.MAX_GRID):
+        raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
+    layouts = layouts.contiguous()
+    if validate:
+        _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
+    shared = layouts.dim() == 2
+    if v3:
+        if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == dev and goals.dim() == 2
+                and goals.shape[1] == 2 and goals.is_contiguous() and (shared or goals.shape[0] == layouts.shape[0])):
+            raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
+        P = int(goals.shape[0])
+    else:
+        if goals is not None:
+            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
+        P = 1 if shared else int(layouts.shape[0])
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or not 1 <= sweeps < 2 ** 31:
+        raise ValueError("sweeps must be an int >= 1")
+    rewards = tuple(float(r) for r in (rewards if rewards is not None else spec["rewards"]))
+    if len(rewards) != 3:
+        raise ValueError("rewards must be (wall, move, goal)")
+    outputs = tuple(outputs)
+    if not set(outputs) <= set(SOLVE_OUTPUTS) or not set(outputs) & {"q", "v", "policy"}:
+        raise ValueError("outputs must name some of %s, at least one of q, v, policy" % (SOLVE_OUTPUTS,))
+    S = G * G
+    if v_init is not None and not (isinstance(v_init, torch.Tensor) and v_init.dtype == torch.float32 and v_init.device == dev
+                                   and v_init.is_contiguous() and tuple(v_init.shape) == (P, S)):
+        raise ValueError("v_init must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
+    shapes = {"q": ((P, S, 4), torch.float32), "v": ((P, S), torch.float32), "policy": ((P, S), torch.uint8),
+              "sweeps_run": ((P,), torch.int32), "delta": ((P,), torch.float32)}
+    out = {k: (torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) if k in outputs else None) for k in SOLVE_OUTPUTS}
+    if P > 0:
+        params = _abi.make_params(spec["id"], G, _abi.LAYOUT_SHARED if shared else _abi.LAYOUT_PER_ENV, spec["step_limit"], *rewards)
+        with torch.cuda.device(dev):
+            rc = _abi.lib.lmaze_solve(C.byref(params), layouts.data_ptr(), goals.data_ptr() if v3 else None, P, float(gamma),
+                                      int(sweeps), None if v_init is None else v_init.data_ptr(),
+                                      *[None if out[k] is None else out[k].data_ptr() for k in SOLVE_OUTPUTS],
+                                      torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check("lmaze_solve", rc)
+    return SolvedTables(*[out[k] for k in SOLVE_OUTPUTS])
 
 
 def _validate_on_device(lay, need_goal=True):

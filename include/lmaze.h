@@ -501,6 +501,61 @@ int lmaze_table_stats(const int32_t* key_t, const int32_t* actions_t, const floa
 int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* text_host, int32_t len);
 
 /*
+ * VALUE ITERATION over the grid mazes: the optimal Q table of every maze, in ONE launch; no reference counterpart (the
+ * reference has no planner).  It is the table lmaze_rollout_policy, lmaze_rollout_sample and lmaze_advantages_table take.
+ * Problem p is one maze of S = G*G states, state s = x * G + y (the ball-cell key of the closed-loop rollouts), and the four
+ * actions.  LMAZE_LAYOUT_SHARED: every problem reads layouts[0 .. G*G); LMAZE_LAYOUT_PER_ENV: problem p reads layouts + p*G*G.
+ * v3 takes the goal of problem p from goal_xy[2p], goal_xy[2p+1], compared as it is (a goal off the grid is never hit); v0
+ * does not read goal_xy, its goal is the layout's 'X'.
+ * The model is the transition of lmaze_step_v0 / _v3 itself (v0:172-195, v0:246-249, v3:224-265, v3:398), asked once per
+ * (cell, action) with a step count that trips no limit: the step limit is not part of the model, this is the
+ * infinite-horizon discounted problem.  For a state on a non-wall cell, with c the character of the target cell:
+ *   c == 'W'                 next = s, r = reward_wall
+ *   v0, c == 'B' / 'X'       next = target, r = reward_move / reward_goal
+ *   v3, any other c          next = target, r = reward_goal if the cell beyond the target is the goal, else reward_move
+ *   a pair is terminal exactly when r == reward_goal as float32 (the step's own done rule: reward_wall == reward_goal makes a
+ *   bump terminal)
+ *   v0, any other c ('S')    a STICKY pair: the step leaves the ball where it is and repeats the previous reward, which is no
+ *                            function of (cell, action).  Sticky pairs are excluded: q(s, a) = -INFINITY, never the maximum;
+ *                            a state all of whose four pairs are excluded gets v = 0, policy = 0.
+ * A state on a 'W' cell has q = 0 for all four actions, v = 0, policy = 0.  Layouts carry a full 'W' border (every target of
+ * a non-wall state is on the grid); on any other bytes a target off the grid counts as the cell itself, nothing is read out of
+ * bounds.
+ * The sweep is Jacobi, in float32, every operation rounded on its own (round to nearest even, never a fused multiply-add), as
+ * lmaze_returns:
+ *   V_0 = v_init (problem p: v_init + p*S) or 0 when v_init is NULL
+ *   Q_k(s, a) = r(s, a) for a terminal pair, else r(s, a) + gamma * V_(k-1)(next)     (the product, then the sum)
+ *   V_k(s) = the first maximum over a = 0, 1, 2, 3 by a strict '>' starting from a = 0; policy(s) = that a
+ * Sweeps run until one leaves the bit pattern of every V(s) of the problem unchanged -- that sweep counts -- or until `sweeps`
+ * have run; stopping early changes no output, the fixed point stays fixed.  Outputs, each nullable:
+ *   q           float[problems, S, 4]  Q_k of the last executed sweep; 16-byte aligned
+ *   v           float[problems, S]     V_k: max_a q bit for bit
+ *   policy      uint8[problems, S]
+ *   sweeps_run  int32[problems]        sweeps executed
+ *   delta       float[problems]        max_s |V_k(s) - V_(k-1)(s)| of the last executed sweep, a maximum over the bit patterns
+ *                                      of non-negative floats: it does not depend on the order of the reduction
+ * One launch of solve_kernel: a problem lives in LDS for the whole solve (two V buffers; the model packed in registers); a wave
+ * per problem while G*G <= 256, four problems per workgroup and no workgroup barrier; a workgroup per problem above, one
+ * barrier per sweep.  params->launch_hint, step_limit are not read.
+ * Refused, in this order: LMAZE_E_NULL params or layouts; LMAZE_E_GRID; LMAZE_E_VARIANT neither v0 nor v3; LMAZE_E_LAYOUT;
+ * LMAZE_E_NULL goal_xy for v3; LMAZE_E_NULL all of q, v and policy; LMAZE_E_COUNT problems outside [0, LMAZE_MAX_ENVS] or
+ * sweeps < 1; LMAZE_E_ALIGN q off 16 bytes, goal_xy (v3) off 8, a float or int32 pointer off 4.  problems == 0 then returns 0
+ * with nothing read.  gamma is not validated, as in lmaze_returns.  A grid beyond 2^24 - 1 workgroups:
+ * hipErrorInvalidConfiguration.
+ */
+int lmaze_solve(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, float gamma,
+                int32_t sweeps, const float* v_init, float* q, float* v, uint8_t* policy, int32_t* sweeps_run, float* delta,
+                void* stream);
+
+/*
+ * The launch lmaze_solve would queue, one line in text_host (HOST, len bytes), written by the code that launches, e.g.
+ * "solve_kernel<v0, wave, 4> grid=65 block=256 lds=8192 problems_per_workgroup=4" or "solve_kernel<v3, workgroup, 2> ..."
+ * (the third argument: cells per lane).  Nothing is queued or dereferenced.  LMAZE_E_NULL params or text_host NULL or
+ * len < 1, then lmaze_solve's refusals of the params and of `problems`; an empty line for problems == 0.
+ */
+int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes
