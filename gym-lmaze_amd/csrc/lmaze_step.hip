@@ -835,9 +835,12 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void step_shared_u8_kernel(const StepA
             if ((unsigned)b0 < 16u) w[b0 >> 2] |= (uint32_t)LMAZE_OBS_BALL << ((b0 & 3) << 3);
             if ((unsigned)b1 < 16u && le + 1 < nb) w[b1 >> 2] |= (uint32_t)LMAZE_OBS_BALL << ((b1 & 3) << 3);
             if (V3) {
-                const int g0 = goalflat[le] - c, g1 = CELLS - c + goalflat[min(le + 1, EPB)];
+                // gn < 0: env le + 1 has no goal on the grid.  Its -64 is no cell: added to CELLS - c it lands inside this
+                // store wherever G*G >= 64, on cell G*G - 64 of env le (rollout_render_u8 asks the same)
+                const int gn = goalflat[min(le + 1, EPB)];
+                const int g0 = goalflat[le] - c, g1 = CELLS - c + gn;
                 if ((unsigned)g0 < 16u) w[g0 >> 2] |= (uint32_t)LMAZE_OBS_GOAL << ((g0 & 3) << 3);
-                if ((unsigned)g1 < 16u && le + 1 < nb) w[g1 >> 2] |= (uint32_t)LMAZE_OBS_GOAL << ((g1 & 3) << 3);
+                if ((unsigned)g1 < 16u && gn >= 0 && le + 1 < nb) w[g1 >> 2] |= (uint32_t)LMAZE_OBS_GOAL << ((g1 & 3) << 3);
             }
             if (a.launch_hint & 0x100) {                                // set by the launcher for large batches: non-temporal stores
                 typedef unsigned v4u __attribute__((ext_vector_type(4)));

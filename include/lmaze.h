@@ -120,6 +120,28 @@ int lmaze_describe_step(const LmazeParams* params, int64_t n, int32_t auto_reset
                         int32_t len);
 
 /*
+ * LOADED STATE -- what lmaze_step_v0 / _v3 (and their *_autoreset and _u8 forms), lmaze_observe / _observe_u8, lmaze_reset
+ * and every lmaze_rollout* entry do with per-env state that no reset produced.  The reference indexes its layout with the
+ * coordinates as they are (v0:172, v3:251) and raises or wraps once they leave the grid; here nothing is read out of
+ * bounds, by these rules, on layouts with a full 'W' border:
+ *   - a step takes the ball clamped to 0..G-1 on each axis, and the target cell (ball + offset) clamped likewise; the
+ *     ball it stores is the clamped one, moved or not.  That is the reference's own step on the maze with one more ring
+ *     of 'W' around it: a ball on a border cell bumps when it walks outwards and moves when the cell inwards is free;
+ *   - an observe-only launch shows the ball at its clamped cell and leaves ball_xy as loaded;
+ *   - the v3 goal is compared as it is (v3:264, with the unclamped cell beyond the ball's new one) and gets its plane bit
+ *     only when it lies on the grid; the closed-loop keys, and only they, clamp it;
+ *   - done on entry (the fused reset's flag, a reset's mask) is set by any non-zero byte; a step stores 0 or 1;
+ *   - a reset with no accepted cell leaves ball_xy and goal_xy untouched -- a fresh env on such a maze keeps its ball at
+ *     (0, 0), a border cell, which the rules above cover -- and still zeroes step_count, reward and done; a v3 reset with
+ *     one accepted cell places the goal there and leaves the ball; with more, the ball's draw skips the goal's cell;
+ *   - a v0 reward that passes through a sticky pair (the target is 'S': v0:172-195 has no else) keeps its 32 bits,
+ *     whatever they are -- a NaN's payload, a signalling NaN, -0.0, a denormal -- in the state and in the reward_t rows;
+ *   - step_count is incremented as it is, from any value (a negative count, or one past the limit: v0's `==` then never
+ *     fires again, v3's `>` fires every step).
+ * tests/loaded_state.py holds these against the reference's own step on the padded maze.
+ */
+
+/*
  * One step() of N v0 mazes: replaces v0:146-237 (action decode 153-170, collision and
  * position update 172-195, reward 174/184/194, done 246-249, plane build 208-215).
  *   action      int32[N]    0:(-1,0) 1:(+1,0) 2:(0,-1) 3:(0,+1), anything else (0,0)
@@ -132,6 +154,7 @@ int lmaze_describe_step(const LmazeParams* params, int64_t n, int32_t auto_reset
  *   obs         int32[N,G,G] compact planes after the move, fully rewritten; may be NULL
  *                           (transition only); 16-byte aligned
  * Envs never auto-reset (the reference does not); stepping after done follows v0 exactly.
+ * Coordinates off the grid, and any other state no reset produced: LOADED STATE above (lmaze_step_v3 alike).
  */
 int lmaze_step_v0(const LmazeParams* params, const uint8_t* layout, const int32_t* action,
                   int32_t* ball_xy, int32_t* step_count, float* reward, uint8_t* done,
@@ -153,7 +176,8 @@ int lmaze_step_v3(const LmazeParams* params, const uint8_t* layout, const int32_
 /*
  * Compact planes of the CURRENT state without stepping: what reset() returns after
  * placement (v0:92-120, v3:166-196).  goal_xy is read for LMAZE_VARIANT_V3 only (NULL
- * otherwise).
+ * otherwise).  A ball off the grid is shown at its clamped cell and ball_xy is not written; a v3 goal
+ * off the grid has no plane bit (LOADED STATE above).
  */
 int lmaze_observe(const LmazeParams* params, const uint8_t* layout, const int32_t* ball_xy,
                   const int32_t* goal_xy, int32_t* obs, int64_t n, void* stream);
@@ -169,7 +193,13 @@ int lmaze_observe(const LmazeParams* params, const uint8_t* layout, const int32_
  * several GPUs draws exactly what one GPU holding the whole batch would.  The reference
  * draws from Python's global Mersenne Twister, so placement parity with it is
  * distributional, not bitwise.  obs (nullable): the planes of the envs that were reset are
- * re-rendered (with a mask, envs outside it keep their current planes untouched).
+ * re-rendered (with a mask, envs outside it keep their current planes: the planes are written in
+ * 16-byte stores, and a store -- at odd G of the specialised sizes, a group of four envs -- that holds cells
+ * of a reset env rewrites the cells of its neighbours too, from their unchanged state.  Planes that were
+ * current stay what they were; stale ones, after steps without obs, may come back partly fresh).
+ * A maze with no accepted cell: the coordinates stay as they are (the counters are still zeroed); a v3 maze
+ * with one: the goal goes there and the ball stays; the render clamps a ball it finds off the grid (LOADED
+ * STATE above).
  */
 int lmaze_reset(const LmazeParams* params, const uint8_t* layout, const uint8_t* mask,
                 uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* ball_xy, int32_t* goal_xy,
@@ -234,7 +264,8 @@ int lmaze_observe_u8(const LmazeParams* params, const uint8_t* layout, const int
  * rollout form; params->launch_hint bits 12-14 = k > 0: 4 << (k - 1) envs per workgroup instead of the size the library
  * picks -- for batches beyond the L2s the largest that keeps the resident workgroups' planes inside them; with per-env
  * layouts at most 64, and halved until their layouts fit one workgroup's 160 KiB of LDS (G > 50: 32); performance only).
- * The caller advances its epoch by T.
+ * The caller advances its epoch by T.  State no reset produced enters every rollout entry point as it enters T step calls
+ * (LOADED STATE above): the same clamps, the same "leave unchanged" placements, the same 32 reward bits in reward_t.
  * LMAZE_E_COUNT T < 0.  T == 0 or n == 0 (once params are valid) returns 0 with nothing read: no pointer is looked at.
  */
 int lmaze_rollout(const LmazeParams* params, const uint8_t* layout, const int32_t* actions, int32_t T, int32_t* ball_xy,

@@ -193,5 +193,32 @@ def greedy_lowers_distance(model, policy, dist):
     return ok & ~model.sticky[s, a]
 
 
+def unreachable_goals(lays, goals, every=4):
+    """v3 goals no step can pay for, written over goals[::every]: off the grid on each side and far off both, and on the
+    border's corners (the look-ahead pays when the cell BEYOND the ball's new cell is the goal -- v3:264 -- so the ball would
+    have to stand on a border cell beside the goal; the other wall cells CAN be paid for, from two cells away, see
+    walled_goals).  Returns (goals, the problems overwritten)."""
+    G = lays.shape[-1]
+    goals = np.array(goals, dtype=np.int32, copy=True)
+    who = np.arange(0, len(goals), every)
+    kinds = ((-1, 3), (2, G), (G, 1), (4, -1), (-3, G + 2), (G + 40, -70), (0, 0), (G - 1, G - 1), (0, G - 1), (G - 1, 0))
+    for j, p in enumerate(who):
+        goals[p] = kinds[j % len(kinds)]
+    return goals, who
+
+
+def walled_goals(lays, goals, seed, every=4):
+    """v3 goals on wall cells other than the corners, border and interior alike, written over goals[1::every]"""
+    rs = np.random.RandomState(seed)
+    G = lays.shape[-1]
+    goals = np.array(goals, dtype=np.int32, copy=True)
+    who = np.arange(1, len(goals), every)
+    corners = {(0, 0), (0, G - 1), (G - 1, 0), (G - 1, G - 1)}
+    for p in who:
+        cells = [tuple(c) for c in np.argwhere(lays[p] == ord("W")) if tuple(c) not in corners]
+        goals[p] = cells[rs.randint(len(cells))]
+    return goals, who
+
+
 def bits(x):
     return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)

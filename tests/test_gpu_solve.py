@@ -121,6 +121,43 @@ def test_per_env_random_mazes(lm, variant, N, G):
         assert ref.sweeps_run.min() < 20                               # ... beside solves that settle at once
 
 
+@pytest.mark.parametrize("N,G,form", [(9, 16, "wave, 4"), (9, 17, "workgroup, 2"), (5, 22, "workgroup, 2"), (5, 23, "workgroup, 4"),
+                                      (5, 33, "workgroup, 8"), (5, 40, "workgroup, 8"), (3, 45, "workgroup, 8"), (3, 46, "workgroup, 16")])
+@pytest.mark.parametrize("variant", ["v0", "v3"])
+def test_every_kernel_form_at_the_edges_of_the_form_table(lm, variant, N, G, form):
+    """Either side of every change of form (G = 16/17, 22/23, 32/33, 45/46), and the form "workgroup, 8 cells per lane"
+    (G = 33..45), which no other case launches."""
+    lays, goals = random_case(variant, N, G)
+    ref = random_ref(variant, N, G, 0.99, 1400)
+    lay_d, goal_d = on_gpu(lays, goals)
+    got = lm.solve_tables(lay_d, variant=variant, goals=goal_d, gamma=0.99, sweeps=1400)
+    assert tuple(got.q.shape) == (N, G * G, 4)
+    same(got, ref, "%s %d x %dx%d" % (variant, N, G, G))
+    p = lm._abi.make_params(lm._abi.VARIANT_V3 if variant == "v3" else lm._abi.VARIANT_V0, G, lm._abi.LAYOUT_PER_ENV, 100, *R.DEFAULT_REWARDS)
+    assert "solve_kernel<%s, %s>" % (variant, form) in lm._abi.describe_solve(p, N)
+
+
+def test_v3_goals_off_the_grid_and_on_wall_cells(lm):
+    """"A goal off the grid is never hit" (include/lmaze.h), nor is one on a corner of the border: no terminal pair, V runs
+    down to reward_move / (1 - gamma) over more than a thousand sweeps (-1 where a state can move, never above).  A goal on
+    any other wall cell is compared as it is too -- the look-ahead pays for it from two cells away -- and the solve equals
+    the reference there as everywhere."""
+    N, G = 257, 8
+    lays, goals = random_case("v3", N, G)
+    goals, off = R.unreachable_goals(lays, goals)
+    goals, walled = R.walled_goals(lays, goals, 5)
+    ref = R.solve_many("v3", lays, goals, 0.99, 1400)
+    lay_d, goal_d = on_gpu(lays, np.ascontiguousarray(goals))
+    got = lm.solve_tables(lay_d, variant="v3", goals=goal_d, gamma=0.99, sweeps=1400)
+    same(got, ref, "v3 goals off the grid and on walls")
+    free = lays.reshape(N, -1) != ord("W")
+    v = got.v.cpu().numpy()
+    assert len(off) == 65 and (got.sweeps_run.cpu().numpy()[off] > 1000).all()
+    assert (v[off][free[off]] <= np.float32(-0.99)).all()
+    assert not np.isin(np.float32(100.0), got.q.cpu().numpy()[off])
+    assert (got.q.cpu().numpy()[walled] == np.float32(100.0)).any()
+
+
 @pytest.mark.parametrize("variant", ["v0", "v3"])
 def test_warm_start(lm, variant):
     lays, goals = random_case(variant, 257, 11)

@@ -93,6 +93,30 @@ def test_batched_reference_is_the_plain_one():
                     assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (variant, gamma, p, f)
 
 
+def test_goals_off_the_grid_and_on_corners_are_never_hit():
+    """The goals test_gpu_solve.py hands to lmaze_solve, through extract_model: a v3 goal off the grid or on a corner of the
+    border gives no terminal pair, so every non-wall state has steps_to_done == inf; a goal on another wall cell is paid for
+    by the look-ahead (v3:264) wherever the ball can stand two cells away in line with it."""
+    lays = H.bordered_random_layouts(257, 8, 7)
+    goals, off = R.unreachable_goals(lays, H.random_free_cells(lays, 3))
+    goals, walled = R.walled_goals(lays, goals, 5)
+    assert len(off) == 65 and len(walled) == 64 and not set(off) & set(walled)
+    assert ((goals[off] < 0) | (goals[off] > 7)).any(1).sum() >= 39            # the rest: the four corners
+    for p in off:
+        m = R.extract_model("v3", lays[p], goals[p])
+        assert not m.terminal.any() and not m.sticky.any(), (p, goals[p])
+        assert np.isinf(R.steps_to_done(m)).all()
+        assert (m.r[~m.wall] != np.float32(100.0)).all()
+    paid = 0
+    for p in walled:
+        assert lays[p][tuple(goals[p])] == ord("W")
+        m = R.extract_model("v3", lays[p], goals[p])
+        paid += int(m.terminal.any())
+        s, a = np.nonzero(m.terminal)
+        assert (m.nxt[s, a] != s).all()                                        # a terminal pair moved: the goal lay beyond
+    assert paid > 20
+
+
 # ------------------------------------------------------------- refusals
 def test_symbols_exported_and_declared(abi):
     header = open(os.path.join(ROOT, "include", "lmaze.h")).read()
