@@ -40,7 +40,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy",
            "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
            "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
-           "lmaze_solve", "lmaze_describe_solve")
+           "lmaze_solve", "lmaze_describe_solve", "lmaze_env_rollout_policy", "lmaze_env_rollout_sample",
+           "lmaze_describe_env_rollout")
 
 
 class LmazeParams(C.Structure):
@@ -179,6 +180,14 @@ def _load():
         getattr(lib, name).argtypes = [P, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
     lib.lmaze_describe_rollout_sample.restype = C.c_int
     lib.lmaze_describe_rollout_sample.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_env_rollout_policy.restype = C.c_int
+    lib.lmaze_env_rollout_policy.argtypes = [P, vp, vp, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64,
+                                             i64, vp, i32, vp]
+    lib.lmaze_env_rollout_sample.restype = C.c_int
+    lib.lmaze_env_rollout_sample.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32,
+                                             vp]
+    lib.lmaze_describe_env_rollout.restype = C.c_int
+    lib.lmaze_describe_env_rollout.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_returns.restype = C.c_int
     lib.lmaze_returns.argtypes = [vp, vp, vp, C.c_float, vp, i32, i64, vp]
     lib.lmaze_advantages.restype = C.c_int
@@ -295,6 +304,19 @@ def describe_rollout_sample(params, n, T, auto_reset=True, with_obs=True, obs_ev
     """As describe_rollout_policy, for the sampling rollouts (lmaze_describe_rollout_sample): the line names where the
     threshold table lives, table=lds or table=global."""
     return _describe_closed("lmaze_describe_rollout_sample", params, n, T, auto_reset, with_obs, obs_every, key)
+
+
+ENV_ROLLOUT_FORMS = {"policy": 0, "sample": 1}
+
+
+def describe_env_rollout(params, n, T, auto_reset=True, with_obs=True, obs_every=0, form="policy"):
+    """As describe_rollout_policy, for the rollouts with a table per env (key="env"; lmaze_describe_env_rollout): form
+    "policy" (lmaze_env_rollout_policy) or "sample" (lmaze_env_rollout_sample); with_obs True / False -- there are no narrow
+    planes.  "rollout_perenv_kernel<v0, policy=env, table=lds, obs_t> T=16 every=3 grid=... lds=... envs_per_workgroup=...":
+    table=lds where the workgroup's byte tables are staged behind its layouts, table=global where the env's rows are read
+    from global memory (shared layouts, and the sampling form)."""
+    return _describe("lmaze_describe_env_rollout", C.byref(params), int(n), int(T), 1 if auto_reset else 0, _planes(with_obs),
+                     int(obs_every), ENV_ROLLOUT_FORMS[form] if form in ENV_ROLLOUT_FORMS else int(form))
 
 
 def describe_table_stats(m, keys, actions=4):

@@ -152,15 +152,19 @@ static int check_recording(int32_t T, const void* slots, int32_t every) {
 }
 
 // What the entry path judges of a rollout's action source: the pointer it needs, that pointer's alignment (1: none; 16: the
-// rows of the sampling thresholds), its key mode (the action rows have none) and whether a recording request comes with it
-struct SourceChecks { const void* rows; uintptr_t align; int32_t key_mode; bool recording; };
-static SourceChecks checks_of(const ActionRows& s) { return {s.actions, 1, 0, s.recording}; }
-static SourceChecks checks_of(const PolicyTable& t) { return {t.table, 1, t.key_mode, true}; }
-static SourceChecks checks_of(const SampleTable& t) { return {t.table, 16, t.key_mode, true}; }
+// rows of the sampling thresholds; 4: the per-env byte tables, staged by dwords), its key mode (the action rows have none),
+// whether a recording request comes with it, and whether it holds a table per env, whose rows n * G^2 must fit the int32 key
+struct SourceChecks { const void* rows; uintptr_t align; int32_t key_mode; bool recording; bool per_env_rows; };
+static SourceChecks checks_of(const ActionRows& s) { return {s.actions, 1, 0, s.recording, false}; }
+static SourceChecks checks_of(const PolicyTable& t) { return {t.table, 1, t.key_mode, true, false}; }
+static SourceChecks checks_of(const SampleTable& t) { return {t.table, 16, t.key_mode, true, false}; }
+static SourceChecks checks_of(const EnvPolicyTable& t) { return {t.table, 4, 0, true, true}; }
+static SourceChecks checks_of(const EnvSampleTable& t) { return {t.table, 16, 0, true, true}; }
 
 // Every grid rollout entry and, with info != null, its describe (then neither the recording request nor any pointer is
 // judged).  slots / every: the recording request as the caller gave it.  The refusals stand in this order: the recording
-// request; the params, the variant and with u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only; T; the key mode -- a
+// request; the params, the variant and with u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only; T; the key mode and,
+// a table per env, LMAZE_E_COUNT for n * G^2 > INT32_MAX (the key is an int32 row) -- a
 // bad argument is refused whether or not there is anything to do --; T == 0 or n == 0 answered before any pointer is looked
 // at; LMAZE_E_NULL with the source among the pointers; LMAZE_E_ALIGN with the source's alignment among the others.
 template <class Source>
@@ -175,6 +179,7 @@ static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const 
     if (T < 0) return LMAZE_E_COUNT;
     if (c.key_mode != 0 && c.key_mode != 1) return LMAZE_E_COUNT;
     if (c.key_mode == 1 && params->variant != LMAZE_VARIANT_V3) return LMAZE_E_VARIANT;   // v0 keeps no goal_xy
+    if (c.per_env_rows && n * params->grid * params->grid > INT32_MAX) return LMAZE_E_COUNT;
     if (T == 0 || n == 0) return 0;                                // nothing to do, nothing read
     if (!info && (rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, c.rows && step_count && reward && done, c.rows, c.align)) != 0)
         return rc;
@@ -570,6 +575,33 @@ int lmaze_describe_rollout_sample(const LmazeParams* params, int64_t n, int32_t 
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len) {
     const SampleTable tab{nullptr, nullptr, nullptr, key_mode, 0};
     return obs_every < 0 ? LMAZE_E_COUNT : describe_rollout(params, tab, n, T, auto_reset, with_obs, obs_every, text_host, len);
+}
+
+int lmaze_env_rollout_policy(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, uint32_t epsilon_u32,
+                             int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
+                             int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
+                             int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t,
+                             int32_t obs_every, void* stream) {
+    const EnvPolicyTable tab{policy, actions_t, key_t, epsilon_u32};
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
+}
+
+int lmaze_env_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t T,
+                             int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
+                             int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
+                             int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t,
+                             int32_t obs_every, void* stream) {
+    const EnvSampleTable tab{reinterpret_cast<const sample_row_t*>(thresholds), actions_t, key_t};
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
+}
+
+int lmaze_describe_env_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                               int32_t obs_every, int32_t form, char* text_host, int32_t len) {
+    if (obs_every < 0 || with_obs == 2 || (form != 0 && form != 1)) return LMAZE_E_COUNT;   // no narrow planes; 0 policy, 1 sample
+    if (form == 0) return describe_rollout(params, EnvPolicyTable{nullptr, nullptr, nullptr, 0}, n, T, auto_reset, with_obs, obs_every, text_host, len);
+    return describe_rollout(params, EnvSampleTable{nullptr, nullptr, nullptr}, n, T, auto_reset, with_obs, obs_every, text_host, len);
 }
 
 int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t, int32_t T,

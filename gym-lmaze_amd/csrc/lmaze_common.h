@@ -139,7 +139,24 @@ struct SampleTable {
     int32_t key_mode;            // 0 ball cell, 1 goal cell * G^2 + ball cell (v3)
     int32_t staged;              // != 0: the workgroup copies the ball-keyed table into LDS and reads it there
 };
+// lmaze_env_rollout_policy / lmaze_env_rollout_sample: a table PER ENV.  Row of env i (the local index, 0 <= i < n) at ball
+// cell c: i * G^2 + c, an int32 (the ABI refuses n * G^2 > INT32_MAX), which is also what key_t holds.  int32 planes only.
+struct EnvPolicyTable {
+    const uint8_t* table;     // uint8[n * G^2], 4-byte aligned: per-env layouts stage a workgroup's rows by dwords
+    int32_t* actions_t;       // [T, N] or null
+    int32_t* key_t;           // [T, N] or null
+    uint32_t epsilon;         // as PolicyTable's
+};
+struct EnvSampleTable {
+    const sample_row_t* table;   // uint32[n * G^2, 4], 16-byte aligned; read from global memory, one row per env-step
+    int32_t* actions_t;          // [T, N] or null
+    int32_t* key_t;              // [T, N] or null
+};
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const ActionRows& src, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvPolicyTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvSampleTable& tab, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const PolicyTable& tab, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);

@@ -8,6 +8,9 @@
 // the env looks its action up by the env's key (policy_act) -- and the ball-keyed table sits in LDS behind the body's other
 // arrays.  The lines of the open-loop forms are the #else branches, untouched.  LMAZE_ROLLOUT_POLICY == 2: the sampling
 // forms (RolloutSampleArgs, u8: RolloutSample8Args) -- the same lines, but the table holds one sample_row_t of thresholds per key.
+// LMAZE_ROLLOUT_POLICY == 3 / 4, bodies 2 and 3: the epsilon-greedy / sampling forms with a table PER ENV (RolloutEnvBytesArgs /
+// RolloutEnvRowsArgs): `tab` is the lane's pointer to its own env's rows -- in LDS for body 3's byte tables, staged behind the
+// layouts (LMAZE_TAB_ENV_BYTES), in global memory everywhere else.
 // Where each array of bodies 2-4 lies in LDS is lmaze_rollout_lds.h's to say, the text the host sizes the launch from (L; the
 // table by the form's kind, which moves no other array).  Not a header of its own.
 #ifndef LMAZE_ROLLOUT_BODY
@@ -108,6 +111,11 @@
     int hits = 0;
     if (ro.pol.staged)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
+#elif LMAZE_ROLLOUT_POLICY >= 3
+    // a table per env, left in global memory: the lane's pointer to its env's own rows (without an env: formed, never followed)
+    const auto tab = env_table_global(ro.pol) + e * CELLS;
+    EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
+    int hits = 0;
 #else
     uint8_t* tab = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_shared(CELLS, EPB, LMAZE_TAB_BYTES).tab);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
@@ -188,6 +196,17 @@
     int hits = 0;
     if (ro.pol.staged)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
+#elif LMAZE_ROLLOUT_POLICY == 3
+    // a byte table per env, staged below behind the layouts and by their copy: [EPB * CELLS], env tid's rows at tid * CELLS
+    uint8_t* tabs = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_perenv(CELLS, EPB, LMAZE_TAB_ENV_BYTES).tab);
+    const env_bytes_lds tab = (env_bytes_lds)tabs + tid * CELLS;
+    EnvState s = policy_load<VARIANT>(a, e, live);
+    int hits = 0;
+#elif LMAZE_ROLLOUT_POLICY == 4
+    // a threshold table per env, 16 bytes per cell: left in global memory, the lane's pointer to its env's own rows
+    const auto tab = env_table_global(ro.pol) + e * CELLS;
+    EnvState s = policy_load<VARIANT>(a, e, live);
+    int hits = 0;
 #else
     uint8_t* tab = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_perenv(CELLS, EPB, LMAZE_TAB_BYTES).tab);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);
@@ -205,6 +224,13 @@
         const int nw = (nb * CELLS) >> 2;
         for (int i = tid; i < nw; i += LMAZE_BLOCK) dst[i] = src[i];
         for (int i = (nw << 2) + tid; i < nb * CELLS; i += LMAZE_BLOCK) lays[i] = a.layout[(size_t)blockbase * CELLS + i];
+#if defined(LMAZE_ROLLOUT_POLICY) && LMAZE_ROLLOUT_POLICY == 3
+        // the same for the workgroup's tables: same offset, and the ABI has checked the table's base for a dword
+        const uint32_t* tsrc = reinterpret_cast<const uint32_t*>(ro.pol.table + (size_t)blockbase * CELLS);
+        uint32_t* tdst = reinterpret_cast<uint32_t*>(tabs);
+        for (int i = tid; i < nw; i += LMAZE_BLOCK) tdst[i] = tsrc[i];
+        for (int i = (nw << 2) + tid; i < nb * CELLS; i += LMAZE_BLOCK) tabs[i] = ro.pol.table[(size_t)blockbase * CELLS + i];
+#endif
     }
     __syncthreads();
 

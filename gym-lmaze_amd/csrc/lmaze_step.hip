@@ -23,6 +23,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "lmaze_common.h"
 #include "lmaze_policy_table.h"
@@ -1283,6 +1284,94 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void rollout_shared_u8_kernel(const St
 #undef LMAZE_ROLLOUT_POLICY
 
 // ------------------------------------------------------------------------------------
+// Closed-loop rollouts with a table PER ENV (lmaze_env_rollout_policy / lmaze_env_rollout_sample): what lmaze_solve returns for
+// per-env layouts, or a population of policies on one shared maze.  The forms above with one more key rule -- row
+// i * G^2 + ball cell of env i, the workgroup-local index blockbase + tid and not env_base + i -- and everything else theirs:
+// the fused reset, the draw, the compares, the rows, the planes.  Again new overloads on new argument types, bodies 2 and 3
+// with LMAZE_ROLLOUT_POLICY == 3 (epsilon-greedy) and 4 (sampling); int32 planes only.
+// Where the table is read.  rollout_perenv_kernel, epsilon-greedy: the workgroup's EPB * G^2 table bytes are staged into LDS
+// once, behind its layouts and by the same dword copy -- the lookup sits on the dependent chain of every env-step (state ->
+// key -> action -> transition -> state), a dependent LDS read costs a quarter of an L2 hit, and the rows are read T times.
+// Sampling (16 bytes per cell and env do not fit beside the layouts) and both forms of rollout_shared_kernel: from global
+// memory, the env's own rows, one byte or one 128-bit read per env-step.
+// ------------------------------------------------------------------------------------
+// EnvPolicyTable, EnvSampleTable: lmaze_common.h
+struct RolloutEnvBytesArgs : RolloutObsArgs { EnvPolicyTable pol; };   // actions: null, never read
+struct RolloutEnvRowsArgs : RolloutObsArgs { EnvSampleTable pol; };
+
+// The lane's table pointers carry their address space, for the reason given above policy_act(SampleTable): a generic load
+// is neither an LDS read nor a global one.
+typedef const __attribute__((address_space(3))) uint8_t* env_bytes_lds;
+typedef const __attribute__((address_space(1))) uint8_t* env_bytes_global;
+typedef const __attribute__((address_space(1))) sample_row_t* env_rows_global;
+__device__ __forceinline__ env_bytes_global env_table_global(const EnvPolicyTable& p) { return (env_bytes_global)p.table; }
+__device__ __forceinline__ env_rows_global env_table_global(const EnvSampleTable& p) { return (env_rows_global)p.table; }
+
+// policy_act(PolicyTable) with the env's own table: row = its G^2 bytes (in LDS or in global memory), e the local index
+template <int VARIANT, class Row>
+__device__ __forceinline__ void policy_act(const StepArgs& a, const EnvPolicyTable& p, Row row, int G, int t, int64_t e, EnvState& s) {
+    const int cell = clampi(s.b.x, 0, G - 1) * G + clampi(s.b.y, 0, G - 1);
+    int act = row[cell];
+    if (p.epsilon != 0) {                                             // uniform
+        const uint4 r = policy_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e);
+        if (r.x < p.epsilon) act = (int)(r.y >> 30);
+    }
+    s.act = act;
+    if (p.actions_t) p.actions_t[(size_t)t * a.n + e] = act;
+    if (p.key_t) p.key_t[(size_t)t * a.n + e] = (int)e * G * G + cell;
+}
+
+// policy_act(SampleTable) with the env's own rows in global memory: one 128-bit read, issued before the draw
+template <int VARIANT>
+__device__ __forceinline__ void policy_act(const StepArgs& a, const EnvSampleTable& p, env_rows_global row, int G, int t, int64_t e,
+                                           EnvState& s) {
+    const int cell = clampi(s.b.x, 0, G - 1) * G + clampi(s.b.y, 0, G - 1);
+    const sample_row_t c = row[cell];
+    const uint32_t r = policy_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e).x;
+    const int act = (int)(r >= c.x) + (int)(r >= c.y) + (int)(r >= c.z);
+    asm volatile("" ::"v"(c.w));
+    s.act = act;
+    if (p.actions_t) p.actions_t[(size_t)t * a.n + e] = act;
+    if (p.key_t) p.key_t[(size_t)t * a.n + e] = (int)e * G * G + cell;
+}
+
+#define LMAZE_ROLLOUT_POLICY 3
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void rollout_shared_kernel(const StepArgs a, const RolloutEnvBytesArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) void rollout_perenv_kernel(const StepArgs a, const RolloutEnvBytesArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+#undef LMAZE_ROLLOUT_POLICY
+
+#define LMAZE_ROLLOUT_POLICY 4
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void rollout_shared_kernel(const StepArgs a, const RolloutEnvRowsArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) void rollout_perenv_kernel(const StepArgs a, const RolloutEnvRowsArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+#undef LMAZE_ROLLOUT_POLICY
+
+// ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
 
@@ -1623,7 +1712,8 @@ struct RolloutPlan {
 // launch (shared layouts: rollout_shared_wave8_kernel for on-die 8x8, rollout_shared_kernel otherwise; per-env layouts:
 // rollout_perenv_kernel); T launches of the step kernel only for T = 1 or when launch_hint bit 8 forces streaming stores.
 // u8: ONE launch of rollout_shared_u8_kernel for any T and any batch size.
-// pol: the table kind of lmaze_rollout_lds.h, which says what each body keeps in LDS and where.  Not LMAZE_TAB_NONE: the
+// pol: the table kind of lmaze_rollout_lds.h, which says what each body keeps in LDS and where (LMAZE_TAB_ENV_BYTES: as many
+// bytes again as the layouts -- the 32-KiB rule stays on the layouts, the 160-KiB clamp is on the total).  Not LMAZE_TAB_NONE: the
 // closed-loop forms (rec != null) -- always one launch of a workgroup kernel (no T-launch fallback, no wave8 form: on-die
 // 8x8 goes through rollout_shared_kernel), the recording form's envs per workgroup, and the table in every LDS size, the
 // fits and clamps below included.
@@ -1708,8 +1798,9 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
 
 // The kernel of a planned rollout, the only place that names a rollout instantiation: by family and variant, and by form an
 // overload on its argument struct -- plain RolloutArgs, recording RolloutObsArgs, epsilon-greedy RolloutPolicyArgs, sampling
-// RolloutSampleArgs; u8: RolloutArgs and the *8Args.  The wave-autonomous family is never planned for a closed-loop form.
-enum RolloutForm { RF_PLAIN, RF_REC, RF_POLICY, RF_SAMPLE };
+// RolloutSampleArgs, with a table per env RolloutEnvBytesArgs / RolloutEnvRowsArgs (int32 planes only: never RO_U8); u8:
+// RolloutArgs and the *8Args.  The wave-autonomous family is never planned for a closed-loop form.
+enum RolloutForm { RF_PLAIN, RF_REC, RF_POLICY, RF_SAMPLE, RF_ENV_POLICY, RF_ENV_SAMPLE };
 template <class Args>
 using RolloutFn = void (*)(const StepArgs, const Args);
 template <class F>
@@ -1719,6 +1810,7 @@ static const void* rollout_kernel(RolloutFamily f, int variant, RolloutForm form
     using P = RolloutFn<RolloutArgs>; using R = RolloutFn<RolloutObsArgs>; using R8 = RolloutFn<RolloutObs8Args>;
     using E = RolloutFn<RolloutPolicyArgs>; using E8 = RolloutFn<RolloutPolicy8Args>;
     using S = RolloutFn<RolloutSampleArgs>; using S8 = RolloutFn<RolloutSample8Args>;
+    using EB = RolloutFn<RolloutEnvBytesArgs>; using ER = RolloutFn<RolloutEnvRowsArgs>;
     constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
     switch (f) {
         case RO_WAVE8: return form == RF_PLAIN ? kernel_of<P>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>)
@@ -1726,11 +1818,15 @@ static const void* rollout_kernel(RolloutFamily f, int variant, RolloutForm form
         case RO_SHARED: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
                                : form == RF_REC    ? kernel_of<R>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
                                : form == RF_POLICY ? kernel_of<E>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
-                                                   : kernel_of<S>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
+                               : form == RF_SAMPLE ? kernel_of<S>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                               : form == RF_ENV_POLICY ? kernel_of<EB>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                                                       : kernel_of<ER>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
         case RO_PERENV: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
                                : form == RF_REC    ? kernel_of<R>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
                                : form == RF_POLICY ? kernel_of<E>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
-                                                   : kernel_of<S>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
+                               : form == RF_SAMPLE ? kernel_of<S>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                               : form == RF_ENV_POLICY ? kernel_of<EB>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                                                       : kernel_of<ER>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
         default: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
                         : form == RF_REC    ? kernel_of<R8>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
                         : form == RF_POLICY ? kernel_of<E8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
@@ -1795,7 +1891,11 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
 
 // The closed-loop rollouts: ONE launch of the planned family's closed-loop form, whatever T and launch_hint bit 8 say.
 // Args / Args8: the kernel argument structs that carry `tab` (int32 / narrow planes); kind: the LMAZE_TAB_* of the form,
-// which the describe name states as "<form>=<ball|goal>[, table=<lds|global>]".
+// which the describe name states as "<form>=<ball|goal|env>[, table=<lds|global>]".  Args8 void: the form has no narrow planes.
+static const char* key_name(const PolicyTable& t) { return t.key_mode ? "goal" : "ball"; }
+static const char* key_name(const SampleTable& t) { return t.key_mode ? "goal" : "ball"; }
+static const char* key_name(const EnvPolicyTable&) { return "env"; }
+static const char* key_name(const EnvSampleTable&) { return "env"; }
 template <class Args, class Args8, class Table>
 static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode, const Table& tab, int kind, RolloutForm form, int32_t T,
                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
@@ -1804,13 +1904,30 @@ static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode
     char name[96] = "";
     if (a0.info)
         snprintf(name, sizeof(name), "%s<v%d, %s=%s%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
-                 form == RF_POLICY ? "policy" : "sample", tab.key_mode ? "goal" : "ball",
-                 kind == LMAZE_TAB_ROWS ? ", table=lds" : kind == LMAZE_TAB_GLOBAL ? ", table=global" : "", rec.obs_t ? ", obs_t" : "",
-                 p.nt ? ", nt" : "", T, rec.every);
+                 form == RF_POLICY || form == RF_ENV_POLICY ? "policy" : "sample", key_name(tab),
+                 kind == LMAZE_TAB_ROWS || kind == LMAZE_TAB_ENV_BYTES ? ", table=lds" : kind == LMAZE_TAB_GLOBAL ? ", table=global" : "",
+                 rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T, rec.every);
     RolloutArgs plain{nullptr, reward_t, done_t, T};
     Args ro{{plain, static_cast<int32_t*>(rec.obs_t), rec.every, p.nt ? 1 : 0}, tab};
-    Args8 ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
-    return launch_planned(p, variant, form, a0, u8 ? (void*)&ro8 : (void*)&ro, name, s);
+    if constexpr (!std::is_void<Args8>::value) {
+        Args8 ro8{{plain, static_cast<uint8_t*>(rec.obs_t), rec.every}, tab};
+        if (u8) return launch_planned(p, variant, form, a0, &ro8, name, s);
+    }
+    return launch_planned(p, variant, form, a0, &ro, name, s);
+}
+
+// lmaze_env_rollout_policy: per-env layouts stage the workgroup's tables in LDS (counted where rollout_plan fits and clamps the
+// envs per workgroup); shared layouts read them from global memory
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvPolicyTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool) {
+    const int kind = layout_mode == LMAZE_LAYOUT_PER_ENV ? LMAZE_TAB_ENV_BYTES : LMAZE_TAB_GLOBAL;
+    return launch_closed<RolloutEnvBytesArgs, void>(variant, a, layout_mode, tab, kind, RF_ENV_POLICY, T, reward_t, done_t, s, rec, false);
+}
+
+// lmaze_env_rollout_sample: the rows stay in global memory
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvSampleTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool) {
+    return launch_closed<RolloutEnvRowsArgs, void>(variant, a, layout_mode, tab, LMAZE_TAB_GLOBAL, RF_ENV_SAMPLE, T, reward_t, done_t, s, rec, false);
 }
 
 // lmaze_rollout_policy / _u8: the epsilon-greedy table, always staged

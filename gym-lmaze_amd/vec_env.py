@@ -347,6 +347,14 @@ class LmazeVecEnv(VecEnvBase):
         q        instead of policy: a float tensor [S, A] of action values, reduced on the device by greedy_table().
         epsilon  exploration rate in [0, 1]: with that probability (in steps of 2**-32) the step takes a uniform action 0-3,
                  drawn by Philox from (seed, env, epoch); 0 draws nothing.
+        key="env"  a table PER ENV (lmaze_env_rollout_policy; int32 planes, shared and per-env layouts): policy uint8
+                 [N, G*G] or flat [N*G*G], q float [N, G*G, A] or [N*G*G, A] -- what solve() returns on per-env layouts, or
+                 a population of policies on one maze.  Row i * G*G + ball cell, which is also what key_t holds, so
+                 gae(values=v.reshape(-1), key_t=..., key_tail=state_keys("env")) and table_stats(keys=N*G*G) take the rows
+                 as they are.  i is this env object's own index 0 <= i < N (a shard's local index, not env_base + i).  v3:
+                 the table is keyed by the ball cell alone and a fused reset re-draws the goal, so tables solved for the
+                 current goals are stale after a reset: use auto_reset=False, or goal-free tables (v0's goal is the layout's
+                 'X' and does not move).
         Returns what rollout() returns -- the final (obs, reward, done), with trajectory=True also reward float32[T,N] and
         done bool[T,N] -- and then, with trajectory=True, actions_t and key_t int32[T,N] (the caller's, or allocated).
         obs_every=k >= 1 records into obs_t as rollout() does; the default 0 stores the final planes only.  The epoch
@@ -355,6 +363,17 @@ class LmazeVecEnv(VecEnvBase):
         T, entries = self._closed_loop_key("rollout_policy()", T, key)
         if (policy is None) == (q is None):
             raise ValueError("rollout_policy() wants exactly one of policy= and q=")
+        if key == "env":
+            N, S = self.num_envs, self.grid ** 2
+            if isinstance(q, torch.Tensor) and q.dim() == 3 and tuple(q.shape[:2]) == (N, S):
+                q = q.reshape(N * S, q.shape[2])
+            if isinstance(policy, torch.Tensor) and tuple(policy.shape) not in ((N, S), (N * S,)):
+                raise ValueError("policy must be uint8 [%d, %d] or flat [%d] (key='env')" % (N, S, N * S))
+            policy = self._greedy_policy(policy, q, entries, "key='env', N=%d, G=%d" % (N, self.grid))
+            if policy.data_ptr() % 4:
+                raise ValueError("policy must be 4-byte aligned (key='env')")
+            return self._rollout_table("env_rollout_policy", (policy.data_ptr(), _abi.epsilon_u32(epsilon)), T, auto_reset,
+                                       trajectory, actions_t, key_t, obs_t, obs_every)
         policy = self._greedy_policy(policy, q, entries, "key=%r, G=%d" % (key, self.grid))
         return self._rollout_table("rollout_policy", (policy.data_ptr(), _abi.KEY_MODES[key], _abi.epsilon_u32(epsilon)), T,
                                    auto_reset, trajectory, actions_t, key_t, obs_t, obs_every)
@@ -372,11 +391,18 @@ class LmazeVecEnv(VecEnvBase):
         S = G*G for key="ball" (ball_x * G + ball_y), G**4 for key="goal" (v3: goal cell * G*G + ball cell).  The action is
         (r >= c0) + (r >= c1) + (r >= c2) for one Philox value r per (seed, env, epoch); a cumulative probability of 1 is
         stored as 1 - 2**-32, so deterministic policies belong to rollout_policy().  Returns what rollout_policy() returns;
-        obs_t / obs_every, the rows and the restrictions are its own too.  The epoch advances by T."""
+        obs_t / obs_every, the rows and the restrictions are its own too.  The epoch advances by T.
+        key="env": a table PER ENV (lmaze_env_rollout_sample), rows [N, G*G, 4] or flat [N*G*G, 4], row i * G*G + ball cell;
+        key_t, the index i and the note on v3 and the fused reset as in rollout_policy(key="env")."""
         T, entries = self._closed_loop_key("rollout_sample()", T, key)
         G = self.grid
         if sum(x is not None for x in (probs, logits, thresholds)) != 1:
             raise ValueError("rollout_sample() wants exactly one of probs=, logits= and thresholds=")
+        if key == "env":                               # contiguous rows [N, G*G, 4] are the flat table's own memory
+            def flat(t):
+                whole = isinstance(t, torch.Tensor) and tuple(t.shape) == (self.num_envs, G * G, 4) and t.is_contiguous()
+                return t.view(entries, 4) if whole else t
+            probs, logits, thresholds = flat(probs), flat(logits), flat(thresholds)
         if thresholds is None:
             src, name = (probs, "probs") if logits is None else (logits, "logits")
             if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
@@ -392,7 +418,8 @@ class LmazeVecEnv(VecEnvBase):
                 and thresholds.data_ptr() % 16 == 0):
             raise ValueError("thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, 4] on %s (key=%r, G=%d)"
                              % (entries, self.device, key, G))
-        return self._rollout_table("rollout_sample", (thresholds.data_ptr(), _abi.KEY_MODES[key]), T, auto_reset, trajectory,
+        table_args = (thresholds.data_ptr(),) if key == "env" else (thresholds.data_ptr(), _abi.KEY_MODES[key])
+        return self._rollout_table("env_rollout_sample" if key == "env" else "rollout_sample", table_args, T, auto_reset, trajectory,
                                    actions_t, key_t, obs_t, obs_every)
 
     def _closed_loop_key(self, who, T, key):
@@ -401,15 +428,22 @@ class LmazeVecEnv(VecEnvBase):
         if self._tuner is not None or torch.cuda.is_current_stream_capturing():
             raise ValueError("%s is not available with a device-resident epoch or while the online tuner runs" % who)
         T = self._steps(T)
+        if key == "env":
+            if self._u8:
+                raise ValueError("key='env' needs the int32 planes: the u8 env has no rollout with a table per env")
+            if self.num_envs * self.grid ** 2 > 2 ** 31 - 1:
+                raise ValueError("key='env' needs N * G*G <= 2**31 - 1: the key is an int32 row")
+            return T, self.num_envs * self.grid ** 2
         if key not in _abi.KEY_MODES:
-            raise ValueError("key must be 'ball' or 'goal'")
+            raise ValueError("key must be 'ball', 'goal' or 'env'")
         if key == "goal" and not self._is_v3:
             raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
         return T, self.grid ** 4 if key == "goal" else self.grid ** 2
 
     def _rollout_table(self, method, table_args, T, auto_reset, trajectory, actions_t, key_t, obs_t, obs_every):
         """The launch of rollout_policy() / rollout_sample(): lmaze_<method> or, for the u8 env, lmaze_<method>_u8, which
-        differ in table_args alone -- (table, key_mode, epsilon_u32) or (table, key_mode)."""
+        differ in table_args alone -- (table, key_mode, epsilon_u32) or (table, key_mode); key="env", lmaze_env_<method>:
+        (table, epsilon_u32) or (table,)."""
         name = "lmaze_" + method + ("_u8" if self._u8 else "")
         k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
 
@@ -478,14 +512,19 @@ class LmazeVecEnv(VecEnvBase):
     def state_keys(self, key="ball"):
         """int32[N]: the key of every env's CURRENT state, by the rule the key_t rows of rollout_policy() / rollout_sample()
         are written with -- coordinates clamped onto the grid, ball_x * G + ball_y, and for key="goal" (v3 only) goal cell
-        * G*G + ball cell.  Right after a rollout this is gae()'s key_tail.  Plain torch ops on ball_xy / goal_xy."""
-        if key not in _abi.KEY_MODES:
+        * G*G + ball cell; for key="env" (rollout_policy(key="env")) i * G*G + ball cell of env i, this object's own index.
+        Right after a rollout this is gae()'s key_tail.  Plain torch ops on ball_xy / goal_xy."""
+        if key != "env" and key not in _abi.KEY_MODES:
             raise ValueError("key must be 'ball' or 'goal'")
         if key == "goal" and not self._is_v3:
             raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
         G = self.grid
         b = self.ball_xy.clamp(0, G - 1)
         k = b[:, 0] * G + b[:, 1]
+        if key == "env":
+            if self.num_envs * G * G > 2 ** 31 - 1:
+                raise ValueError("key='env' needs N * G*G <= 2**31 - 1: the key is an int32 row")
+            k = k + torch.arange(self.num_envs, dtype=k.dtype, device=k.device) * (G * G)
         if key == "goal":
             g = self.goal_xy.clamp(0, G - 1)
             k = k + (g[:, 0] * G + g[:, 1]) * (G * G)
@@ -499,7 +538,8 @@ class LmazeVecEnv(VecEnvBase):
                                     0-d.  v3 needs goal=(x, y): a shared-layout v3 env has no single goal.
         shared layout, key="goal"   v3 only: G*G problems, one per goal cell in row-major order; q [G**4, 4], v [G**4],
                                     policy [G**4], indexed by the key of state_keys("goal"); sweeps_run, delta [G*G].
-        per-env layouts             N problems, env i's layout and (v3) its current goal_xy: q [N, G*G, 4], ...
+        per-env layouts             N problems, env i's layout and (v3) its current goal_xy: q [N, G*G, 4], ... -- the tables
+                                    rollout_policy(q=..., key="env") / rollout_sample(logits=..., key="env") run.
         v_init: float32 [problems, G*G].  Returns SolvedTables(q, v, policy, sweeps_run, delta)."""
         if key not in _abi.KEY_MODES:
             raise ValueError("key must be 'ball' or 'goal'")

@@ -458,6 +458,66 @@ int lmaze_describe_rollout_sample(const LmazeParams* params, int64_t n, int32_t 
                                   int32_t obs_every, int32_t key_mode, char* text_host, int32_t len);
 
 /*
+ * CLOSED-LOOP rollout with a table PER ENV: lmaze_rollout_policy with a third key rule, the one that runs what lmaze_solve
+ * returns for per-env layouts (policy uint8[N, G^2]) or a population of policies on one shared maze.  Replaces the user loop
+ * of T x (gather policy[i, ball cell], mix in exploration, step(): v0:146-237, v3:220-402, with auto_reset != 0 the reset()
+ * of done envs first, v0:64-110) by ONE launch; the action selection itself has no reference counterpart.  The arguments of
+ * lmaze_rollout_policy without key_mode, and
+ *   policy       uint8[n * G^2], 4-byte aligned: row i * G^2 + c is the action id of env i at ball cell
+ *                c = clamp(ball_x) * G + clamp(ball_y).  i is the LOCAL index 0 <= i < n of this call's buffers, not
+ *                env_base + i: a shard passes its own envs' tables.  Ids above 3 are no move; nothing is validated
+ *   key_t        int32[T,N], nullable: i * G^2 + c, the row the action was looked up in -- so values[key_t] gathers from a
+ *                flat float32[n * G^2] table (lmaze_advantages_table) and lmaze_table_stats bins with keys = n * G^2
+ * Everything else is lmaze_rollout_policy's to the bit: the fused reset and its draw, the exploration draw (counter word
+ * ep_hi ^ 0x80000000, global env index e = env_base + i), r.y >> 30 when r.x < epsilon_u32, planes stored on recorded steps
+ * and after the last one only, the caller's epoch advancing by T, always ONE launch (launch_hint bit 8 is not read; bits
+ * 12-14 and bit 15 as in lmaze_rollout_obs).  int32 planes, v0 and v3, shared and per-env layouts.
+ * v3: the table is keyed by the ball cell alone.  A fused reset re-draws the env's goal, so a table solved for the current
+ * goal_xy is stale after it: pass auto_reset = 0, or tables that do not depend on the goal.  v0's goal is the layout's 'X'.
+ * Where the table is read: per-env layouts ("rollout_perenv_kernel<v0, policy=env, table=lds, obs_t>") stage the workgroup's
+ * envs_per_workgroup * G^2 table bytes into LDS once, behind its layouts -- counted where the envs per workgroup are clamped
+ * to LDS --; shared layouts ("rollout_shared_kernel<v0, policy=env, table=global>") read one byte per env-step from global
+ * memory.
+ * Refusals: lmaze_rollout_policy's, in its order, with this in the place of the key mode's: LMAZE_E_COUNT when
+ * n * G^2 > INT32_MAX (refused whether or not key_t is given, and before T == 0 or n == 0 returns 0 with nothing read, not even
+ * an alignment); LMAZE_E_ALIGN for a policy that is not 4-byte aligned joins the other alignment refusals.
+ */
+int lmaze_env_rollout_policy(const LmazeParams* params, const uint8_t* layout, const uint8_t* policy, uint32_t epsilon_u32,
+                             int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
+                             int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
+                             int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t,
+                             int32_t obs_every, void* stream);
+
+/*
+ * SAMPLING closed-loop rollout with a table PER ENV: lmaze_rollout_sample with lmaze_env_rollout_policy's key rule.  Replaces
+ * the user loop of T x (gather probs[i, ball cell], draw the action, step(): v0:146-237, v3:220-402, with auto_reset != 0 the
+ * reset() of done envs first, v0:64-110) by ONE launch; the action selection itself has no reference counterpart.  The
+ * arguments of lmaze_rollout_sample without key_mode, and
+ *   thresholds   uint32[n * G^2, 4], 16-byte aligned: row i * G^2 + c holds (c0, c1, c2, reserved) of env i (local index) at
+ *                ball cell c; lmaze_rollout_sample's sampling rule, draw and conversion
+ * key_t as in lmaze_env_rollout_policy, and its note on v3 and the fused reset.  Every env-step makes one 128-bit read of
+ * its env's own row from global memory ("rollout_perenv_kernel<v3, sample=env, table=global>"): 16 bytes per cell and env do
+ * not fit LDS beside the layouts, and none is reserved.
+ * Refusals: lmaze_env_rollout_policy's, with LMAZE_E_ALIGN for thresholds that are not 16-byte aligned.
+ */
+int lmaze_env_rollout_sample(const LmazeParams* params, const uint8_t* layout, const uint32_t* thresholds, int32_t T,
+                             int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done,
+                             int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t, int32_t* key_t,
+                             int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* obs_t,
+                             int32_t obs_every, void* stream);
+
+/*
+ * As lmaze_describe_rollout_policy, for the rollouts with a table per env: form 0 lmaze_env_rollout_policy, 1
+ * lmaze_env_rollout_sample; with_obs 0 (obs NULL) or 1 (int32 obs), e.g. "rollout_perenv_kernel<v0, policy=env, table=lds,
+ * obs_t> T=16 every=3 grid=... lds=... envs_per_workgroup=..." or "rollout_shared_kernel<v3, sample=env, table=global> ...".
+ * Nothing is queued or dereferenced; no reference counterpart.  LMAZE_E_COUNT for obs_every < 0, with_obs == 2 (there are
+ * no narrow planes here) or a form outside {0, 1}; then the calls' own refusals that need no buffer; T == 0 or n == 0: an
+ * empty line.
+ */
+int lmaze_describe_env_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                               int32_t obs_every, int32_t form, char* text_host, int32_t len);
+
+/*
  * Discounted returns-to-go over the [T, N] rows a rollout writes; no reference counterpart (the reference keeps no
  * trajectories).  Replaces the T dependent steps of a host-driven reverse loop by ONE launch, one lane per env:
  *   ret = tail[i] (0 when tail is NULL); for t = T-1 .. 0:
