@@ -41,7 +41,7 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
            "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
            "lmaze_solve", "lmaze_describe_solve", "lmaze_env_rollout_policy", "lmaze_env_rollout_sample",
-           "lmaze_describe_env_rollout")
+           "lmaze_describe_env_rollout", "lmaze_env_rollout_qlearn", "lmaze_describe_env_rollout_qlearn")
 
 
 class LmazeParams(C.Structure):
@@ -188,6 +188,11 @@ def _load():
                                              vp]
     lib.lmaze_describe_env_rollout.restype = C.c_int
     lib.lmaze_describe_env_rollout.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
+    lib.lmaze_env_rollout_qlearn.restype = C.c_int
+    lib.lmaze_env_rollout_qlearn.argtypes = [P, vp, vp, C.c_float, C.c_float, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, i64, i32, u64, u64, i64, vp, i32, vp]
+    lib.lmaze_describe_env_rollout_qlearn.restype = C.c_int
+    lib.lmaze_describe_env_rollout_qlearn.argtypes = [P, i64, i32, i32, i32, i32, C.c_char_p, i32]
     lib.lmaze_returns.restype = C.c_int
     lib.lmaze_returns.argtypes = [vp, vp, vp, C.c_float, vp, i32, i64, vp]
     lib.lmaze_advantages.restype = C.c_int
@@ -317,6 +322,14 @@ def describe_env_rollout(params, n, T, auto_reset=True, with_obs=True, obs_every
     from global memory (shared layouts, and the sampling form)."""
     return _describe("lmaze_describe_env_rollout", C.byref(params), int(n), int(T), 1 if auto_reset else 0, _planes(with_obs),
                      int(obs_every), ENV_ROLLOUT_FORMS[form] if form in ENV_ROLLOUT_FORMS else int(form))
+
+
+def describe_env_rollout_qlearn(params, n, T, auto_reset=True, with_obs=True, obs_every=0):
+    """As describe_env_rollout, for the Q-learner inside the rollout (lmaze_describe_env_rollout_qlearn):
+    "rollout_perenv_kernel<v0, qlearn=env, table=global, obs_t> T=16 every=3 grid=... lds=... envs_per_workgroup=..." -- the
+    table is always read and written in global memory."""
+    return _describe("lmaze_describe_env_rollout_qlearn", C.byref(params), int(n), int(T), 1 if auto_reset else 0, _planes(with_obs),
+                     int(obs_every))
 
 
 def describe_table_stats(m, keys, actions=4):

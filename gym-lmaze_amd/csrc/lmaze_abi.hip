@@ -154,19 +154,22 @@ static int check_recording(int32_t T, const void* slots, int32_t every) {
 // What the entry path judges of a rollout's action source: the pointer it needs, that pointer's alignment (1: none; 16: the
 // rows of the sampling thresholds; 4: the per-env byte tables, staged by dwords), its key mode (the action rows have none),
 // whether a recording request comes with it, and whether it holds a table per env, whose rows n * G^2 must fit the int32 key
-struct SourceChecks { const void* rows; uintptr_t align; int32_t key_mode; bool recording; bool per_env_rows; };
+// -- and one more row the source fills whose alignment is judged (the Q-learner's td_t, floats: 4)
+struct SourceChecks { const void* rows; uintptr_t align; int32_t key_mode; bool recording; bool per_env_rows; const void* filled = nullptr; };
 static SourceChecks checks_of(const ActionRows& s) { return {s.actions, 1, 0, s.recording, false}; }
 static SourceChecks checks_of(const PolicyTable& t) { return {t.table, 1, t.key_mode, true, false}; }
 static SourceChecks checks_of(const SampleTable& t) { return {t.table, 16, t.key_mode, true, false}; }
 static SourceChecks checks_of(const EnvPolicyTable& t) { return {t.table, 4, 0, true, true}; }
 static SourceChecks checks_of(const EnvSampleTable& t) { return {t.table, 16, 0, true, true}; }
+static SourceChecks checks_of(const EnvQTable& t) { return {t.q, 16, 0, true, true, t.td_t}; }
 
 // Every grid rollout entry and, with info != null, its describe (then neither the recording request nor any pointer is
 // judged).  slots / every: the recording request as the caller gave it.  The refusals stand in this order: the recording
 // request; the params, the variant and with u8 (lmaze_step_u8's refusals) shared layouts and G >= 4 only; T; the key mode and,
 // a table per env, LMAZE_E_COUNT for n * G^2 > INT32_MAX (the key is an int32 row) -- a
 // bad argument is refused whether or not there is anything to do --; T == 0 or n == 0 answered before any pointer is looked
-// at; LMAZE_E_NULL with the source among the pointers; LMAZE_E_ALIGN with the source's alignment among the others.
+// at; LMAZE_E_NULL with the source among the pointers; LMAZE_E_ALIGN with the source's alignment among the others, and that of
+// a row it fills (the Q-learner's td_t).
 template <class Source>
 static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const Source& src, int32_t T, int32_t* ball_xy,
                         int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* goal_count, void* obs, bool u8,
@@ -183,6 +186,7 @@ static int grid_rollout(const LmazeParams* params, const uint8_t* layout, const 
     if (T == 0 || n == 0) return 0;                                // nothing to do, nothing read
     if (!info && (rc = check_buffers(params, u8, layout, ball_xy, goal_xy, obs, c.rows && step_count && reward && done, c.rows, c.align)) != 0)
         return rc;
+    if (!info && misaligned(c.filled, 4)) return LMAZE_E_ALIGN;
     StepArgs a = grid_args(params, layout, nullptr, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, u8, n, auto_reset,
                            seed, epoch, env_base);
     a.info = info;
@@ -602,6 +606,23 @@ int lmaze_describe_env_rollout(const LmazeParams* params, int64_t n, int32_t T, 
     if (obs_every < 0 || with_obs == 2 || (form != 0 && form != 1)) return LMAZE_E_COUNT;   // no narrow planes; 0 policy, 1 sample
     if (form == 0) return describe_rollout(params, EnvPolicyTable{nullptr, nullptr, nullptr, 0}, n, T, auto_reset, with_obs, obs_every, text_host, len);
     return describe_rollout(params, EnvSampleTable{nullptr, nullptr, nullptr}, n, T, auto_reset, with_obs, obs_every, text_host, len);
+}
+
+int lmaze_env_rollout_qlearn(const LmazeParams* params, const uint8_t* layout, float* q, float alpha, float gamma,
+                             uint32_t epsilon_u32, int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                             uint8_t* done, int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t,
+                             int32_t* key_t, float* td_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                             int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream) {
+    const EnvQTable tab{reinterpret_cast<q_row_t*>(q), alpha, gamma, epsilon_u32, actions_t, key_t, td_t};
+    return grid_rollout(params, layout, tab, T, ball_xy, goal_xy, step_count, reward, done, goal_count, obs, false, reward_t, done_t, n,
+                        auto_reset, seed, epoch, env_base, obs_t, obs_every, nullptr, stream);
+}
+
+int lmaze_describe_env_rollout_qlearn(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                      int32_t obs_every, char* text_host, int32_t len) {
+    if (obs_every < 0 || with_obs == 2) return LMAZE_E_COUNT;      // no narrow planes
+    return describe_rollout(params, EnvQTable{nullptr, 0.0f, 0.0f, 0, nullptr, nullptr, nullptr}, n, T, auto_reset, with_obs, obs_every,
+                            text_host, len);
 }
 
 int lmaze_returns(const float* reward_t, const uint8_t* done_t, const float* tail, float gamma, float* returns_t, int32_t T,

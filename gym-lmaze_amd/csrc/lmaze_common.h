@@ -152,7 +152,21 @@ struct EnvSampleTable {
     int32_t* actions_t;          // [T, N] or null
     int32_t* key_t;              // [T, N] or null
 };
+// lmaze_env_rollout_qlearn: a Q table per env that the rollout acts on AND updates, one Q-learning step per env-step.  The
+// lane that steps env i is the only reader and writer of its rows, so the updates of an env are one sequential float32
+// recurrence.  Rows as EnvSampleTable's: i * G^2 + c, 16 bytes each, read and written in global memory.
+typedef float q_row_t __attribute__((ext_vector_type(4)));              // one cell's row: q(c, 0..3)
+struct EnvQTable {
+    q_row_t* q;               // float32[n * G^2, 4], 16-byte aligned, updated in place: neither const nor __restrict__
+    float alpha, gamma;       // not validated
+    uint32_t epsilon;         // as PolicyTable's
+    int32_t* actions_t;       // [T, N] or null
+    int32_t* key_t;           // [T, N] or null
+    float* td_t;              // [T, N] or null: the TD error target - q(c, a) of every step
+};
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const ActionRows& src, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvQTable& tab, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvPolicyTable& tab, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8);

@@ -1,6 +1,7 @@
 // The per-element arithmetic of the learner-side kernels (lmaze_advantages, lmaze_table_stats: include/lmaze.h), shared by
 // the kernels (lmaze_aux.hip) and by a host-compiled program (tests/csrc/learn_host.cpp, CPU suite) that runs the same text
-// against a numpy restatement, bit for bit.
+// against a numpy restatement, bit for bit.  And of the learner inside the rollout (lmaze_env_rollout_qlearn, lmaze_step.hip;
+// tests/csrc/qlearn_host.cpp).
 #ifndef LMAZE_LEARN_H_
 #define LMAZE_LEARN_H_
 
@@ -34,6 +35,40 @@ LMAZE_HD float lmaze_gae_step(float r, int done, float v, float v_next, float ga
 
 // the value target of a row: advantage + value, one rounding
 LMAZE_HD float lmaze_gae_target(float adv, float v) { return adv + v; }
+
+// The arithmetic of the in-kernel Q-learner (lmaze_env_rollout_qlearn; tests/csrc/qlearn_host.cpp runs the same text on the
+// host).  The same rule as lmaze_gae_step: every operation rounded on its own, never an fma.
+// The greedy action of a row and its value: the FIRST maximum, by a strict > from a = 0 on -- solve_cell's rule
+// (lmaze_solve.hip).  A NaN never wins a compare, and nothing beats a NaN in q[0]: such a row keeps action 0 and returns the NaN.
+LMAZE_HD float lmaze_q_first_max(const float q[4], int* action) {
+    float best = q[0];
+    int act = 0;
+    for (int a = 1; a < 4; ++a)
+        if (q[a] > best) { best = q[a]; act = a; }
+    *action = act;
+    return best;
+}
+
+// The one-step target: r for a transition that ended the episode, else r + gamma * v_next -- the product rounded, then the
+// sum.  A done row is r itself (no "+ gamma * 0": a -0.0 stays -0.0, an infinite v_next makes no NaN).
+LMAZE_HD float lmaze_q_target(float r, int done, float gamma, float v_next) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (done) return r;
+    const float boot = gamma * v_next;
+    return r + boot;
+}
+
+// q(s, a) += alpha * (target - q(s, a)) in three roundings; *delta: the TD error target - q(s, a)
+LMAZE_HD float lmaze_q_update(float q_sa, float alpha, float target, float* delta) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    *delta = target - q_sa;
+    const float step = alpha * *delta;
+    return q_sa + step;
+}
 
 LMAZE_HD uint32_t lmaze_learn_bits(float f) { union { uint32_t u; float f; } c; c.f = f; return c.u; }
 

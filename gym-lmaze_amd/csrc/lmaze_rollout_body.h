@@ -10,7 +10,9 @@
 // forms (RolloutSampleArgs, u8: RolloutSample8Args) -- the same lines, but the table holds one sample_row_t of thresholds per key.
 // LMAZE_ROLLOUT_POLICY == 3 / 4, bodies 2 and 3: the epsilon-greedy / sampling forms with a table PER ENV (RolloutEnvBytesArgs /
 // RolloutEnvRowsArgs): `tab` is the lane's pointer to its own env's rows -- in LDS for body 3's byte tables, staged behind the
-// layouts (LMAZE_TAB_ENV_BYTES), in global memory everywhere else.
+// layouts (LMAZE_TAB_ENV_BYTES), in global memory everywhere else.  LMAZE_ROLLOUT_POLICY == 5, bodies 2 and 3: the Q-learner
+// (RolloutEnvQArgs): `tab` is the lane's QLane -- its env's rows in global memory, the cell policy_act looked up and the row carried
+// from the step before -- and after the transition qlearn_update writes that cell's row back.
 // Where each array of bodies 2-4 lies in LDS is lmaze_rollout_lds.h's to say, the text the host sizes the launch from (L; the
 // table by the form's kind, which moves no other array).  Not a header of its own.
 #ifndef LMAZE_ROLLOUT_BODY
@@ -111,6 +113,11 @@
     int hits = 0;
     if (ro.pol.staged)
         for (int i = tid; i < CELLS; i += LMAZE_BLOCK) tab[i] = ro.pol.table[i];      // 16-byte copies
+#elif LMAZE_ROLLOUT_POLICY == 5
+    // a Q table per env, read and written in global memory: the lane's rows and, from policy_act on, the step's cell
+    QLane tab{env_table_global(ro.pol) + e * CELLS, 0, {}, -1, {}};           // next_cell -1: no row carried yet
+    EnvState s = policy_load<VARIANT>(a, e, live);                            // in flight over the set-up
+    int hits = 0;
 #elif LMAZE_ROLLOUT_POLICY >= 3
     // a table per env, left in global memory: the lane's pointer to its env's own rows (without an env: formed, never followed)
     const auto tab = env_table_global(ro.pol) + e * CELLS;
@@ -155,6 +162,9 @@
             policy_act<VARIANT>(a, ro.pol, tab, G, t, e, s);                          // the action of the state just reset
 #endif
             hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lay[tx * G + ty]; }, s) ? 1 : 0;
+#if defined(LMAZE_ROLLOUT_POLICY) && LMAZE_ROLLOUT_POLICY == 5
+            qlearn_update(ro.pol, tab, G, a.n, t, e, s);                              // learns from what the step returned
+#endif
             rollout_record(ro, a.n, t, e, s);
             ballflat[tid] = ball_cell_of(s.b, G);
             if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);
@@ -207,6 +217,11 @@
     const auto tab = env_table_global(ro.pol) + e * CELLS;
     EnvState s = policy_load<VARIANT>(a, e, live);
     int hits = 0;
+#elif LMAZE_ROLLOUT_POLICY == 5
+    // a Q table per env, read and written in global memory: the lane's rows and, from policy_act on, the step's cell
+    QLane tab{env_table_global(ro.pol) + e * CELLS, 0, {}, -1, {}};
+    EnvState s = policy_load<VARIANT>(a, e, live);
+    int hits = 0;
 #else
     uint8_t* tab = reinterpret_cast<uint8_t*>(lds + lmaze_rollout_lds_perenv(CELLS, EPB, LMAZE_TAB_BYTES).tab);   // [CELLS] the ball-keyed table
     EnvState s = policy_load<VARIANT>(a, e, live);
@@ -255,6 +270,9 @@
                 policy_act<VARIANT>(a, ro.pol, tab, G, t, e, s);                      // the action of the state just reset
 #endif
                 hits += env_advance<VARIANT>(a, G, [&](int tx, int ty) { return lays[tid * CELLS + tx * G + ty]; }, s) ? 1 : 0;
+#if defined(LMAZE_ROLLOUT_POLICY) && LMAZE_ROLLOUT_POLICY == 5
+                qlearn_update(ro.pol, tab, G, a.n, t, e, s);                          // learns from what the step returned
+#endif
                 rollout_record(ro, a.n, t, e, s);
                 ballflat[tid] = ball_cell_of(s.b, G);
                 if (V3) goalflat[tid] = goal_cell_of<VARIANT>(s.g, G);

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "lmaze_common.h"
+#include "lmaze_learn.h"
 #include "lmaze_policy_table.h"
 #include "lmaze_rollout_lds.h"
 
@@ -1372,6 +1373,100 @@ __global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))
 #undef LMAZE_ROLLOUT_POLICY
 
 // ------------------------------------------------------------------------------------
+// Q-learning inside the rollout (lmaze_env_rollout_qlearn): the forms with a table per env, where the table is float32 action
+// values that the lane acts on epsilon-greedily AND updates after every transition -- N independent tabular learners, acting,
+// stepping and learning T steps in ONE launch.  The lane that steps env i is the only reader and writer of table i, so an
+// env's updates are a sequential float32 recurrence (lmaze_learn.h: lmaze_q_first_max, lmaze_q_target, lmaze_q_update, no
+// fma) that a host loop reproduces bit for bit; a shared table would need atomics and an arbitrary update order.
+// Per env-step: the row of the cell c the env stands on, after the transition the row of the cell c' it reached (128 bits,
+// read BEFORE the write: the target bootstraps from the table as it stood), and the row of c written back whole with word a
+// replaced.  Every access goes through one pointer type, q_rows_global -- address space 1, neither const nor __restrict__
+// -- so no read of a later step can move above an earlier step's write of the same row (c' == c on every wall bump, and a
+// ball that walks back reads what it wrote two steps before).
+// The row of c' IS the row of c at step t + 1 unless a reset moves the ball, so the lane keeps it in registers (QLane::next_*,
+// on a bump the row it has just written) and reads the table only where the cells differ: one dependent global round trip
+// per env-step instead of two.  Measured against the build that reads both rows (tools/bench_qlearn.py, T = 64, us per step,
+// medians of 9 rounds, two processes each, alternating): 16 384 x 11x11 per-env 1.86 against 1.99, 65 536 x 11x11 per-env
+// 3.46 against 3.55, 16 384 x 32x32 per-env 3.63 against 3.72, 65 536 x 11x11 shared 2.64 against 2.76.  The five more
+// registers do not fit the siblings' occupancy targets without 12 bytes of scratch per lane: 7 waves per SIMD asked for the
+// shared-layout kernel (67 / 72 VGPRs, v0 / v3) and 6 for the per-env one (72 / 77); the figures above are at these.
+// Bodies 2 and 3 with LMAZE_ROLLOUT_POLICY == 5; the table stays in global memory (LMAZE_TAB_GLOBAL: 16 bytes per cell and env
+// do not fit LDS beside the layouts), int32 planes only.
+// ------------------------------------------------------------------------------------
+// EnvQTable, q_row_t: lmaze_common.h
+struct RolloutEnvQArgs : RolloutObsArgs { EnvQTable pol; };           // actions: null, never read
+
+typedef __attribute__((address_space(1))) q_row_t* q_rows_global;
+__device__ __forceinline__ q_rows_global env_table_global(const EnvQTable& p) { return (q_rows_global)p.q; }
+// What the owning lane carries: its env's rows; from the lookup to the update the cell it acted from and that cell's row;
+// from the update to the next lookup the cell it reached and that cell's row
+struct QLane {
+    q_rows_global rows;
+    int cell;
+    q_row_t row;
+    int next_cell;            // the cell the last transition reached (-1: none yet) and its row as the table now holds it
+    q_row_t next_row;
+};
+
+// policy_act(EnvPolicyTable) with the greedy action taken from the env's own row of values: the first maximum
+template <int VARIANT>
+__device__ __forceinline__ void policy_act(const StepArgs& a, const EnvQTable& p, QLane& q, int G, int t, int64_t e, EnvState& s) {
+    q.cell = clampi(s.b.x, 0, G - 1) * G + clampi(s.b.y, 0, G - 1);
+    if (q.cell == q.next_cell) q.row = q.next_row;                    // carried: the same words the table holds
+    else q.row = q.rows[q.cell];                                      // the first step, or a reset moved the ball
+    const float v[4] = {q.row.x, q.row.y, q.row.z, q.row.w};
+    int act;
+    (void)lmaze_q_first_max(v, &act);
+    if (p.epsilon != 0) {                                             // uniform
+        const uint4 r = policy_draw(a.seed, a.epoch + (uint64_t)t, a.env_base + e);
+        if (r.x < p.epsilon) act = (int)(r.y >> 30);
+    }
+    s.act = act;
+    if (p.actions_t) p.actions_t[(size_t)t * a.n + e] = act;
+    if (p.key_t) p.key_t[(size_t)t * a.n + e] = (int)e * G * G + q.cell;
+}
+
+// The update of the transition env_advance just made: s holds the cell reached, the step's reward and its own done flag
+// (the step limit counts).  The word is chosen by compares, not by an index into the row: no scratch.
+__device__ __forceinline__ void qlearn_update(const EnvQTable& p, QLane& q, int G, int64_t n, int t, int64_t e, const EnvState& s) {
+    const q_row_t next = q.rows[ball_cell_of(s.b, G)];                // as the table stands before this step's write
+    const float v[4] = {next.x, next.y, next.z, next.w};
+    int greedy;
+    const float v_next = lmaze_q_first_max(v, &greedy);
+    const int act = s.act;
+    const float q_sa = act == 0 ? q.row.x : act == 1 ? q.row.y : act == 2 ? q.row.z : q.row.w;
+    float delta;
+    const float q_new = lmaze_q_update(q_sa, p.alpha, lmaze_q_target(s.r, s.done, p.gamma, v_next), &delta);
+    q_row_t w = q.row;
+    w.x = act == 0 ? q_new : w.x;
+    w.y = act == 1 ? q_new : w.y;
+    w.z = act == 2 ? q_new : w.z;
+    w.w = act == 3 ? q_new : w.w;
+    q.rows[q.cell] = w;
+    q.next_cell = ball_cell_of(s.b, G);
+    q.next_row = q.next_cell == q.cell ? w : next;                    // a bump: the row just written
+    if (p.td_t) p.td_t[(size_t)t * n + e] = delta;
+}
+
+#define LMAZE_ROLLOUT_POLICY 5
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) void rollout_shared_kernel(const StepArgs a, const RolloutEnvQArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 2
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void rollout_perenv_kernel(const StepArgs a, const RolloutEnvQArgs ro) {
+    constexpr bool REC = true;
+#define LMAZE_ROLLOUT_BODY 3
+#include "lmaze_rollout_body.h"
+#undef LMAZE_ROLLOUT_BODY
+}
+#undef LMAZE_ROLLOUT_POLICY
+
+// ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
 
@@ -1799,8 +1894,9 @@ static RolloutPlan rollout_plan(const StepArgs& a, int layout_mode, int32_t T, c
 // The kernel of a planned rollout, the only place that names a rollout instantiation: by family and variant, and by form an
 // overload on its argument struct -- plain RolloutArgs, recording RolloutObsArgs, epsilon-greedy RolloutPolicyArgs, sampling
 // RolloutSampleArgs, with a table per env RolloutEnvBytesArgs / RolloutEnvRowsArgs (int32 planes only: never RO_U8); u8:
-// RolloutArgs and the *8Args.  The wave-autonomous family is never planned for a closed-loop form.
-enum RolloutForm { RF_PLAIN, RF_REC, RF_POLICY, RF_SAMPLE, RF_ENV_POLICY, RF_ENV_SAMPLE };
+// RolloutArgs and the *8Args; the Q-learner RolloutEnvQArgs (int32 planes only).  The wave-autonomous family is never planned
+// for a closed-loop form.
+enum RolloutForm { RF_PLAIN, RF_REC, RF_POLICY, RF_SAMPLE, RF_ENV_POLICY, RF_ENV_SAMPLE, RF_ENV_QLEARN };
 template <class Args>
 using RolloutFn = void (*)(const StepArgs, const Args);
 template <class F>
@@ -1810,7 +1906,7 @@ static const void* rollout_kernel(RolloutFamily f, int variant, RolloutForm form
     using P = RolloutFn<RolloutArgs>; using R = RolloutFn<RolloutObsArgs>; using R8 = RolloutFn<RolloutObs8Args>;
     using E = RolloutFn<RolloutPolicyArgs>; using E8 = RolloutFn<RolloutPolicy8Args>;
     using S = RolloutFn<RolloutSampleArgs>; using S8 = RolloutFn<RolloutSample8Args>;
-    using EB = RolloutFn<RolloutEnvBytesArgs>; using ER = RolloutFn<RolloutEnvRowsArgs>;
+    using EB = RolloutFn<RolloutEnvBytesArgs>; using ER = RolloutFn<RolloutEnvRowsArgs>; using EQ = RolloutFn<RolloutEnvQArgs>;
     constexpr int V0 = LMAZE_VARIANT_V0, V3 = LMAZE_VARIANT_V3;
     switch (f) {
         case RO_WAVE8: return form == RF_PLAIN ? kernel_of<P>(variant, rollout_shared_wave8_kernel<V3, 64>, rollout_shared_wave8_kernel<V0, 64>)
@@ -1820,13 +1916,15 @@ static const void* rollout_kernel(RolloutFamily f, int variant, RolloutForm form
                                : form == RF_POLICY ? kernel_of<E>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
                                : form == RF_SAMPLE ? kernel_of<S>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
                                : form == RF_ENV_POLICY ? kernel_of<EB>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
-                                                       : kernel_of<ER>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
+                               : form == RF_ENV_SAMPLE ? kernel_of<ER>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>)
+                                                       : kernel_of<EQ>(variant, rollout_shared_kernel<V3>, rollout_shared_kernel<V0>);
         case RO_PERENV: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
                                : form == RF_REC    ? kernel_of<R>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
                                : form == RF_POLICY ? kernel_of<E>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
                                : form == RF_SAMPLE ? kernel_of<S>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
                                : form == RF_ENV_POLICY ? kernel_of<EB>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
-                                                       : kernel_of<ER>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
+                               : form == RF_ENV_SAMPLE ? kernel_of<ER>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>)
+                                                       : kernel_of<EQ>(variant, rollout_perenv_kernel<V3>, rollout_perenv_kernel<V0>);
         default: return form == RF_PLAIN    ? kernel_of<P>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
                         : form == RF_REC    ? kernel_of<R8>(variant, rollout_shared_u8_kernel<V3>, rollout_shared_u8_kernel<V0>)
                         : form == RF_POLICY ? kernel_of<E8>(variant, rollout_shared_u8_kernel<V3, true>, rollout_shared_u8_kernel<V0, true>)
@@ -1891,11 +1989,12 @@ hipError_t launch_rollout(int variant, const StepArgs& a0, int layout_mode, cons
 
 // The closed-loop rollouts: ONE launch of the planned family's closed-loop form, whatever T and launch_hint bit 8 say.
 // Args / Args8: the kernel argument structs that carry `tab` (int32 / narrow planes); kind: the LMAZE_TAB_* of the form,
-// which the describe name states as "<form>=<ball|goal|env>[, table=<lds|global>]".  Args8 void: the form has no narrow planes.
+// which the describe name states as "<policy|sample|qlearn>=<ball|goal|env>[, table=<lds|global>]".  Args8 void: the form has no narrow planes.
 static const char* key_name(const PolicyTable& t) { return t.key_mode ? "goal" : "ball"; }
 static const char* key_name(const SampleTable& t) { return t.key_mode ? "goal" : "ball"; }
 static const char* key_name(const EnvPolicyTable&) { return "env"; }
 static const char* key_name(const EnvSampleTable&) { return "env"; }
+static const char* key_name(const EnvQTable&) { return "env"; }
 template <class Args, class Args8, class Table>
 static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode, const Table& tab, int kind, RolloutForm form, int32_t T,
                                 float* reward_t, uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool u8) {
@@ -1904,7 +2003,7 @@ static hipError_t launch_closed(int variant, const StepArgs& a0, int layout_mode
     char name[96] = "";
     if (a0.info)
         snprintf(name, sizeof(name), "%s<v%d, %s=%s%s%s%s> T=%d every=%d", kRolloutKernel[p.family], variant,
-                 form == RF_POLICY || form == RF_ENV_POLICY ? "policy" : "sample", key_name(tab),
+                 form == RF_POLICY || form == RF_ENV_POLICY ? "policy" : form == RF_ENV_QLEARN ? "qlearn" : "sample", key_name(tab),
                  kind == LMAZE_TAB_ROWS || kind == LMAZE_TAB_ENV_BYTES ? ", table=lds" : kind == LMAZE_TAB_GLOBAL ? ", table=global" : "",
                  rec.obs_t ? ", obs_t" : "", p.nt ? ", nt" : "", T, rec.every);
     RolloutArgs plain{nullptr, reward_t, done_t, T};
@@ -1928,6 +2027,12 @@ hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const
 hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvSampleTable& tab, int32_t T, float* reward_t,
                           uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool) {
     return launch_closed<RolloutEnvRowsArgs, void>(variant, a, layout_mode, tab, LMAZE_TAB_GLOBAL, RF_ENV_SAMPLE, T, reward_t, done_t, s, rec, false);
+}
+
+// lmaze_env_rollout_qlearn: the Q rows are read and written in global memory, nothing of them in LDS
+hipError_t launch_rollout(int variant, const StepArgs& a, int layout_mode, const EnvQTable& tab, int32_t T, float* reward_t,
+                          uint8_t* done_t, hipStream_t s, const RolloutRec& rec, bool) {
+    return launch_closed<RolloutEnvQArgs, void>(variant, a, layout_mode, tab, LMAZE_TAB_GLOBAL, RF_ENV_QLEARN, T, reward_t, done_t, s, rec, false);
 }
 
 // lmaze_rollout_policy / _u8: the epsilon-greedy table, always staged

@@ -422,6 +422,41 @@ class LmazeVecEnv(VecEnvBase):
         return self._rollout_table("env_rollout_sample" if key == "env" else "rollout_sample", table_args, T, auto_reset, trajectory,
                                    actions_t, key_t, obs_t, obs_every)
 
+    def rollout_qlearn(self, T, q, alpha=0.1, gamma=0.99, epsilon=0.1, auto_reset=True, trajectory=True, td_t=None,
+                       actions_t=None, key_t=None, obs_t=None, obs_every=0):
+        """T steps of tabular Q-LEARNING in ONE launch, a learner per env (include/lmaze.h lmaze_env_rollout_qlearn): every
+        env acts epsilon-greedily on its own table of action values, steps, and updates the table from the transition.
+        q        float32 device tensor [N, G*G, 4] or flat [N*G*G, 4], contiguous and 16-byte aligned, UPDATED IN PLACE and
+                 never copied (anything else is a ValueError: a silent copy would lose the update).  Row i * G*G + ball
+                 cell, i this env object's own index, as rollout_policy(key="env").
+        alpha, gamma  step size and discount, rounded to float32; not validated.
+        epsilon  exploration rate in [0, 1], as rollout_policy()'s.
+        td_t     optional float32 [T, N] device tensor, filled with every step's TD error.
+        Per env-step: the greedy action is the FIRST maximum of the row (solve()'s rule), epsilon mixes in a uniform action
+        by rollout_policy()'s draw, the step is step()'s, and q[c, a] += alpha * (target - q[c, a]) with target = reward
+        when the step returned done (the step limit counts), else reward + gamma * max q[c'] read before the write; float32,
+        every operation rounded on its own, so a numpy loop reproduces the table bit for bit.
+        Returns what rollout_policy(key="env") returns: (obs, reward, done) and, with trajectory=True (the default here),
+        reward_t, done_t, actions_t, key_t.  Its refusals too: not the u8 env, not under stream capture, not while the
+        online tuner runs, N * G*G <= 2**31 - 1.  The epoch advances by T.
+        What composes with it: solve() gives the table it converges towards (v0; and a v_init-style warm start goes the
+        other way: q.max(-1) of a learnt table starts solve()); rollout_policy(q=q, key="env") runs the learnt table
+        without learning; state_keys("env") / gae(values=..., key_t=...) / table_stats(keys=N*G*G) take its rows as they
+        are.  v3: the key is the ball cell alone and a fused reset re-draws the goal, so with auto_reset what is learnt is
+        goal-free."""
+        T, entries = self._closed_loop_key("rollout_qlearn()", T, "env")
+        N, S = self.num_envs, self.grid ** 2
+        if not (isinstance(q, torch.Tensor) and q.dtype == torch.float32 and q.device == self.device and q.is_contiguous()
+                and tuple(q.shape) in ((N, S, 4), (entries, 4)) and q.data_ptr() % 16 == 0):
+            raise ValueError("q must be a contiguous, 16-byte aligned float32 tensor [%d, %d, 4] or [%d, 4] on %s: it is updated "
+                             "in place" % (N, S, entries, self.device))
+        if td_t is not None and not (isinstance(td_t, torch.Tensor) and td_t.dtype == torch.float32 and td_t.device == self.device
+                                     and td_t.is_contiguous() and tuple(td_t.shape) == (T, N)):
+            raise ValueError("td_t must be a contiguous float32 tensor [%d, %d] on %s" % (T, N, self.device))
+        table_args = (q.data_ptr(), C.c_float(float(alpha)), C.c_float(float(gamma)), _abi.epsilon_u32(epsilon))
+        return self._rollout_table("env_rollout_qlearn", table_args, T, auto_reset, trajectory, actions_t, key_t, obs_t, obs_every,
+                                   after_rows=(None if td_t is None else td_t.data_ptr(),))
+
     def _closed_loop_key(self, who, T, key):
         """What rollout_policy() and rollout_sample() refuse before they look at their table; returns T as an int and the
         number of keys, i.e. of table rows."""
@@ -440,10 +475,11 @@ class LmazeVecEnv(VecEnvBase):
             raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
         return T, self.grid ** 4 if key == "goal" else self.grid ** 2
 
-    def _rollout_table(self, method, table_args, T, auto_reset, trajectory, actions_t, key_t, obs_t, obs_every):
+    def _rollout_table(self, method, table_args, T, auto_reset, trajectory, actions_t, key_t, obs_t, obs_every, after_rows=()):
         """The launch of rollout_policy() / rollout_sample(): lmaze_<method> or, for the u8 env, lmaze_<method>_u8, which
         differ in table_args alone -- (table, key_mode, epsilon_u32) or (table, key_mode); key="env", lmaze_env_<method>:
-        (table, epsilon_u32) or (table,)."""
+        (table, epsilon_u32) or (table,); rollout_qlearn(): (q, alpha, gamma, epsilon_u32) and after_rows = (td_t,), the row
+        addresses that follow key_t's."""
         name = "lmaze_" + method + ("_u8" if self._u8 else "")
         k = self._obs_slots(T, obs_every, obs_t, self.obs, allow_final=True)
 
@@ -451,7 +487,7 @@ class LmazeVecEnv(VecEnvBase):
             return getattr(_abi.lib, name)(
                 self._pp, self._p_layout, *table_args, T, self._p_ball, self._p_goal if self._is_v3 else None, self._p_step,
                 self._p_reward, self._p_done, None if self._is_v3 else self._p_gc, self._p_obs, *(rows or (None, None)),
-                p_actions, p_key, self.num_envs, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base,
+                p_actions, p_key, *after_rows, self.num_envs, 1 if auto_reset else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base,
                 slots, k, self._stream())
         return self._closed_loop(method + "()", name, call, T, k, obs_t, trajectory, actions_t, key_t)
 

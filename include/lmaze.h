@@ -518,6 +518,56 @@ int lmaze_describe_env_rollout(const LmazeParams* params, int64_t n, int32_t T, 
                                int32_t obs_every, int32_t form, char* text_host, int32_t len);
 
 /*
+ * Q-LEARNING inside the closed-loop rollout, a learner PER ENV: lmaze_env_rollout_policy acting on a table of action values
+ * that the same launch updates after every transition.  Replaces the user loop of T x (gather q[i, ball cell], take the
+ * maximum, mix in exploration, step(): v0:146-237, v3:220-402, with auto_reset != 0 the reset() of done envs first,
+ * v0:64-110, gather the next row, take its maximum, scatter one update) by ONE launch; the learner itself has no reference
+ * counterpart.  The arguments of lmaze_env_rollout_policy with q, alpha, gamma in the place of policy, and td_t:
+ *   q            float32[n * G^2, 4], 16-byte aligned, UPDATED IN PLACE: row i * G^2 + c holds the four action values of env i
+ *                (the LOCAL index 0 <= i < n, as lmaze_env_rollout_policy's) at ball cell c = clamp(ball_x) * G + clamp(ball_y)
+ *   alpha, gamma the step size and the discount, float32; not validated (as lmaze_returns' gamma)
+ *   td_t         float32[T,N], nullable, 4-byte aligned: the TD error of every step
+ * Env i at step t, global index e = env_base + i, ep = epoch + t:
+ *   1. the fused reset of a done env when auto_reset != 0: lmaze_env_rollout_policy's, same draw, same epoch;
+ *   2. c as above, row = q[i * G^2 + c] (128 bits), greedy = the FIRST maximum of the row, by a strict > from action 0
+ *      on -- lmaze_solve's rule; a NaN never wins, a row whose q[.., 0] is NaN keeps action 0;
+ *   3. exploration as lmaze_rollout_policy's to the bit: epsilon_u32 == 0 draws nothing, else r = the policy draw of
+ *      (seed, ep, e) and the action is r.y >> 30 when r.x < epsilon_u32; actions_t[t, i] and key_t[t, i] = i * G^2 + c;
+ *   4. the transition of lmaze_step_v0 / _v3 with that action (sticky pairs, step limit and all);
+ *   5. c' the ball cell after it, d the step's own done flag (the step limit counts), v_next = the first maximum of
+ *      q[i * G^2 + c'] read BEFORE this step's write; target = reward when d, else reward + gamma * v_next (the product
+ *      rounded, then the sum); delta = target - q[c, a]; q[c, a] = q[c, a] + alpha * delta (the product rounded, then the
+ *      sum; never a fused multiply-add); td_t[t, i] = delta;
+ *   6. reward_t / done_t rows and the planes as in the other closed-loop forms.
+ * An env that enters a step done without auto_reset steps on as lmaze_step_* does and updates all the same.  Only env i's
+ * own lane reads or writes its rows, so an env's updates are one sequential float32 recurrence, reproducible bit for bit
+ * (csrc/lmaze_learn.h holds the arithmetic); the caller's epoch advances by T; always ONE launch (launch_hint bits 12-14 and
+ * bit 15 as in lmaze_rollout_obs).  int32 planes, v0 and v3, shared and per-env layouts.
+ * v3: the key is the ball cell alone and a fused reset re-draws the env's goal, so what v3 learns with auto_reset != 0 is
+ * goal-free: values averaged over the goals drawn.  v0's goal is the layout's 'X' and does not move.
+ * Where the table lives: global memory, the env's own rows read and written by its lane ("rollout_perenv_kernel<v0,
+ * qlearn=env, table=global, obs_t>"): 16 bytes per cell and env do not fit LDS beside the layouts, and none is reserved.
+ * The row read in 5 is the row of 2 at the next step unless a reset moves the ball; the lane keeps it in registers (on a
+ * wall bump, c' == c, the row it has just written) and reads the table again only where the cells differ.
+ * Refusals: lmaze_env_rollout_policy's, in its order, with q in the place of policy: LMAZE_E_COUNT when n * G^2 > INT32_MAX
+ * (before T == 0 or n == 0 returns 0 with nothing read), LMAZE_E_NULL for a missing q, LMAZE_E_ALIGN for a q that is not
+ * 16-byte aligned or a td_t that is not 4-byte aligned.
+ */
+int lmaze_env_rollout_qlearn(const LmazeParams* params, const uint8_t* layout, float* q, float alpha, float gamma,
+                             uint32_t epsilon_u32, int32_t T, int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward,
+                             uint8_t* done, int32_t* goal_count, int32_t* obs, float* reward_t, uint8_t* done_t, int32_t* actions_t,
+                             int32_t* key_t, float* td_t, int64_t n, int32_t auto_reset, uint64_t seed, uint64_t epoch,
+                             int64_t env_base, int32_t* obs_t, int32_t obs_every, void* stream);
+
+/*
+ * As lmaze_describe_env_rollout, for lmaze_env_rollout_qlearn (an entry of its own: lmaze_describe_env_rollout keeps its
+ * forms 0 and 1), e.g. "rollout_perenv_kernel<v0, qlearn=env, table=global, obs_t> T=16 every=3 grid=... lds=...
+ * envs_per_workgroup=...".  LMAZE_E_COUNT for obs_every < 0 or with_obs == 2; T == 0 or n == 0: an empty line.
+ */
+int lmaze_describe_env_rollout_qlearn(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs,
+                                      int32_t obs_every, char* text_host, int32_t len);
+
+/*
  * Discounted returns-to-go over the [T, N] rows a rollout writes; no reference counterpart (the reference keeps no
  * trajectories).  Replaces the T dependent steps of a host-driven reverse loop by ONE launch, one lane per env:
  *   ret = tail[i] (0 when tail is NULL); for t = T-1 .. 0:
