@@ -41,7 +41,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
            "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
            "lmaze_solve", "lmaze_describe_solve", "lmaze_env_rollout_policy", "lmaze_env_rollout_sample",
-           "lmaze_describe_env_rollout", "lmaze_env_rollout_qlearn", "lmaze_describe_env_rollout_qlearn")
+           "lmaze_describe_env_rollout", "lmaze_env_rollout_qlearn", "lmaze_describe_env_rollout_qlearn",
+           "lmaze_generate", "lmaze_describe_generate")
 
 
 class LmazeParams(C.Structure):
@@ -230,6 +231,10 @@ def _load():
     lib.lmaze_solve.argtypes = [P, vp, vp, i64, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.lmaze_describe_solve.restype = C.c_int
     lib.lmaze_describe_solve.argtypes = [P, i64, C.c_char_p, i32]
+    lib.lmaze_generate.restype = C.c_int
+    lib.lmaze_generate.argtypes = [i32, i64, u64, i64, C.c_uint32, vp, vp, vp]
+    lib.lmaze_describe_generate.restype = C.c_int
+    lib.lmaze_describe_generate.argtypes = [i32, i64, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -343,6 +348,13 @@ def describe_solve(params, problems):
     (lmaze_describe_solve): "solve_kernel<v0, wave, 2> ..." while G*G <= 256, "solve_kernel<v0, workgroup, 4> ..." above; "" for
     no problem."""
     return _describe("lmaze_describe_solve", C.byref(params), int(problems))
+
+
+def describe_generate(G, mazes):
+    """The kernel form / grid / LDS / mazes per workgroup lmaze_generate would queue for `mazes` mazes of G x G cells
+    (lmaze_describe_generate): "generate_kernel<wave, 1> ..." while G <= 33, "generate_kernel<workgroup, 4> ..." above (the
+    second argument: rooms per lane); "" for no maze."""
+    return _describe("lmaze_describe_generate", int(G), int(mazes))
 
 
 def sampling_thresholds(probs, actions=4):

@@ -724,6 +724,32 @@ int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text
     return describe_solve(params->variant, plan_solve(params->grid, problems), text_host, len);
 }
 
+// What lmaze_generate and lmaze_describe_generate judge of the grid side and of the counts, in the header's order
+static int check_generate_counts(int32_t grid, int64_t mazes, int64_t maze_base) {
+    if (grid < 5 || grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;
+    if (mazes < 0 || mazes > LMAZE_MAX_ENVS || maze_base < 0 || maze_base > INT64_MAX - mazes) return LMAZE_E_COUNT;
+    return 0;
+}
+
+int lmaze_generate(int32_t grid, int64_t mazes, uint64_t seed, int64_t maze_base, uint32_t loops_u32, uint8_t* layouts,
+                   int32_t* goal_xy, void* stream) {
+    if (!layouts) return LMAZE_E_NULL;
+    const int rc = check_generate_counts(grid, mazes, maze_base);
+    if (rc) return rc;
+    if (misaligned(layouts, 16) || misaligned(goal_xy, 8)) return LMAZE_E_ALIGN;
+    if (mazes == 0) return 0;
+    const GenerateArgs a{layouts, reinterpret_cast<int2*>(goal_xy), mazes, maze_base, seed, loops_u32, grid};
+    return (int)launch_generate(a, (hipStream_t)stream);
+}
+
+int lmaze_describe_generate(int32_t grid, int64_t mazes, char* text_host, int32_t len) {
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const int rc = check_generate_counts(grid, mazes, 0);
+    if (rc || mazes == 0) return rc;
+    return describe_generate(plan_generate(grid, mazes), text_host, len);
+}
+
 int lmaze_describe_rollout(const LmazeParams* params, int64_t n, int32_t T, int32_t auto_reset, int32_t with_obs, int32_t obs_every,
                            char* text_host, int32_t len) {
     // this describe's own order: the params, the variant and T before the text buffer, and the narrow planes' refusals

@@ -239,6 +239,28 @@ struct SolvePlan {
 SolvePlan plan_solve(int32_t G, int64_t problems);
 int describe_solve(int variant, const SolvePlan& p, char* text, int32_t len);
 hipError_t launch_solve(int variant, const SolveArgs& a, hipStream_t s);
+// Spanning-tree mazes (lmaze_generate, lmaze_generate.hip): maze p of the launch is global maze maze_base + p, built in LDS
+// from its own Philox draws and written once.  The draws' counter is (maze lo, maze hi, room, 0x40000000): the reset and
+// exploration streams carry epoch_hi and epoch_hi ^ 0x80000000 in that last word, epochs stay far below 2^62, so the word is
+// neither and the three streams never meet.
+struct GenerateArgs {
+    uint8_t* layouts;         // [mazes, G, G]
+    int2* goal_xy;            // [mazes] or null: the 'X' cell
+    int64_t mazes, maze_base;
+    uint64_t seed;
+    uint32_t loops_u32;
+    int32_t grid;
+};
+// What the launcher decides from G alone, and what lmaze_describe_generate prints: a wave per maze while G <= 33 (at most 256
+// rooms; four mazes per workgroup, no workgroup barrier), a workgroup per maze above; rooms_per_lane rooms of a maze per lane.
+struct GeneratePlan {
+    bool wave;
+    int32_t rooms_per_lane, mazes_per_workgroup;
+    int64_t grid, lds_bytes;
+};
+GeneratePlan plan_generate(int32_t G, int64_t mazes);
+int describe_generate(const GeneratePlan& p, char* text, int32_t len);
+hipError_t launch_generate(const GenerateArgs& a, hipStream_t s);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);

@@ -253,3 +253,38 @@ def random_walled(num_envs, G, device, p_wall=0.25, seed=7, block=1 << 17):
         flat[rows, pick[rows]] = ord("X")
         out[lo:lo + n] = lay
     return out
+
+
+def mazes(num_envs, G, device, seed=7, loops=0.0, maze_base=0, out=None, return_goals=False):
+    """Per-env spanning-tree mazes as uint8[N,G,G] on `device`, in ONE launch (include/lmaze.h lmaze_generate, which carries
+    the whole specification): rooms on the odd cells, the walls between them opened along the minimum spanning tree of
+    per-edge Philox weights, so every maze is different, every free cell reaches the one 'X', and the bytes are a function
+    of (G, seed, maze index, loops) alone.  There is no 'S' cell; the ball goes to a free cell at reset().
+    loops       in [0, 1]: the share of the remaining walls between rooms that is opened as well (0: a perfect maze).
+    maze_base   index of the first maze: a shard passes its env offset and holds exactly its slice of the one-batch result.
+    out         a contiguous uint8[N,G,G] tensor on a GPU to write into (then `device` is not read).
+    return_goals  also return int32[N,2], the 'X' cell of each maze: solve_tables(goals=) for v3.
+    The result is what LmazeVecEnv(per_env_layouts=) and solve_tables(layouts=) take as it is."""
+    import torch
+    from . import _abi
+    N, G = int(num_envs), int(G)
+    if not 5 <= G <= _abi.MAX_GRID:
+        raise ValueError("grid side must be in [5, %d]: a maze needs two rooms per side" % _abi.MAX_GRID)
+    if N < 0 or int(maze_base) < 0:
+        raise ValueError("num_envs and maze_base must be >= 0")
+    if not 0.0 <= float(loops) <= 1.0:
+        raise ValueError("loops must be in [0, 1]")
+    loops_u32 = _abi.epsilon_u32(loops)
+    if out is None:
+        out = torch.empty((N, G, G), dtype=torch.uint8, device=device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
+              and tuple(out.shape) == (N, G, G)):
+        raise ValueError("out must be a contiguous uint8[%d, %d, %d] tensor on a GPU" % (N, G, G))
+    dev = out.device
+    goals = torch.empty((N, 2), dtype=torch.int32, device=dev) if return_goals else None
+    if N > 0:                                   # an empty tensor has no address to hand over
+        with torch.cuda.device(dev):
+            rc = _abi.lib.lmaze_generate(G, N, int(seed) & 0xFFFFFFFFFFFFFFFF, int(maze_base), loops_u32, out.data_ptr(),
+                                         None if goals is None else goals.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check("lmaze_generate", rc)
+    return (out, goals) if return_goals else out

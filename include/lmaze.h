@@ -697,6 +697,53 @@ int lmaze_solve(const LmazeParams* params, const uint8_t* layouts, const int32_t
 int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
 
 /*
+ * MAZE GENERATION: `mazes` spanning-tree mazes of G x G cells, every one different, every free cell connected to its goal,
+ * in ONE launch; no reference counterpart (the reference only has literal layouts).  The result is what LAYOUT_PER_ENV
+ * entries and lmaze_solve read: layouts uint8[mazes, G, G] of the reference's cell characters.  Maze p of the call is the
+ * global maze m = maze_base + p: a shard that passes its env offset as maze_base writes exactly its slice of the one-batch
+ * result.  The maze is a function of (G, seed, m, loops_u32) alone, specified so that a numpy loop reproduces every byte:
+ *   rooms   R = (G - 1) / 2 per side (integer division; G in [5, LMAZE_MAX_GRID], so R >= 2 and R*R <= 961).  Room (i, j),
+ *           0 <= i, j < R, is cell (1 + 2i, 1 + 2j), its index r = i*R + j.  For even G row and column G - 2 hold no room
+ *           and stay 'W'.
+ *   edges   edge k = 2r joins room (i, j) to (i+1, j), exists iff i + 1 < R, its wall cell is (2 + 2i, 1 + 2j);
+ *           edge k = 2r + 1 joins (i, j) to (i, j+1), exists iff j + 1 < R, its wall cell is (1 + 2i, 2 + 2j).
+ *           k < 2 R*R <= 1922 < 2048.
+ *   draws   one Philox4x32-10 call per room: counter (m_lo, m_hi, r, 0x40000000), key (seed_lo, seed_hi).  .x is the weight
+ *           of edge 2r and .y of edge 2r + 1; .z is the loop draw of edge 2r and .w of edge 2r + 1.  The goal draw is the .x
+ *           word of the call with r = R*R.  The last counter word cannot meet the reset or the exploration stream: those
+ *           carry epoch_hi and epoch_hi ^ 0x80000000 there, with epochs far below 2^62.
+ *   keys    key(k) = (weight(k) & 0xFFFFF800) | k: distinct within a maze.
+ *   tree    the opened edges are the minimum spanning tree of the room graph under these keys.  Distinct keys make the tree
+ *           unique, so the result does not depend on how it is computed; Kruskal in ascending key order is the definition.
+ *   loops   if loops_u32 != 0, an existing non-tree edge is opened as well iff its loop draw < loops_u32 (unsigned);
+ *           loops_u32 == 0 gives a perfect maze, R*R - 1 opened wall cells.
+ *   goal    gr = (uint64(goal draw) * R*R) >> 32; room gr's cell becomes 'X'.
+ *   bytes   room cells and the wall cells of opened edges are 'B', one of the rooms is 'X' instead, everything else -- the
+ *           full border included -- is 'W'.  There is no 'S': v0's sticky pairs stay out of generated mazes.
+ * By construction the layout has a full 'W' border and one 'X', and every free cell reaches the goal.
+ *   layouts  uint8[mazes, G, G], 16-byte aligned; only written, and nothing outside [layouts, layouts + mazes*G*G)
+ *   goal_xy  int32[mazes, 2], 8-byte aligned, nullable: the 'X' cell (x = row, y = column) of each maze, what lmaze_solve
+ *            takes as a v3 goal
+ * One launch of generate_kernel: a maze lives in LDS from its draws to its bytes, the tree found by Boruvka rounds (LDS
+ * atomic minimum per component, hook, pointer jumping, relabel) whose loops run at most ceil(log2(R*R)) times each; a wave per
+ * maze while G <= 33, four mazes per workgroup and no workgroup barrier; a workgroup per maze above.
+ * Refused before anything is queued, in this order: LMAZE_E_NULL layouts; LMAZE_E_GRID grid outside [5, LMAZE_MAX_GRID];
+ * LMAZE_E_COUNT mazes outside [0, LMAZE_MAX_ENVS], maze_base < 0, or maze_base + mazes beyond int64; LMAZE_E_ALIGN layouts off
+ * 16 bytes or goal_xy off 8.  mazes == 0 then returns 0 with nothing written.  A grid beyond 2^24 - 1 workgroups:
+ * hipErrorInvalidConfiguration.
+ */
+int lmaze_generate(int32_t grid, int64_t mazes, uint64_t seed, int64_t maze_base, uint32_t loops_u32, uint8_t* layouts,
+                   int32_t* goal_xy, void* stream);
+
+/*
+ * The launch lmaze_generate would queue, one line in text_host (HOST, len bytes), written by the code that launches, e.g.
+ * "generate_kernel<wave, 4> grid=4096 block=256 lds=26944 mazes_per_workgroup=4" or "generate_kernel<workgroup, 2> ..." (the
+ * second argument: rooms per lane).  Nothing is queued or dereferenced.  LMAZE_E_NULL text_host NULL or len < 1, then
+ * lmaze_generate's refusals of the grid and of `mazes`; an empty line for mazes == 0.
+ */
+int lmaze_describe_generate(int32_t grid, int64_t mazes, char* text_host, int32_t len);
+
+/*
  * Reference-layout observation: replaces the 5-deep upsample loop (v0:217-234,
  * v3:295-301).  out[i, c, x*E+xx, y*E+yy] = float((obs[i,x,y] & channel_mask[c]) != 0).
  *   obs           int32[N,G,G]        compact planes
