@@ -42,7 +42,7 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
            "lmaze_solve", "lmaze_describe_solve", "lmaze_env_rollout_policy", "lmaze_env_rollout_sample",
            "lmaze_describe_env_rollout", "lmaze_env_rollout_qlearn", "lmaze_describe_env_rollout_qlearn",
-           "lmaze_generate", "lmaze_describe_generate")
+           "lmaze_generate", "lmaze_describe_generate", "lmaze_score", "lmaze_describe_score")
 
 
 class LmazeParams(C.Structure):
@@ -235,6 +235,10 @@ def _load():
     lib.lmaze_generate.argtypes = [i32, i64, u64, i64, C.c_uint32, vp, vp, vp]
     lib.lmaze_describe_generate.restype = C.c_int
     lib.lmaze_describe_generate.argtypes = [i32, i64, C.c_char_p, i32]
+    lib.lmaze_score.restype = C.c_int
+    lib.lmaze_score.argtypes = [P, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.lmaze_describe_score.restype = C.c_int
+    lib.lmaze_describe_score.argtypes = [P, i64, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -348,6 +352,13 @@ def describe_solve(params, problems):
     (lmaze_describe_solve): "solve_kernel<v0, wave, 2> ..." while G*G <= 256, "solve_kernel<v0, workgroup, 4> ..." above; "" for
     no problem."""
     return _describe("lmaze_describe_solve", C.byref(params), int(problems))
+
+
+def describe_score(params, problems):
+    """The kernel form / grid / LDS / problems per workgroup lmaze_score would queue for `problems` tables with these LmazeParams
+    (lmaze_describe_score): "score_kernel<v0, wave, 2> ..." while G*G <= 256, "score_kernel<v0, workgroup, 4> ..." above -- the
+    plan is lmaze_solve's; "" for no problem."""
+    return _describe("lmaze_describe_score", C.byref(params), int(problems))
 
 
 def describe_generate(G, mazes):

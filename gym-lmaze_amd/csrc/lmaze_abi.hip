@@ -724,6 +724,38 @@ int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text
     return describe_solve(params->variant, plan_solve(params->grid, problems), text_host, len);
 }
 
+int lmaze_score(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
+                const float* q, int32_t* optimal, int32_t* steps, int32_t* summary, void* stream) {
+    // lmaze_solve's refusals, in its order, with the table and the outputs judged where it judges its outputs
+    if (!params || !layouts) return LMAZE_E_NULL;
+    const int rc = check_solve_params(params);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (v3 && !goal_xy) return LMAZE_E_NULL;
+    if (!optimal && !steps && !summary) return LMAZE_E_NULL;
+    if (policy && q) return LMAZE_E_NULL;
+    if (steps && !policy && !q) return LMAZE_E_NULL;
+    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    if (misaligned(q, 16) || (v3 && misaligned(goal_xy, 8)) || misaligned(policy, 4) || misaligned(optimal, 4) || misaligned(steps, 4) ||
+        misaligned(summary, 4))
+        return LMAZE_E_ALIGN;
+    if (problems == 0) return 0;
+    const ScoreArgs a{layouts, v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr, policy, reinterpret_cast<const float4*>(q), optimal,
+                      steps, summary, problems, params->grid, params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0, params->reward_wall,
+                      params->reward_move, params->reward_goal};
+    return (int)launch_score(params->variant, a, (hipStream_t)stream);
+}
+
+int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    if (!params || !text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const int rc = check_solve_params(params);
+    if (rc) return rc;
+    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    if (problems == 0) return 0;
+    return describe_score(params->variant, plan_solve(params->grid, problems), text_host, len);
+}
+
 // What lmaze_generate and lmaze_describe_generate judge of the grid side and of the counts, in the header's order
 static int check_generate_counts(int32_t grid, int64_t mazes, int64_t maze_base) {
     if (grid < 5 || grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;

@@ -239,6 +239,22 @@ struct SolvePlan {
 SolvePlan plan_solve(int32_t G, int64_t problems);
 int describe_solve(int variant, const SolvePlan& p, char* text, int32_t len);
 hipError_t launch_solve(int variant, const SolveArgs& a, hipStream_t s);
+// Scoring tables on the grid mazes (lmaze_score, lmaze_score.hip): the fewest steps to done and the length of a table's greedy
+// walk from every cell, one problem = one maze and one table, in LDS in one launch.  The plan is plan_solve's.
+struct ScoreArgs {
+    const uint8_t* layouts;   // [G*G] shared or [problems*G*G]
+    const int2* goal;         // v3: [problems]
+    const uint8_t* policy;    // [problems, G*G] or null: the action of every state
+    const float4* q;          // [problems, G*G] or null: its first maximum is the action
+    int32_t* optimal;         // [problems, G*G] or null
+    int32_t* steps;           // [problems, G*G] or null
+    int32_t* summary;         // [problems, 4] or null: reachable, arrived, shortest, excess
+    int64_t problems;
+    int32_t grid, per_env;
+    float reward_wall, reward_move, reward_goal;
+};
+int describe_score(int variant, const SolvePlan& p, char* text, int32_t len);
+hipError_t launch_score(int variant, const ScoreArgs& a, hipStream_t s);
 // Spanning-tree mazes (lmaze_generate, lmaze_generate.hip): maze p of the launch is global maze maze_base + p, built in LDS
 // from its own Philox draws and written once.  The draws' counter is (maze lo, maze hi, room, 0x40000000): the reset and
 // exploration streams carry epoch_hi and epoch_hi ^ 0x80000000 in that last word, epochs stay far below 2^62, so the word is

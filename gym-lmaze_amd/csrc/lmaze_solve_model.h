@@ -1,0 +1,61 @@
+// The model of one grid maze as the kernels that plan it and score it keep it (lmaze_solve.hip, lmaze_score.hip): sixteen bits
+// per cell, taken from transition_rule<VARIANT> itself, and what both kernels share of a problem's life in LDS -- the sync
+// between two phases and where the rule's StepArgs and the vote words stand behind the two buffers.  The model is stated once,
+// here, by asking the rule.
+#ifndef LMAZE_SOLVE_MODEL_H_
+#define LMAZE_SOLVE_MODEL_H_
+
+#include "lmaze_common.h"
+
+namespace lmaze {
+
+// a pair's four bits: which reward constant, the rule's done flag, whether the ball moved onto the target cell
+enum { SOLVE_WALL = 0, SOLVE_MOVE = 1, SOLVE_GOAL = 2, SOLVE_EXCLUDED = 3, SOLVE_TERMINAL = 4, SOLVE_MOVED = 8 };
+#define SOLVE_ALL_EXCLUDED 0x3333u
+#define SOLVE_WALL_STATE 0x10000u     // the cell itself is 'W': q = v = 0, policy 0
+#define SOLVE_VOTE_BYTES 64           // workgroup form: 2 x 4 vote words, 4 words of the last reduction
+#define SOLVE_MODEL_BYTES ((sizeof(StepArgs) + 15) & ~(size_t)15)   // the StepArgs the rule is asked with, behind the two buffers
+
+// The sixteen bits of cell s (a non-wall cell of a bordered layout has every target on the grid; the clamp keeps any other
+// input inside the problem's own LDS: a clamped target is the cell itself)
+template <int VARIANT>
+__device__ __forceinline__ uint32_t solve_descriptor(const StepArgs& m, const uint8_t* lay, int G, int s, int gx, int gy) {
+    if (lay[s] == 'W') return SOLVE_WALL_STATE;
+    const int x = s / G, y = s - x * G;
+    uint32_t d = 0;
+#pragma unroll
+    for (int act = 0; act < 4; ++act) {
+        int ox, oy;
+        decode_action(act, ox, oy);
+        const int tx = clampi(x + ox, 0, G - 1), ty = clampi(y + oy, 0, G - 1);
+        const uint8_t c = lay[tx * G + ty];
+        int bx = x, by = y, bx1 = x, by1 = y;
+        float r, r1;
+        bool dn, dn1;
+        transition_rule<VARIANT>(m, c, ox, oy, tx, ty, 0, 0.0f, gx, gy, bx, by, r, dn);
+        transition_rule<VARIANT>(m, c, ox, oy, tx, ty, 0, 1.0f, gx, gy, bx1, by1, r1, dn1);
+        uint32_t nib = SOLVE_EXCLUDED;
+        if (__float_as_uint(r) == __float_as_uint(r1)) {
+            const uint32_t rb = __float_as_uint(r);
+            nib = rb == __float_as_uint(m.reward_goal) ? SOLVE_GOAL : (rb == __float_as_uint(m.reward_move) ? SOLVE_MOVE : SOLVE_WALL);
+            nib |= (dn ? SOLVE_TERMINAL : 0) | (bx * G + by != s ? SOLVE_MOVED : 0);
+        }
+        d |= nib << (4 * act);
+    }
+    return d;
+}
+
+// what one problem's threads wait on between two phases that exchange data through its LDS
+template <bool WAVE>
+__device__ __forceinline__ void solve_sync() {
+    if constexpr (WAVE) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+}  // namespace lmaze
+#endif

@@ -606,6 +606,62 @@ class LmazeVecEnv(VecEnvBase):
             return SolvedTables(t.q.reshape(G ** 4, 4), t.v.reshape(G ** 4), t.policy.reshape(G ** 4), t.sweeps_run, t.delta)
         return SolvedTables(t.q[0], t.v[0], t.policy[0], t.sweeps_run[0], t.delta[0])
 
+    def score(self, policy=None, q=None, key="ball", goal=None):
+        """How good tables are on this env's own maze(s), in ONE launch (score_tables(), include/lmaze.h lmaze_score): from
+        every cell the fewest steps to done, the steps the table's greedy walk takes (-1: it never arrives), and per problem
+        the counts (reachable, arrived, shortest, excess).  The problems are chosen as solve() chooses them; the rewards are
+        the env's.  policy uint8 or q float32 (first maximum), at most one; neither: distances only, steps is None.
+        shared layout, key="ball"   one problem: policy [G*G] / q [G*G, 4]; optimal, steps int32[G*G], summary int32[4].  v3
+                                    needs goal=(x, y).
+        shared layout, key="goal"   v3 only: G*G problems, one per goal cell; policy [G**4] / q [G**4, 4] indexed by the key of
+                                    state_keys("goal"); optimal, steps [G**4], summary [G*G, 4].
+        shared layout, key="env"    N tables on the one maze, v3 with env i's current goal: policy [N, G*G] / q [N, G*G, 4];
+                                    optimal, steps [N, G*G], summary [N, 4].
+        per-env layouts             env i's maze and (v3) its current goal, tables [N, G*G] / [N, G*G, 4]: what solve() returns
+                                    and rollout_qlearn() updates; outputs as key="env".
+        Returns ScoredTables(optimal, steps, summary)."""
+        if key not in ("ball", "goal", "env"):
+            raise ValueError("key must be 'ball', 'goal' or 'env'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        if policy is not None and q is not None:
+            raise ValueError("give policy= or q=, not both")
+        G, N, dev = self.grid, self.num_envs, self.device
+        S = G * G
+        shared = self.layout_mode == _abi.LAYOUT_SHARED
+        if goal is not None and not (shared and key == "ball" and self._is_v3):
+            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
+        if not shared and key == "goal":
+            raise ValueError("key='goal' scores one shared layout for every goal cell; per-env layouts score each env's own goal")
+        single = shared and key == "ball"
+        P = 1 if single else (S if key == "goal" else N)
+        goals = None
+        if self._is_v3:
+            if single:
+                if goal is None or len(goal) != 2:
+                    raise ValueError("score(key='ball') on a shared-layout v3 env needs goal=(x, y)")
+                goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
+            elif key == "goal":
+                cells = torch.arange(S, dtype=torch.int32, device=dev)
+                goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
+            else:
+                goals = self.goal_xy
+        table = policy if policy is not None else q
+        if table is not None:
+            if not isinstance(table, torch.Tensor) or table.numel() != P * S * (1 if policy is not None else 4):
+                raise ValueError("the table must be a tensor of %d problems x %d states%s" % (P, S, "" if policy is not None else " x 4"))
+            table = table.reshape((P, S) if policy is not None else (P, S, 4))
+        outputs = SCORE_OUTPUTS if table is not None else ("optimal", "summary")
+        if shared and key == "env" and table is None and not self._is_v3:
+            raise ValueError("key='env' on a shared v0 layout scores N tables on one maze: without a table use key='ball'")
+        t = score_tables(self.layout, policy=table if policy is not None else None, q=table if q is not None else None,
+                         variant=self.variant, goals=goals, rewards=self.rewards, outputs=outputs, validate=False)
+        if single:
+            return ScoredTables(t.optimal[0], None if t.steps is None else t.steps[0], t.summary[0])
+        if key == "goal":
+            return ScoredTables(t.optimal.reshape(G ** 4), None if t.steps is None else t.steps.reshape(G ** 4), t.summary)
+        return t
+
     def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
         """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
         observations (obs_t / obs_every) is not captured: ValueError."""
@@ -866,6 +922,89 @@ def solve_tables(layouts, variant="v0", goals=None, gamma=0.99, sweeps=4096, rew
                                       torch.cuda.current_stream(dev).cuda_stream)
         _abi.check("lmaze_solve", rc)
     return SolvedTables(*[out[k] for k in SOLVE_OUTPUTS])
+
+
+class ScoredTables(collections.namedtuple("ScoredTables", "optimal steps summary")):
+    """What score_tables() returns: optimal int32[P, S], steps int32[P, S], summary int32[P, 4] (reachable, arrived, shortest,
+    excess); an output that was not asked for is None."""
+    __slots__ = ()
+
+
+SCORE_OUTPUTS = ("optimal", "steps", "summary")
+
+
+def score_tables(layouts, policy=None, q=None, variant="v0", goals=None, rewards=None, outputs=SCORE_OUTPUTS, validate=True):
+    """How good a table is, exactly and from every cell at once, in ONE launch (include/lmaze.h lmaze_score): no rollout, no
+    step limit, and a loop is told from a long path.
+    layouts  uint8 device tensor [G, G] (one maze for every problem) or [P, G, G], as solve_tables().
+    policy   uint8 [P, G*G]: the action of every state (what solve_tables().policy is) -- or
+    q        float32 [P, G*G, 4]: the action is the first maximum by a strict '>' (what solve_tables().q is and what
+             rollout_qlearn() updates).  At most one of the two; none when only "optimal" is asked for.  With a [G, G] layout
+             and v0, P is the table's length: a population of tables on one maze.
+    variant, goals, rewards   as solve_tables(): the model is the same.
+    outputs  some of "optimal" (the fewest steps after which done can be set, -1: never, and on walls), "steps" (the steps
+             after which the table's walk sets it, -1: never -- a cycle, a wall bump, a sticky pair, an action above 3) and
+             "summary" (per problem: cells that can reach done, cells whose walk arrives, cells whose walk is a shortest one,
+             and the steps the arriving walks take beyond the fewest).
+    validate=False skips the layouts' check and the device-side check that no policy byte is above 3.
+    Returns ScoredTables(optimal, steps, summary)."""
+    if variant not in VARIANTS:
+        raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
+    spec = VARIANTS[variant]
+    v3 = variant == "v3"
+    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
+            and layouts.shape[-1] == layouts.shape[-2]):
+        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
+    dev = layouts.device
+    G = int(layouts.shape[-1])
+    if not (3 <= G <= _abi.MAX_GRID):
+        raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
+    S = G * G
+    layouts = layouts.contiguous()
+    if validate:
+        _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
+    shared = layouts.dim() == 2
+    if policy is not None and q is not None:
+        raise ValueError("give policy= or q=, not both")
+    table = policy if policy is not None else q
+    if table is not None:
+        want = (torch.uint8, 2) if policy is not None else (torch.float32, 3)
+        if not (isinstance(table, torch.Tensor) and table.dtype == want[0] and table.device == dev and table.dim() == want[1]
+                and table.is_contiguous() and tuple(table.shape[1:]) == ((S,) if policy is not None else (S, 4))):
+            raise ValueError("policy must be a contiguous uint8[P, %d] and q a contiguous float32[P, %d, 4] tensor on layouts' device"
+                             % (S, S))
+    if v3:
+        if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == dev and goals.dim() == 2
+                and goals.shape[1] == 2 and goals.is_contiguous() and (shared or goals.shape[0] == layouts.shape[0])):
+            raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
+        P = int(goals.shape[0])
+    else:
+        if goals is not None:
+            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
+        P = int(layouts.shape[0]) if not shared else (1 if table is None else int(table.shape[0]))
+    if table is not None and int(table.shape[0]) != P:
+        raise ValueError("the table has %d problems, the mazes %d" % (int(table.shape[0]), P))
+    rewards = tuple(float(r) for r in (rewards if rewards is not None else spec["rewards"]))
+    if len(rewards) != 3:
+        raise ValueError("rewards must be (wall, move, goal)")
+    outputs = tuple(outputs)
+    if not outputs or not set(outputs) <= set(SCORE_OUTPUTS):
+        raise ValueError("outputs must name some of %s" % (SCORE_OUTPUTS,))
+    if "steps" in outputs and table is None:
+        raise ValueError("'steps' needs a table: policy= or q=")
+    if validate and policy is not None and bool((policy > 3).any()):
+        raise ValueError("policy holds a byte above 3: the actions are 0..3")
+    shapes = {"optimal": (P, S), "steps": (P, S), "summary": (P, 4)}
+    out = {k: (torch.zeros(shapes[k], dtype=torch.int32, device=dev) if k in outputs else None) for k in SCORE_OUTPUTS}
+    if P > 0:
+        params = _abi.make_params(spec["id"], G, _abi.LAYOUT_SHARED if shared else _abi.LAYOUT_PER_ENV, spec["step_limit"], *rewards)
+        with torch.cuda.device(dev):
+            rc = _abi.lib.lmaze_score(C.byref(params), layouts.data_ptr(), goals.data_ptr() if v3 else None, P,
+                                      None if policy is None else policy.data_ptr(), None if q is None else q.data_ptr(),
+                                      *[None if out[k] is None else out[k].data_ptr() for k in SCORE_OUTPUTS],
+                                      torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check("lmaze_score", rc)
+    return ScoredTables(*[out[k] for k in SCORE_OUTPUTS])
 
 
 def _validate_on_device(lay, need_goal=True):

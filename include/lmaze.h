@@ -697,6 +697,54 @@ int lmaze_solve(const LmazeParams* params, const uint8_t* layouts, const int32_t
 int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
 
 /*
+ * SCORING TABLES on the grid mazes: from every cell, the fewest steps after which done can be set, and the number of steps
+ * after which the walk that takes a table's action in every cell sets it, in ONE launch; no reference counterpart.  It tells
+ * how good the tables are that lmaze_solve plans, lmaze_env_rollout_policy runs and lmaze_env_rollout_qlearn learns, exactly
+ * and from every start cell at once: no rollout, no step limit, and a loop is told from a long path.
+ * Problems and the model.  Problem p has S = G*G states, s = x * G + y.  Its model is lmaze_solve's, word for word: the
+ * transition of lmaze_step_v0 / _v3 asked once per (cell, action) with a step count that trips no limit; the same wall, move
+ * and goal pairs; a pair is terminal exactly when its reward equals reward_goal as float32; v0's sticky pairs are excluded;
+ * wall states and targets off the grid as in lmaze_solve.  LMAZE_LAYOUT_SHARED: every problem reads the one layout and its own
+ * table (a population of tables on one maze, v3 with one goal per problem, the goal-keyed tables); LMAZE_LAYOUT_PER_ENV: problem
+ * p reads layouts + p*G*G.  v3 reads goal_xy[2p], goal_xy[2p+1].
+ * The table of problem p.  Exactly one of two inputs gives the action a(s) of every state:
+ *   policy  uint8[problems, S], 4-byte aligned: a(s) itself
+ *   q       float[problems, S, 4], 16-byte aligned: a(s) is the first maximum by a strict '>' from action 0 on, the rule of
+ *           lmaze_solve and lmaze_env_rollout_qlearn; a NaN never wins, a NaN in word 0 keeps action 0
+ * Both may be NULL when only distances are asked for.
+ * Outputs, each nullable and 4-byte aligned, at least one required; all integers, so the result depends on no schedule:
+ *   optimal  int32[problems, S]  the fewest steps after which an env started on s can have done set by the model: 1 if s owns
+ *            a usable (not excluded) terminal pair, else 1 + the minimum over s's usable, non-terminal pairs of optimal[next];
+ *            -1 where no terminal pair can be reached, and on walls
+ *   steps    int32[problems, S]  the walk that takes a(s) in every state: the number of steps at which done is first set, -1 if
+ *            that never happens -- the walk enters a cycle (a wall bump is a cycle of one), takes an excluded pair, meets a
+ *            policy byte above 3, or starts on a wall
+ *   summary  int32[problems, 4]  reachable = #{s : optimal >= 1}, arrived = #{s : steps >= 1}, shortest = #{s : steps ==
+ *            optimal >= 1}, excess = the sum over arrived s of (steps - optimal); without a table the last three are 0
+ * An arriving walk visits distinct non-wall states, so steps <= (G - 2)^2 < S.
+ * One launch of score_kernel, shaped as solve_kernel: a problem lives in LDS from its layout bytes to its results; a wave per
+ * problem while G*G <= 256, four problems per workgroup and no workgroup barrier; a workgroup per problem above.  Distances:
+ * Jacobi min-plus sweeps between two buffers, ended by the sweep that changes nothing, at most S of them.  Walk lengths:
+ * pointer doubling between the same two buffers, ceil(log2 S) <= 12 rounds at most.  params->launch_hint, step_limit are not
+ * read.
+ * Refused, in this order: LMAZE_E_NULL params or layouts; LMAZE_E_GRID; LMAZE_E_VARIANT neither v0 nor v3; LMAZE_E_LAYOUT;
+ * LMAZE_E_NULL goal_xy for v3; LMAZE_E_NULL all of optimal, steps and summary; LMAZE_E_NULL both policy and q given;
+ * LMAZE_E_NULL steps without a table; LMAZE_E_COUNT problems outside [0, LMAZE_MAX_ENVS]; LMAZE_E_ALIGN q off 16 bytes,
+ * goal_xy (v3) off 8, policy or an output off 4.  problems == 0 then returns 0 with nothing read.  A grid beyond 2^24 - 1
+ * workgroups: hipErrorInvalidConfiguration.
+ */
+int lmaze_score(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
+                const float* q, int32_t* optimal, int32_t* steps, int32_t* summary, void* stream);
+
+/*
+ * The launch lmaze_score would queue, one line in text_host (HOST, len bytes), written by the code that launches, e.g.
+ * "score_kernel<v0, wave, 4> grid=65 block=256 lds=8384 problems_per_workgroup=4" or "score_kernel<v3, workgroup, 2> ..."
+ * (the third argument: cells per lane; the plan is lmaze_solve's).  Nothing is queued or dereferenced.  LMAZE_E_NULL params or
+ * text_host NULL or len < 1, then lmaze_score's refusals of the params and of `problems`; an empty line for problems == 0.
+ */
+int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
+
+/*
  * MAZE GENERATION: `mazes` spanning-tree mazes of G x G cells, every one different, every free cell connected to its goal,
  * in ONE launch; no reference counterpart (the reference only has literal layouts).  The result is what LAYOUT_PER_ENV
  * entries and lmaze_solve read: layouts uint8[mazes, G, G] of the reference's cell characters.  Maze p of the call is the
