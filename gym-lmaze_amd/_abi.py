@@ -42,7 +42,8 @@ SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_st
            "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
            "lmaze_solve", "lmaze_describe_solve", "lmaze_env_rollout_policy", "lmaze_env_rollout_sample",
            "lmaze_describe_env_rollout", "lmaze_env_rollout_qlearn", "lmaze_describe_env_rollout_qlearn",
-           "lmaze_generate", "lmaze_describe_generate", "lmaze_score", "lmaze_describe_score")
+           "lmaze_generate", "lmaze_describe_generate", "lmaze_score", "lmaze_describe_score", "lmaze_evaluate",
+           "lmaze_describe_evaluate")
 
 
 class LmazeParams(C.Structure):
@@ -239,6 +240,10 @@ def _load():
     lib.lmaze_score.argtypes = [P, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.lmaze_describe_score.restype = C.c_int
     lib.lmaze_describe_score.argtypes = [P, i64, C.c_char_p, i32]
+    lib.lmaze_evaluate.restype = C.c_int
+    lib.lmaze_evaluate.argtypes = [P, vp, vp, i64, vp, vp, C.c_uint32, vp, C.c_float, i32, C.c_float, vp, vp, vp, vp, vp, vp]
+    lib.lmaze_describe_evaluate.restype = C.c_int
+    lib.lmaze_describe_evaluate.argtypes = [P, i64, C.c_char_p, i32]
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib
@@ -359,6 +364,13 @@ def describe_score(params, problems):
     (lmaze_describe_score): "score_kernel<v0, wave, 2> ..." while G*G <= 256, "score_kernel<v0, workgroup, 4> ..." above -- the
     plan is lmaze_solve's; "" for no problem."""
     return _describe("lmaze_describe_score", C.byref(params), int(problems))
+
+
+def describe_evaluate(params, problems):
+    """The kernel form / grid / LDS / problems per workgroup lmaze_evaluate would queue for `problems` tables with these
+    LmazeParams (lmaze_describe_evaluate): "evaluate_kernel<v0, wave, 2> ..." while G*G <= 256, "evaluate_kernel<v0, workgroup,
+    4> ..." above -- the plan is lmaze_solve's; "" for no problem."""
+    return _describe("lmaze_describe_evaluate", C.byref(params), int(problems))
 
 
 def describe_generate(G, mazes):

@@ -756,6 +756,39 @@ int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text
     return describe_score(params->variant, plan_solve(params->grid, problems), text_host, len);
 }
 
+int lmaze_evaluate(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
+                   const float* q, uint32_t epsilon_u32, const uint32_t* thresholds, float gamma, int32_t sweeps, float tol,
+                   const float* v_init, float* q_out, float* v_out, int32_t* sweeps_run, float* delta, void* stream) {
+    // lmaze_score's refusals, in its order, with the policy inputs judged where it judges its tables
+    if (!params || !layouts) return LMAZE_E_NULL;
+    const int rc = check_solve_params(params);
+    if (rc) return rc;
+    const bool v3 = params->variant == LMAZE_VARIANT_V3;
+    if (v3 && !goal_xy) return LMAZE_E_NULL;
+    if (!q_out && !v_out) return LMAZE_E_NULL;
+    if ((policy ? 1 : 0) + (q ? 1 : 0) + (thresholds ? 1 : 0) != 1) return LMAZE_E_NULL;
+    if (problems < 0 || problems > LMAZE_MAX_ENVS || sweeps < 1) return LMAZE_E_COUNT;
+    if (misaligned(thresholds, 16) || misaligned(q, 16) || misaligned(q_out, 16) || (v3 && misaligned(goal_xy, 8)) ||
+        misaligned(v_init, 4) || misaligned(v_out, 4) || misaligned(sweeps_run, 4) || misaligned(delta, 4))
+        return LMAZE_E_ALIGN;
+    if (problems == 0) return 0;
+    const EvaluateArgs a{layouts, v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr, policy, reinterpret_cast<const float4*>(q),
+                         reinterpret_cast<const uint4*>(thresholds), v_init, reinterpret_cast<float4*>(q_out), v_out, sweeps_run, delta,
+                         problems, params->grid, sweeps, params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0, epsilon_u32, gamma, tol,
+                         params->reward_wall, params->reward_move, params->reward_goal};
+    return (int)launch_evaluate(params->variant, a, (hipStream_t)stream);
+}
+
+int lmaze_describe_evaluate(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    if (!params || !text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    const int rc = check_solve_params(params);
+    if (rc) return rc;
+    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
+    if (problems == 0) return 0;
+    return describe_evaluate(params->variant, plan_solve(params->grid, problems), text_host, len);
+}
+
 // What lmaze_generate and lmaze_describe_generate judge of the grid side and of the counts, in the header's order
 static int check_generate_counts(int32_t grid, int64_t mazes, int64_t maze_base) {
     if (grid < 5 || grid > LMAZE_MAX_GRID) return LMAZE_E_GRID;

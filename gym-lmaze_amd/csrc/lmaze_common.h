@@ -255,6 +255,26 @@ struct ScoreArgs {
 };
 int describe_score(int variant, const SolvePlan& p, char* text, int32_t len);
 hipError_t launch_score(int variant, const ScoreArgs& a, hipStream_t s);
+// Exact policy evaluation on the grid mazes (lmaze_evaluate, lmaze_evaluate.hip): V^pi and Q^pi of one stochastic table per
+// problem, the linear twin of lmaze_solve -- the same model, the same two V buffers in LDS, the same plan (plan_solve).
+struct EvaluateArgs {
+    const uint8_t* layouts;   // [G*G] shared or [problems*G*G]
+    const int2* goal;         // v3: [problems]
+    const uint8_t* policy;    // exactly one of policy, q, thresholds: [problems, G*G], the greedy action, mixed with epsilon
+    const float4* q;          // [problems, G*G]: the first maximum is the greedy action, mixed with epsilon
+    const uint4* thresholds;  // [problems, G*G]: the sampler's cumulative thresholds, word 3 ignored
+    const float* v_init;      // [problems, G*G] or null (0)
+    float4* q_out;            // [problems, G*G] or null
+    float* v_out;             // [problems, G*G] or null
+    int32_t* sweeps_run;      // [problems] or null
+    float* delta;             // [problems] or null
+    int64_t problems;
+    int32_t grid, sweeps, per_env;
+    uint32_t epsilon;         // as PolicyTable's
+    float gamma, tol, reward_wall, reward_move, reward_goal;
+};
+int describe_evaluate(int variant, const SolvePlan& p, char* text, int32_t len);
+hipError_t launch_evaluate(int variant, const EvaluateArgs& a, hipStream_t s);
 // Spanning-tree mazes (lmaze_generate, lmaze_generate.hip): maze p of the launch is global maze maze_base + p, built in LDS
 // from its own Philox draws and written once.  The draws' counter is (maze lo, maze hi, room, 0x40000000): the reset and
 // exploration streams carry epoch_hi and epoch_hi ^ 0x80000000 in that last word, epochs stay far below 2^62, so the word is

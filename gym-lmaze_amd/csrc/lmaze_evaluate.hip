@@ -1,0 +1,250 @@
+// lmaze_evaluate.hip -- exact policy evaluation on the grid mazes (lmaze_evaluate / lmaze_describe_evaluate, include/lmaze.h):
+// V^pi and Q^pi of the stochastic table a closed-loop rollout would run, the linear twin of lmaze_solve.hip.
+//
+// One problem = one maze of S = G*G states and one table.  The model is solve_kernel's, from the function it uses
+// (solve_descriptor over transition_rule, lmaze_solve_model.h): sixteen bits per cell in a register of the lane that owns the
+// cell.  The table is read from global memory once, at setup, and reduced there to the four probabilities of the cell --
+// integer weights in units of 2^-34, the weight on an excluded pair dropped, one correctly rounded division each -- which stay
+// in registers beside the descriptor for the whole solve, in every form: 16 bytes per cell in LDS would add four reads per cell
+// and sweep to the five the sweep already makes, and give the kernel an LDS size other than plan_solve's (not built, not timed).
+//
+// The rest is solve_kernel's: two V buffers in LDS, Jacobi sweeps between them, the layout's bytes borrowing the second while
+// the descriptors are built, the plan of plan_solve (a wave per problem while S <= 256, a workgroup per problem above), one
+// fence or one barrier per sweep, and an exit that every thread of a problem takes in the same sweep.  A vote carries two bits:
+// "a value changed" and "a value moved by more than tol".
+#include <limits.h>
+#include <math.h>
+#include <stdio.h>
+
+#include "lmaze_common.h"
+#include "lmaze_learn.h"
+#include "lmaze_solve_model.h"
+
+namespace lmaze {
+
+// The four probabilities of a cell.  w_a in units of 2^-34: the epsilon-greedy mixture of lmaze_rollout_policy or the threshold
+// differences of lmaze_rollout_sample; w'_a = 0 on an excluded pair; p_a = fl(fl(w'_a) / fl(W)), W the integer sum.  A wall
+// state has no probabilities, and W == 0 leaves none either.
+__device__ __forceinline__ void evaluate_probs(const EvaluateArgs& a, int64_t row, uint32_t d, float (&p)[4]) {
+    uint64_t w[4];
+    if (a.thresholds) {
+        const uint4 c = a.thresholds[row];                        // one 128-bit load per state; word 3 is not looked at
+        w[0] = 4ull * c.x;
+        w[1] = 4ull * (uint32_t)(c.y - c.x);                      // mod 2^32, as the sampler's compares give them
+        w[2] = 4ull * (uint32_t)(c.z - c.y);
+        w[3] = 4ull * (0x100000000ull - c.z);
+    } else {
+        uint32_t greedy;
+        if (a.q) {
+            const float4 r4 = a.q[row];
+            const float r[4] = {r4.x, r4.y, r4.z, r4.w};
+            int first;
+            lmaze_q_first_max(r, &first);
+            greedy = (uint32_t)first;
+        } else {
+            greedy = a.policy[row];                               // above 3: the greedy share goes to no action
+        }
+        const uint64_t e = a.epsilon;
+#pragma unroll
+        for (int act = 0; act < 4; ++act) w[act] = e + (greedy == (uint32_t)act ? 4ull * (0x100000000ull - e) : 0ull);
+    }
+    uint64_t W = 0;
+#pragma unroll
+    for (int act = 0; act < 4; ++act) {
+        if ((d & SOLVE_WALL_STATE) || ((d >> (4 * act)) & 3u) == SOLVE_EXCLUDED) w[act] = 0;
+        W += w[act];
+    }
+    const float fW = __ull2float_rn(W);
+#pragma unroll
+    for (int act = 0; act < 4; ++act) p[act] = w[act] ? __fdiv_rn(__ull2float_rn(w[act]), fW) : 0.0f;
+}
+
+// Q_k(s, .) from V_(k-1) and V_k(s) = sum_a p_a Q_k(s, a): in the order a = 0..3, from the first term itself, over the actions
+// that carry weight (an excluded pair carries none, so -inf * 0 never occurs); every product and sum rounded on its own
+__device__ __forceinline__ float evaluate_cell(const EvaluateArgs& a, uint32_t d, const float (&p)[4], int s, const float* vo,
+                                               float (&q)[4]) {
+#pragma clang fp contract(off)
+    if (d & SOLVE_WALL_STATE) {
+        q[0] = q[1] = q[2] = q[3] = 0.0f;
+        return 0.0f;
+    }
+    solve_action_values(a, d, s, vo, q);
+    float v = 0.0f;
+    bool first = true;
+#pragma unroll
+    for (int act = 0; act < 4; ++act) {
+        if (p[act] != 0.0f) {
+            const float term = p[act] * q[act];
+            const float sum = v + term;
+            v = first ? term : sum;
+            first = false;
+        }
+    }
+    return v;
+}
+
+// Sixteen cells per lane keep 80 registers for the whole solve and the compiler hoists what else a sweep repeats (targets,
+// rewards); asked for two waves per SIMD it stays inside 256 registers without scratch, so two workgroups share a CU and one
+// sweeps while the other stands at its barrier.
+template <int VARIANT, int CPL, bool WAVE>
+__global__ __launch_bounds__(LMAZE_BLOCK, (CPL == 16 ? 2 : 1)) void evaluate_kernel(const EvaluateArgs a) {
+    constexpr int TPP = WAVE ? 64 : LMAZE_BLOCK;        // threads per problem
+    constexpr int PPW = LMAZE_BLOCK / TPP;              // problems per workgroup
+    constexpr int SP = CPL * TPP;                       // floats of one V buffer, >= S
+    extern __shared__ __align__(16) unsigned char evaluate_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = WAVE ? lane : (int)threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * PPW + (WAVE ? wave : 0);
+    // wave form: a whole wave without a problem, and no barrier in that form waits for it; workgroup form: never
+    if (p >= a.problems) return;
+    float* const vbuf = reinterpret_cast<float*>(evaluate_lds) + (WAVE ? wave : 0) * 2 * SP;
+    uint32_t* const vote = reinterpret_cast<uint32_t*>(evaluate_lds + (size_t)PPW * 2 * SP * sizeof(float) + SOLVE_MODEL_BYTES);   // workgroup form only
+    const int G = a.grid, S = G * G;
+    const int64_t base = p * S;
+
+    // the layout's bytes borrow the second V buffer until the descriptors are built; V_0 goes into the first
+    uint8_t* const lay = reinterpret_cast<uint8_t*>(vbuf + SP);
+    const uint8_t* const lay_g = a.layouts + (a.per_env ? base : 0);
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        const int s = t + j * TPP;
+        if (s < S) {
+            lay[s] = lay_g[s];
+            vbuf[s] = a.v_init ? a.v_init[base + s] : 0.0f;
+        }
+    }
+    int gx = -1, gy = -1;
+    if (VARIANT == LMAZE_VARIANT_V3) {
+        const int2 g = a.goal[p];
+        gx = g.x;
+        gy = g.y;
+    }
+    // what transition_rule reads when it is asked for the model, in LDS as in solve_kernel (v3's rule selects between two of
+    // the rewards by address); every wave writes the same four words and reads them behind its own fence
+    StepArgs* const m = reinterpret_cast<StepArgs*>(evaluate_lds + (size_t)PPW * 2 * SP * sizeof(float));
+    if (lane == 0) {
+        m->reward_wall = a.reward_wall;
+        m->reward_move = a.reward_move;
+        m->reward_goal = a.reward_goal;
+        m->step_limit = INT_MAX;
+    }
+    solve_sync<WAVE>();
+    uint32_t desc[CPL];
+    float prob[CPL][4];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        const int s = t + j * TPP;
+        desc[j] = SOLVE_WALL_STATE;
+        prob[j][0] = prob[j][1] = prob[j][2] = prob[j][3] = 0.0f;
+        if (s < S) {
+            desc[j] = solve_descriptor<VARIANT>(*m, lay, G, s, gx, gy);
+            evaluate_probs(a, base + s, desc[j], prob[j]);
+        }
+    }
+    solve_sync<WAVE>();                // the layout's bytes are read: the second buffer is free
+
+    // tol as a bit pattern: deltas are non-negative floats or NaNs, which order as unsigned integers with every NaN on top
+    const bool use_tol = a.tol > 0.0f;
+    const uint32_t tol_bits = __float_as_uint(a.tol);
+    int cur = 0, k = 0;                // V_(k-1) is vbuf[cur]
+    uint32_t dbits;
+    for (;;) {
+        ++k;
+        const float* const vo = vbuf + cur * SP;
+        float* const vn = vbuf + (cur ^ 1) * SP;
+        bool changed = false;
+        dbits = 0;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int s = t + j * TPP;
+            if (s < S) {
+                float q[4];
+                const float v = evaluate_cell(a, desc[j], prob[j], s, vo, q);
+                const float old = vo[s];
+                vn[s] = v;
+                changed |= __float_as_uint(v) != __float_as_uint(old);
+                dbits = max(dbits, __float_as_uint(v - old) & 0x7FFFFFFFu);
+            }
+        }
+        const bool far = !use_tol || dbits > tol_bits;
+        bool any_changed = __ballot(changed) != 0ull, any_far = __ballot(far) != 0ull;
+        if constexpr (WAVE) {
+            solve_sync<true>();
+        } else {
+            uint32_t* const mine = vote + (k & 1) * 4;
+            if (lane == 0) mine[wave] = (any_changed ? 1u : 0u) | (any_far ? 2u : 0u);
+            __syncthreads();           // V_k and the four votes; every thread of the workgroup is here, every sweep
+            const uint32_t all = mine[0] | mine[1] | mine[2] | mine[3];
+            any_changed = (all & 1u) != 0u;
+            any_far = (all & 2u) != 0u;
+        }
+        cur ^= 1;
+        if (!any_changed || !any_far || k == a.sweeps) break;   // the same answer in every thread of the problem
+    }
+
+    // Q_k of the last sweep from V_(k-1), which the other buffer still holds
+    const float* const vo = vbuf + (cur ^ 1) * SP;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        const int s = t + j * TPP;
+        if (s < S) {
+            float q[4];
+            const float v = evaluate_cell(a, desc[j], prob[j], s, vo, q);
+            if (a.q_out) a.q_out[base + s] = make_float4(q[0], q[1], q[2], q[3]);
+            if (a.v_out) a.v_out[base + s] = v;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dbits = max(dbits, (uint32_t)__shfl_xor((int)dbits, off, 64));
+    if constexpr (!WAVE) {
+        uint32_t* const red = vote + 8;
+        if (lane == 0) red[wave] = dbits;
+        __syncthreads();
+        dbits = max(max(red[0], red[1]), max(red[2], red[3]));
+    }
+    if (t == 0) {
+        if (a.sweeps_run) a.sweeps_run[p] = k;
+        if (a.delta) a.delta[p] = __uint_as_float(dbits);
+    }
+}
+
+int describe_evaluate(int variant, const SolvePlan& p, char* text, int32_t len) {
+    if (!text || len < 1) return LMAZE_E_NULL;
+    snprintf(text, (size_t)len, "evaluate_kernel<%s, %s, %d> grid=%lld block=%d lds=%lld problems_per_workgroup=%d",
+             variant == LMAZE_VARIANT_V3 ? "v3" : "v0", p.wave ? "wave" : "workgroup", p.cells_per_lane, (long long)p.grid, LMAZE_BLOCK,
+             (long long)p.lds_bytes, p.problems_per_workgroup);
+    return 0;
+}
+
+template <int VARIANT, int CPL, bool WAVE>
+static hipError_t evaluate_launch(const EvaluateArgs& a, const SolvePlan& p, hipStream_t s) {
+    hipLaunchKernelGGL((evaluate_kernel<VARIANT, CPL, WAVE>), dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a);
+    return hipGetLastError();
+}
+
+template <int VARIANT>
+static hipError_t evaluate_dispatch(const EvaluateArgs& a, const SolvePlan& p, hipStream_t s) {
+    if (p.wave) {
+        switch (p.cells_per_lane) {
+            case 1: return evaluate_launch<VARIANT, 1, true>(a, p, s);
+            case 2: return evaluate_launch<VARIANT, 2, true>(a, p, s);
+            default: return evaluate_launch<VARIANT, 4, true>(a, p, s);
+        }
+    }
+    switch (p.cells_per_lane) {
+        case 2: return evaluate_launch<VARIANT, 2, false>(a, p, s);
+        case 4: return evaluate_launch<VARIANT, 4, false>(a, p, s);
+        case 8: return evaluate_launch<VARIANT, 8, false>(a, p, s);
+        default: return evaluate_launch<VARIANT, 16, false>(a, p, s);
+    }
+}
+
+// the plan is plan_solve's: the same two buffers of S floats per problem, the same model and vote words behind them
+hipError_t launch_evaluate(int variant, const EvaluateArgs& a, hipStream_t s) {
+    if (a.problems == 0) return hipSuccess;
+    const SolvePlan p = plan_solve(a.grid, a.problems);
+    if (!grid_ok(p.grid)) return hipErrorInvalidConfiguration;
+    return variant == LMAZE_VARIANT_V3 ? evaluate_dispatch<LMAZE_VARIANT_V3>(a, p, s) : evaluate_dispatch<LMAZE_VARIANT_V0>(a, p, s);
+}
+
+}  // namespace lmaze

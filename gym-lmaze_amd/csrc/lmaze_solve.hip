@@ -25,25 +25,9 @@
 
 namespace lmaze {
 
-// r + gamma * v with the product and the sum rounded separately, as returns_step (lmaze_aux.hip): never an fma
-__device__ __forceinline__ float solve_backup(float r, float gamma, float v) {
-#pragma clang fp contract(off)
-    const float discounted = gamma * v;
-    return r + discounted;
-}
-
-// Q_k(s, .) from V_(k-1), the first maximum by strict '>' and its action
+// Q_k(s, .) from V_(k-1) (solve_action_values, lmaze_solve_model.h), the first maximum by strict '>' and its action
 __device__ __forceinline__ float solve_cell(const SolveArgs& a, uint32_t d, int s, const float* vo, float (&q)[4], int& pol) {
-    const int G = a.grid;
-#pragma unroll
-    for (int act = 0; act < 4; ++act) {
-        const uint32_t nib = (d >> (4 * act)) & 15u, sel = nib & 3u;
-        const int step = act == 0 ? -G : (act == 1 ? G : (act == 2 ? -1 : 1));
-        const float r = sel == SOLVE_GOAL ? a.reward_goal : (sel == SOLVE_MOVE ? a.reward_move : a.reward_wall);
-        const float vn = vo[(nib & SOLVE_MOVED) ? s + step : s];
-        const float backed = (nib & SOLVE_TERMINAL) ? r : solve_backup(r, a.gamma, vn);
-        q[act] = sel == SOLVE_EXCLUDED ? -INFINITY : backed;
-    }
+    solve_action_values(a, d, s, vo, q);
     float best = q[0];
     pol = 0;
 #pragma unroll

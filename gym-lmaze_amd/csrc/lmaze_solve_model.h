@@ -1,9 +1,11 @@
-// The model of one grid maze as the kernels that plan it and score it keep it (lmaze_solve.hip, lmaze_score.hip): sixteen bits
-// per cell, taken from transition_rule<VARIANT> itself, and what both kernels share of a problem's life in LDS -- the sync
-// between two phases and where the rule's StepArgs and the vote words stand behind the two buffers.  The model is stated once,
-// here, by asking the rule.
+// The model of one grid maze as the kernels that plan it, score it and evaluate policies on it keep it (lmaze_solve.hip,
+// lmaze_score.hip, lmaze_evaluate.hip): sixteen bits per cell, taken from transition_rule<VARIANT> itself, and what the kernels
+// share of a problem's life in LDS -- the sync between two phases, where the rule's StepArgs and the vote words stand behind
+// the two buffers, and the one-step backup of the two that sweep values.  The model is stated once, here, by asking the rule.
 #ifndef LMAZE_SOLVE_MODEL_H_
 #define LMAZE_SOLVE_MODEL_H_
+
+#include <math.h>
 
 #include "lmaze_common.h"
 
@@ -43,6 +45,29 @@ __device__ __forceinline__ uint32_t solve_descriptor(const StepArgs& m, const ui
         d |= nib << (4 * act);
     }
     return d;
+}
+
+// r + gamma * v with the product and the sum rounded separately, as returns_step (lmaze_aux.hip): never an fma
+__device__ __forceinline__ float solve_backup(float r, float gamma, float v) {
+#pragma clang fp contract(off)
+    const float discounted = gamma * v;
+    return r + discounted;
+}
+
+// Q_k(s, .) from V_(k-1) for a non-wall cell: r on a terminal pair, else r + gamma * V_(k-1)(next), -inf on an excluded pair.
+// Args: SolveArgs or EvaluateArgs (grid, gamma and the three rewards).
+template <class Args>
+__device__ __forceinline__ void solve_action_values(const Args& a, uint32_t d, int s, const float* vo, float (&q)[4]) {
+    const int G = a.grid;
+#pragma unroll
+    for (int act = 0; act < 4; ++act) {
+        const uint32_t nib = (d >> (4 * act)) & 15u, sel = nib & 3u;
+        const int step = act == 0 ? -G : (act == 1 ? G : (act == 2 ? -1 : 1));
+        const float r = sel == SOLVE_GOAL ? a.reward_goal : (sel == SOLVE_MOVE ? a.reward_move : a.reward_wall);
+        const float vn = vo[(nib & SOLVE_MOVED) ? s + step : s];
+        const float backed = (nib & SOLVE_TERMINAL) ? r : solve_backup(r, a.gamma, vn);
+        q[act] = sel == SOLVE_EXCLUDED ? -INFINITY : backed;
+    }
 }
 
 // what one problem's threads wait on between two phases that exchange data through its LDS

@@ -662,6 +662,65 @@ class LmazeVecEnv(VecEnvBase):
             return ScoredTables(t.optimal.reshape(G ** 4), None if t.steps is None else t.steps.reshape(G ** 4), t.summary)
         return t
 
+    def evaluate(self, policy=None, q=None, epsilon=0.0, probs=None, logits=None, temperature=1.0, thresholds=None, key="ball",
+                 goal=None, gamma=0.99, sweeps=4096, tol=0.0, v_init=None):
+        """What the table a closed-loop rollout runs is WORTH on this env's own maze(s), exactly, in ONE launch
+        (evaluate_tables(), include/lmaze.h lmaze_evaluate): Q^pi and V^pi of the epsilon-greedy policy rollout_policy() runs
+        (policy= or q=, with epsilon=) or of the categorical one rollout_sample() runs (probs=, logits= with temperature=, or
+        thresholds=); exactly one table.  The problems are chosen as score() chooses them; the rewards are the env's.
+        shared layout, key="ball"   one problem: policy [G*G], the others [G*G, 4]; q float32[G*G, 4], v float32[G*G],
+                                    sweeps_run and delta 0-d.  v3 needs goal=(x, y).
+        shared layout, key="goal"   v3 only: G*G problems, one per goal cell; policy [G**4], the others [G**4, 4], indexed by
+                                    the key of state_keys("goal"); q [G**4, 4], v [G**4], sweeps_run, delta [G*G].
+        shared layout, key="env"    N tables on the one maze, v3 with env i's current goal: policy [N, G*G], the others
+                                    [N, G*G, 4]; q [N, G*G, 4], v [N, G*G], sweeps_run, delta [N].
+        per-env layouts             env i's maze and (v3) its current goal; tables and outputs as key="env".  v.reshape(-1)
+                                    is the critic gae(values=, key_t=, key_tail=state_keys("env")) takes.
+        v_init: float32 [problems, G*G].  Returns EvaluatedTables(q, v, sweeps_run, delta)."""
+        if key not in ("ball", "goal", "env"):
+            raise ValueError("key must be 'ball', 'goal' or 'env'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        tables = {"policy": policy, "q": q, "probs": probs, "logits": logits, "thresholds": thresholds}
+        given = [n for n, t in tables.items() if t is not None]
+        if len(given) != 1:
+            raise ValueError("evaluate() wants exactly one of policy=, q=, probs=, logits= and thresholds=")
+        G, N, dev = self.grid, self.num_envs, self.device
+        S = G * G
+        shared = self.layout_mode == _abi.LAYOUT_SHARED
+        if goal is not None and not (shared and key == "ball" and self._is_v3):
+            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
+        if not shared and key == "goal":
+            raise ValueError("key='goal' evaluates one shared layout for every goal cell; per-env layouts evaluate each env's own goal")
+        single = shared and key == "ball"
+        P = 1 if single else (S if key == "goal" else N)
+        goals = None
+        if self._is_v3:
+            if single:
+                if goal is None or len(goal) != 2:
+                    raise ValueError("evaluate(key='ball') on a shared-layout v3 env needs goal=(x, y)")
+                goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
+            elif key == "goal":
+                cells = torch.arange(S, dtype=torch.int32, device=dev)
+                goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
+            else:
+                goals = self.goal_xy
+        name = given[0]
+        table = tables[name]
+        width = 1 if name == "policy" else 4
+        if not isinstance(table, torch.Tensor) or table.numel() != P * S * width:
+            raise ValueError("%s must be a tensor of %d problems x %d states%s" % (name, P, S, "" if width == 1 else " x 4"))
+        tables[name] = table.reshape((P, S) if width == 1 else (P, S, 4))
+        if isinstance(v_init, torch.Tensor) and v_init.numel() == P * S:      # what evaluate() and solve() return: [G*G], [G**4]
+            v_init = v_init.reshape(P, S)
+        t = evaluate_tables(self.layout, epsilon=epsilon, temperature=temperature, variant=self.variant, goals=goals, gamma=gamma,
+                            sweeps=sweeps, tol=tol, rewards=self.rewards, v_init=v_init, validate=False, **tables)
+        if single:
+            return EvaluatedTables(t.q[0], t.v[0], t.sweeps_run[0], t.delta[0])
+        if key == "goal":
+            return EvaluatedTables(t.q.reshape(G ** 4, 4), t.v.reshape(G ** 4), t.sweeps_run, t.delta)
+        return t
+
     def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
         """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
         observations (obs_t / obs_every) is not captured: ValueError."""
@@ -1005,6 +1064,124 @@ def score_tables(layouts, policy=None, q=None, variant="v0", goals=None, rewards
                                       torch.cuda.current_stream(dev).cuda_stream)
         _abi.check("lmaze_score", rc)
     return ScoredTables(*[out[k] for k in SCORE_OUTPUTS])
+
+
+class EvaluatedTables(collections.namedtuple("EvaluatedTables", "q v sweeps_run delta")):
+    """What evaluate_tables() returns: q float32[P, S, 4] (Q^pi), v float32[P, S] (V^pi), sweeps_run int32[P], delta
+    float32[P]; an output that was not asked for is None."""
+    __slots__ = ()
+
+
+EVALUATE_OUTPUTS = ("q", "v", "sweeps_run", "delta")
+
+
+def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logits=None, temperature=1.0, thresholds=None,
+                    variant="v0", goals=None, gamma=0.99, sweeps=4096, tol=0.0, rewards=None, v_init=None,
+                    outputs=EVALUATE_OUTPUTS, validate=True):
+    """Exact policy evaluation on the GPU: V^pi and Q^pi of the stochastic table a closed-loop rollout would run, for every
+    maze, in ONE launch (include/lmaze.h lmaze_evaluate) -- no Monte-Carlo estimate, no host loop.
+    layouts  uint8 device tensor [G, G] (one maze for every problem) or [P, G, G], as solve_tables().
+    Exactly one of
+    policy      uint8 [P, G*G] with epsilon: the epsilon-greedy policy rollout_policy(policy=, epsilon=) runs;
+    q           float32 [P, G*G, 4] with epsilon: the same, the greedy action being the first maximum by a strict '>';
+    probs       float [P, G*G, 4] of non-negative weights, converted by _abi.sampling_thresholds() as rollout_sample() does;
+    logits      float [P, G*G, 4]: sampling_thresholds(softmax(logits.double() / temperature)), temperature > 0;
+    thresholds  the table itself, uint32 (or int32, the same bits) [P, G*G, 4], contiguous and 16-byte aligned.
+    What is evaluated is exactly the table that would be run: epsilon converts as rollout_policy() converts it, the
+    categorical inputs go through rollout_sample()'s conversion (a row of probability 1 keeps 2**-32 on action 3); epsilon
+    != 0 with a categorical input is refused.  With a [G, G] layout and v0, P is the table's length.
+    variant, goals, rewards, gamma, v_init   as solve_tables(): the model is the same.
+    sweeps, tol   a problem stops at the first Jacobi sweep that leaves every value's bits unchanged (that sweep counts), at
+             the first whose delta is <= tol when tol > 0, or after `sweeps`.
+    outputs  some of "q", "v", "sweeps_run", "delta"; at least one of the first two.
+    What the evaluator is and is not: the grid variants only; the infinite-horizon discounted problem, the step limit is not
+    in the model; the mass a policy puts on v0's sticky pairs, which solve_tables() excludes, is renormalised over the usable
+    pairs (a state with no usable mass has v = 0); float32 Jacobi with every operation rounded on its own, so a float32 numpy
+    loop reproduces every bit.  validate=False skips the layouts' check.
+    Returns EvaluatedTables(q, v, sweeps_run, delta)."""
+    if variant not in VARIANTS:
+        raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
+    spec = VARIANTS[variant]
+    v3 = variant == "v3"
+    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
+            and layouts.shape[-1] == layouts.shape[-2]):
+        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
+    dev = layouts.device
+    G = int(layouts.shape[-1])
+    if not (3 <= G <= _abi.MAX_GRID):
+        raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
+    S = G * G
+    layouts = layouts.contiguous()
+    if validate:
+        _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
+    shared = layouts.dim() == 2
+    given = [n for n, t in (("policy", policy), ("q", q), ("probs", probs), ("logits", logits), ("thresholds", thresholds))
+             if t is not None]
+    if len(given) != 1:
+        raise ValueError("evaluate_tables() wants exactly one of policy=, q=, probs=, logits= and thresholds=")
+    kind = given[0]
+    eps = _abi.epsilon_u32(epsilon)
+    if kind in ("probs", "logits", "thresholds") and eps != 0:
+        raise ValueError("epsilon belongs to policy= and q=: a categorical table already says how it explores")
+    if kind in ("probs", "logits"):
+        src = probs if kind == "probs" else logits
+        if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == dev and src.dim() == 3
+                and tuple(src.shape[1:]) == (S, 4)):
+            raise ValueError("%s must be a float tensor [P, %d, 4] on layouts' device" % (kind, S))
+        if kind == "logits":
+            if not float(temperature) > 0.0:
+                raise ValueError("temperature must be > 0")
+            src = torch.softmax(src.double() / float(temperature), -1)
+        thresholds = _abi.sampling_thresholds(src.reshape(-1, 4)).view(src.shape[0], S, 4)
+    if kind == "policy":
+        table, ok = policy, (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.dim() == 2
+                             and tuple(policy.shape[1:]) == (S,))
+    elif kind == "q":
+        table, ok = q, (isinstance(q, torch.Tensor) and q.dtype == torch.float32 and q.dim() == 3 and tuple(q.shape[1:]) == (S, 4)
+                        and q.data_ptr() % 16 == 0)
+    else:
+        table, ok = thresholds, (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
+                                 and thresholds.dim() == 3 and tuple(thresholds.shape[1:]) == (S, 4)
+                                 and thresholds.data_ptr() % 16 == 0)
+    if not (ok and table.device == dev and table.is_contiguous()):
+        raise ValueError("policy must be a contiguous uint8[P, %d], q a contiguous float32[P, %d, 4] and thresholds a contiguous, "
+                         "16-byte aligned uint32[P, %d, 4] tensor on layouts' device" % (S, S, S))
+    if v3:
+        if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == dev and goals.dim() == 2
+                and goals.shape[1] == 2 and goals.is_contiguous() and (shared or goals.shape[0] == layouts.shape[0])):
+            raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
+        P = int(goals.shape[0])
+    else:
+        if goals is not None:
+            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
+        P = int(layouts.shape[0]) if not shared else int(table.shape[0])
+    if int(table.shape[0]) != P:
+        raise ValueError("the table has %d problems, the mazes %d" % (int(table.shape[0]), P))
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or not 1 <= sweeps < 2 ** 31:
+        raise ValueError("sweeps must be an int >= 1")
+    rewards = tuple(float(r) for r in (rewards if rewards is not None else spec["rewards"]))
+    if len(rewards) != 3:
+        raise ValueError("rewards must be (wall, move, goal)")
+    outputs = tuple(outputs)
+    if not set(outputs) <= set(EVALUATE_OUTPUTS) or not set(outputs) & {"q", "v"}:
+        raise ValueError("outputs must name some of %s, at least one of q, v" % (EVALUATE_OUTPUTS,))
+    if v_init is not None and not (isinstance(v_init, torch.Tensor) and v_init.dtype == torch.float32 and v_init.device == dev
+                                   and v_init.is_contiguous() and tuple(v_init.shape) == (P, S)):
+        raise ValueError("v_init must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
+    shapes = {"q": ((P, S, 4), torch.float32), "v": ((P, S), torch.float32), "sweeps_run": ((P,), torch.int32),
+              "delta": ((P,), torch.float32)}
+    out = {k: (torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) if k in outputs else None) for k in EVALUATE_OUTPUTS}
+    if P > 0:
+        params = _abi.make_params(spec["id"], G, _abi.LAYOUT_SHARED if shared else _abi.LAYOUT_PER_ENV, spec["step_limit"], *rewards)
+        with torch.cuda.device(dev):
+            rc = _abi.lib.lmaze_evaluate(C.byref(params), layouts.data_ptr(), goals.data_ptr() if v3 else None, P,
+                                         table.data_ptr() if kind == "policy" else None, table.data_ptr() if kind == "q" else None,
+                                         eps, table.data_ptr() if kind not in ("policy", "q") else None, float(gamma), int(sweeps),
+                                         float(tol), None if v_init is None else v_init.data_ptr(),
+                                         *[None if out[k] is None else out[k].data_ptr() for k in EVALUATE_OUTPUTS],
+                                         torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check("lmaze_evaluate", rc)
+    return EvaluatedTables(*[out[k] for k in EVALUATE_OUTPUTS])
 
 
 def _validate_on_device(lay, need_goal=True):

@@ -658,7 +658,9 @@ int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* t
  *   bump terminal)
  *   v0, any other c ('S')    a STICKY pair: the step leaves the ball where it is and repeats the previous reward, which is no
  *                            function of (cell, action).  Sticky pairs are excluded: q(s, a) = -INFINITY, never the maximum;
- *                            a state all of whose four pairs are excluded gets v = 0, policy = 0.
+ *                            a state all of whose four pairs are excluded gets v = 0, policy = 0.  (lmaze_evaluate, which
+ *                            takes an expectation where this takes a maximum, renormalises the mass a policy puts on
+ *                            excluded pairs over the usable ones.)
  * A state on a 'W' cell has q = 0 for all four actions, v = 0, policy = 0.  Layouts carry a full 'W' border (every target of
  * a non-wall state is on the grid); on any other bytes a target off the grid counts as the cell itself, nothing is read out of
  * bounds.
@@ -743,6 +745,76 @@ int lmaze_score(const LmazeParams* params, const uint8_t* layouts, const int32_t
  * text_host NULL or len < 1, then lmaze_score's refusals of the params and of `problems`; an empty line for problems == 0.
  */
 int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
+
+/*
+ * EXACT POLICY EVALUATION on the grid mazes: V^pi and Q^pi of the stochastic table a closed-loop rollout runs, in ONE launch;
+ * no reference counterpart.  The linear twin of lmaze_solve: where that takes the maximum over the actions, this takes the
+ * policy's expectation.  It gives the critic lmaze_advantages_table wants for a policy that explores, the expected return of a
+ * half-learnt lmaze_env_rollout_qlearn table under the epsilon it is run with, and the Q^pi whose first maximum is the next
+ * policy of policy iteration.
+ * Problems, the model, the layout modes and the goals are lmaze_score's, word for word: problem p has S = G*G states,
+ * s = x * G + y; the transition of lmaze_step_v0 / _v3 asked once per (cell, action) with a step count that trips no limit
+ * (infinite horizon: the step limit is not in the model); the same wall, move and goal pairs; a pair is terminal exactly when
+ * its reward equals reward_goal as float32; v0's sticky pairs are excluded; wall states and targets off the grid as in
+ * lmaze_solve.  LMAZE_LAYOUT_SHARED: every problem reads the one layout and its own table (a population of tables on one maze,
+ * v3 with one goal per problem, the goal-keyed tables); LMAZE_LAYOUT_PER_ENV: problem p reads layouts + p*G*G.  v3 reads
+ * goal_xy[2p], goal_xy[2p+1].
+ * The policy of problem p.  Exactly one of three inputs is given; each reduces to four integer weights w_0..w_3 per state, in
+ * units of 2^-34:
+ *   policy      uint8[problems, S] with epsilon_u32: lmaze_rollout_policy's rule (explore when r.x < epsilon_u32, then take
+ *               action r.y >> 30): w_a = e + (a == policy[s] ? 4 * (2^32 - e) : 0), e = epsilon_u32.  A byte above 3 gives its
+ *               greedy share to no action
+ *   q           float[problems, S, 4], 16-byte aligned, with epsilon_u32: the same, the greedy action being the first maximum
+ *               by a strict '>' from action 0 on -- lmaze_score's rule: a NaN never wins, a NaN in word 0 keeps action 0
+ *   thresholds  uint32[problems, S, 4], 16-byte aligned: lmaze_rollout_sample's rule, w_a = 4 * (c_a - c_(a-1)) with
+ *               c_(-1) = 0 and c_3 = 2^32; word 3 is ignored, epsilon_u32 is not read.  The two inner differences are taken
+ *               mod 2^32, so a non-monotone row, which the sampler does not refuse either, still has weights: they sum to
+ *               2^34, 2^35 or 3 * 2^34.  A row of probability 1 is stored as 1 - 2^-32 (see lmaze_rollout_sample): its action
+ *               gets 4 * (2^32 - 1) and action 3 gets 4
+ * Probabilities, computed once per state before the first sweep:
+ *   w'_a = w_a if the pair (s, a) is usable, 0 if the model excludes it (v0's sticky pairs);  W = w'_0 + w'_1 + w'_2 + w'_3,
+ *   an integer;  p_a = fl(fl(w'_a) / fl(W)): both integers rounded to float32 (ties to even), one correctly rounded division.
+ *   Where nothing is excluded and the row is monotone, W = 2^34 and the division is an exact scaling.  W == 0 -- every pair
+ *   that carries weight is excluded, or a byte above 3 at epsilon_u32 == 0 -- gives p_a = 0 for every action and v = 0.
+ * So where lmaze_solve excludes a sticky pair from the maximum, the mass a policy puts on excluded pairs is RENORMALISED over the
+ * usable ones: the step repeats the previous reward there and leaves the ball in place, which has no value of its own; the
+ * evaluated policy is the one conditioned on taking a usable pair.
+ * The sweep is Jacobi, in float32, every operation rounded on its own (round to nearest even, never a fused multiply-add):
+ *   V_0 = v_init (problem p: v_init + p*S) or 0 when v_init is NULL
+ *   Q_k(s, a) = lmaze_solve's: r(s, a) for a terminal pair, else r(s, a) + gamma * V_(k-1)(next); -INFINITY for an excluded pair
+ *   V_k(s) = the sum over a = 0, 1, 2, 3, in that order, of p_a * Q_k(s, a), over the actions with w'_a != 0 only (so
+ *            -INFINITY * 0 never occurs), starting from the first such term itself, not from 0 + term; 0 if there is none
+ *   a state on a 'W' cell has q = 0 for all four actions and v = 0
+ * A problem stops at the first sweep that leaves the bit pattern of every V(s) unchanged -- that sweep counts --, or, when
+ * tol > 0, at the first sweep whose delta (below) is <= tol, compared as bit patterns so that a NaN delta never passes, or
+ * after `sweeps` sweeps.  tol is not validated: a negative or NaN tol never stops a solve.  With epsilon_u32 == 0, policy =
+ * lmaze_solve's policy and v_init = lmaze_solve's settled v, the first sweep changes no bit: V^pi is V* bit for bit.
+ * Outputs, each nullable, one of q_out / v_out required:
+ *   q_out       float[problems, S, 4]  Q_k of the last executed sweep; 16-byte aligned
+ *   v_out       float[problems, S]     V_k
+ *   sweeps_run  int32[problems]        sweeps executed
+ *   delta       float[problems]        max_s |V_k(s) - V_(k-1)(s)| of the last executed sweep, as lmaze_solve's
+ * One launch of evaluate_kernel, shaped as solve_kernel and with its plan: a problem lives in LDS for the whole solve (two V
+ * buffers; the model and the four probabilities of a cell in registers, read from global memory once); a wave per problem while
+ * G*G <= 256, four problems per workgroup and no workgroup barrier; a workgroup per problem above, one barrier per sweep.
+ * params->launch_hint, step_limit are not read.
+ * Refused, in this order: LMAZE_E_NULL params or layouts; LMAZE_E_GRID; LMAZE_E_VARIANT neither v0 nor v3; LMAZE_E_LAYOUT;
+ * LMAZE_E_NULL goal_xy for v3; LMAZE_E_NULL both q_out and v_out NULL; LMAZE_E_NULL unless exactly one of policy, q and
+ * thresholds is given; LMAZE_E_COUNT problems outside [0, LMAZE_MAX_ENVS] or sweeps < 1; LMAZE_E_ALIGN thresholds, q or q_out
+ * off 16 bytes, goal_xy (v3) off 8, a float or int32 pointer off 4.  problems == 0 then returns 0 with nothing read.  gamma is
+ * not validated.  A grid beyond 2^24 - 1 workgroups: hipErrorInvalidConfiguration.
+ */
+int lmaze_evaluate(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
+                   const float* q, uint32_t epsilon_u32, const uint32_t* thresholds, float gamma, int32_t sweeps, float tol,
+                   const float* v_init, float* q_out, float* v_out, int32_t* sweeps_run, float* delta, void* stream);
+
+/*
+ * The launch lmaze_evaluate would queue, one line in text_host (HOST, len bytes), written by the code that launches, e.g.
+ * "evaluate_kernel<v0, wave, 4> grid=65 block=256 lds=8208 problems_per_workgroup=4" or "evaluate_kernel<v3, workgroup, 2> ..."
+ * (the third argument: cells per lane; the plan is lmaze_solve's).  Nothing is queued or dereferenced.  LMAZE_E_NULL params or
+ * text_host NULL or len < 1, then lmaze_evaluate's refusals of the params and of `problems`; an empty line for problems == 0.
+ */
+int lmaze_describe_evaluate(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
 
 /*
  * MAZE GENERATION: `mazes` spanning-tree mazes of G x G cells, every one different, every free cell connected to its goal,
