@@ -694,99 +694,115 @@ static int check_solve_params(const LmazeParams* p) {
     return 0;
 }
 
-int lmaze_solve(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, float gamma,
-                int32_t sweeps, const float* v_init, float* q, float* v, uint8_t* policy, int32_t* sweeps_run, float* delta,
-                void* stream) {
+// The head lmaze_solve, lmaze_score and lmaze_evaluate judge alike, before anything of their own: params and layouts, the
+// params' values, v3's goal
+static int check_problems_head(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy) {
     if (!params || !layouts) return LMAZE_E_NULL;
     const int rc = check_solve_params(params);
     if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (v3 && !goal_xy) return LMAZE_E_NULL;
-    if (!q && !v && !policy) return LMAZE_E_NULL;
-    if (problems < 0 || problems > LMAZE_MAX_ENVS || sweeps < 1) return LMAZE_E_COUNT;
-    if (misaligned(q, 16) || (v3 && misaligned(goal_xy, 8)) || misaligned(v_init, 4) || misaligned(v, 4) || misaligned(sweeps_run, 4) ||
-        misaligned(delta, 4))
-        return LMAZE_E_ALIGN;
-    if (problems == 0) return 0;
-    const SolveArgs a{layouts, v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr, v_init, reinterpret_cast<float4*>(q), v, policy,
-                      sweeps_run, delta, problems, params->grid, sweeps, params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0, gamma,
-                      params->reward_wall, params->reward_move, params->reward_goal};
-    return (int)launch_solve(params->variant, a, (hipStream_t)stream);
+    if (params->variant == LMAZE_VARIANT_V3 && !goal_xy) return LMAZE_E_NULL;
+    return 0;
 }
 
-int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
-    if (!params || !text_host || len < 1) return LMAZE_E_NULL;
-    text_host[0] = 0;
-    const int rc = check_solve_params(params);
+// ... and the tail, behind their own pointers: the counts (the entry's own with the problems' range), the alignments (the
+// entry's own with the goal's).  The caller returns the code, or 0 when problems == 0: nothing to do
+static int check_problems_tail(const LmazeParams* params, const int32_t* goal_xy, int64_t problems, bool own_counts_ok,
+                               bool own_aligned) {
+    if (problems < 0 || problems > LMAZE_MAX_ENVS || !own_counts_ok) return LMAZE_E_COUNT;
+    if (!own_aligned || (params->variant == LMAZE_VARIANT_V3 && misaligned(goal_xy, 8))) return LMAZE_E_ALIGN;
+    return 0;
+}
+
+int lmaze_solve(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, float gamma,
+                int32_t sweeps, const float* v_init, float* q, float* v, uint8_t* policy, int32_t* sweeps_run, float* delta,
+                void* stream) {
+    int rc = check_problems_head(params, layouts, goal_xy);
     if (rc) return rc;
-    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
-    if (problems == 0) return 0;
-    return describe_solve(params->variant, plan_solve(params->grid, problems), text_host, len);
+    if (!q && !v && !policy) return LMAZE_E_NULL;
+    rc = check_problems_tail(params, goal_xy, problems, sweeps >= 1,
+                             !(misaligned(q, 16) || misaligned(v_init, 4) || misaligned(v, 4) || misaligned(sweeps_run, 4) ||
+                               misaligned(delta, 4)));
+    if (rc || problems == 0) return rc;
+    SolveArgs a = problem_args<SolveArgs>(params, layouts, goal_xy, problems);
+    a.v_init = v_init;
+    a.q = reinterpret_cast<float4*>(q);
+    a.v = v;
+    a.policy = policy;
+    a.sweeps_run = sweeps_run;
+    a.delta = delta;
+    a.sweeps = sweeps;
+    a.gamma = gamma;
+    return (int)launch_solve(params->variant, a, (hipStream_t)stream);
 }
 
 int lmaze_score(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
                 const float* q, int32_t* optimal, int32_t* steps, int32_t* summary, void* stream) {
-    // lmaze_solve's refusals, in its order, with the table and the outputs judged where it judges its outputs
-    if (!params || !layouts) return LMAZE_E_NULL;
-    const int rc = check_solve_params(params);
+    int rc = check_problems_head(params, layouts, goal_xy);
     if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (v3 && !goal_xy) return LMAZE_E_NULL;
     if (!optimal && !steps && !summary) return LMAZE_E_NULL;
     if (policy && q) return LMAZE_E_NULL;
     if (steps && !policy && !q) return LMAZE_E_NULL;
-    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
-    if (misaligned(q, 16) || (v3 && misaligned(goal_xy, 8)) || misaligned(policy, 4) || misaligned(optimal, 4) || misaligned(steps, 4) ||
-        misaligned(summary, 4))
-        return LMAZE_E_ALIGN;
-    if (problems == 0) return 0;
-    const ScoreArgs a{layouts, v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr, policy, reinterpret_cast<const float4*>(q), optimal,
-                      steps, summary, problems, params->grid, params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0, params->reward_wall,
-                      params->reward_move, params->reward_goal};
+    rc = check_problems_tail(params, goal_xy, problems, true,
+                             !(misaligned(q, 16) || misaligned(policy, 4) || misaligned(optimal, 4) || misaligned(steps, 4) ||
+                               misaligned(summary, 4)));
+    if (rc || problems == 0) return rc;
+    ScoreArgs a = problem_args<ScoreArgs>(params, layouts, goal_xy, problems);
+    a.policy = policy;
+    a.q = reinterpret_cast<const float4*>(q);
+    a.optimal = optimal;
+    a.steps = steps;
+    a.summary = summary;
     return (int)launch_score(params->variant, a, (hipStream_t)stream);
-}
-
-int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
-    if (!params || !text_host || len < 1) return LMAZE_E_NULL;
-    text_host[0] = 0;
-    const int rc = check_solve_params(params);
-    if (rc) return rc;
-    if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
-    if (problems == 0) return 0;
-    return describe_score(params->variant, plan_solve(params->grid, problems), text_host, len);
 }
 
 int lmaze_evaluate(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
                    const float* q, uint32_t epsilon_u32, const uint32_t* thresholds, float gamma, int32_t sweeps, float tol,
                    const float* v_init, float* q_out, float* v_out, int32_t* sweeps_run, float* delta, void* stream) {
-    // lmaze_score's refusals, in its order, with the policy inputs judged where it judges its tables
-    if (!params || !layouts) return LMAZE_E_NULL;
-    const int rc = check_solve_params(params);
+    int rc = check_problems_head(params, layouts, goal_xy);
     if (rc) return rc;
-    const bool v3 = params->variant == LMAZE_VARIANT_V3;
-    if (v3 && !goal_xy) return LMAZE_E_NULL;
     if (!q_out && !v_out) return LMAZE_E_NULL;
     if ((policy ? 1 : 0) + (q ? 1 : 0) + (thresholds ? 1 : 0) != 1) return LMAZE_E_NULL;
-    if (problems < 0 || problems > LMAZE_MAX_ENVS || sweeps < 1) return LMAZE_E_COUNT;
-    if (misaligned(thresholds, 16) || misaligned(q, 16) || misaligned(q_out, 16) || (v3 && misaligned(goal_xy, 8)) ||
-        misaligned(v_init, 4) || misaligned(v_out, 4) || misaligned(sweeps_run, 4) || misaligned(delta, 4))
-        return LMAZE_E_ALIGN;
-    if (problems == 0) return 0;
-    const EvaluateArgs a{layouts, v3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr, policy, reinterpret_cast<const float4*>(q),
-                         reinterpret_cast<const uint4*>(thresholds), v_init, reinterpret_cast<float4*>(q_out), v_out, sweeps_run, delta,
-                         problems, params->grid, sweeps, params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0, epsilon_u32, gamma, tol,
-                         params->reward_wall, params->reward_move, params->reward_goal};
+    rc = check_problems_tail(params, goal_xy, problems, sweeps >= 1,
+                             !(misaligned(thresholds, 16) || misaligned(q, 16) || misaligned(q_out, 16) || misaligned(v_init, 4) ||
+                               misaligned(v_out, 4) || misaligned(sweeps_run, 4) || misaligned(delta, 4)));
+    if (rc || problems == 0) return rc;
+    EvaluateArgs a = problem_args<EvaluateArgs>(params, layouts, goal_xy, problems);
+    a.policy = policy;
+    a.q = reinterpret_cast<const float4*>(q);
+    a.thresholds = reinterpret_cast<const uint4*>(thresholds);
+    a.v_init = v_init;
+    a.q_out = reinterpret_cast<float4*>(q_out);
+    a.v_out = v_out;
+    a.sweeps_run = sweeps_run;
+    a.delta = delta;
+    a.sweeps = sweeps;
+    a.epsilon = epsilon_u32;
+    a.gamma = gamma;
+    a.tol = tol;
     return (int)launch_evaluate(params->variant, a, (hipStream_t)stream);
 }
 
-int lmaze_describe_evaluate(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+// what the three lmaze_describe_* judge and print: `kernel` names the family's kernel
+static int describe_problems(const LmazeParams* params, int64_t problems, char* text_host, int32_t len, const char* kernel) {
     if (!params || !text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
     const int rc = check_solve_params(params);
     if (rc) return rc;
     if (problems < 0 || problems > LMAZE_MAX_ENVS) return LMAZE_E_COUNT;
     if (problems == 0) return 0;
-    return describe_evaluate(params->variant, plan_solve(params->grid, problems), text_host, len);
+    return describe_problems_plan(kernel, params->variant, plan_solve(params->grid, problems), text_host, len);
+}
+
+int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    return describe_problems(params, problems, text_host, len, "solve_kernel");
+}
+
+int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    return describe_problems(params, problems, text_host, len, "score_kernel");
+}
+
+int lmaze_describe_evaluate(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    return describe_problems(params, problems, text_host, len, "evaluate_kernel");
 }
 
 // What lmaze_generate and lmaze_describe_generate judge of the grid side and of the counts, in the header's order

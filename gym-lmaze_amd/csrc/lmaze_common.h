@@ -237,7 +237,8 @@ struct SolvePlan {
     int64_t grid, lds_bytes;
 };
 SolvePlan plan_solve(int32_t G, int64_t problems);
-int describe_solve(int variant, const SolvePlan& p, char* text, int32_t len);
+// the line lmaze_describe_solve, _score and _evaluate print: the kernel's name ("solve_kernel", ...) and the plan
+int describe_problems_plan(const char* kernel, int variant, const SolvePlan& p, char* text, int32_t len);
 hipError_t launch_solve(int variant, const SolveArgs& a, hipStream_t s);
 // Scoring tables on the grid mazes (lmaze_score, lmaze_score.hip): the fewest steps to done and the length of a table's greedy
 // walk from every cell, one problem = one maze and one table, in LDS in one launch.  The plan is plan_solve's.
@@ -253,7 +254,6 @@ struct ScoreArgs {
     int32_t grid, per_env;
     float reward_wall, reward_move, reward_goal;
 };
-int describe_score(int variant, const SolvePlan& p, char* text, int32_t len);
 hipError_t launch_score(int variant, const ScoreArgs& a, hipStream_t s);
 // Exact policy evaluation on the grid mazes (lmaze_evaluate, lmaze_evaluate.hip): V^pi and Q^pi of one stochastic table per
 // problem, the linear twin of lmaze_solve -- the same model, the same two V buffers in LDS, the same plan (plan_solve).
@@ -273,8 +273,21 @@ struct EvaluateArgs {
     uint32_t epsilon;         // as PolicyTable's
     float gamma, tol, reward_wall, reward_move, reward_goal;
 };
-int describe_evaluate(int variant, const SolvePlan& p, char* text, int32_t len);
 hipError_t launch_evaluate(int variant, const EvaluateArgs& a, hipStream_t s);
+// the eight fields SolveArgs, ScoreArgs and EvaluateArgs share, from an entry's checked arguments; the rest zero
+template <class Args>
+inline Args problem_args(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems) {
+    Args a{};
+    a.layouts = layouts;
+    a.goal = params->variant == LMAZE_VARIANT_V3 ? reinterpret_cast<const int2*>(goal_xy) : nullptr;
+    a.problems = problems;
+    a.grid = params->grid;
+    a.per_env = params->layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0;
+    a.reward_wall = params->reward_wall;
+    a.reward_move = params->reward_move;
+    a.reward_goal = params->reward_goal;
+    return a;
+}
 // Spanning-tree mazes (lmaze_generate, lmaze_generate.hip): maze p of the launch is global maze maze_base + p, built in LDS
 // from its own Philox draws and written once.  The draws' counter is (maze lo, maze hi, room, 0x40000000): the reset and
 // exploration streams carry epoch_hi and epoch_hi ^ 0x80000000 in that last word, epochs stay far below 2^62, so the word is

@@ -88,60 +88,15 @@ __device__ __forceinline__ float evaluate_cell(const EvaluateArgs& a, uint32_t d
 // sweeps while the other stands at its barrier.
 template <int VARIANT, int CPL, bool WAVE>
 __global__ __launch_bounds__(LMAZE_BLOCK, (CPL == 16 ? 2 : 1)) void evaluate_kernel(const EvaluateArgs a) {
-    constexpr int TPP = WAVE ? 64 : LMAZE_BLOCK;        // threads per problem
-    constexpr int PPW = LMAZE_BLOCK / TPP;              // problems per workgroup
-    constexpr int SP = CPL * TPP;                       // floats of one V buffer, >= S
     extern __shared__ __align__(16) unsigned char evaluate_lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = WAVE ? lane : (int)threadIdx.x;
-    const int64_t p = (int64_t)blockIdx.x * PPW + (WAVE ? wave : 0);
-    // wave form: a whole wave without a problem, and no barrier in that form waits for it; workgroup form: never
-    if (p >= a.problems) return;
-    float* const vbuf = reinterpret_cast<float*>(evaluate_lds) + (WAVE ? wave : 0) * 2 * SP;
-    uint32_t* const vote = reinterpret_cast<uint32_t*>(evaluate_lds + (size_t)PPW * 2 * SP * sizeof(float) + SOLVE_MODEL_BYTES);   // workgroup form only
-    const int G = a.grid, S = G * G;
-    const int64_t base = p * S;
-
-    // the layout's bytes borrow the second V buffer until the descriptors are built; V_0 goes into the first
-    uint8_t* const lay = reinterpret_cast<uint8_t*>(vbuf + SP);
-    const uint8_t* const lay_g = a.layouts + (a.per_env ? base : 0);
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int s = t + j * TPP;
-        if (s < S) {
-            lay[s] = lay_g[s];
-            vbuf[s] = a.v_init ? a.v_init[base + s] : 0.0f;
-        }
-    }
-    int gx = -1, gy = -1;
-    if (VARIANT == LMAZE_VARIANT_V3) {
-        const int2 g = a.goal[p];
-        gx = g.x;
-        gy = g.y;
-    }
-    // what transition_rule reads when it is asked for the model, in LDS as in solve_kernel (v3's rule selects between two of
-    // the rewards by address); every wave writes the same four words and reads them behind its own fence
-    StepArgs* const m = reinterpret_cast<StepArgs*>(evaluate_lds + (size_t)PPW * 2 * SP * sizeof(float));
-    if (lane == 0) {
-        m->reward_wall = a.reward_wall;
-        m->reward_move = a.reward_move;
-        m->reward_goal = a.reward_goal;
-        m->step_limit = INT_MAX;
-    }
-    solve_sync<WAVE>();
-    uint32_t desc[CPL];
     float prob[CPL][4];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int s = t + j * TPP;
-        desc[j] = SOLVE_WALL_STATE;
-        prob[j][0] = prob[j][1] = prob[j][2] = prob[j][3] = 0.0f;
-        if (s < S) {
-            desc[j] = solve_descriptor<VARIANT>(*m, lay, G, s, gx, gy);
-            evaluate_probs(a, base + s, desc[j], prob[j]);
-        }
-    }
-    solve_sync<WAVE>();                // the layout's bytes are read: the second buffer is free
+#define PROBLEM_LDS evaluate_lds
+#define PROBLEM_WORD float
+#define PROBLEM_AT_COPY(s) buf[s] = a.v_init ? a.v_init[base + s] : 0.0f   // V_0 goes into the first buffer
+#define PROBLEM_AT_CELL(j) prob[j][0] = prob[j][1] = prob[j][2] = prob[j][3] = 0.0f   // like a wall state: no probabilities
+#define PROBLEM_AT_DESC(j, s, d) evaluate_probs(a, base + s, d, prob[j])
+#include "lmaze_problem_frame.h"
+    float* const vbuf = buf;
 
     // tol as a bit pattern: deltas are non-negative floats or NaNs, which order as unsigned integers with every NaN on top
     const bool use_tol = a.tol > 0.0f;
@@ -208,43 +163,11 @@ __global__ __launch_bounds__(LMAZE_BLOCK, (CPL == 16 ? 2 : 1)) void evaluate_ker
     }
 }
 
-int describe_evaluate(int variant, const SolvePlan& p, char* text, int32_t len) {
-    if (!text || len < 1) return LMAZE_E_NULL;
-    snprintf(text, (size_t)len, "evaluate_kernel<%s, %s, %d> grid=%lld block=%d lds=%lld problems_per_workgroup=%d",
-             variant == LMAZE_VARIANT_V3 ? "v3" : "v0", p.wave ? "wave" : "workgroup", p.cells_per_lane, (long long)p.grid, LMAZE_BLOCK,
-             (long long)p.lds_bytes, p.problems_per_workgroup);
-    return 0;
-}
-
-template <int VARIANT, int CPL, bool WAVE>
-static hipError_t evaluate_launch(const EvaluateArgs& a, const SolvePlan& p, hipStream_t s) {
-    hipLaunchKernelGGL((evaluate_kernel<VARIANT, CPL, WAVE>), dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a);
-    return hipGetLastError();
-}
-
-template <int VARIANT>
-static hipError_t evaluate_dispatch(const EvaluateArgs& a, const SolvePlan& p, hipStream_t s) {
-    if (p.wave) {
-        switch (p.cells_per_lane) {
-            case 1: return evaluate_launch<VARIANT, 1, true>(a, p, s);
-            case 2: return evaluate_launch<VARIANT, 2, true>(a, p, s);
-            default: return evaluate_launch<VARIANT, 4, true>(a, p, s);
-        }
-    }
-    switch (p.cells_per_lane) {
-        case 2: return evaluate_launch<VARIANT, 2, false>(a, p, s);
-        case 4: return evaluate_launch<VARIANT, 4, false>(a, p, s);
-        case 8: return evaluate_launch<VARIANT, 8, false>(a, p, s);
-        default: return evaluate_launch<VARIANT, 16, false>(a, p, s);
-    }
-}
-
-// the plan is plan_solve's: the same two buffers of S floats per problem, the same model and vote words behind them
-hipError_t launch_evaluate(int variant, const EvaluateArgs& a, hipStream_t s) {
-    if (a.problems == 0) return hipSuccess;
-    const SolvePlan p = plan_solve(a.grid, a.problems);
-    if (!grid_ok(p.grid)) return hipErrorInvalidConfiguration;
-    return variant == LMAZE_VARIANT_V3 ? evaluate_dispatch<LMAZE_VARIANT_V3>(a, p, s) : evaluate_dispatch<LMAZE_VARIANT_V0>(a, p, s);
-}
+struct EvaluateFamily {
+    using Args = EvaluateArgs;
+    template <int VARIANT, int CPL, bool WAVE>
+    static constexpr auto kernel() { return &evaluate_kernel<VARIANT, CPL, WAVE>; }
+};
+hipError_t launch_evaluate(int variant, const EvaluateArgs& a, hipStream_t s) { return launch_problems<EvaluateFamily>(variant, a, s); }
 
 }  // namespace lmaze

@@ -68,9 +68,6 @@ __device__ __forceinline__ uint32_t score_first_word(uint32_t d, int s, int G) {
     return ((uint32_t)(s + score_step((int)act, G)) << 16) | 1u;
 }
 
-// "does any thread of the problem say so", and the sync between two phases: a ballot in the wave form; in the workgroup form a
-// word per wave, written before the barrier and read behind it by every thread, the two parities of solve_kernel's vote words
-// taken in turn (tick counts every vote of the kernel), so a fast wave's next vote stays off a slow wave's read
 template <bool WAVE>
 __device__ __forceinline__ bool score_vote(bool mine, uint32_t* vote, int& tick, int lane, int wave) {
     bool any = __ballot(mine) != 0ull;
@@ -88,68 +85,25 @@ __device__ __forceinline__ bool score_vote(bool mine, uint32_t* vote, int& tick,
 
 template <int VARIANT, int CPL, bool WAVE>
 __global__ __launch_bounds__(LMAZE_BLOCK) void score_kernel(const ScoreArgs a) {
-    constexpr int TPP = WAVE ? 64 : LMAZE_BLOCK;        // threads per problem
-    constexpr int PPW = LMAZE_BLOCK / TPP;              // problems per workgroup
-    constexpr int SP = CPL * TPP;                       // words of one buffer, >= S
     extern __shared__ __align__(16) unsigned char score_lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = WAVE ? lane : (int)threadIdx.x;
-    const int64_t p = (int64_t)blockIdx.x * PPW + (WAVE ? wave : 0);
-    // wave form: a whole wave without a problem, and no barrier in that form waits for it; workgroup form: never
-    if (p >= a.problems) return;
-    int* const buf = reinterpret_cast<int*>(score_lds) + (WAVE ? wave : 0) * 2 * SP;
-    uint32_t* const vote = reinterpret_cast<uint32_t*>(score_lds + (size_t)PPW * 2 * SP * sizeof(int) + SOLVE_MODEL_BYTES);   // workgroup form only
-    const int G = a.grid, S = G * G;
-    const int64_t base = p * S;
-    const bool table = a.policy || a.q;
-
-    // the layout's bytes borrow the second buffer until the descriptors are built
-    uint8_t* const lay = reinterpret_cast<uint8_t*>(buf + SP);
-    const uint8_t* const lay_g = a.layouts + (a.per_env ? base : 0);
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int s = t + j * TPP;
-        if (s < S) lay[s] = lay_g[s];
-    }
-    int gx = -1, gy = -1;
-    if (VARIANT == LMAZE_VARIANT_V3) {
-        const int2 g = a.goal[p];
-        gx = g.x;
-        gy = g.y;
-    }
-    // what transition_rule reads when it is asked for the model, in LDS as in solve_kernel (v3's rule selects between two of
-    // the rewards by address); every wave writes the same four words and reads them behind its own fence
-    StepArgs* const m = reinterpret_cast<StepArgs*>(score_lds + (size_t)PPW * 2 * SP * sizeof(int));
-    if (lane == 0) {
-        m->reward_wall = a.reward_wall;
-        m->reward_move = a.reward_move;
-        m->reward_goal = a.reward_goal;
-        m->step_limit = INT_MAX;
-    }
-    if (!WAVE && threadIdx.x < 4) vote[8 + threadIdx.x] = 0u;      // the four sums of the summary
-    solve_sync<WAVE>();
-    uint32_t desc[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int s = t + j * TPP;
-        uint32_t d = SOLVE_WALL_STATE;
-        if (s < S) {
-            d = solve_descriptor<VARIANT>(*m, lay, G, s, gx, gy);
-            uint32_t act = 0;
-            if (a.q) {
-                const float4 row = a.q[base + s];                 // one 128-bit load per state
-                const float r[4] = {row.x, row.y, row.z, row.w};
-                int first;
-                lmaze_q_first_max(r, &first);
-                act = (uint32_t)first;
-            } else if (a.policy) {
-                act = a.policy[base + s];
-            }
-            d |= act << SCORE_ACT_SHIFT;
-        }
-        desc[j] = d;
-    }
-    solve_sync<WAVE>();                // the layout's bytes are read: the second buffer is free
+#define PROBLEM_LDS score_lds
+#define PROBLEM_WORD int
+#define PROBLEM_LOCALS const bool table = a.policy || a.q
+#define PROBLEM_AT_COPY(s)
+#define PROBLEM_BEFORE_SYNC if (!WAVE && threadIdx.x < 4) vote[8 + threadIdx.x] = 0u   // the four sums of the summary
+#define PROBLEM_AT_DESC(j, s, d)                                                                     \
+    uint32_t act = 0;                                                                                \
+    if (a.q) {                                                                                       \
+        const float4 row = a.q[base + s]; /* one 128-bit load per state */                           \
+        const float r[4] = {row.x, row.y, row.z, row.w};                                             \
+        int first;                                                                                   \
+        lmaze_q_first_max(r, &first);                                                                \
+        act = (uint32_t)first;                                                                       \
+    } else if (a.policy) {                                                                           \
+        act = a.policy[base + s];                                                                    \
+    }                                                                                                \
+    d |= act << SCORE_ACT_SHIFT
+#include "lmaze_problem_frame.h"
 
     // ---- distances: d_0 into the first buffer, then sweeps
     int tick = 0, cur = 0;             // d_(k-1) is buf[cur]
@@ -265,43 +219,11 @@ __global__ __launch_bounds__(LMAZE_BLOCK) void score_kernel(const ScoreArgs a) {
     }
 }
 
-int describe_score(int variant, const SolvePlan& p, char* text, int32_t len) {
-    if (!text || len < 1) return LMAZE_E_NULL;
-    snprintf(text, (size_t)len, "score_kernel<%s, %s, %d> grid=%lld block=%d lds=%lld problems_per_workgroup=%d",
-             variant == LMAZE_VARIANT_V3 ? "v3" : "v0", p.wave ? "wave" : "workgroup", p.cells_per_lane, (long long)p.grid, LMAZE_BLOCK,
-             (long long)p.lds_bytes, p.problems_per_workgroup);
-    return 0;
-}
-
-template <int VARIANT, int CPL, bool WAVE>
-static hipError_t score_launch(const ScoreArgs& a, const SolvePlan& p, hipStream_t s) {
-    hipLaunchKernelGGL((score_kernel<VARIANT, CPL, WAVE>), dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a);
-    return hipGetLastError();
-}
-
-template <int VARIANT>
-static hipError_t score_dispatch(const ScoreArgs& a, const SolvePlan& p, hipStream_t s) {
-    if (p.wave) {
-        switch (p.cells_per_lane) {
-            case 1: return score_launch<VARIANT, 1, true>(a, p, s);
-            case 2: return score_launch<VARIANT, 2, true>(a, p, s);
-            default: return score_launch<VARIANT, 4, true>(a, p, s);
-        }
-    }
-    switch (p.cells_per_lane) {
-        case 2: return score_launch<VARIANT, 2, false>(a, p, s);
-        case 4: return score_launch<VARIANT, 4, false>(a, p, s);
-        case 8: return score_launch<VARIANT, 8, false>(a, p, s);
-        default: return score_launch<VARIANT, 16, false>(a, p, s);
-    }
-}
-
-// the plan is plan_solve's: the same two buffers of S words per problem, the same model and vote words behind them
-hipError_t launch_score(int variant, const ScoreArgs& a, hipStream_t s) {
-    if (a.problems == 0) return hipSuccess;
-    const SolvePlan p = plan_solve(a.grid, a.problems);
-    if (!grid_ok(p.grid)) return hipErrorInvalidConfiguration;
-    return variant == LMAZE_VARIANT_V3 ? score_dispatch<LMAZE_VARIANT_V3>(a, p, s) : score_dispatch<LMAZE_VARIANT_V0>(a, p, s);
-}
+struct ScoreFamily {
+    using Args = ScoreArgs;
+    template <int VARIANT, int CPL, bool WAVE>
+    static constexpr auto kernel() { return &score_kernel<VARIANT, CPL, WAVE>; }
+};
+hipError_t launch_score(int variant, const ScoreArgs& a, hipStream_t s) { return launch_problems<ScoreFamily>(variant, a, s); }
 
 }  // namespace lmaze

@@ -44,56 +44,13 @@ __device__ __forceinline__ float solve_cell(const SolveArgs& a, uint32_t d, int 
 
 template <int VARIANT, int CPL, bool WAVE>
 __global__ __launch_bounds__(LMAZE_BLOCK) void solve_kernel(const SolveArgs a) {
-    constexpr int TPP = WAVE ? 64 : LMAZE_BLOCK;        // threads per problem
-    constexpr int PPW = LMAZE_BLOCK / TPP;              // problems per workgroup
-    constexpr int SP = CPL * TPP;                       // floats of one V buffer, >= S
     extern __shared__ __align__(16) unsigned char solve_lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = WAVE ? lane : (int)threadIdx.x;
-    const int64_t p = (int64_t)blockIdx.x * PPW + (WAVE ? wave : 0);
-    // wave form: a whole wave without a problem, and no barrier in that form waits for it; workgroup form: never
-    if (p >= a.problems) return;
-    float* const vbuf = reinterpret_cast<float*>(solve_lds) + (WAVE ? wave : 0) * 2 * SP;
-    uint32_t* const vote = reinterpret_cast<uint32_t*>(solve_lds + (size_t)PPW * 2 * SP * sizeof(float) + SOLVE_MODEL_BYTES);   // workgroup form only
-    const int G = a.grid, S = G * G;
-    const int64_t base = p * S;
-
-    // the layout's bytes borrow the second V buffer until the descriptors are built; V_0 goes into the first
-    uint8_t* const lay = reinterpret_cast<uint8_t*>(vbuf + SP);
-    const uint8_t* const lay_g = a.layouts + (a.per_env ? base : 0);
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int s = t + j * TPP;
-        if (s < S) {
-            lay[s] = lay_g[s];
-            vbuf[s] = a.v_init ? a.v_init[base + s] : 0.0f;
-        }
-    }
-    int gx = -1, gy = -1;
-    if (VARIANT == LMAZE_VARIANT_V3) {
-        const int2 g = a.goal[p];
-        gx = g.x;
-        gy = g.y;
-    }
-    // What transition_rule reads when it is asked for the model: the three rewards, and a step_limit that the step count it is
-    // asked with (0) never meets -- INT_MAX: neither v0's "==" nor v3's ">"; the limit is not in the model.  The struct stands
-    // in LDS: v3's rule selects between two of its rewards by address, which would pin a private copy in scratch.  Every wave
-    // writes the same four words and reads them behind its own fence.
-    StepArgs* const m = reinterpret_cast<StepArgs*>(solve_lds + (size_t)PPW * 2 * SP * sizeof(float));
-    if (lane == 0) {
-        m->reward_wall = a.reward_wall;
-        m->reward_move = a.reward_move;
-        m->reward_goal = a.reward_goal;
-        m->step_limit = INT_MAX;
-    }
-    solve_sync<WAVE>();
-    uint32_t desc[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        const int s = t + j * TPP;
-        desc[j] = s < S ? solve_descriptor<VARIANT>(*m, lay, G, s, gx, gy) : SOLVE_WALL_STATE;
-    }
-    solve_sync<WAVE>();
+#define PROBLEM_LDS solve_lds
+#define PROBLEM_WORD float
+#define PROBLEM_AT_COPY(s) buf[s] = a.v_init ? a.v_init[base + s] : 0.0f   // V_0 goes into the first buffer
+#define PROBLEM_AT_DESC(j, s, d)
+#include "lmaze_problem_frame.h"
+    float* const vbuf = buf;
 
     int cur = 0, k = 0;                // V_(k-1) is vbuf[cur]
     uint32_t dbits;
@@ -172,42 +129,20 @@ SolvePlan plan_solve(int32_t G, int64_t problems) {
     return p;
 }
 
-int describe_solve(int variant, const SolvePlan& p, char* text, int32_t len) {
+// what lmaze_describe_solve, _score and _evaluate print: the kernel's name and the plan
+int describe_problems_plan(const char* kernel, int variant, const SolvePlan& p, char* text, int32_t len) {
     if (!text || len < 1) return LMAZE_E_NULL;
-    snprintf(text, (size_t)len, "solve_kernel<%s, %s, %d> grid=%lld block=%d lds=%lld problems_per_workgroup=%d",
+    snprintf(text, (size_t)len, "%s<%s, %s, %d> grid=%lld block=%d lds=%lld problems_per_workgroup=%d", kernel,
              variant == LMAZE_VARIANT_V3 ? "v3" : "v0", p.wave ? "wave" : "workgroup", p.cells_per_lane, (long long)p.grid, LMAZE_BLOCK,
              (long long)p.lds_bytes, p.problems_per_workgroup);
     return 0;
 }
 
-template <int VARIANT, int CPL, bool WAVE>
-static hipError_t solve_launch(const SolveArgs& a, const SolvePlan& p, hipStream_t s) {
-    hipLaunchKernelGGL((solve_kernel<VARIANT, CPL, WAVE>), dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a);
-    return hipGetLastError();
-}
-
-template <int VARIANT>
-static hipError_t solve_dispatch(const SolveArgs& a, const SolvePlan& p, hipStream_t s) {
-    if (p.wave) {
-        switch (p.cells_per_lane) {
-            case 1: return solve_launch<VARIANT, 1, true>(a, p, s);
-            case 2: return solve_launch<VARIANT, 2, true>(a, p, s);
-            default: return solve_launch<VARIANT, 4, true>(a, p, s);
-        }
-    }
-    switch (p.cells_per_lane) {
-        case 2: return solve_launch<VARIANT, 2, false>(a, p, s);
-        case 4: return solve_launch<VARIANT, 4, false>(a, p, s);
-        case 8: return solve_launch<VARIANT, 8, false>(a, p, s);
-        default: return solve_launch<VARIANT, 16, false>(a, p, s);
-    }
-}
-
-hipError_t launch_solve(int variant, const SolveArgs& a, hipStream_t s) {
-    if (a.problems == 0) return hipSuccess;
-    const SolvePlan p = plan_solve(a.grid, a.problems);
-    if (!grid_ok(p.grid)) return hipErrorInvalidConfiguration;
-    return variant == LMAZE_VARIANT_V3 ? solve_dispatch<LMAZE_VARIANT_V3>(a, p, s) : solve_dispatch<LMAZE_VARIANT_V0>(a, p, s);
-}
+struct SolveFamily {
+    using Args = SolveArgs;
+    template <int VARIANT, int CPL, bool WAVE>
+    static constexpr auto kernel() { return &solve_kernel<VARIANT, CPL, WAVE>; }
+};
+hipError_t launch_solve(int variant, const SolveArgs& a, hipStream_t s) { return launch_problems<SolveFamily>(variant, a, s); }
 
 }  // namespace lmaze

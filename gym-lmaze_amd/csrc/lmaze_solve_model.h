@@ -2,6 +2,7 @@
 // lmaze_score.hip, lmaze_evaluate.hip): sixteen bits per cell, taken from transition_rule<VARIANT> itself, and what the kernels
 // share of a problem's life in LDS -- the sync between two phases, where the rule's StepArgs and the vote words stand behind
 // the two buffers, and the one-step backup of the two that sweep values.  The model is stated once, here, by asking the rule.
+// The kernels' common opening is lmaze_problem_frame.h, included into each; their one launcher is at the end of this file.
 #ifndef LMAZE_SOLVE_MODEL_H_
 #define LMAZE_SOLVE_MODEL_H_
 
@@ -80,6 +81,40 @@ __device__ __forceinline__ void solve_sync() {
     } else {
         __syncthreads();
     }
+}
+
+// One launch site for the three families.  Family: its Args type and kernel<VARIANT, CPL, WAVE>(), the instantiation's address.
+template <class Family, int VARIANT, int CPL, bool WAVE>
+static hipError_t problem_launch(const typename Family::Args& a, const SolvePlan& p, hipStream_t s) {
+    hipLaunchKernelGGL((Family::template kernel<VARIANT, CPL, WAVE>()), dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a);
+    return hipGetLastError();
+}
+
+template <class Family, int VARIANT>
+static hipError_t problem_dispatch(const typename Family::Args& a, const SolvePlan& p, hipStream_t s) {
+    if (p.wave) {
+        switch (p.cells_per_lane) {
+            case 1: return problem_launch<Family, VARIANT, 1, true>(a, p, s);
+            case 2: return problem_launch<Family, VARIANT, 2, true>(a, p, s);
+            default: return problem_launch<Family, VARIANT, 4, true>(a, p, s);
+        }
+    }
+    switch (p.cells_per_lane) {
+        case 2: return problem_launch<Family, VARIANT, 2, false>(a, p, s);
+        case 4: return problem_launch<Family, VARIANT, 4, false>(a, p, s);
+        case 8: return problem_launch<Family, VARIANT, 8, false>(a, p, s);
+        default: return problem_launch<Family, VARIANT, 16, false>(a, p, s);
+    }
+}
+
+// the plan is plan_solve's for every family: the same two buffers of S words per problem, the same model and vote words
+template <class Family>
+static hipError_t launch_problems(int variant, const typename Family::Args& a, hipStream_t s) {
+    if (a.problems == 0) return hipSuccess;
+    const SolvePlan p = plan_solve(a.grid, a.problems);
+    if (!grid_ok(p.grid)) return hipErrorInvalidConfiguration;
+    return variant == LMAZE_VARIANT_V3 ? problem_dispatch<Family, LMAZE_VARIANT_V3>(a, p, s)
+                                       : problem_dispatch<Family, LMAZE_VARIANT_V0>(a, p, s);
 }
 
 }  // namespace lmaze

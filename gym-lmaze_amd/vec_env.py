@@ -566,6 +566,38 @@ class LmazeVecEnv(VecEnvBase):
             k = k + (g[:, 0] * G + g[:, 1]) * (G * G)
         return k.to(torch.int32).contiguous()
 
+    def _problem_key(self, key, env_ok=True):
+        """What solve(), score() and evaluate() ask of key before anything of their own."""
+        if key not in ("ball", "goal") + (("env",) if env_ok else ()):
+            raise ValueError("key must be 'ball', 'goal' or 'env'" if env_ok else "key must be 'ball' or 'goal'")
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+
+    def _problems(self, who, key, goal):
+        """The problems `who` ("solve", "score", "evaluate") runs for a judged key: (goals, P, single).  One problem on a shared
+        layout with key="ball" (single; v3 takes its goal from goal=), G*G with key="goal", one per goal cell in row-major order,
+        else N, v3 with each env's current goal.  goals is int32[P, 2] on v3 and None on v0."""
+        G, S, dev = self.grid, self.grid * self.grid, self.device
+        shared = self.layout_mode == _abi.LAYOUT_SHARED
+        if goal is not None and not (shared and key == "ball" and self._is_v3):
+            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
+        if not shared and key == "goal":
+            raise ValueError("key='goal' %ss one shared layout for every goal cell; per-env layouts %s each env's own goal" % (who, who))
+        single = shared and key == "ball"
+        P = 1 if single else (S if key == "goal" else self.num_envs)
+        goals = None
+        if self._is_v3:
+            if single:
+                if goal is None or len(goal) != 2:
+                    raise ValueError("%s(key='ball') on a shared-layout v3 env needs goal=(x, y)" % who)
+                goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
+            elif key == "goal":
+                cells = torch.arange(S, dtype=torch.int32, device=dev)
+                goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
+            else:
+                goals = self.goal_xy
+        return goals, P, single
+
     def solve(self, gamma=0.99, sweeps=4096, key="ball", rewards=None, v_init=None, goal=None):
         """Value iteration on this env's own maze(s), in ONE launch (solve_tables(), include/lmaze.h lmaze_solve): the
         tables rollout_policy(q=...), rollout_sample(logits=...) and gae(values=...) take.  It reads no planes, so the u8
@@ -577,34 +609,11 @@ class LmazeVecEnv(VecEnvBase):
         per-env layouts             N problems, env i's layout and (v3) its current goal_xy: q [N, G*G, 4], ... -- the tables
                                     rollout_policy(q=..., key="env") / rollout_sample(logits=..., key="env") run.
         v_init: float32 [problems, G*G].  Returns SolvedTables(q, v, policy, sweeps_run, delta)."""
-        if key not in _abi.KEY_MODES:
-            raise ValueError("key must be 'ball' or 'goal'")
-        if key == "goal" and not self._is_v3:
-            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
-        G, dev = self.grid, self.device
-        rewards = self.rewards if rewards is None else rewards
-        shared = self.layout_mode == _abi.LAYOUT_SHARED
-        if goal is not None and not (shared and key == "ball" and self._is_v3):
-            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
-        goals = None
-        if not shared:
-            if key == "goal":
-                raise ValueError("key='goal' solves one shared layout for every goal cell; per-env layouts solve each env's own goal")
-            goals = self.goal_xy if self._is_v3 else None
-        elif key == "goal":
-            cells = torch.arange(G * G, dtype=torch.int32, device=dev)
-            goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
-        elif self._is_v3:
-            if goal is None or len(goal) != 2:
-                raise ValueError("solve(key='ball') on a shared-layout v3 env needs goal=(x, y)")
-            goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
-        t = solve_tables(self.layout, self.variant, goals=goals, gamma=gamma, sweeps=sweeps, rewards=rewards, v_init=v_init,
-                         validate=False)
-        if not shared:
-            return t
-        if key == "goal":
-            return SolvedTables(t.q.reshape(G ** 4, 4), t.v.reshape(G ** 4), t.policy.reshape(G ** 4), t.sweeps_run, t.delta)
-        return SolvedTables(t.q[0], t.v[0], t.policy[0], t.sweeps_run[0], t.delta[0])
+        self._problem_key(key, env_ok=False)
+        goals, _, single = self._problems("solve", key, goal)
+        t = solve_tables(self.layout, self.variant, goals=goals, gamma=gamma, sweeps=sweeps,
+                         rewards=self.rewards if rewards is None else rewards, v_init=v_init, validate=False)
+        return _unbatch(t, key, single, ("sweeps_run", "delta"))
 
     def score(self, policy=None, q=None, key="ball", goal=None):
         """How good tables are on this env's own maze(s), in ONE launch (score_tables(), include/lmaze.h lmaze_score): from
@@ -620,32 +629,11 @@ class LmazeVecEnv(VecEnvBase):
         per-env layouts             env i's maze and (v3) its current goal, tables [N, G*G] / [N, G*G, 4]: what solve() returns
                                     and rollout_qlearn() updates; outputs as key="env".
         Returns ScoredTables(optimal, steps, summary)."""
-        if key not in ("ball", "goal", "env"):
-            raise ValueError("key must be 'ball', 'goal' or 'env'")
-        if key == "goal" and not self._is_v3:
-            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        self._problem_key(key)
         if policy is not None and q is not None:
             raise ValueError("give policy= or q=, not both")
-        G, N, dev = self.grid, self.num_envs, self.device
-        S = G * G
-        shared = self.layout_mode == _abi.LAYOUT_SHARED
-        if goal is not None and not (shared and key == "ball" and self._is_v3):
-            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
-        if not shared and key == "goal":
-            raise ValueError("key='goal' scores one shared layout for every goal cell; per-env layouts score each env's own goal")
-        single = shared and key == "ball"
-        P = 1 if single else (S if key == "goal" else N)
-        goals = None
-        if self._is_v3:
-            if single:
-                if goal is None or len(goal) != 2:
-                    raise ValueError("score(key='ball') on a shared-layout v3 env needs goal=(x, y)")
-                goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
-            elif key == "goal":
-                cells = torch.arange(S, dtype=torch.int32, device=dev)
-                goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
-            else:
-                goals = self.goal_xy
+        goals, P, single = self._problems("score", key, goal)
+        S, shared = self.grid * self.grid, self.layout_mode == _abi.LAYOUT_SHARED
         table = policy if policy is not None else q
         if table is not None:
             if not isinstance(table, torch.Tensor) or table.numel() != P * S * (1 if policy is not None else 4):
@@ -656,11 +644,7 @@ class LmazeVecEnv(VecEnvBase):
             raise ValueError("key='env' on a shared v0 layout scores N tables on one maze: without a table use key='ball'")
         t = score_tables(self.layout, policy=table if policy is not None else None, q=table if q is not None else None,
                          variant=self.variant, goals=goals, rewards=self.rewards, outputs=outputs, validate=False)
-        if single:
-            return ScoredTables(t.optimal[0], None if t.steps is None else t.steps[0], t.summary[0])
-        if key == "goal":
-            return ScoredTables(t.optimal.reshape(G ** 4), None if t.steps is None else t.steps.reshape(G ** 4), t.summary)
-        return t
+        return _unbatch(t, key, single, ("summary",))
 
     def evaluate(self, policy=None, q=None, epsilon=0.0, probs=None, logits=None, temperature=1.0, thresholds=None, key="ball",
                  goal=None, gamma=0.99, sweeps=4096, tol=0.0, v_init=None):
@@ -677,34 +661,13 @@ class LmazeVecEnv(VecEnvBase):
         per-env layouts             env i's maze and (v3) its current goal; tables and outputs as key="env".  v.reshape(-1)
                                     is the critic gae(values=, key_t=, key_tail=state_keys("env")) takes.
         v_init: float32 [problems, G*G].  Returns EvaluatedTables(q, v, sweeps_run, delta)."""
-        if key not in ("ball", "goal", "env"):
-            raise ValueError("key must be 'ball', 'goal' or 'env'")
-        if key == "goal" and not self._is_v3:
-            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        self._problem_key(key)
         tables = {"policy": policy, "q": q, "probs": probs, "logits": logits, "thresholds": thresholds}
         given = [n for n, t in tables.items() if t is not None]
         if len(given) != 1:
             raise ValueError("evaluate() wants exactly one of policy=, q=, probs=, logits= and thresholds=")
-        G, N, dev = self.grid, self.num_envs, self.device
-        S = G * G
-        shared = self.layout_mode == _abi.LAYOUT_SHARED
-        if goal is not None and not (shared and key == "ball" and self._is_v3):
-            raise ValueError("goal= belongs to key='ball' on a shared-layout v3 env")
-        if not shared and key == "goal":
-            raise ValueError("key='goal' evaluates one shared layout for every goal cell; per-env layouts evaluate each env's own goal")
-        single = shared and key == "ball"
-        P = 1 if single else (S if key == "goal" else N)
-        goals = None
-        if self._is_v3:
-            if single:
-                if goal is None or len(goal) != 2:
-                    raise ValueError("evaluate(key='ball') on a shared-layout v3 env needs goal=(x, y)")
-                goals = torch.tensor([[int(goal[0]), int(goal[1])]], dtype=torch.int32, device=dev)
-            elif key == "goal":
-                cells = torch.arange(S, dtype=torch.int32, device=dev)
-                goals = torch.stack([torch.div(cells, G, rounding_mode="floor"), cells % G], dim=1).to(torch.int32).contiguous()
-            else:
-                goals = self.goal_xy
+        goals, P, single = self._problems("evaluate", key, goal)
+        S = self.grid * self.grid
         name = given[0]
         table = tables[name]
         width = 1 if name == "policy" else 4
@@ -715,11 +678,7 @@ class LmazeVecEnv(VecEnvBase):
             v_init = v_init.reshape(P, S)
         t = evaluate_tables(self.layout, epsilon=epsilon, temperature=temperature, variant=self.variant, goals=goals, gamma=gamma,
                             sweeps=sweeps, tol=tol, rewards=self.rewards, v_init=v_init, validate=False, **tables)
-        if single:
-            return EvaluatedTables(t.q[0], t.v[0], t.sweeps_run[0], t.delta[0])
-        if key == "goal":
-            return EvaluatedTables(t.q.reshape(G ** 4, 4), t.v.reshape(G ** 4), t.sweeps_run, t.delta)
-        return t
+        return _unbatch(t, key, single, ("sweeps_run", "delta"))
 
     def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
         """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
@@ -907,6 +866,86 @@ def table_means(count, total, fill=0.0):
     return torch.where(seen, mean, torch.full_like(mean, float(fill)))
 
 
+def _unbatch(t, key, single, per_problem):
+    """What an env method returns of the *_tables() result t: its only problem without the batch dimension; for key="goal" the
+    per-state outputs [G*G, G*G, ...] as [G**4, ...], indexed by the key of state_keys("goal"), those named in per_problem as
+    they are; else t."""
+    if single:
+        return type(t)(*[None if x is None else x[0] for x in t])
+    if key == "goal":
+        return t._replace(**{n: x.reshape(-1, *x.shape[2:]) for n, x in t._asdict().items() if x is not None and n not in per_problem})
+    return t
+
+
+class _Mazes(collections.namedtuple("_Mazes", "spec v3 dev G S shared layouts")):
+    """The maze side of a solve_tables() / score_tables() / evaluate_tables() call, checked: the variant's spec, whether it is
+    v3, layouts' device, the grid side, G*G, whether one [G, G] layout serves every problem, and the contiguous layouts."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, layouts, variant, validate):
+        if variant not in VARIANTS:
+            raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
+        v3 = variant == "v3"
+        if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
+                and layouts.shape[-1] == layouts.shape[-2]):
+            raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
+        G = int(layouts.shape[-1])
+        if not (3 <= G <= _abi.MAX_GRID):
+            raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
+        layouts = layouts.contiguous()
+        if validate:
+            _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
+        return cls(VARIANTS[variant], v3, layouts.device, G, G * G, layouts.dim() == 2, layouts)
+
+    def problems(self, goals, table=None):
+        """P, from the checked goals (v3) or the layouts; one shared v0 layout leaves it to the table: its length, or 1."""
+        if self.v3:
+            if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == self.dev and goals.dim() == 2
+                    and goals.shape[1] == 2 and goals.is_contiguous() and (self.shared or goals.shape[0] == self.layouts.shape[0])):
+                raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
+            return int(goals.shape[0])
+        if goals is not None:
+            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
+        if not self.shared:
+            return int(self.layouts.shape[0])
+        return 1 if table is None else int(table.shape[0])
+
+    def rewards(self, rewards):
+        rewards = tuple(float(r) for r in (rewards if rewards is not None else self.spec["rewards"]))
+        if len(rewards) != 3:
+            raise ValueError("rewards must be (wall, move, goal)")
+        return rewards
+
+    def launch(self, entry, rewards, goals, P, own, out):
+        """lmaze_solve / _score / _evaluate on layouts' device and current stream: the maze side, the entry's `own` arguments,
+        the outputs in their order.  P == 0 launches nothing."""
+        if P > 0:
+            params = _abi.make_params(self.spec["id"], self.G, _abi.LAYOUT_SHARED if self.shared else _abi.LAYOUT_PER_ENV,
+                                      self.spec["step_limit"], *rewards)
+            with torch.cuda.device(self.dev):
+                rc = getattr(_abi.lib, entry)(C.byref(params), self.layouts.data_ptr(), goals.data_ptr() if self.v3 else None, P, *own,
+                                              *[None if o is None else o.data_ptr() for o in out.values()],
+                                              torch.cuda.current_stream(self.dev).cuda_stream)
+            _abi.check(entry, rc)
+
+
+def _check_sweeps(sweeps):
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or not 1 <= sweeps < 2 ** 31:
+        raise ValueError("sweeps must be an int >= 1")
+
+
+def _check_v_init(v_init, dev, P, S):
+    if v_init is not None and not (isinstance(v_init, torch.Tensor) and v_init.dtype == torch.float32 and v_init.device == dev
+                                   and v_init.is_contiguous() and tuple(v_init.shape) == (P, S)):
+        raise ValueError("v_init must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
+
+
+def _alloc_outputs(shapes, outputs, dev):
+    """{name: zeros or None} in shapes' order, from name -> (shape, dtype) and the names asked for."""
+    return {k: (torch.zeros(shape, dtype=dtype, device=dev) if k in outputs else None) for k, (shape, dtype) in shapes.items()}
+
+
 class SolvedTables(collections.namedtuple("SolvedTables", "q v policy sweeps_run delta")):
     """What solve_tables() returns: q float32[P, S, 4], v float32[P, S], policy uint8[P, S], sweeps_run int32[P], delta
     float32[P]; an output that was not asked for is None."""
@@ -933,54 +972,18 @@ def solve_tables(layouts, variant="v0", goals=None, gamma=0.99, sweeps=4096, rew
     the step refuses while repeating the previous reward) have no reward of their own and are excluded, q = -inf; a state on a
     'W' cell has q = v = 0.  float32 with every operation rounded on its own, so a float32 numpy loop reproduces every bit.
     Returns SolvedTables(q, v, policy, sweeps_run, delta)."""
-    if variant not in VARIANTS:
-        raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
-    spec = VARIANTS[variant]
-    v3 = variant == "v3"
-    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
-            and layouts.shape[-1] == layouts.shape[-2]):
-        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
-    dev = layouts.device
-    G = int(layouts.shape[-1])
-    if not (3 <= G <= _abi.MAX_GRID):
-        raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
-    layouts = layouts.contiguous()
-    if validate:
-        _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
-    shared = layouts.dim() == 2
-    if v3:
-        if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == dev and goals.dim() == 2
-                and goals.shape[1] == 2 and goals.is_contiguous() and (shared or goals.shape[0] == layouts.shape[0])):
-            raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
-        P = int(goals.shape[0])
-    else:
-        if goals is not None:
-            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
-        P = 1 if shared else int(layouts.shape[0])
-    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or not 1 <= sweeps < 2 ** 31:
-        raise ValueError("sweeps must be an int >= 1")
-    rewards = tuple(float(r) for r in (rewards if rewards is not None else spec["rewards"]))
-    if len(rewards) != 3:
-        raise ValueError("rewards must be (wall, move, goal)")
+    m = _Mazes.of(layouts, variant, validate)
+    P, S = m.problems(goals), m.S
+    _check_sweeps(sweeps)
+    rewards = m.rewards(rewards)
     outputs = tuple(outputs)
     if not set(outputs) <= set(SOLVE_OUTPUTS) or not set(outputs) & {"q", "v", "policy"}:
         raise ValueError("outputs must name some of %s, at least one of q, v, policy" % (SOLVE_OUTPUTS,))
-    S = G * G
-    if v_init is not None and not (isinstance(v_init, torch.Tensor) and v_init.dtype == torch.float32 and v_init.device == dev
-                                   and v_init.is_contiguous() and tuple(v_init.shape) == (P, S)):
-        raise ValueError("v_init must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
-    shapes = {"q": ((P, S, 4), torch.float32), "v": ((P, S), torch.float32), "policy": ((P, S), torch.uint8),
-              "sweeps_run": ((P,), torch.int32), "delta": ((P,), torch.float32)}
-    out = {k: (torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) if k in outputs else None) for k in SOLVE_OUTPUTS}
-    if P > 0:
-        params = _abi.make_params(spec["id"], G, _abi.LAYOUT_SHARED if shared else _abi.LAYOUT_PER_ENV, spec["step_limit"], *rewards)
-        with torch.cuda.device(dev):
-            rc = _abi.lib.lmaze_solve(C.byref(params), layouts.data_ptr(), goals.data_ptr() if v3 else None, P, float(gamma),
-                                      int(sweeps), None if v_init is None else v_init.data_ptr(),
-                                      *[None if out[k] is None else out[k].data_ptr() for k in SOLVE_OUTPUTS],
-                                      torch.cuda.current_stream(dev).cuda_stream)
-        _abi.check("lmaze_solve", rc)
-    return SolvedTables(*[out[k] for k in SOLVE_OUTPUTS])
+    _check_v_init(v_init, m.dev, P, S)
+    out = _alloc_outputs({"q": ((P, S, 4), torch.float32), "v": ((P, S), torch.float32), "policy": ((P, S), torch.uint8),
+                          "sweeps_run": ((P,), torch.int32), "delta": ((P,), torch.float32)}, outputs, m.dev)
+    m.launch("lmaze_solve", rewards, goals, P, (float(gamma), int(sweeps), None if v_init is None else v_init.data_ptr()), out)
+    return SolvedTables(**out)
 
 
 class ScoredTables(collections.namedtuple("ScoredTables", "optimal steps summary")):
@@ -1007,22 +1010,8 @@ def score_tables(layouts, policy=None, q=None, variant="v0", goals=None, rewards
              and the steps the arriving walks take beyond the fewest).
     validate=False skips the layouts' check and the device-side check that no policy byte is above 3.
     Returns ScoredTables(optimal, steps, summary)."""
-    if variant not in VARIANTS:
-        raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
-    spec = VARIANTS[variant]
-    v3 = variant == "v3"
-    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
-            and layouts.shape[-1] == layouts.shape[-2]):
-        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
-    dev = layouts.device
-    G = int(layouts.shape[-1])
-    if not (3 <= G <= _abi.MAX_GRID):
-        raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
-    S = G * G
-    layouts = layouts.contiguous()
-    if validate:
-        _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
-    shared = layouts.dim() == 2
+    m = _Mazes.of(layouts, variant, validate)
+    S, dev = m.S, m.dev
     if policy is not None and q is not None:
         raise ValueError("give policy= or q=, not both")
     table = policy if policy is not None else q
@@ -1032,20 +1021,10 @@ def score_tables(layouts, policy=None, q=None, variant="v0", goals=None, rewards
                 and table.is_contiguous() and tuple(table.shape[1:]) == ((S,) if policy is not None else (S, 4))):
             raise ValueError("policy must be a contiguous uint8[P, %d] and q a contiguous float32[P, %d, 4] tensor on layouts' device"
                              % (S, S))
-    if v3:
-        if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == dev and goals.dim() == 2
-                and goals.shape[1] == 2 and goals.is_contiguous() and (shared or goals.shape[0] == layouts.shape[0])):
-            raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
-        P = int(goals.shape[0])
-    else:
-        if goals is not None:
-            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
-        P = int(layouts.shape[0]) if not shared else (1 if table is None else int(table.shape[0]))
+    P = m.problems(goals, table)
     if table is not None and int(table.shape[0]) != P:
         raise ValueError("the table has %d problems, the mazes %d" % (int(table.shape[0]), P))
-    rewards = tuple(float(r) for r in (rewards if rewards is not None else spec["rewards"]))
-    if len(rewards) != 3:
-        raise ValueError("rewards must be (wall, move, goal)")
+    rewards = m.rewards(rewards)
     outputs = tuple(outputs)
     if not outputs or not set(outputs) <= set(SCORE_OUTPUTS):
         raise ValueError("outputs must name some of %s" % (SCORE_OUTPUTS,))
@@ -1053,17 +1032,11 @@ def score_tables(layouts, policy=None, q=None, variant="v0", goals=None, rewards
         raise ValueError("'steps' needs a table: policy= or q=")
     if validate and policy is not None and bool((policy > 3).any()):
         raise ValueError("policy holds a byte above 3: the actions are 0..3")
-    shapes = {"optimal": (P, S), "steps": (P, S), "summary": (P, 4)}
-    out = {k: (torch.zeros(shapes[k], dtype=torch.int32, device=dev) if k in outputs else None) for k in SCORE_OUTPUTS}
-    if P > 0:
-        params = _abi.make_params(spec["id"], G, _abi.LAYOUT_SHARED if shared else _abi.LAYOUT_PER_ENV, spec["step_limit"], *rewards)
-        with torch.cuda.device(dev):
-            rc = _abi.lib.lmaze_score(C.byref(params), layouts.data_ptr(), goals.data_ptr() if v3 else None, P,
-                                      None if policy is None else policy.data_ptr(), None if q is None else q.data_ptr(),
-                                      *[None if out[k] is None else out[k].data_ptr() for k in SCORE_OUTPUTS],
-                                      torch.cuda.current_stream(dev).cuda_stream)
-        _abi.check("lmaze_score", rc)
-    return ScoredTables(*[out[k] for k in SCORE_OUTPUTS])
+    out = _alloc_outputs({"optimal": ((P, S), torch.int32), "steps": ((P, S), torch.int32), "summary": ((P, 4), torch.int32)},
+                         outputs, dev)
+    m.launch("lmaze_score", rewards, goals, P,
+             (None if policy is None else policy.data_ptr(), None if q is None else q.data_ptr()), out)
+    return ScoredTables(**out)
 
 
 class EvaluatedTables(collections.namedtuple("EvaluatedTables", "q v sweeps_run delta")):
@@ -1099,22 +1072,8 @@ def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logit
     pairs (a state with no usable mass has v = 0); float32 Jacobi with every operation rounded on its own, so a float32 numpy
     loop reproduces every bit.  validate=False skips the layouts' check.
     Returns EvaluatedTables(q, v, sweeps_run, delta)."""
-    if variant not in VARIANTS:
-        raise ValueError("unknown variant %r (have %s)" % (variant, sorted(VARIANTS)))
-    spec = VARIANTS[variant]
-    v3 = variant == "v3"
-    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.is_cuda and layouts.dim() in (2, 3)
-            and layouts.shape[-1] == layouts.shape[-2]):
-        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G] on a GPU")
-    dev = layouts.device
-    G = int(layouts.shape[-1])
-    if not (3 <= G <= _abi.MAX_GRID):
-        raise ValueError("grid side must be in [3, %d]" % _abi.MAX_GRID)
-    S = G * G
-    layouts = layouts.contiguous()
-    if validate:
-        _validate_on_device(layouts.reshape(-1, G, G), need_goal=not v3)
-    shared = layouts.dim() == 2
+    m = _Mazes.of(layouts, variant, validate)
+    S, dev = m.S, m.dev
     given = [n for n, t in (("policy", policy), ("q", q), ("probs", probs), ("logits", logits), ("thresholds", thresholds))
              if t is not None]
     if len(given) != 1:
@@ -1146,42 +1105,22 @@ def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logit
     if not (ok and table.device == dev and table.is_contiguous()):
         raise ValueError("policy must be a contiguous uint8[P, %d], q a contiguous float32[P, %d, 4] and thresholds a contiguous, "
                          "16-byte aligned uint32[P, %d, 4] tensor on layouts' device" % (S, S, S))
-    if v3:
-        if not (isinstance(goals, torch.Tensor) and goals.dtype == torch.int32 and goals.device == dev and goals.dim() == 2
-                and goals.shape[1] == 2 and goals.is_contiguous() and (shared or goals.shape[0] == layouts.shape[0])):
-            raise ValueError("goals must be a contiguous int32 tensor [P,2] on layouts' device (v3)")
-        P = int(goals.shape[0])
-    else:
-        if goals is not None:
-            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
-        P = int(layouts.shape[0]) if not shared else int(table.shape[0])
+    P = m.problems(goals, table)
     if int(table.shape[0]) != P:
         raise ValueError("the table has %d problems, the mazes %d" % (int(table.shape[0]), P))
-    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or not 1 <= sweeps < 2 ** 31:
-        raise ValueError("sweeps must be an int >= 1")
-    rewards = tuple(float(r) for r in (rewards if rewards is not None else spec["rewards"]))
-    if len(rewards) != 3:
-        raise ValueError("rewards must be (wall, move, goal)")
+    _check_sweeps(sweeps)
+    rewards = m.rewards(rewards)
     outputs = tuple(outputs)
     if not set(outputs) <= set(EVALUATE_OUTPUTS) or not set(outputs) & {"q", "v"}:
         raise ValueError("outputs must name some of %s, at least one of q, v" % (EVALUATE_OUTPUTS,))
-    if v_init is not None and not (isinstance(v_init, torch.Tensor) and v_init.dtype == torch.float32 and v_init.device == dev
-                                   and v_init.is_contiguous() and tuple(v_init.shape) == (P, S)):
-        raise ValueError("v_init must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
-    shapes = {"q": ((P, S, 4), torch.float32), "v": ((P, S), torch.float32), "sweeps_run": ((P,), torch.int32),
-              "delta": ((P,), torch.float32)}
-    out = {k: (torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) if k in outputs else None) for k in EVALUATE_OUTPUTS}
-    if P > 0:
-        params = _abi.make_params(spec["id"], G, _abi.LAYOUT_SHARED if shared else _abi.LAYOUT_PER_ENV, spec["step_limit"], *rewards)
-        with torch.cuda.device(dev):
-            rc = _abi.lib.lmaze_evaluate(C.byref(params), layouts.data_ptr(), goals.data_ptr() if v3 else None, P,
-                                         table.data_ptr() if kind == "policy" else None, table.data_ptr() if kind == "q" else None,
-                                         eps, table.data_ptr() if kind not in ("policy", "q") else None, float(gamma), int(sweeps),
-                                         float(tol), None if v_init is None else v_init.data_ptr(),
-                                         *[None if out[k] is None else out[k].data_ptr() for k in EVALUATE_OUTPUTS],
-                                         torch.cuda.current_stream(dev).cuda_stream)
-        _abi.check("lmaze_evaluate", rc)
-    return EvaluatedTables(*[out[k] for k in EVALUATE_OUTPUTS])
+    _check_v_init(v_init, dev, P, S)
+    out = _alloc_outputs({"q": ((P, S, 4), torch.float32), "v": ((P, S), torch.float32), "sweeps_run": ((P,), torch.int32),
+                          "delta": ((P,), torch.float32)}, outputs, dev)
+    m.launch("lmaze_evaluate", rewards, goals, P,
+             (table.data_ptr() if kind == "policy" else None, table.data_ptr() if kind == "q" else None, eps,
+              table.data_ptr() if kind not in ("policy", "q") else None, float(gamma), int(sweeps), float(tol),
+              None if v_init is None else v_init.data_ptr()), out)
+    return EvaluatedTables(**out)
 
 
 def _validate_on_device(lay, need_goal=True):

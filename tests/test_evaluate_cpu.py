@@ -288,3 +288,6 @@ def test_evaluate_kernels_use_no_scratch():
     for name, v in mine.items():
         assert v.get("ScratchSize", 0) == 0, (name, v)
         print(name, v)
+        wave = "Lb1E" in name                                       # and no form above what it had before the shared frame
+        cpl = int(re.search(r"ILi\dELi(\d+)E", name).group(1))
+        assert v["VGPRs"] <= ({1: 32, 2: 40, 4: 65} if wave else {2: 39, 4: 64, 8: 117, 16: 226})[cpl], (name, v)

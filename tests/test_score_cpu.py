@@ -237,4 +237,6 @@ def test_score_kernels_use_no_scratch():
         wave = "Lb1E" in name
         cpl = int(re.search(r"ILi\dELi(\d+)E", name).group(1))
         assert v["VGPRs"] <= (40 if wave else {2: 32, 4: 40, 8: 80, 16: 112}[cpl]), (name, v)
+        # and no form above what it had before the shared frame
+        assert v["VGPRs"] <= ({1: 29, 2: 35, 4: 39} if wave else {2: 26, 4: 33, 8: 75, 16: 111})[cpl], (name, v)
         assert v["Occupancy"] >= (8 if wave or cpl == 2 else {4: 7, 8: 6, 16: 4}[cpl]), (name, v)

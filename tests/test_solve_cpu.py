@@ -239,3 +239,6 @@ def test_solve_kernels_use_no_scratch():
     for name, v in mine.items():
         assert v.get("ScratchSize", 0) == 0, (name, v)
         assert v["VGPRs"] <= 256, (name, v)                         # two waves per SIMD at the least: 4 workgroups per CU
+        wave = "Lb1E" in name                                       # and no form above what it had before the shared frame
+        cpl = int(re.search(r"ILi\dELi(\d+)E", name).group(1))
+        assert v["VGPRs"] <= ({1: 30, 2: 33, 4: 49} if wave else {2: 27, 4: 46, 8: 98, 16: 159})[cpl], (name, v)
