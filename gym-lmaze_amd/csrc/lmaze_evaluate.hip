@@ -22,17 +22,21 @@
 
 namespace lmaze {
 
-// The four probabilities of a cell.  w_a in units of 2^-34: the epsilon-greedy mixture of lmaze_rollout_policy or the threshold
-// differences of lmaze_rollout_sample; w'_a = 0 on an excluded pair; p_a = fl(fl(w'_a) / fl(W)), W the integer sum.  A wall
-// state has no probabilities, and W == 0 leaves none either.
+// The four probabilities of a cell.  w_a in units of 2^-34: the epsilon-greedy mixture of lmaze_rollout_policy or the differences
+// of lmaze_rollout_sample's three thresholds taken in ascending order; w'_a = 0 on an excluded pair; p_a = fl(fl(w'_a) / fl(W)),
+// W the integer sum.  A wall state has no probabilities, and W == 0 leaves none either.
 __device__ __forceinline__ void evaluate_probs(const EvaluateArgs& a, int64_t row, uint32_t d, float (&p)[4]) {
     uint64_t w[4];
     if (a.thresholds) {
         const uint4 c = a.thresholds[row];                        // one 128-bit load per state; word 3 is not looked at
-        w[0] = 4ull * c.x;
-        w[1] = 4ull * (uint32_t)(c.y - c.x);                      // mod 2^32, as the sampler's compares give them
-        w[2] = 4ull * (uint32_t)(c.z - c.y);
-        w[3] = 4ull * (0x100000000ull - c.z);
+        // The sampler counts the words that r reaches, (r >= c0) + (r >= c1) + (r >= c2), so the action law of a row is that
+        // of its three words in ascending order, whatever order they are stored in: a sort of three, once per state.
+        const uint32_t lo = min(c.x, c.y), hi = max(c.x, c.y);
+        const uint32_t s0 = min(lo, c.z), s2 = max(hi, c.z), s1 = max(lo, min(hi, c.z));
+        w[0] = 4ull * s0;
+        w[1] = 4ull * (s1 - s0);
+        w[2] = 4ull * (s2 - s1);
+        w[3] = 4ull * (0x100000000ull - s2);
     } else {
         uint32_t greedy;
         if (a.q) {

@@ -1061,8 +1061,11 @@ def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logit
     logits      float [P, G*G, 4]: sampling_thresholds(softmax(logits.double() / temperature)), temperature > 0;
     thresholds  the table itself, uint32 (or int32, the same bits) [P, G*G, 4], contiguous and 16-byte aligned.
     What is evaluated is exactly the table that would be run: epsilon converts as rollout_policy() converts it, the
-    categorical inputs go through rollout_sample()'s conversion (a row of probability 1 keeps 2**-32 on action 3); epsilon
-    != 0 with a categorical input is refused.  With a [G, G] layout and v0, P is the table's length.
+    categorical inputs go through rollout_sample()'s conversion (a row of probability 1 keeps 2**-32 on action 3) and a
+    thresholds row that is not monotone is weighed by its three words in ascending order, the law the sampler's compares
+    give it; epsilon != 0 with a categorical input is refused.  q= is read by the learner's rule (rollout_qlearn()'s first
+    maximum, also on a row with a NaN); rollout_policy(q=) reads a row with a NaN as "no move", so policy=greedy_table(q)
+    evaluates exactly what it runs.  With a [G, G] layout and v0, P is the table's length.
     variant, goals, rewards, gamma, v_init   as solve_tables(): the model is the same.
     sweeps, tol   a problem stops at the first Jacobi sweep that leaves every value's bits unchanged (that sweep counts), at
              the first whose delta is <= tol when tol > 0, or after `sweeps`.

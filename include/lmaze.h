@@ -712,7 +712,10 @@ int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text
  * The table of problem p.  Exactly one of two inputs gives the action a(s) of every state:
  *   policy  uint8[problems, S], 4-byte aligned: a(s) itself
  *   q       float[problems, S, 4], 16-byte aligned: a(s) is the first maximum by a strict '>' from action 0 on, the rule of
- *           lmaze_solve and lmaze_env_rollout_qlearn; a NaN never wins, a NaN in word 0 keeps action 0
+ *           lmaze_solve and lmaze_env_rollout_qlearn; a NaN never wins, a NaN in word 0 keeps action 0.  This is
+ *           lmaze_q_first_max, the learner's rule, for a row that holds a NaN too; the host wrapper rollout_policy(q=) reads
+ *           such a row as "no move" (greedy_table() gives it id 4) and agrees on every other row, so policy =
+ *           greedy_table(q) scores exactly the walk rollout_policy(q=) takes
  * Both may be NULL when only distances are asked for.
  * Outputs, each nullable and 4-byte aligned, at least one required; all integers, so the result depends on no schedule:
  *   optimal  int32[problems, S]  the fewest steps after which an env started on s can have done set by the model: 1 if s owns
@@ -720,7 +723,10 @@ int lmaze_describe_solve(const LmazeParams* params, int64_t problems, char* text
  *            -1 where no terminal pair can be reached, and on walls
  *   steps    int32[problems, S]  the walk that takes a(s) in every state: the number of steps at which done is first set, -1 if
  *            that never happens -- the walk enters a cycle (a wall bump is a cycle of one), takes an excluded pair, meets a
- *            policy byte above 3, or starts on a wall
+ *            policy byte above 3, or starts on a wall.  This is the walk lmaze_rollout_policy takes at epsilon 0, with one
+ *            exception: the step reads a byte above 3 as a move of (0, 0), and on the one cell where such a step pays the goal
+ *            -- v0's 'X', on which only a loaded state stands, and v3's goal cell, which a walk can cross without being paid --
+ *            the rollout sets done where steps says -1.  The (cell, no move) pair is not one of the model's four
  *   summary  int32[problems, 4]  reachable = #{s : optimal >= 1}, arrived = #{s : steps >= 1}, shortest = #{s : steps ==
  *            optimal >= 1}, excess = the sum over arrived s of (steps - optimal); without a table the last three are 0
  * An arriving walk visits distinct non-wall states, so steps <= (G - 2)^2 < S.
@@ -765,16 +771,22 @@ int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text
  *               action r.y >> 30): w_a = e + (a == policy[s] ? 4 * (2^32 - e) : 0), e = epsilon_u32.  A byte above 3 gives its
  *               greedy share to no action
  *   q           float[problems, S, 4], 16-byte aligned, with epsilon_u32: the same, the greedy action being the first maximum
- *               by a strict '>' from action 0 on -- lmaze_score's rule: a NaN never wins, a NaN in word 0 keeps action 0
- *   thresholds  uint32[problems, S, 4], 16-byte aligned: lmaze_rollout_sample's rule, w_a = 4 * (c_a - c_(a-1)) with
- *               c_(-1) = 0 and c_3 = 2^32; word 3 is ignored, epsilon_u32 is not read.  The two inner differences are taken
- *               mod 2^32, so a non-monotone row, which the sampler does not refuse either, still has weights: they sum to
- *               2^34, 2^35 or 3 * 2^34.  A row of probability 1 is stored as 1 - 2^-32 (see lmaze_rollout_sample): its action
- *               gets 4 * (2^32 - 1) and action 3 gets 4
+ *               by a strict '>' from action 0 on -- lmaze_score's rule: a NaN never wins, a NaN in word 0 keeps action 0.
+ *               That is lmaze_q_first_max, the learner's rule (lmaze_env_rollout_qlearn), for a row that holds a NaN too.
+ *               The host wrapper rollout_policy(q=) reduces q by greedy_table() instead, which agrees on every row without a
+ *               NaN and reads a row with one as id 4, "no move": to evaluate exactly the table rollout_policy(q=) runs, pass
+ *               policy = greedy_table(q) (its id 4 then gives its greedy share to no action, as any byte above 3)
+ *   thresholds  uint32[problems, S, 4], 16-byte aligned: lmaze_rollout_sample's rule, w_a = 4 * (s_a - s_(a-1)) with
+ *               s_0 <= s_1 <= s_2 the words c_0, c_1, c_2 of the row in ascending order, s_(-1) = 0 and s_3 = 2^32; word 3 is
+ *               ignored, epsilon_u32 is not read.  The sampler's action (r >= c0) + (r >= c1) + (r >= c2) counts the words r
+ *               reaches and so does not depend on their order: w_a / 4 is the number of the 2^32 values of r that give
+ *               action a, on a non-monotone row, which the sampler does not refuse either, as on a monotone one.  Every row
+ *               sums to 2^34.  A row of probability 1 is stored as 1 - 2^-32 (see lmaze_rollout_sample): its action gets
+ *               4 * (2^32 - 1) and action 3 gets 4
  * Probabilities, computed once per state before the first sweep:
  *   w'_a = w_a if the pair (s, a) is usable, 0 if the model excludes it (v0's sticky pairs);  W = w'_0 + w'_1 + w'_2 + w'_3,
  *   an integer;  p_a = fl(fl(w'_a) / fl(W)): both integers rounded to float32 (ties to even), one correctly rounded division.
- *   Where nothing is excluded and the row is monotone, W = 2^34 and the division is an exact scaling.  W == 0 -- every pair
+ *   Where nothing is excluded, W = 2^34 and the division is an exact scaling.  W == 0 -- every pair
  *   that carries weight is excluded, or a byte above 3 at epsilon_u32 == 0 -- gives p_a = 0 for every action and v = 0.
  * So where lmaze_solve excludes a sticky pair from the maximum, the mass a policy puts on excluded pairs is RENORMALISED over the
  * usable ones: the step repeats the previous reward there and leaves the ball in place, which has no value of its own; the

@@ -37,6 +37,16 @@ def env_keys(ball_xy, G, first=0):
     return ((np.arange(len(b), dtype=np.int64) + first) * G * G + b[:, 0] * G + b[:, 1]).astype(np.int32)
 
 
+def epsilon_greedy(entry, eps32, rx, ry):
+    """The epsilon-greedy decision alone, a pure function of (table entry, eps32, r.x, r.y) as arrays or scalars: explore when
+    r.x < eps32 and then take r.y >> 30, else the entry.  Returns (action int32, explore bool).  policy_law.py counts the
+    draws of every action through this function; greedy_action() below replays the GPU with it."""
+    entry = np.asarray(entry).astype(np.int32)
+    rx, ry = np.asarray(rx, dtype=np.uint64), np.asarray(ry, dtype=np.uint64)
+    explore = rx < np.uint64(eps32)
+    return np.where(explore, (ry >> np.uint64(30)).astype(np.int32), entry).astype(np.int32), explore
+
+
 def greedy_action(table, eps32, seed, epoch0):
     """action(key, t, env_global) of rollout_policy(key="env"): the flat table's entry, or, exploring, r.y >> 30.
     .explored counts the exploring env-steps."""
@@ -46,9 +56,8 @@ def greedy_action(table, eps32, seed, epoch0):
         act = flat[key_ref].astype(np.int32)
         if eps32:
             r = explore_draw(seed, epoch0 + t, eg)
-            explore = r[0] < np.uint64(eps32)
+            act, explore = epsilon_greedy(act, eps32, r[0], r[1])
             action.explored += int(explore.sum())
-            act = np.where(explore, (r[1] >> np.uint64(30)).astype(np.int32), act).astype(np.int32)
         return act
     action.explored = 0
     return action

@@ -10,7 +10,7 @@ import solve_ref as SR
 
 Evaluated = collections.namedtuple("Evaluated", "q v sweeps_run delta")
 TWO32 = 1 << 32
-FULL = 1 << 34                      # the weights of a state sum to this where nothing is excluded (monotone thresholds)
+FULL = 1 << 34                      # the weights of a state sum to this where nothing is excluded
 
 
 def first_max(q):
@@ -31,7 +31,8 @@ def weights(policy=None, q=None, epsilon_u32=0, thresholds=None):
     assert sum(x is not None for x in (policy, q, thresholds)) == 1
     if thresholds is not None:
         c = np.asarray(thresholds).astype(np.int64) & (TWO32 - 1)            # uint32 or int32 bits
-        d = np.stack([c[..., 0], (c[..., 1] - c[..., 0]) % TWO32, (c[..., 2] - c[..., 1]) % TWO32, TWO32 - c[..., 2]], -1)
+        s = np.sort(c[..., :3], axis=-1)                                     # the sampler counts the words r reaches
+        d = np.stack([s[..., 0], s[..., 1] - s[..., 0], s[..., 2] - s[..., 1], TWO32 - s[..., 2]], -1)
         return 4 * d
     greedy = first_max(q) if q is not None else np.asarray(policy, np.uint8)
     e = int(epsilon_u32)

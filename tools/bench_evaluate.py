@@ -34,8 +34,8 @@ def torch_probs(model, policy=None, epsilon_u32=0, thresholds=None):
     """float32[P, S, 4]: the header's weight rule in int64, the weight on an excluded pair dropped, one division"""
     _, _, _, excluded, wall = model
     if thresholds is not None:
-        c = thresholds.to(torch.int64) & (TWO32 - 1)
-        w = 4 * torch.stack([c[..., 0], (c[..., 1] - c[..., 0]) % TWO32, (c[..., 2] - c[..., 1]) % TWO32, TWO32 - c[..., 2]], dim=-1)
+        c = (thresholds.to(torch.int64) & (TWO32 - 1))[..., :3].sort(dim=-1).values
+        w = 4 * torch.stack([c[..., 0], c[..., 1] - c[..., 0], c[..., 2] - c[..., 1], TWO32 - c[..., 2]], dim=-1)
     else:
         hit = policy[..., None].to(torch.int64) == torch.arange(4, device=policy.device)
         w = epsilon_u32 + torch.where(hit, 4 * (TWO32 - epsilon_u32), 0)
