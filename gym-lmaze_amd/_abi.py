@@ -24,27 +24,6 @@ LAYOUT_SHARED, LAYOUT_PER_ENV = 0, 1
 OBS_BALL, OBS_WALL, OBS_GOAL, OBS_FREE = 1, 2, 4, 8
 MAX_GRID, MAX_CHANNELS = 64, 8
 
-# every symbol include/lmaze.h declares (tests/test_abi_symbols.py parses the header and
-# checks this list and the loaded library against it)
-SYMBOLS = ("lmaze_abi_version", "lmaze_strerror", "lmaze_device_info", "lmaze_step_v0", "lmaze_step_v3",
-           "lmaze_step_v0_autoreset", "lmaze_step_v3_autoreset", "lmaze_observe", "lmaze_reset",
-           "lmaze_episode_stats", "lmaze_bandwidth_probe", "lmaze_render_expanded", "lmaze_foveal_step", "lmaze_foveal_step_autoreset", "lmaze_foveal_reset", "lmaze_v1_set_foveal_goal",
-           "lmaze_v5_planner_step", "lmaze_v5_hier_step", "lmaze_v6_safe_foveal_goal", "lmaze_expand_planes",
-           "lmaze_foveal_visit_bytes", "lmaze_foveal_materialise_visit", "lmaze_foveal_load_visit",
-           "lmaze_describe_step", "lmaze_describe_foveal_step", "lmaze_rollout",
-           "lmaze_step_u8", "lmaze_observe_u8", "lmaze_foveal_rollout", "lmaze_describe_foveal_rollout",
-           "lmaze_rollout_obs", "lmaze_foveal_rollout_obs", "lmaze_rollout_u8", "lmaze_rollout_obs_u8",
-           "lmaze_describe_rollout", "lmaze_rollout_policy", "lmaze_rollout_policy_u8", "lmaze_describe_rollout_policy",
-           "lmaze_rollout_sample", "lmaze_rollout_sample_u8", "lmaze_describe_rollout_sample", "lmaze_returns",
-           "lmaze_describe_foveal_rollout_obs", "lmaze_advantages", "lmaze_advantages_table", "lmaze_table_stats",
-           "lmaze_describe_table_stats", "lmaze_foveal_rollout_policy", "lmaze_describe_foveal_rollout_policy",
-           "lmaze_foveal_rollout_sample", "lmaze_describe_foveal_rollout_sample", "lmaze_v5_rollout_policy",
-           "lmaze_describe_v5_rollout_policy", "lmaze_v5_rollout_sample", "lmaze_describe_v5_rollout_sample",
-           "lmaze_solve", "lmaze_describe_solve", "lmaze_env_rollout_policy", "lmaze_env_rollout_sample",
-           "lmaze_describe_env_rollout", "lmaze_env_rollout_qlearn", "lmaze_describe_env_rollout_qlearn",
-           "lmaze_generate", "lmaze_describe_generate", "lmaze_score", "lmaze_describe_score", "lmaze_evaluate",
-           "lmaze_describe_evaluate")
-
 
 class LmazeParams(C.Structure):
     """struct LmazeParams of include/lmaze.h (constants the reference hard-codes in __init__)."""
@@ -76,6 +55,98 @@ class LmazeError(RuntimeError):
         RuntimeError.__init__(self, "%s failed: %d (%s)" % (fn, code, strerror(code)))
 
 
+def _signatures():
+    """name -> argument types of every function include/lmaze.h declares; a family that shares a list is written once.
+    tests/test_abi_symbols.py reads the header's prototypes and checks every entry here against them: the return type, the
+    number of arguments, each argument's kind and width."""
+    vp, i32, i64, u32, u64, f32, text = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_char_p
+    P, FP, FB = C.POINTER(LmazeParams), C.POINTER(LmazeFovealParams), C.POINTER(LmazeFovealBuffers)
+    draw = [u64, u64, i64]                                    # seed, epoch, env_base
+    epochs = draw + [vp, vp, vp]                              # ... epoch_in_dev, epoch_out_dev, stream
+    batch = [i64, i32] + draw                                 # n, auto_reset, seed, epoch, env_base
+    slots = [vp, i32, vp]                                     # obs_t, obs_every, stream
+
+    def same(names, args):
+        return dict.fromkeys(names.split(), args)
+
+    def describe(first, flags):
+        """(params or counts, n, int32 flags ..., text_host, len)"""
+        return first + [i64] + [i32] * flags + [text, i32]
+
+    def grid_rollout(table, rows):
+        """(params, layout, actions or table ..., T, state and row pointers ..., n, auto_reset, seed, epoch, env_base -- then
+        the stream, or the slots"""
+        return [P, vp] + table + [i32] + [vp] * rows + batch
+
+    def foveal_rollout(table, auto_reset, rows):
+        """(params, layouts, table ..., T, buffers, n, [auto_reset,] seed, epoch, env_base, row and slot pointers ..., k, stream)"""
+        return [FP, vp] + table + [i32, FB, i64] + [i32] * auto_reset + draw + [vp] * rows + [i32, vp]
+
+    return {
+        "lmaze_abi_version": [],
+        "lmaze_strerror": [C.c_int],
+        "lmaze_device_info": [C.c_int, C.POINTER(i32), text, i32],
+        **same("lmaze_step_v0 lmaze_step_v3", [P] + [vp] * 8 + [i64, vp]),
+        **same("lmaze_step_v0_autoreset lmaze_step_v3_autoreset", [P] + [vp] * 8 + [i64] + epochs),
+        "lmaze_step_u8": [P] + [vp] * 9 + [i64, i32] + epochs,
+        "lmaze_observe": [P] + [vp] * 4 + [i64, vp],
+        "lmaze_observe_u8": [P] + [vp] * 5 + [i64, vp],
+        "lmaze_reset": [P, vp, vp] + draw + [vp] * 6 + [i64, vp],
+        "lmaze_episode_stats": [vp] * 4 + [f32, i64, vp, vp],
+        "lmaze_bandwidth_probe": [vp, vp, i64, vp],
+        "lmaze_render_expanded": [vp, i32, i32, C.POINTER(i32), i32, vp, i64, vp],
+        "lmaze_expand_planes": [vp, i32, i32, i32, vp, i64, vp],
+        # the grid rollouts: actions, or a table in their place
+        **same("lmaze_rollout lmaze_rollout_u8", grid_rollout([vp], 9) + [vp]),
+        **same("lmaze_rollout_obs lmaze_rollout_obs_u8", grid_rollout([vp], 9) + slots),
+        **same("lmaze_rollout_policy lmaze_rollout_policy_u8", grid_rollout([vp, i32, u32], 11) + slots),
+        **same("lmaze_rollout_sample lmaze_rollout_sample_u8", grid_rollout([vp, i32], 11) + slots),
+        "lmaze_env_rollout_policy": grid_rollout([vp, u32], 11) + slots,
+        "lmaze_env_rollout_sample": grid_rollout([vp], 11) + slots,
+        "lmaze_env_rollout_qlearn": grid_rollout([vp, f32, f32, u32], 12) + slots,
+        # the foveal variants
+        "lmaze_foveal_step": [FP, vp, vp, FB, i64, vp],
+        "lmaze_foveal_step_autoreset": [FP, vp, vp, FB, i64] + epochs,
+        "lmaze_foveal_reset": [FP, vp, vp, i32] + draw + [FB, i64, vp],
+        **same("lmaze_v1_set_foveal_goal lmaze_v5_planner_step", [FP, vp, vp, vp, FB, i64, vp]),
+        "lmaze_v5_hier_step": [FP, vp, vp, vp, FB, i64] + epochs,
+        "lmaze_v6_safe_foveal_goal": [FP, vp] + draw + [FB, vp, i64, vp],
+        "lmaze_foveal_visit_bytes": [i32, i64],
+        **same("lmaze_foveal_materialise_visit lmaze_foveal_load_visit", [FP, FB, vp, i64, vp]),
+        "lmaze_foveal_rollout": [FP, vp, vp, vp, i32, FB] + batch + [vp] * 5,
+        "lmaze_foveal_rollout_obs": [FP, vp, vp, vp, i32, FB] + batch + [vp] * 6 + [i32, vp],
+        "lmaze_foveal_rollout_policy": foveal_rollout([vp, u32], 1, 7),
+        "lmaze_foveal_rollout_sample": foveal_rollout([vp], 1, 7),
+        "lmaze_v5_rollout_policy": foveal_rollout([vp, i32, u32, vp, u32], 0, 10),
+        "lmaze_v5_rollout_sample": foveal_rollout([vp, i32, vp], 0, 10),
+        # learning from rows, and planning
+        "lmaze_returns": [vp, vp, vp, f32, vp, i32, i64, vp],
+        "lmaze_advantages": [vp] * 4 + [f32, f32, vp, vp, i32, i64, vp],
+        "lmaze_advantages_table": [vp] * 5 + [i64, f32, f32, vp, vp, i32, i64, vp],
+        "lmaze_table_stats": [vp, vp, vp, i64, i64, i32, vp, vp, vp],
+        "lmaze_solve": [P, vp, vp, i64, f32, i32] + [vp] * 7,
+        "lmaze_score": [P, vp, vp, i64] + [vp] * 6,
+        "lmaze_evaluate": [P, vp, vp, i64, vp, vp, u32, vp, f32, i32, f32] + [vp] * 6,
+        "lmaze_generate": [i32, i64, u64, i64, u32, vp, vp, vp],
+        # what a call would launch, as a line of text
+        "lmaze_describe_step": describe([P], 2),
+        **same("lmaze_describe_rollout lmaze_describe_env_rollout_qlearn", describe([P], 4)),
+        **same("lmaze_describe_rollout_policy lmaze_describe_rollout_sample lmaze_describe_env_rollout", describe([P], 5)),
+        **same("lmaze_describe_solve lmaze_describe_score lmaze_describe_evaluate", describe([P], 0)),
+        "lmaze_describe_foveal_step": describe([FP], 1),
+        **same("lmaze_describe_foveal_rollout lmaze_describe_foveal_rollout_policy lmaze_describe_foveal_rollout_sample "
+               "lmaze_describe_v5_rollout_policy lmaze_describe_v5_rollout_sample", describe([FP], 3)),
+        "lmaze_describe_foveal_rollout_obs": describe([FP], 4),
+        "lmaze_describe_table_stats": describe([i64], 1),
+        "lmaze_describe_generate": describe([i32], 0),
+    }
+
+
+SIGNATURES = _signatures()
+RESTYPES = {"lmaze_strerror": C.c_char_p, "lmaze_foveal_visit_bytes": C.c_int64}      # every other function returns int
+SYMBOLS = tuple(SIGNATURES)                                   # every symbol include/lmaze.h declares
+
+
 def _sources():
     """csrc/*.hip, csrc/*.h and include/lmaze.h: what liblmaze_hip.so is built from."""
     src = os.path.join(HERE, "csrc")
@@ -100,150 +171,9 @@ def _load():
                           % (os.path.basename(LIB_PATH), ", ".join(os.path.basename(f) for f in stale),
                              os.path.join(HERE, "csrc")), RuntimeWarning, stacklevel=3)
     lib = C.CDLL(LIB_PATH)
-    vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
-    P = C.POINTER(LmazeParams)
-    lib.lmaze_abi_version.restype = C.c_int
-    lib.lmaze_abi_version.argtypes = []
-    lib.lmaze_strerror.restype = C.c_char_p
-    lib.lmaze_strerror.argtypes = [C.c_int]
-    lib.lmaze_device_info.restype = C.c_int
-    lib.lmaze_device_info.argtypes = [C.c_int, C.POINTER(i32), C.c_char_p, i32]
-    lib.lmaze_step_v0.restype = C.c_int
-    lib.lmaze_step_v0.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.lmaze_step_v3.restype = C.c_int
-    lib.lmaze_step_v3.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.lmaze_step_v0_autoreset.restype = C.c_int
-    lib.lmaze_step_v0_autoreset.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, i64, u64, u64, i64, vp, vp, vp]
-    lib.lmaze_step_v3_autoreset.restype = C.c_int
-    lib.lmaze_step_v3_autoreset.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, i64, u64, u64, i64, vp, vp, vp]
-    lib.lmaze_observe.restype = C.c_int
-    lib.lmaze_observe.argtypes = [P, vp, vp, vp, vp, i64, vp]
-    lib.lmaze_reset.restype = C.c_int
-    lib.lmaze_reset.argtypes = [P, vp, vp, u64, u64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.lmaze_render_expanded.restype = C.c_int
-    lib.lmaze_render_expanded.argtypes = [vp, i32, i32, C.POINTER(i32), i32, vp, i64, vp]
-    lib.lmaze_bandwidth_probe.restype = C.c_int
-    lib.lmaze_bandwidth_probe.argtypes = [vp, vp, i64, vp]
-    lib.lmaze_episode_stats.restype = C.c_int
-    lib.lmaze_episode_stats.argtypes = [vp, vp, vp, vp, C.c_float, i64, vp, vp]
-    FP, FB = C.POINTER(LmazeFovealParams), C.POINTER(LmazeFovealBuffers)
-    lib.lmaze_foveal_step.restype = C.c_int
-    lib.lmaze_foveal_step.argtypes = [FP, vp, vp, FB, i64, vp]
-    lib.lmaze_foveal_step_autoreset.restype = C.c_int
-    lib.lmaze_foveal_step_autoreset.argtypes = [FP, vp, vp, FB, i64, u64, u64, i64, vp, vp, vp]
-    lib.lmaze_foveal_reset.restype = C.c_int
-    lib.lmaze_foveal_reset.argtypes = [FP, vp, vp, i32, u64, u64, i64, FB, i64, vp]
-    lib.lmaze_v1_set_foveal_goal.restype = C.c_int
-    lib.lmaze_v1_set_foveal_goal.argtypes = [FP, vp, vp, vp, FB, i64, vp]
-    lib.lmaze_v5_planner_step.restype = C.c_int
-    lib.lmaze_v5_planner_step.argtypes = [FP, vp, vp, vp, FB, i64, vp]
-    lib.lmaze_v5_hier_step.restype = C.c_int
-    lib.lmaze_v5_hier_step.argtypes = [FP, vp, vp, vp, FB, i64, u64, u64, i64, vp, vp, vp]
-    lib.lmaze_v6_safe_foveal_goal.restype = C.c_int
-    lib.lmaze_v6_safe_foveal_goal.argtypes = [FP, vp, u64, u64, i64, FB, vp, i64, vp]
-    lib.lmaze_expand_planes.restype = C.c_int
-    lib.lmaze_expand_planes.argtypes = [vp, i32, i32, i32, vp, i64, vp]
-    lib.lmaze_foveal_visit_bytes.restype = i64
-    lib.lmaze_foveal_visit_bytes.argtypes = [i32, i64]
-    lib.lmaze_foveal_materialise_visit.restype = C.c_int
-    lib.lmaze_foveal_materialise_visit.argtypes = [FP, FB, vp, i64, vp]
-    lib.lmaze_foveal_load_visit.restype = C.c_int
-    lib.lmaze_foveal_load_visit.argtypes = [FP, FB, vp, i64, vp]
-    lib.lmaze_step_u8.restype = C.c_int
-    lib.lmaze_step_u8.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, vp, vp]
-    lib.lmaze_observe_u8.restype = C.c_int
-    lib.lmaze_observe_u8.argtypes = [P, vp, vp, vp, vp, vp, i64, vp]
-    lib.lmaze_rollout.restype = C.c_int
-    lib.lmaze_rollout.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp]
-    lib.lmaze_describe_step.restype = C.c_int
-    lib.lmaze_describe_step.argtypes = [P, i64, i32, i32, C.c_char_p, i32]
-    lib.lmaze_describe_foveal_step.restype = C.c_int
-    lib.lmaze_describe_foveal_step.argtypes = [FP, i64, i32, C.c_char_p, i32]
-    lib.lmaze_foveal_rollout.restype = C.c_int
-    lib.lmaze_foveal_rollout.argtypes = [FP, vp, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp]
-    lib.lmaze_rollout_obs.restype = C.c_int
-    lib.lmaze_rollout_obs.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
-    lib.lmaze_foveal_rollout_obs.restype = C.c_int
-    lib.lmaze_foveal_rollout_obs.argtypes = [FP, vp, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.lmaze_rollout_u8.restype = C.c_int
-    lib.lmaze_rollout_u8.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp]
-    lib.lmaze_rollout_obs_u8.restype = C.c_int
-    lib.lmaze_rollout_obs_u8.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
-    lib.lmaze_describe_rollout.restype = C.c_int
-    lib.lmaze_describe_rollout.argtypes = [P, i64, i32, i32, i32, i32, C.c_char_p, i32]
-    for name in ("lmaze_rollout_policy", "lmaze_rollout_policy_u8"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [P, vp, vp, i32, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64,
-                                       i64, vp, i32, vp]
-    lib.lmaze_describe_rollout_policy.restype = C.c_int
-    lib.lmaze_describe_rollout_policy.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
-    for name in ("lmaze_rollout_sample", "lmaze_rollout_sample_u8"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [P, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32, vp]
-    lib.lmaze_describe_rollout_sample.restype = C.c_int
-    lib.lmaze_describe_rollout_sample.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_env_rollout_policy.restype = C.c_int
-    lib.lmaze_env_rollout_policy.argtypes = [P, vp, vp, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64,
-                                             i64, vp, i32, vp]
-    lib.lmaze_env_rollout_sample.restype = C.c_int
-    lib.lmaze_env_rollout_sample.argtypes = [P, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, u64, u64, i64, vp, i32,
-                                             vp]
-    lib.lmaze_describe_env_rollout.restype = C.c_int
-    lib.lmaze_describe_env_rollout.argtypes = [P, i64, i32, i32, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_env_rollout_qlearn.restype = C.c_int
-    lib.lmaze_env_rollout_qlearn.argtypes = [P, vp, vp, C.c_float, C.c_float, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                             vp, i64, i32, u64, u64, i64, vp, i32, vp]
-    lib.lmaze_describe_env_rollout_qlearn.restype = C.c_int
-    lib.lmaze_describe_env_rollout_qlearn.argtypes = [P, i64, i32, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_returns.restype = C.c_int
-    lib.lmaze_returns.argtypes = [vp, vp, vp, C.c_float, vp, i32, i64, vp]
-    lib.lmaze_advantages.restype = C.c_int
-    lib.lmaze_advantages.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, i64, vp]
-    lib.lmaze_advantages_table.restype = C.c_int
-    lib.lmaze_advantages_table.argtypes = [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, i32, i64, vp]
-    lib.lmaze_table_stats.restype = C.c_int
-    lib.lmaze_table_stats.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp]
-    lib.lmaze_describe_table_stats.restype = C.c_int
-    lib.lmaze_describe_table_stats.argtypes = [i64, i64, i32, C.c_char_p, i32]
-    lib.lmaze_describe_foveal_rollout.restype = C.c_int
-    lib.lmaze_describe_foveal_rollout.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_describe_foveal_rollout_obs.restype = C.c_int
-    lib.lmaze_describe_foveal_rollout_obs.argtypes = [FP, i64, i32, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_foveal_rollout_policy.restype = C.c_int
-    lib.lmaze_foveal_rollout_policy.argtypes = [FP, vp, vp, C.c_uint32, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp,
-                                                i32, vp]
-    lib.lmaze_describe_foveal_rollout_policy.restype = C.c_int
-    lib.lmaze_describe_foveal_rollout_policy.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_foveal_rollout_sample.restype = C.c_int
-    lib.lmaze_foveal_rollout_sample.argtypes = [FP, vp, vp, i32, FB, i64, i32, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.lmaze_describe_foveal_rollout_sample.restype = C.c_int
-    lib.lmaze_describe_foveal_rollout_sample.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_v5_rollout_policy.restype = C.c_int
-    lib.lmaze_v5_rollout_policy.argtypes = [FP, vp, vp, i32, C.c_uint32, vp, C.c_uint32, i32, FB, i64, u64, u64, i64, vp, vp, vp, vp, vp,
-                                            vp, vp, vp, vp, vp, i32, vp]
-    lib.lmaze_describe_v5_rollout_policy.restype = C.c_int
-    lib.lmaze_describe_v5_rollout_policy.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_v5_rollout_sample.restype = C.c_int
-    lib.lmaze_v5_rollout_sample.argtypes = [FP, vp, vp, i32, vp, i32, FB, i64, u64, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                            i32, vp]
-    lib.lmaze_describe_v5_rollout_sample.restype = C.c_int
-    lib.lmaze_describe_v5_rollout_sample.argtypes = [FP, i64, i32, i32, i32, C.c_char_p, i32]
-    lib.lmaze_solve.restype = C.c_int
-    lib.lmaze_solve.argtypes = [P, vp, vp, i64, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.lmaze_describe_solve.restype = C.c_int
-    lib.lmaze_describe_solve.argtypes = [P, i64, C.c_char_p, i32]
-    lib.lmaze_generate.restype = C.c_int
-    lib.lmaze_generate.argtypes = [i32, i64, u64, i64, C.c_uint32, vp, vp, vp]
-    lib.lmaze_describe_generate.restype = C.c_int
-    lib.lmaze_describe_generate.argtypes = [i32, i64, C.c_char_p, i32]
-    lib.lmaze_score.restype = C.c_int
-    lib.lmaze_score.argtypes = [P, vp, vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.lmaze_describe_score.restype = C.c_int
-    lib.lmaze_describe_score.argtypes = [P, i64, C.c_char_p, i32]
-    lib.lmaze_evaluate.restype = C.c_int
-    lib.lmaze_evaluate.argtypes = [P, vp, vp, i64, vp, vp, C.c_uint32, vp, C.c_float, i32, C.c_float, vp, vp, vp, vp, vp, vp]
-    lib.lmaze_describe_evaluate.restype = C.c_int
-    lib.lmaze_describe_evaluate.argtypes = [P, i64, C.c_char_p, i32]
+    for name, argtypes in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = RESTYPES.get(name, C.c_int), argtypes
     if lib.lmaze_abi_version() != ABI_VERSION:
         raise ImportError("liblmaze_hip.so ABI %d != binding %d: rebuild" % (lib.lmaze_abi_version(), ABI_VERSION))
     return lib

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from . import _tables
 from . import _tuning
 
 _NUMPY = {torch.int32: np.int32, torch.float32: np.float32, torch.uint8: np.uint8}
@@ -145,29 +146,7 @@ class VecEnvBase(object):
             raise ValueError("T must be an int >= 0")
         return int(T)
 
-    @staticmethod
-    def greedy_table(q):
-        """The greedy action table uint8[S] of a float tensor q[S, A] (A <= 255), on q's device: the FIRST maximum of every
-        row, spelled out (the lowest index whose value equals the row's maximum) and not left to argmax's tie behaviour.
-        A row that holds a NaN equals its maximum nowhere and gets the id A, which every step treats as no move."""
-        if not (isinstance(q, torch.Tensor) and q.dim() == 2 and q.is_floating_point() and 1 <= q.shape[1] <= 255):
-            raise ValueError("q must be a float tensor [S, A] with 1 <= A <= 255")
-        A = q.shape[1]
-        idx = torch.arange(A, device=q.device, dtype=torch.int32).expand_as(q)
-        first = torch.where(q == q.max(dim=1, keepdim=True).values, idx, torch.full_like(idx, A)).min(dim=1).values
-        return first.to(torch.uint8)
-
-    def _greedy_policy(self, policy, q, entries, shape):
-        """rollout_policy()'s table: policy itself, or greedy_table(q), as a contiguous uint8 tensor of `entries` entries
-        on the device.  shape: what the refusal says of the table's size."""
-        if q is not None:
-            if not isinstance(q, torch.Tensor) or q.device != self.device:
-                raise ValueError("q must be a float tensor [S, A] on %s" % self.device)
-            policy = self.greedy_table(q)
-        if not (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.device == self.device
-                and policy.is_contiguous() and policy.numel() == entries):
-            raise ValueError("policy must be a contiguous uint8 tensor of %d entries on %s (%s)" % (entries, self.device, shape))
-        return policy
+    greedy_table = staticmethod(_tables.greedy_table)
 
     def _closed_loop(self, who, name, call, T, k, obs_t, trajectory, actions_t, key_t, streams=1, more=None):
         """What every closed-loop rollout does around its ABI call `name`, once its table and its recording request (k =

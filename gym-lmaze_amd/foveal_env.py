@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from . import _tables
 from . import layouts as L
 from ._base import VecEnvBase
 
@@ -184,18 +185,13 @@ class LmazeFovealVecEnv(VecEnvBase):
         each recorded step launch); v5/v6 also obs_local_t (T // k, N, 4, 5, 5), optional.  The final obs, state and rows
         are those of the plain rollout.  Not with device_epoch."""
         hier = goals is not None
-        k = None
         if obs_every is not None:
             self._check_rows("rollout()", actions, goals)
             if device_epoch:
                 raise ValueError("rollout(obs_every=...) is not available with a device-resident epoch")
             if obs_local_t is not None and not self._two_level:
                 raise ValueError("obs_local_t: v5/v6 only")
-            k = self._obs_slots(int(actions.shape[0]), obs_every, obs_t, self.obs)
-            if obs_local_t is not None:
-                self._obs_slots(int(actions.shape[0]), obs_every, obs_local_t, self.obs_local, name="obs_local_t")
-        elif obs_t is not None or obs_local_t is not None:
-            raise ValueError("obs_t / obs_local_t need obs_every")
+        k = self._recording(0 if obs_every is None else int(actions.shape[0]), obs_every, obs_t, obs_local_t)
         self._check_rows("rollout()", actions, goals)
         if hier and (not self._two_level or goals.shape[0] != actions.shape[0]):
             raise ValueError("planner goals: v5/v6 only, one row per step")
@@ -217,7 +213,7 @@ class LmazeFovealVecEnv(VecEnvBase):
             self._step_loop(T, lambda t: launch(t, t))
             return self.obs, self.reward, self.done
         rows = self._traj_rows(T, 2 if self.variant in ("v1", "v5", "v6") else 1) if trajectory else None
-        if ((k is not None and ((hier and self.grid != 18) or (self.variant == "v1" and self.grid != 14)))
+        if ((k and ((hier and self.grid != 18) or (self.variant == "v1" and self.grid != 14)))
                 or (self._two_level and not hier)):
             # T launches: the two-level recording form exists at G = 18 only, v1's at G = 14 only (include/lmaze.h
             # lmaze_foveal_rollout_obs), and the plain v5/v6 step has no one-launch form (lmaze_foveal_rollout)
@@ -229,14 +225,14 @@ class LmazeFovealVecEnv(VecEnvBase):
             args = (self._pp, self._p_layouts, base, goals.data_ptr() if hier else None, T, self._pb, N,
                     1 if resets else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *ptrs)
             with self._guard():
-                if k is None:
+                if not k:
                     rc = _abi.lib.lmaze_foveal_rollout(*args, self._stream())
                 else:
                     some = obs_t.shape[0] > 0
                     rc = _abi.lib.lmaze_foveal_rollout_obs(*args, obs_t.data_ptr() if some else None,
                                                            obs_local_t.data_ptr() if some and obs_local_t is not None else None,
                                                            k, self._stream())
-            _abi.check("lmaze_foveal_rollout" if k is None else "lmaze_foveal_rollout_obs", rc)
+            _abi.check("lmaze_foveal_rollout_obs" if k else "lmaze_foveal_rollout", rc)
             if resets:
                 self._epoch += T
         return self._rollout_result(rows)
@@ -258,25 +254,15 @@ class LmazeFovealVecEnv(VecEnvBase):
         if self._two_level:
             raise ValueError("rollout_policy() is not available for v5/v6: their two-level step needs two tables")
         T = self._steps(T)
-        if (policy is None) == (q is None):
-            raise ValueError("rollout_policy() wants exactly one of policy= and q=")
+        _tables.exactly_one("rollout_policy()", policy=policy, q=q)
         eps = _abi.epsilon_u32(epsilon)
         if torch.cuda.is_current_stream_capturing():
             raise ValueError("rollout_policy() is not available with a device-resident epoch (under stream capture)")
-        policy = self._greedy_policy(policy, q, self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid))
-        k = 0
-        if obs_every is not None:
-            k = self._obs_slots(T, obs_every, obs_t, self.obs)
-        elif obs_t is not None:
-            raise ValueError("obs_t needs obs_every")
-
-        def call(rows, p_actions, p_key, slots):
-            return _abi.lib.lmaze_foveal_rollout_policy(
-                self._pp, self._p_layouts, policy.data_ptr(), eps, T, self._pb, self.num_envs, 1 if auto_reset else 0,
-                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key, slots, k,
-                self._stream())
-        return self._closed_loop("rollout_policy()", "lmaze_foveal_rollout_policy", call, T, k, obs_t, trajectory, actions_t, key_t,
-                                 streams=2 if self.variant == "v1" else 1)
+        policy = _tables.greedy_policy(policy, q, self.n_layouts * self.grid * self.grid, self.device,
+                                       "L=%d, G=%d" % (self.n_layouts, self.grid))
+        k = self._recording(T, obs_every, obs_t)
+        return self._launch_closed("rollout_policy()", "lmaze_foveal_rollout_policy", (policy.data_ptr(), eps), T, k, obs_t,
+                                   trajectory, actions_t, key_t, streams=2 if self.variant == "v1" else 1, auto_reset=auto_reset)
 
     def rollout_sample(self, T, probs=None, logits=None, temperature=1.0, thresholds=None, auto_reset=True, trajectory=False,
                        actions_t=None, key_t=None, obs_t=None, obs_every=None):
@@ -295,41 +281,15 @@ class LmazeFovealVecEnv(VecEnvBase):
         if self._two_level:
             raise ValueError("rollout_sample() is not available for v5/v6: their two-level step needs two tables")
         T = self._steps(T)
-        if sum(x is not None for x in (probs, logits, thresholds)) != 1:
-            raise ValueError("rollout_sample() wants exactly one of probs=, logits= and thresholds=")
+        _tables.exactly_one("rollout_sample()", probs=probs, logits=logits, thresholds=thresholds)
         if torch.cuda.is_current_stream_capturing():
             raise ValueError("rollout_sample() is not available with a device-resident epoch (under stream capture)")
-        A = 4 if self.variant == "v1" else _abi.FOVEA * _abi.FOVEA
-        W = 4 if A == 4 else A - 1
-        entries, what = self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid)
-        if thresholds is None:
-            src, name = (probs, "probs") if logits is None else (logits, "logits")
-            if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
-                    and tuple(src.shape) == (entries, A)):
-                raise ValueError("%s must be a float tensor [%d, %d] on %s (%s)" % (name, entries, A, self.device, what))
-            if logits is not None:
-                if not float(temperature) > 0.0:
-                    raise ValueError("temperature must be > 0")
-                src = torch.softmax(logits.double() / float(temperature), -1)
-            thresholds = _abi.sampling_thresholds(src, actions=A)
-        if not (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
-                and thresholds.device == self.device and thresholds.is_contiguous() and tuple(thresholds.shape) == (entries, W)
-                and thresholds.data_ptr() % 16 == 0):
-            raise ValueError("thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, %d] on %s (%s)"
-                             % (entries, W, self.device, what))
-        k = 0
-        if obs_every is not None:
-            k = self._obs_slots(T, obs_every, obs_t, self.obs)
-        elif obs_t is not None:
-            raise ValueError("obs_t needs obs_every")
-
-        def call(rows, p_actions, p_key, slots):
-            return _abi.lib.lmaze_foveal_rollout_sample(
-                self._pp, self._p_layouts, thresholds.data_ptr(), T, self._pb, self.num_envs, 1 if auto_reset else 0,
-                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key, slots, k,
-                self._stream())
-        return self._closed_loop("rollout_sample()", "lmaze_foveal_rollout_sample", call, T, k, obs_t, trajectory, actions_t, key_t,
-                                 streams=2 if self.variant == "v1" else 1)
+        table = _tables.threshold_table(probs, logits, thresholds, temperature, self.n_layouts * self.grid * self.grid,
+                                        4 if self.variant == "v1" else _abi.FOVEA * _abi.FOVEA, self.device,
+                                        "L=%d, G=%d" % (self.n_layouts, self.grid))
+        k = self._recording(T, obs_every, obs_t)
+        return self._launch_closed("rollout_sample()", "lmaze_foveal_rollout_sample", (table.data_ptr(),), T, k, obs_t,
+                                   trajectory, actions_t, key_t, streams=2 if self.variant == "v1" else 1, auto_reset=auto_reset)
 
     def rollout_hier_policy(self, T, controller=None, controller_q=None, planner=None, planner_q=None, epsilon=0.0,
                             planner_epsilon=0.0, controller_key="offset", trajectory=False, actions_t=None, key_t=None,
@@ -352,38 +312,23 @@ class LmazeFovealVecEnv(VecEnvBase):
         if not self._two_level:
             raise ValueError("rollout_hier_policy() is the two-level closed loop of v5/v6; v1/v2/v4 have rollout_policy()")
         T = self._steps(T)
-        if (controller is None) == (controller_q is None):
-            raise ValueError("rollout_hier_policy() wants exactly one of controller= and controller_q=")
-        if (planner is None) == (planner_q is None):
-            raise ValueError("rollout_hier_policy() wants exactly one of planner= and planner_q=")
+        _tables.exactly_one("rollout_hier_policy()", controller=controller, controller_q=controller_q)
+        _tables.exactly_one("rollout_hier_policy()", planner=planner, planner_q=planner_q)
         eps, peps = _abi.epsilon_u32(epsilon), _abi.epsilon_u32(planner_epsilon)
-        ck = _abi.controller_key_id(controller_key)
-        if ck not in (0, 1):
-            raise ValueError("controller_key must be 'offset' or 'cell'")
+        ck = self._controller_key(controller_key)
         if torch.cuda.is_current_stream_capturing():
             raise ValueError("rollout_hier_policy() is not available with a device-resident epoch (under stream capture)")
         cells, what = self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid)
         for q, A, name in ((controller_q, 4, "controller_q"), (planner_q, _abi.FOVEA * _abi.FOVEA, "planner_q")):
             if q is not None and not (isinstance(q, torch.Tensor) and q.dim() == 2 and q.shape[1] == A):
                 raise ValueError("%s must be a float tensor [keys, %d]" % (name, A))
-        controller = self._greedy_policy(controller, controller_q, 100 * cells if ck else 100, "controller_key=%r, %s" % (controller_key, what))
-        planner = self._greedy_policy(planner, planner_q, cells, what)
-        k = 0
-        if obs_every is not None:
-            k = self._obs_slots(T, obs_every, obs_t, self.obs)
-            if obs_local_t is not None:
-                self._obs_slots(T, obs_every, obs_local_t, self.obs_local, name="obs_local_t")
-        elif obs_t is not None or obs_local_t is not None:
-            raise ValueError("obs_t / obs_local_t need obs_every")
-
-        def call(rows, p_actions, p_key, slots, goal_rows):
-            return _abi.lib.lmaze_v5_rollout_policy(
-                self._pp, self._p_layouts, controller.data_ptr(), ck, eps, planner.data_ptr(), peps, T, self._pb, self.num_envs,
-                self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key,
-                *goal_rows, slots, obs_local_t.data_ptr() if slots is not None and obs_local_t is not None else None, k,
-                self._stream())
-        return self._closed_loop("rollout_hier_policy()", "lmaze_v5_rollout_policy", call, T, k, obs_t, trajectory, actions_t, key_t,
-                                 streams=2, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
+        controller = _tables.greedy_policy(controller, controller_q, 100 * cells if ck else 100, self.device,
+                                           "controller_key=%r, %s" % (controller_key, what))
+        planner = _tables.greedy_policy(planner, planner_q, cells, self.device, what)
+        k = self._recording(T, obs_every, obs_t, obs_local_t)
+        return self._launch_closed("rollout_hier_policy()", "lmaze_v5_rollout_policy",
+                                   (controller.data_ptr(), ck, eps, planner.data_ptr(), peps), T, k, obs_t, trajectory, actions_t,
+                                   key_t, streams=2, obs_local_t=obs_local_t, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
 
     def rollout_hier_sample(self, T, controller_probs=None, controller_logits=None, controller_thresholds=None, planner_probs=None,
                             planner_logits=None, planner_thresholds=None, temperature=1.0, planner_temperature=None,
@@ -409,57 +354,62 @@ class LmazeFovealVecEnv(VecEnvBase):
         if not self._two_level:
             raise ValueError("rollout_hier_sample() is the two-level closed loop of v5/v6; v1/v2/v4 have rollout_sample()")
         T = self._steps(T)
-        for level, given in (("controller", (controller_probs, controller_logits, controller_thresholds)),
-                             ("planner", (planner_probs, planner_logits, planner_thresholds))):
-            if sum(x is not None for x in given) != 1:
-                raise ValueError("rollout_hier_sample() wants exactly one of %s_probs=, %s_logits= and %s_thresholds=" % ((level,) * 3))
-        ck = _abi.controller_key_id(controller_key)
-        if ck not in (0, 1):
-            raise ValueError("controller_key must be 'offset' or 'cell'")
+        _tables.exactly_one("rollout_hier_sample()", controller_probs=controller_probs, controller_logits=controller_logits,
+                            controller_thresholds=controller_thresholds)
+        _tables.exactly_one("rollout_hier_sample()", planner_probs=planner_probs, planner_logits=planner_logits,
+                            planner_thresholds=planner_thresholds)
+        ck = self._controller_key(controller_key)
         if torch.cuda.is_current_stream_capturing():
             raise ValueError("rollout_hier_sample() is not available with a device-resident epoch (under stream capture)")
         cells, what = self.n_layouts * self.grid * self.grid, "L=%d, G=%d" % (self.n_layouts, self.grid)
-        if planner_temperature is None:
-            planner_temperature = temperature
+        controller = _tables.threshold_table(controller_probs, controller_logits, controller_thresholds, temperature,
+                                             100 * cells if ck else 100, 4, self.device,
+                                             "controller_key=%r, %s" % (controller_key, what), prefix="controller_")
+        planner = _tables.threshold_table(planner_probs, planner_logits, planner_thresholds,
+                                          temperature if planner_temperature is None else planner_temperature, cells,
+                                          _abi.FOVEA * _abi.FOVEA, self.device, what, prefix="planner_")
+        k = self._recording(T, obs_every, obs_t, obs_local_t)
+        return self._launch_closed("rollout_hier_sample()", "lmaze_v5_rollout_sample",
+                                   (controller.data_ptr(), ck, planner.data_ptr()), T, k, obs_t, trajectory, actions_t, key_t,
+                                   streams=2, obs_local_t=obs_local_t, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
 
-        def table(level, probs, logits, thresholds, temp, keys, A, what):
-            W = 4 if A == 4 else A - 1
-            if thresholds is None:
-                src, name = (probs, level + "_probs") if logits is None else (logits, level + "_logits")
-                if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
-                        and tuple(src.shape) == (keys, A)):
-                    raise ValueError("%s must be a float tensor [%d, %d] on %s (%s)" % (name, keys, A, self.device, what))
-                if logits is not None:
-                    if not float(temp) > 0.0:
-                        raise ValueError("temperature and planner_temperature must be > 0")
-                    src = torch.softmax(logits.double() / float(temp), -1)
-                thresholds = _abi.sampling_thresholds(src, actions=A)
-            if not (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
-                    and thresholds.device == self.device and thresholds.is_contiguous() and tuple(thresholds.shape) == (keys, W)
-                    and thresholds.data_ptr() % 16 == 0):
-                raise ValueError("%s_thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, %d] on %s (%s)"
-                                 % (level, keys, W, self.device, what))
-            return thresholds
-        controller = table("controller", controller_probs, controller_logits, controller_thresholds, temperature,
-                           100 * cells if ck else 100, 4, "controller_key=%r, %s" % (controller_key, what))
-        planner = table("planner", planner_probs, planner_logits, planner_thresholds, planner_temperature, cells,
-                        _abi.FOVEA * _abi.FOVEA, what)
-        k = 0
-        if obs_every is not None:
-            k = self._obs_slots(T, obs_every, obs_t, self.obs)
-            if obs_local_t is not None:
-                self._obs_slots(T, obs_every, obs_local_t, self.obs_local, name="obs_local_t")
-        elif obs_t is not None or obs_local_t is not None:
-            raise ValueError("obs_t / obs_local_t need obs_every")
+    def _recording(self, T, obs_every, obs_t, obs_local_t=None):
+        """A rollout's recording request, checked before anything is launched: k = obs_every with obs_t -- and, v5/v6,
+        obs_local_t, optional -- shaped for T steps (_obs_slots); 0 when nothing is to be recorded (obs_every None), where
+        there may be nowhere to record to either."""
+        if obs_every is None:
+            if obs_local_t is not None or (self._two_level and obs_t is not None):
+                raise ValueError("obs_t / obs_local_t need obs_every")
+            if obs_t is not None:
+                raise ValueError("obs_t needs obs_every")
+            return 0
+        k = self._obs_slots(T, obs_every, obs_t, self.obs)
+        if obs_local_t is not None:
+            self._obs_slots(T, obs_every, obs_local_t, self.obs_local, name="obs_local_t")
+        return k
 
-        def call(rows, p_actions, p_key, slots, goal_rows):
-            return _abi.lib.lmaze_v5_rollout_sample(
-                self._pp, self._p_layouts, controller.data_ptr(), ck, planner.data_ptr(), T, self._pb, self.num_envs,
+    def _launch_closed(self, who, entry, table_args, T, k, obs_t, trajectory, actions_t, key_t, streams, auto_reset=None,
+                       obs_local_t=None, more=None):
+        """The launch of the four closed-loop methods, through _closed_loop: `entry`(params, layouts, *table_args, T, buffers,
+        N, [auto_reset,] seed, epoch, env_base, the trajectory rows padded to four, actions_t, key_t, [goals_t, goal_key_t,]
+        obs_t, [obs_local_t,] k, stream).  The bracketed ones part the one-level entries (auto_reset) from the two-level
+        ones (more = the goal rows, and obs_local_t's slots beside obs_t's)."""
+        two_level = more is not None
+
+        def call(rows, p_actions, p_key, slots, goal_rows=()):
+            local = obs_local_t.data_ptr() if slots is not None and obs_local_t is not None else None
+            return getattr(_abi.lib, entry)(
+                self._pp, self._p_layouts, *table_args, T, self._pb, self.num_envs, *(() if two_level else (1 if auto_reset else 0,)),
                 self.seed & (2 ** 64 - 1), self._epoch, self.env_base, *(rows + [None] * (4 - len(rows))), p_actions, p_key,
-                *goal_rows, slots, obs_local_t.data_ptr() if slots is not None and obs_local_t is not None else None, k,
-                self._stream())
-        return self._closed_loop("rollout_hier_sample()", "lmaze_v5_rollout_sample", call, T, k, obs_t, trajectory, actions_t, key_t,
-                                 streams=2, more=[("goals_t", goals_t), ("goal_key_t", goal_key_t)])
+                *goal_rows, slots, *((local,) if two_level else ()), k, self._stream())
+        return self._closed_loop(who, entry, call, T, k, obs_t, trajectory, actions_t, key_t, streams=streams, more=more)
+
+    @staticmethod
+    def _controller_key(controller_key):
+        ck = _abi.controller_key_id(controller_key)
+        if ck not in (0, 1):
+            raise ValueError("controller_key must be 'offset' or 'cell'")
+        return ck
 
     def controller_keys(self, controller_key="offset"):
         """v5/v6, int32[N]: the controller key of every env's CURRENT state, by the rule the key_t rows of
@@ -467,9 +417,7 @@ class LmazeFovealVecEnv(VecEnvBase):
         and for "cell" state_keys() * 100 + d.  Plain torch ops; state_keys() is the planner key."""
         if not self._two_level:
             raise ValueError("controller_keys() is the two-level controller's key: v5/v6 only")
-        ck = _abi.controller_key_id(controller_key)
-        if ck not in (0, 1):
-            raise ValueError("controller_key must be 'offset' or 'cell'")
+        ck = self._controller_key(controller_key)
         o = (self.fgoal_xy.to(torch.int64) - self.ball_xy.to(torch.int64) + 4).clamp(0, 9)
         d = o[:, 0] * 10 + o[:, 1]
         if ck:

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from . import _tables
 from . import layouts as L
 from ._base import VecEnvBase
 from ._tuning import OnlineTuner
@@ -361,20 +362,19 @@ class LmazeVecEnv(VecEnvBase):
         advances by T whether or not auto_reset is set: exploration consumes epochs too.  Not with a device-resident epoch
         (under stream capture: the host's epoch would be frozen into the graph), nor while the online tuner runs."""
         T, entries = self._closed_loop_key("rollout_policy()", T, key)
-        if (policy is None) == (q is None):
-            raise ValueError("rollout_policy() wants exactly one of policy= and q=")
+        _tables.exactly_one("rollout_policy()", policy=policy, q=q)
         if key == "env":
             N, S = self.num_envs, self.grid ** 2
             if isinstance(q, torch.Tensor) and q.dim() == 3 and tuple(q.shape[:2]) == (N, S):
                 q = q.reshape(N * S, q.shape[2])
             if isinstance(policy, torch.Tensor) and tuple(policy.shape) not in ((N, S), (N * S,)):
                 raise ValueError("policy must be uint8 [%d, %d] or flat [%d] (key='env')" % (N, S, N * S))
-            policy = self._greedy_policy(policy, q, entries, "key='env', N=%d, G=%d" % (N, self.grid))
+            policy = _tables.greedy_policy(policy, q, entries, self.device, "key='env', N=%d, G=%d" % (N, self.grid))
             if policy.data_ptr() % 4:
                 raise ValueError("policy must be 4-byte aligned (key='env')")
             return self._rollout_table("env_rollout_policy", (policy.data_ptr(), _abi.epsilon_u32(epsilon)), T, auto_reset,
                                        trajectory, actions_t, key_t, obs_t, obs_every)
-        policy = self._greedy_policy(policy, q, entries, "key=%r, G=%d" % (key, self.grid))
+        policy = _tables.greedy_policy(policy, q, entries, self.device, "key=%r, G=%d" % (key, self.grid))
         return self._rollout_table("rollout_policy", (policy.data_ptr(), _abi.KEY_MODES[key], _abi.epsilon_u32(epsilon)), T,
                                    auto_reset, trajectory, actions_t, key_t, obs_t, obs_every)
 
@@ -396,28 +396,14 @@ class LmazeVecEnv(VecEnvBase):
         key_t, the index i and the note on v3 and the fused reset as in rollout_policy(key="env")."""
         T, entries = self._closed_loop_key("rollout_sample()", T, key)
         G = self.grid
-        if sum(x is not None for x in (probs, logits, thresholds)) != 1:
-            raise ValueError("rollout_sample() wants exactly one of probs=, logits= and thresholds=")
+        _tables.exactly_one("rollout_sample()", probs=probs, logits=logits, thresholds=thresholds)
         if key == "env":                               # contiguous rows [N, G*G, 4] are the flat table's own memory
             def flat(t):
                 whole = isinstance(t, torch.Tensor) and tuple(t.shape) == (self.num_envs, G * G, 4) and t.is_contiguous()
                 return t.view(entries, 4) if whole else t
             probs, logits, thresholds = flat(probs), flat(logits), flat(thresholds)
-        if thresholds is None:
-            src, name = (probs, "probs") if logits is None else (logits, "logits")
-            if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == self.device
-                    and tuple(src.shape) == (entries, 4)):
-                raise ValueError("%s must be a float tensor [%d, 4] on %s (key=%r, G=%d)" % (name, entries, self.device, key, G))
-            if logits is not None:
-                if not float(temperature) > 0.0:
-                    raise ValueError("temperature must be > 0")
-                src = torch.softmax(logits.double() / float(temperature), -1)
-            thresholds = _abi.sampling_thresholds(src)
-        if not (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
-                and thresholds.device == self.device and thresholds.is_contiguous() and tuple(thresholds.shape) == (entries, 4)
-                and thresholds.data_ptr() % 16 == 0):
-            raise ValueError("thresholds must be a contiguous, 16-byte aligned uint32 tensor [%d, 4] on %s (key=%r, G=%d)"
-                             % (entries, self.device, key, G))
+        thresholds = _tables.threshold_table(probs, logits, thresholds, temperature, entries, 4, self.device,
+                                             "key=%r, G=%d" % (key, G))
         table_args = (thresholds.data_ptr(),) if key == "env" else (thresholds.data_ptr(), _abi.KEY_MODES[key])
         return self._rollout_table("env_rollout_sample" if key == "env" else "rollout_sample", table_args, T, auto_reset, trajectory,
                                    actions_t, key_t, obs_t, obs_every)
@@ -663,12 +649,9 @@ class LmazeVecEnv(VecEnvBase):
         v_init: float32 [problems, G*G].  Returns EvaluatedTables(q, v, sweeps_run, delta)."""
         self._problem_key(key)
         tables = {"policy": policy, "q": q, "probs": probs, "logits": logits, "thresholds": thresholds}
-        given = [n for n, t in tables.items() if t is not None]
-        if len(given) != 1:
-            raise ValueError("evaluate() wants exactly one of policy=, q=, probs=, logits= and thresholds=")
+        name = _tables.exactly_one("evaluate()", **tables)
         goals, P, single = self._problems("evaluate", key, goal)
         S = self.grid * self.grid
-        name = given[0]
         table = tables[name]
         width = 1 if name == "policy" else 4
         if not isinstance(table, torch.Tensor) or table.numel() != P * S * width:
@@ -1077,24 +1060,18 @@ def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logit
     Returns EvaluatedTables(q, v, sweeps_run, delta)."""
     m = _Mazes.of(layouts, variant, validate)
     S, dev = m.S, m.dev
-    given = [n for n, t in (("policy", policy), ("q", q), ("probs", probs), ("logits", logits), ("thresholds", thresholds))
-             if t is not None]
-    if len(given) != 1:
-        raise ValueError("evaluate_tables() wants exactly one of policy=, q=, probs=, logits= and thresholds=")
-    kind = given[0]
+    kind = _tables.exactly_one("evaluate_tables()", policy=policy, q=q, probs=probs, logits=logits, thresholds=thresholds)
     eps = _abi.epsilon_u32(epsilon)
     if kind in ("probs", "logits", "thresholds") and eps != 0:
         raise ValueError("epsilon belongs to policy= and q=: a categorical table already says how it explores")
     if kind in ("probs", "logits"):
         src = probs if kind == "probs" else logits
-        if not (isinstance(src, torch.Tensor) and src.is_floating_point() and src.device == dev and src.dim() == 3
-                and tuple(src.shape[1:]) == (S, 4)):
+        if not (isinstance(src, torch.Tensor) and src.dim() == 3 and tuple(src.shape[1:]) == (S, 4)):
             raise ValueError("%s must be a float tensor [P, %d, 4] on layouts' device" % (kind, S))
-        if kind == "logits":
-            if not float(temperature) > 0.0:
-                raise ValueError("temperature must be > 0")
-            src = torch.softmax(src.double() / float(temperature), -1)
-        thresholds = _abi.sampling_thresholds(src.reshape(-1, 4)).view(src.shape[0], S, 4)
+        P = int(src.shape[0])                       # the source's: one shared v0 layout leaves P to the table
+        rows = src.reshape(P * S, 4)
+        thresholds = _tables.threshold_table(rows if kind == "probs" else None, rows if kind == "logits" else None, None,
+                                             temperature, P * S, 4, dev, "P=%d, G=%d" % (P, m.G)).view(P, S, 4)
     if kind == "policy":
         table, ok = policy, (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.dim() == 2
                              and tuple(policy.shape[1:]) == (S,))

@@ -127,6 +127,20 @@ def make_env(kind, variant, G, N, seed=21, step_limit=7, env_base=ENV_BASE, epoc
     return env, lay
 
 
+def bare_grid_env(monkeypatch, variant="v0", u8=False, G=5, N=8):
+    """An LmazeVecEnv that never saw a device, with only what the closed-loop methods' Python refusals read: no tuner, the
+    variant and plane flags, G, N and the host as its device.  obs is there for the recording request alone, the last
+    refusal: a call that gets as far as "obs_every must be ..." has had its table accepted.  torch's capture query needs a
+    device; it is answered here, "no"."""
+    pkg = importlib.import_module("gym-lmaze_amd")
+    env = object.__new__(pkg.LmazeVecEnv)
+    env._tuner, env._u8, env._is_v3, env.grid, env.num_envs = None, u8, variant == "v3", G, N
+    env.device = torch.device("cpu")
+    env.obs = torch.zeros((N, G, G), dtype=torch.uint8 if u8 else torch.int32)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    return env
+
+
 # ------------------------------------------------------------- one call against the oracle
 def replay(env, lay, kind, T, auto_reset, k, key, rollout, action, window=None):
     """One closed-loop rollout of env against the oracle stepped T times from the env's host_state().

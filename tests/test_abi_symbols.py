@@ -33,6 +33,62 @@ def test_header_symbols_exported(abi):
         assert hasattr(abi.lib, n), n
 
 
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "float": C.c_float, "uint8_t": C.c_uint8}
+
+
+def declared_prototypes():
+    """{name: (return type, [argument types])} of every lmaze_* prototype of the header, each type as (base, stars) with
+    const and the parameter's name dropped: ("int64_t", 0), ("LmazeParams", 1), ("void", 1)."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+
+    def ctype(decl, named):
+        words = re.findall(r"[A-Za-z_]\w*|\*", decl)
+        stars = words.count("*")
+        words = [w for w in words if w not in ("*", "const")]
+        if named:                                   # every parameter of the header carries a name
+            assert len(words) == 2, decl
+            words = words[:1]
+        assert len(words) == 1, decl
+        return words[0], stars
+
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t\*]*?)\s*\b(lmaze_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in out, name
+        args = args.strip()
+        out[name] = (ctype(ret, False), [] if args == "void" else [ctype(a, True) for a in args.split(",")])
+    return out
+
+
+def _matches(abi, declared, bound):
+    """Whether the ctypes type `bound` passes what the header's (base, stars) takes: the same kind and width."""
+    base, stars = declared
+    if stars == 0:
+        return bound is _SCALARS[base]
+    assert stars == 1, declared
+    if base in ("LmazeParams", "LmazeFovealParams", "LmazeFovealBuffers"):
+        return bound is C.POINTER(getattr(abi, base))
+    if base == "char":
+        return bound is C.c_char_p
+    return bound is C.c_void_p or (base in _SCALARS and bound is C.POINTER(_SCALARS[base]))
+
+
+def test_binding_signatures_match_header(abi):
+    """Every prototype of include/lmaze.h against what the binding declares for it: the return type, the number of
+    arguments, and each argument's kind and width.  Most CPU tests call the entries with made-up addresses and two dozen
+    positional arguments; an int32 where the header has int64_t would be silent undefined behaviour there."""
+    protos = declared_prototypes()
+    assert len(protos) == len(abi.SYMBOLS)          # a prototype the regex skipped fails here, it does not thin the test
+    assert sorted(protos) == sorted(abi.SYMBOLS)
+    for name, (ret, args) in sorted(protos.items()):
+        fn = getattr(abi.lib, name)
+        assert _matches(abi, ret, fn.restype), (name, "returns", ret, fn.restype)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(args), (name, len(args))
+        for i, (declared, bound) in enumerate(zip(args, fn.argtypes)):
+            assert _matches(abi, declared, bound), (name, i, declared, bound)
+
+
 def test_header_cites_reference_lines():
     text = open(HEADER).read()
     for needle in ("v0:146-237", "v3:220-402", "v0:217-234", "v0:246-249"):

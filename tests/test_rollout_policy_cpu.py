@@ -8,8 +8,9 @@ import re
 import subprocess
 
 import pytest
+import torch
 
-from closed_loop_ref import (fields as _fields, grid_params as _params, perenv_lds as _perenv_lds, shared_lds as _shared_lds,
+from closed_loop_ref import (bare_grid_env, fields as _fields, grid_params as _params, perenv_lds as _perenv_lds, shared_lds as _shared_lds,
                              u8_lds as _u8_lds)
 from helpers import HIPCC, kernel_usage
 
@@ -185,6 +186,125 @@ def test_epsilon_conversion(abi):
     for bad in (-1e-9, 1.0000001, float("nan"), float("inf")):
         with pytest.raises(ValueError):
             f(bad)
+
+
+# ------------------------------------------------------------- the Python surface without a device
+def test_python_argument_errors_that_need_no_device(abi, monkeypatch):
+    """What LmazeVecEnv.rollout_policy() and rollout_qlearn() refuse before they touch the device, in their order of
+    precedence, on an env object that never saw one (G = 5, N = 8; its tensors are the host's).  Every call carries what the
+    LATER refusals would object to as well, so the one that answers is the earlier one."""
+    G, N = 5, 8
+    S = G * G
+    env = bare_grid_env(monkeypatch)
+    policy, q = torch.zeros(S, dtype=torch.uint8), torch.zeros(S, 4)
+    junk = dict(policy=object(), q=object(), epsilon=2.0)                   # two tables, neither a tensor, a bad epsilon
+    # 1. stream capture and the online tuner, before T
+    with monkeypatch.context() as m:
+        m.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+        with pytest.raises(ValueError, match=r"rollout_policy\(\) is not available with a device-resident epoch or while the online"):
+            env.rollout_policy(-1, key="nope", **junk)
+        with pytest.raises(ValueError, match=r"rollout_qlearn\(\) is not available with a device-resident epoch or while the online"):
+            env.rollout_qlearn(-1, object(), epsilon=2.0)
+    env._tuner = object()
+    with pytest.raises(ValueError, match="while the online tuner runs"):
+        env.rollout_policy(-1, key="nope", **junk)
+    with pytest.raises(ValueError, match="while the online tuner runs"):
+        env.rollout_qlearn(-1, object(), epsilon=2.0)
+    env._tuner = None
+    # 2. T, before the key
+    for T in (-1, 2.5, None, True):
+        with pytest.raises(ValueError, match="T must be an int"):
+            env.rollout_policy(T, key="nope", **junk)
+        with pytest.raises(ValueError, match="T must be an int"):
+            env.rollout_qlearn(T, object(), epsilon=2.0)
+    # 3. the key, before the tables are counted
+    for key in ("nope", None, 0):
+        with pytest.raises(ValueError, match="key must be 'ball', 'goal' or 'env'"):
+            env.rollout_policy(4, key=key, **junk)
+    with pytest.raises(ValueError, match="key='goal' needs the v3 variant"):
+        env.rollout_policy(4, key="goal", **junk)
+    env._u8 = True
+    with pytest.raises(ValueError, match="key='env' needs the int32 planes"):
+        env.rollout_policy(4, key="env", **junk)
+    with pytest.raises(ValueError, match="key='env' needs the int32 planes"):
+        env.rollout_qlearn(4, object(), epsilon=2.0)
+    env._u8 = False
+    env.num_envs = (2 ** 31 - 1) // S + 1
+    with pytest.raises(ValueError, match=r"N \* G\*G <= 2\*\*31 - 1"):
+        env.rollout_policy(4, key="env", **junk)
+    with pytest.raises(ValueError, match=r"N \* G\*G <= 2\*\*31 - 1"):
+        env.rollout_qlearn(4, object(), epsilon=2.0)
+    env.num_envs = N
+    # 4. exactly one table, before either is looked at and before epsilon
+    for key in ("ball", "env"):
+        for kw in (dict(), dict(policy=object(), q=object())):
+            with pytest.raises(ValueError, match="exactly one of policy= and q="):
+                env.rollout_policy(4, key=key, epsilon=2.0, **kw)
+    # 5. q: a float tensor [S, A] on the env's device, before the table's size is asked
+    for bad in (object(), [[0.0] * 4] * S, torch.zeros(S, 4, device="meta")):
+        with pytest.raises(ValueError, match=r"q must be a float tensor \[S, A\] on cpu"):
+            env.rollout_policy(4, q=bad, epsilon=2.0)
+    for bad in (torch.zeros(S), torch.zeros(S, 4, dtype=torch.int32), torch.zeros(S, 256), torch.zeros(S, 0), torch.zeros(2, S, 4)):
+        with pytest.raises(ValueError, match=r"q must be a float tensor \[S, A\] with 1 <= A <= 255"):
+            env.rollout_policy(4, q=bad, epsilon=2.0)
+    with pytest.raises(ValueError, match=r"q must be a float tensor \[S, A\] with 1 <= A <= 255"):
+        env.rollout_policy(4, q=torch.zeros(N, S + 1, 4), key="env", epsilon=2.0)    # not [N, G*G, A]: stays 3-d
+    # 6. the table: uint8, on the device, contiguous, of the key's size -- before epsilon
+    for bad in (object(), policy.to(torch.int32), policy[:-1], torch.zeros(2 * S, dtype=torch.uint8)[::2],
+                torch.zeros(S, dtype=torch.uint8, device="meta")):
+        with pytest.raises(ValueError, match=r"policy must be a contiguous uint8 tensor of 25 entries on cpu \(key='ball', G=5\)"):
+            env.rollout_policy(4, policy=bad, epsilon=2.0)
+    with pytest.raises(ValueError, match=r"policy must be a contiguous uint8 tensor of 25 entries on cpu \(key='ball', G=5\)"):
+        env.rollout_policy(4, q=torch.zeros(S + 1, 4), epsilon=2.0)          # greedy_table(q) has a row too many
+    env._is_v3 = True
+    with pytest.raises(ValueError, match=r"of 625 entries on cpu \(key='goal', G=5\)"):
+        env.rollout_policy(4, policy=policy, key="goal", epsilon=2.0)
+    env._is_v3 = False
+    for bad in (policy, torch.zeros(S, N, dtype=torch.uint8), torch.zeros(N, S, 1, dtype=torch.uint8)):
+        with pytest.raises(ValueError, match=r"policy must be uint8 \[8, 25\] or flat \[200\] \(key='env'\)"):
+            env.rollout_policy(4, policy=bad, key="env", epsilon=2.0)
+    for bad in (object(), torch.zeros(N, S, dtype=torch.int32), torch.zeros(N, 2 * S, dtype=torch.uint8)[:, ::2]):
+        with pytest.raises(ValueError, match=r"of 200 entries on cpu \(key='env', N=8, G=5\)"):
+            env.rollout_policy(4, policy=bad, key="env", epsilon=2.0)
+    with pytest.raises(ValueError, match=r"of 200 entries on cpu \(key='env', N=8, G=5\)"):
+        env.rollout_policy(4, q=torch.zeros(N * S + 1, 4), key="env", epsilon=2.0)
+    odd = torch.zeros(N * S + 4, dtype=torch.uint8)
+    assert odd.data_ptr() % 4 == 0
+    for off in (1, 2, 3):
+        with pytest.raises(ValueError, match=r"policy must be 4-byte aligned \(key='env'\)"):
+            env.rollout_policy(4, policy=odd[off:off + N * S], key="env", epsilon=2.0)
+    # 7. epsilon, before the recording request; then that, which only an accepted table reaches
+    for key, tables in (("ball", (dict(policy=policy), dict(q=q), dict(q=torch.zeros(S, 7, dtype=torch.float64)))),
+                        ("env", (dict(policy=torch.zeros(N, S, dtype=torch.uint8)), dict(policy=torch.zeros(N * S, dtype=torch.uint8)),
+                                 dict(q=torch.zeros(N, S, 4)), dict(q=torch.zeros(N * S, 4)), dict(policy=odd[4:])))):
+        for kw in tables:
+            for bad in (-0.1, 1.5, float("nan"), 2.0):
+                with pytest.raises(ValueError, match=r"epsilon must be in \[0, 1\]"):
+                    env.rollout_policy(4, key=key, epsilon=bad, obs_every=-1, **kw)
+            with pytest.raises(ValueError, match="obs_every must be >= 0"):
+                env.rollout_policy(4, key=key, obs_every=-1, **kw)
+    with pytest.raises(ValueError, match="obs_every=0 records the final planes only"):
+        env.rollout_policy(4, policy=policy, obs_t=torch.zeros(1))
+    # rollout_qlearn(): q is the learner's own memory -- float32, contiguous, 16-byte aligned, one of two shapes, never copied
+    ql = torch.zeros(N, S, 4)
+    flat = torch.zeros(N * S * 4 + 1)
+    assert flat.data_ptr() % 16 == 0
+    for bad in (object(), None, ql.double(), ql.to(torch.int32), torch.zeros(N, S, 8)[:, :, ::2], torch.zeros(N, 4, S).transpose(1, 2),
+                torch.zeros(S, 4), torch.zeros(N, S), torch.zeros(N * S * 4), torch.zeros(N, S, 4, device="meta"),
+                flat[1:].view(N, S, 4), flat[1:].view(N * S, 4)):
+        with pytest.raises(ValueError, match=r"q must be a contiguous, 16-byte aligned float32 tensor \[8, 25, 4\] or \[200, 4\] on cpu: "
+                                             r"it is updated in place"):
+            env.rollout_qlearn(4, bad, epsilon=2.0, td_t=object())
+    for bad in (object(), torch.zeros(4, N, dtype=torch.float64), torch.zeros(3, N), torch.zeros(4, N + 1), torch.zeros(4 * N),
+                torch.zeros(4, 2 * N)[:, ::2], torch.zeros(N, 4).t(), torch.zeros(4, N, device="meta")):
+        with pytest.raises(ValueError, match=r"td_t must be a contiguous float32 tensor \[4, 8\] on cpu"):
+            env.rollout_qlearn(4, ql, epsilon=2.0, td_t=bad)
+    for good in (ql, ql.view(N * S, 4)):
+        for td in (None, torch.zeros(4, N)):
+            with pytest.raises(ValueError, match=r"epsilon must be in \[0, 1\]"):
+                env.rollout_qlearn(4, good, epsilon=2.0, td_t=td, obs_every=-1)
+            with pytest.raises(ValueError, match="obs_every must be >= 0"):
+                env.rollout_qlearn(4, good, td_t=td, obs_every=-1)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from closed_loop_ref import (explore_draw, fields as _fields, grid_params as _params, perenv_lds as _perenv_lds,
+from closed_loop_ref import (bare_grid_env, explore_draw, fields as _fields, grid_params as _params, perenv_lds as _perenv_lds,
                              shared_lds as _shared_lds, u8_lds as _u8_lds)
 from closed_loop_ref import test_numpy_philox_known_answers  # noqa: F401  (collected here: the draws below are philox's)
 from helpers import HIPCC, kernel_usage
@@ -234,6 +234,113 @@ def test_describe_refusals_and_empty_lines(abi):
     assert d(C.byref(_params(abi, "v0", 11, abi.LAYOUT_PER_ENV)), 100, 6, 1, 2, 0, 0, buf, 256) == E_LAYOUT
     assert d(C.byref(_params(abi, "v0", 3, abi.LAYOUT_SHARED)), 100, 6, 1, 2, 0, 0, buf, 256) == E_GRID
     assert abi.describe_rollout_sample(p, 0, 6) == "" and abi.describe_rollout_sample(p, 100, 0) == ""
+
+
+# ------------------------------------------------------------- the Python surface without a device
+def test_python_argument_errors_that_need_no_device(abi, monkeypatch):
+    """What LmazeVecEnv.rollout_sample() refuses before it touches the device, in its order of precedence, on an env object
+    that never saw one (G = 5, N = 8; its tensors are the host's).  Every call carries what the LATER refusals would object
+    to as well, so the one that answers is the earlier one."""
+    G, N = 5, 8
+    S = G * G
+    env = bare_grid_env(monkeypatch)
+    probs = torch.ones(S, 4)
+    thr = abi.sampling_thresholds(probs)
+    junk = dict(probs=object(), logits=object(), temperature=0.0)           # two sources, neither a tensor, a bad temperature
+    # 1. stream capture and the online tuner, before T
+    with monkeypatch.context() as m:
+        m.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+        with pytest.raises(ValueError, match="device-resident epoch or while the online tuner runs"):
+            env.rollout_sample(-1, key="nope", **junk)
+    env._tuner = object()
+    with pytest.raises(ValueError, match="device-resident epoch or while the online tuner runs"):
+        env.rollout_sample(-1, key="nope", **junk)
+    env._tuner = None
+    # 2. T, before the key
+    for T in (-1, 2.5, None, True):
+        with pytest.raises(ValueError, match="T must be an int"):
+            env.rollout_sample(T, key="nope", **junk)
+    # 3. the key, before the sources are counted
+    for key in ("nope", None, 0):
+        with pytest.raises(ValueError, match="key must be 'ball', 'goal' or 'env'"):
+            env.rollout_sample(4, key=key, **junk)
+    with pytest.raises(ValueError, match="key='goal' needs the v3 variant"):
+        env.rollout_sample(4, key="goal", **junk)
+    env._u8 = True
+    with pytest.raises(ValueError, match="key='env' needs the int32 planes"):
+        env.rollout_sample(4, key="env", **junk)
+    env._u8 = False
+    env.num_envs = (2 ** 31 - 1) // S + 1
+    with pytest.raises(ValueError, match=r"N \* G\*G <= 2\*\*31 - 1"):
+        env.rollout_sample(4, key="env", **junk)
+    env.num_envs = (2 ** 31 - 1) // S                                        # the largest N the key still fits
+    with pytest.raises(ValueError, match="exactly one of"):
+        env.rollout_sample(4, key="env", **junk)
+    env.num_envs = N
+    # 4. exactly one source, before any is looked at
+    for kw in (dict(), dict(probs=object(), logits=object()), dict(probs=object(), thresholds=object()),
+               dict(logits=object(), thresholds=object()), dict(probs=object(), logits=object(), thresholds=object())):
+        for key in ("ball", "env"):
+            with pytest.raises(ValueError, match="exactly one of probs=, logits= and thresholds="):
+                env.rollout_sample(4, key=key, temperature=0.0, **kw)
+    # 5. the source's shape, dtype and device, before the temperature
+    meta = torch.ones(S, 4, device="meta")
+    for name in ("probs", "logits"):
+        for bad in (object(), [[0.25] * 4] * S, torch.ones(S, 5), torch.ones(S - 1, 4), torch.ones(S * 4), torch.ones(1, S, 4),
+                    torch.ones(N * S, 4), torch.ones(S, 4, dtype=torch.int32), torch.ones(S, 4, dtype=torch.int64), meta):
+            with pytest.raises(ValueError, match=r"%s must be a float tensor \[25, 4\] on cpu \(key='ball', G=5\)" % name):
+                env.rollout_sample(4, temperature=0.0, **{name: bad})
+        for bad in (torch.ones(S, 4), torch.ones(N, S, 5), torch.ones(N * S, 4, dtype=torch.int32),
+                    torch.ones(N, 4, S).transpose(1, 2)):                    # [N, G*G, 4], but not the flat table's memory
+            with pytest.raises(ValueError, match=r"%s must be a float tensor \[200, 4\] on cpu \(key='env', G=5\)" % name):
+                env.rollout_sample(4, key="env", temperature=0.0, **{name: bad})
+    env._is_v3 = True
+    with pytest.raises(ValueError, match=r"probs must be a float tensor \[625, 4\] on cpu \(key='goal', G=5\)"):
+        env.rollout_sample(4, key="goal", probs=probs)
+    env._is_v3 = False
+    # 6. the temperature: logits only, and after the logits' own check
+    for bad in (0, 0.0, -1, float("nan")):
+        with pytest.raises(ValueError, match="temperature must be > 0"):
+            env.rollout_sample(4, logits=probs, temperature=bad, obs_every=-1)
+        with pytest.raises(ValueError, match="obs_every must be >= 0"):      # not read with probs= or thresholds=
+            env.rollout_sample(4, probs=probs, temperature=bad, obs_every=-1)
+        with pytest.raises(ValueError, match="obs_every must be >= 0"):
+            env.rollout_sample(4, thresholds=thr, temperature=bad, obs_every=-1)
+    # 7. the converter's own refusals, before the recording request
+    with pytest.raises(ValueError, match="finite and non-negative"):
+        env.rollout_sample(4, probs=-probs, obs_every=-1)
+    with pytest.raises(ValueError, match="positive, finite sum"):
+        env.rollout_sample(4, probs=0 * probs, obs_every=-1)
+    # 8. thresholds: dtype, shape, device, contiguity, 16-byte alignment -- one refusal, before the recording request
+    flat = torch.zeros(S * 4 + 1, dtype=torch.int32)
+    assert flat.data_ptr() % 16 == 0
+    for bad in (object(), thr.view(torch.int32).to(torch.int64), thr.view(torch.int32).float(), thr.view(torch.int32).to(torch.uint8),
+                thr.view(torch.int32)[:, :3].contiguous(), thr.view(torch.int32)[:-1], thr.view(torch.int32).reshape(-1),
+                torch.zeros(S, 4, dtype=torch.int32, device="meta"), torch.zeros(S, 8, dtype=torch.int32)[:, ::2],
+                flat[1:].view(S, 4)):
+        with pytest.raises(ValueError, match=r"thresholds must be a contiguous, 16-byte aligned uint32 tensor \[25, 4\] on cpu "
+                                             r"\(key='ball', G=5\)"):
+            env.rollout_sample(4, thresholds=bad, obs_every=-1)
+    # ... and what it takes: uint32 or int32, the caller's memory; for key="env" flat rows or the [N, G*G, 4] view of them
+    envthr = abi.sampling_thresholds(torch.ones(N * S, 4))
+    for key, good in (("ball", thr), ("ball", thr.view(torch.int32)), ("env", envthr), ("env", envthr.view(N, S, 4)),
+                      ("env", envthr.view(torch.int32).view(N, S, 4))):
+        with pytest.raises(ValueError, match="obs_every must be >= 0"):
+            env.rollout_sample(4, key=key, thresholds=good, obs_every=-1)
+    for name in ("probs", "logits"):
+        for good in (torch.ones(N * S, 4), torch.ones(N, S, 4), torch.ones(N, S, 4, dtype=torch.float64)):
+            with pytest.raises(ValueError, match="obs_every must be >= 0"):
+                env.rollout_sample(4, key="env", obs_every=-1, **{name: good})
+    for bad in (torch.zeros(N, S, 8, dtype=torch.int32)[:, :, ::2], torch.zeros(N, 4, S, dtype=torch.int32).transpose(1, 2),
+                envthr.view(torch.int32).view(N, S, 4)[:-1], thr):
+        with pytest.raises(ValueError, match=r"thresholds must be a contiguous, 16-byte aligned uint32 tensor \[200, 4\] on cpu "
+                                             r"\(key='env', G=5\)"):
+            env.rollout_sample(4, key="env", thresholds=bad, obs_every=-1)
+    # 9. the recording request, last
+    with pytest.raises(ValueError, match="obs_every=0 records the final planes only"):
+        env.rollout_sample(4, thresholds=thr, obs_t=torch.zeros(1))
+    with pytest.raises(ValueError, match="obs_every must be an int"):
+        env.rollout_sample(4, thresholds=thr, obs_every=None)
 
 
 # ------------------------------------------------------------- the host conversion
