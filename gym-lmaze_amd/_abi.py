@@ -127,12 +127,13 @@ def _signatures():
         "lmaze_solve": [P, vp, vp, i64, f32, i32] + [vp] * 7,
         "lmaze_score": [P, vp, vp, i64] + [vp] * 6,
         "lmaze_evaluate": [P, vp, vp, i64, vp, vp, u32, vp, f32, i32, f32] + [vp] * 6,
+        "lmaze_occupancy": [P, vp, vp, i64, vp, vp, u32, vp, vp, f32, i32, f32] + [vp] * 6,
         "lmaze_generate": [i32, i64, u64, i64, u32, vp, vp, vp],
         # what a call would launch, as a line of text
         "lmaze_describe_step": describe([P], 2),
         **same("lmaze_describe_rollout lmaze_describe_env_rollout_qlearn", describe([P], 4)),
         **same("lmaze_describe_rollout_policy lmaze_describe_rollout_sample lmaze_describe_env_rollout", describe([P], 5)),
-        **same("lmaze_describe_solve lmaze_describe_score lmaze_describe_evaluate", describe([P], 0)),
+        **same("lmaze_describe_solve lmaze_describe_score lmaze_describe_evaluate lmaze_describe_occupancy", describe([P], 0)),
         "lmaze_describe_foveal_step": describe([FP], 1),
         **same("lmaze_describe_foveal_rollout lmaze_describe_foveal_rollout_policy lmaze_describe_foveal_rollout_sample "
                "lmaze_describe_v5_rollout_policy lmaze_describe_v5_rollout_sample", describe([FP], 3)),
@@ -301,6 +302,12 @@ def describe_evaluate(params, problems):
     LmazeParams (lmaze_describe_evaluate): "evaluate_kernel<v0, wave, 2> ..." while G*G <= 256, "evaluate_kernel<v0, workgroup,
     4> ..." above -- the plan is lmaze_solve's; "" for no problem."""
     return _describe("lmaze_describe_evaluate", C.byref(params), int(problems))
+
+
+def describe_occupancy(params, problems):
+    """The kernel form / grid / LDS / problems per workgroup lmaze_occupancy would queue for `problems` tables with these
+    LmazeParams (lmaze_describe_occupancy): "occupancy_kernel<v0, wave, 2> ..."; the plan is lmaze_solve's."""
+    return _describe("lmaze_describe_occupancy", C.byref(params), int(problems))
 
 
 def describe_generate(G, mazes):

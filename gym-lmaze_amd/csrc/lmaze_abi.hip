@@ -694,7 +694,7 @@ static int check_solve_params(const LmazeParams* p) {
     return 0;
 }
 
-// The head lmaze_solve, lmaze_score and lmaze_evaluate judge alike, before anything of their own: params and layouts, the
+// The head lmaze_solve, lmaze_score, lmaze_evaluate and lmaze_occupancy judge alike, before anything of their own: params and layouts, the
 // params' values, v3's goal
 static int check_problems_head(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy) {
     if (!params || !layouts) return LMAZE_E_NULL;
@@ -782,7 +782,36 @@ int lmaze_evaluate(const LmazeParams* params, const uint8_t* layouts, const int3
     return (int)launch_evaluate(params->variant, a, (hipStream_t)stream);
 }
 
-// what the three lmaze_describe_* judge and print: `kernel` names the family's kernel
+int lmaze_occupancy(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
+                    const float* q, uint32_t epsilon_u32, const uint32_t* thresholds, const float* start, float gamma, int32_t sweeps,
+                    float tol, const float* d_init, float* d_out, float* dsa_out, int32_t* sweeps_run, float* delta, void* stream) {
+    int rc = check_problems_head(params, layouts, goal_xy);
+    if (rc) return rc;
+    if (!d_out && !dsa_out) return LMAZE_E_NULL;
+    if ((policy ? 1 : 0) + (q ? 1 : 0) + (thresholds ? 1 : 0) != 1) return LMAZE_E_NULL;
+    if (!start) return LMAZE_E_NULL;
+    rc = check_problems_tail(params, goal_xy, problems, sweeps >= 1,
+                             !(misaligned(thresholds, 16) || misaligned(q, 16) || misaligned(dsa_out, 16) || misaligned(start, 4) ||
+                               misaligned(d_init, 4) || misaligned(d_out, 4) || misaligned(sweeps_run, 4) || misaligned(delta, 4)));
+    if (rc || problems == 0) return rc;
+    OccupancyArgs a = problem_args<OccupancyArgs>(params, layouts, goal_xy, problems);
+    a.policy = policy;
+    a.q = reinterpret_cast<const float4*>(q);
+    a.thresholds = reinterpret_cast<const uint4*>(thresholds);
+    a.start = start;
+    a.d_init = d_init;
+    a.d_out = d_out;
+    a.dsa_out = reinterpret_cast<float4*>(dsa_out);
+    a.sweeps_run = sweeps_run;
+    a.delta = delta;
+    a.sweeps = sweeps;
+    a.epsilon = epsilon_u32;
+    a.gamma = gamma;
+    a.tol = tol;
+    return (int)launch_occupancy(params->variant, a, (hipStream_t)stream);
+}
+
+// what the four lmaze_describe_* judge and print: `kernel` names the family's kernel
 static int describe_problems(const LmazeParams* params, int64_t problems, char* text_host, int32_t len, const char* kernel) {
     if (!params || !text_host || len < 1) return LMAZE_E_NULL;
     text_host[0] = 0;
@@ -803,6 +832,10 @@ int lmaze_describe_score(const LmazeParams* params, int64_t problems, char* text
 
 int lmaze_describe_evaluate(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
     return describe_problems(params, problems, text_host, len, "evaluate_kernel");
+}
+
+int lmaze_describe_occupancy(const LmazeParams* params, int64_t problems, char* text_host, int32_t len) {
+    return describe_problems(params, problems, text_host, len, "occupancy_kernel");
 }
 
 // What lmaze_generate and lmaze_describe_generate judge of the grid side and of the counts, in the header's order

@@ -274,7 +274,27 @@ struct EvaluateArgs {
     float gamma, tol, reward_wall, reward_move, reward_goal;
 };
 hipError_t launch_evaluate(int variant, const EvaluateArgs& a, hipStream_t s);
-// the eight fields SolveArgs, ScoreArgs and EvaluateArgs share, from an entry's checked arguments; the rest zero
+// The discounted occupancy of the same tables (lmaze_occupancy, lmaze_occupancy.hip): the fixed point of the transpose of the
+// operator lmaze_evaluate sweeps, from a start distribution -- the same model, the same probabilities, the same plan.
+struct OccupancyArgs {
+    const uint8_t* layouts;   // [G*G] shared or [problems*G*G]
+    const int2* goal;         // v3: [problems]
+    const uint8_t* policy;    // exactly one of policy, q, thresholds, as EvaluateArgs'
+    const float4* q;
+    const uint4* thresholds;
+    const float* start;       // [problems, G*G]: the mass every sweep adds
+    const float* d_init;      // [problems, G*G] or null (0)
+    float* d_out;             // [problems, G*G] or null
+    float4* dsa_out;          // [problems, G*G] or null: d(s) * p_a(s)
+    int32_t* sweeps_run;      // [problems] or null
+    float* delta;             // [problems] or null
+    int64_t problems;
+    int32_t grid, sweeps, per_env;
+    uint32_t epsilon;         // as PolicyTable's
+    float gamma, tol, reward_wall, reward_move, reward_goal;
+};
+hipError_t launch_occupancy(int variant, const OccupancyArgs& a, hipStream_t s);
+// the eight fields SolveArgs, ScoreArgs, EvaluateArgs and OccupancyArgs share, from an entry's checked arguments; the rest zero
 template <class Args>
 inline Args problem_args(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems) {
     Args a{};

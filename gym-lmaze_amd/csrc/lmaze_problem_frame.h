@@ -1,8 +1,9 @@
-// lmaze_problem_frame.h -- a problem from its indices to its descriptors: the opening lines of solve_kernel, score_kernel and
-// evaluate_kernel (lmaze_solve.hip, lmaze_score.hip, lmaze_evaluate.hip), included into each as lmaze_rollout_body.h is into
-// its kernels: through a __device__ function the kernels compiled to other register allocations, included they keep their code.
-// In scope: `a` (SolveArgs, ScoreArgs or EvaluateArgs: layouts, goal, problems, grid, per_env and the three rewards) and the
-// compile-time VARIANT, CPL, WAVE.  The kernel defines
+// lmaze_problem_frame.h -- a problem from its indices to its descriptors: the opening lines of solve_kernel, score_kernel,
+// evaluate_kernel and occupancy_kernel (lmaze_solve.hip, lmaze_score.hip, lmaze_evaluate.hip, lmaze_occupancy.hip), included
+// into each as lmaze_rollout_body.h is into its kernels: through a __device__ function the kernels compiled to other register
+// allocations, included they keep their code.
+// In scope: `a` (SolveArgs, ScoreArgs, EvaluateArgs or OccupancyArgs: layouts, goal, problems, grid, per_env and the three
+// rewards) and the compile-time VARIANT, CPL, WAVE.  The kernel defines
 //   PROBLEM_LDS              its extern __shared__ bytes: per workgroup two buffers of SP words for each of its PPW problems,
 //                            the StepArgs the rule is asked with, and the vote words (SOLVE_VOTE_BYTES, workgroup form only)
 //   PROBLEM_WORD             what a buffer's word is to it (float, int)
@@ -11,7 +12,8 @@
 // and may define, each for a line that one kernel alone has there,
 //   PROBLEM_LOCALS           a declaration behind the early return (score_kernel: whether it has a table)
 //   PROBLEM_BEFORE_SYNC      a statement before the first sync, when vote stands (score_kernel clears its sums there)
-//   PROBLEM_AT_CELL(j)       a statement for each of the lane's cells, s < S or not (evaluate_kernel: no probabilities yet)
+//   PROBLEM_AT_CELL(j)       a statement for each of the lane's cells, s < S or not (evaluate_kernel, occupancy_kernel: no
+//                            probabilities yet)
 // and finds behind it TPP, PPW, SP, lane, wave, t, p, buf, vote, G, S, base and desc[CPL], the second buffer free again.  The
 // hooks keep each kernel's global loads, and every other line of it, where they were between the syncs.  Not a header of its own.
 #if !defined(PROBLEM_LDS) || !defined(PROBLEM_WORD) || !defined(PROBLEM_AT_COPY) || !defined(PROBLEM_AT_DESC)

@@ -83,7 +83,8 @@ __device__ __forceinline__ void solve_sync() {
     }
 }
 
-// One launch site for the three families.  Family: its Args type and kernel<VARIANT, CPL, WAVE>(), the instantiation's address.
+// One launch site for the four families (solve, score, evaluate, occupancy).  Family: its Args type and
+// kernel<VARIANT, CPL, WAVE>(), the instantiation's address.
 template <class Family, int VARIANT, int CPL, bool WAVE>
 static hipError_t problem_launch(const typename Family::Args& a, const SolvePlan& p, hipStream_t s) {
     hipLaunchKernelGGL((Family::template kernel<VARIANT, CPL, WAVE>()), dim3((unsigned)p.grid), dim3(LMAZE_BLOCK), (size_t)p.lds_bytes, s, a);

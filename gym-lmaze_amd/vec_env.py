@@ -663,6 +663,56 @@ class LmazeVecEnv(VecEnvBase):
                             sweeps=sweeps, tol=tol, rewards=self.rewards, v_init=v_init, validate=False, **tables)
         return _unbatch(t, key, single, ("sweeps_run", "delta"))
 
+    def _occupancy_start(self, start, key, goals, P, single):
+        """occupancy()'s start as float32[P, G*G]: "reset", "state" (refused for key="goal") or a tensor of that many elements"""
+        if not isinstance(start, torch.Tensor):
+            if start not in ("reset", "state"):
+                raise ValueError("start must be 'reset', 'state' or a tensor")
+            if start == "state" and key == "goal":
+                raise ValueError("start='state' has no meaning for key='goal': its problems are goal cells, not envs")
+        S = self.grid * self.grid
+        if isinstance(start, torch.Tensor):
+            if start.numel() != P * S:
+                raise ValueError("start must be a float32 tensor of %d problems x %d states" % (P, S))
+            return start.reshape(P, S)
+        if start == "reset":
+            start = reset_distribution(self.layout, self.variant, goals)
+            return start if start.shape[0] == P else start.expand(P, S).contiguous()
+        cells = self.state_keys("ball").long()
+        if single:                                   # the envs' histogram on the one problem
+            return (torch.bincount(cells, minlength=S).to(torch.float32) / float(self.num_envs)).reshape(1, S)
+        start = torch.zeros((P, S), dtype=torch.float32, device=self.device)
+        start[torch.arange(P, device=self.device), cells] = 1.0
+        return start
+
+    def occupancy(self, policy=None, q=None, epsilon=0.0, probs=None, logits=None, temperature=1.0, thresholds=None, key="ball",
+                  goal=None, start="reset", gamma=0.99, sweeps=4096, tol=0.0, d_init=None):
+        """WHERE the table a closed-loop rollout runs spends its discounted time on this env's own maze(s), exactly, in ONE
+        launch (occupancy_tables(), include/lmaze.h lmaze_occupancy): evaluate()'s adjoint.  The table inputs, the problems
+        (key=, goal=) and the shapes are evaluate()'s; d is shaped like its v and d_sa like its q.
+        start  "reset": reset_distribution(), the law of the cell reset() places the ball on;
+               "state": the envs' current ball cells -- one-hot per problem where the problems are the envs (key="env", per-env
+               layouts), their histogram / N on the one problem of a shared layout with key="ball"; refused for key="goal";
+               or a float32 tensor shaped like evaluate()'s v.
+        With evaluate() of the same table, (start * v).sum(-1) = (d_sa * r).sum() is the expected return.
+        d_init: float32 [problems, G*G].  Returns OccupancyTables(d, d_sa, sweeps_run, delta)."""
+        self._problem_key(key)
+        tables = {"policy": policy, "q": q, "probs": probs, "logits": logits, "thresholds": thresholds}
+        name = _tables.exactly_one("occupancy()", **tables)
+        goals, P, single = self._problems("occupancy", key, goal)
+        S = self.grid * self.grid
+        table = tables[name]
+        width = 1 if name == "policy" else 4
+        if not isinstance(table, torch.Tensor) or table.numel() != P * S * width:
+            raise ValueError("%s must be a tensor of %d problems x %d states%s" % (name, P, S, "" if width == 1 else " x 4"))
+        tables[name] = table.reshape((P, S) if width == 1 else (P, S, 4))
+        start = self._occupancy_start(start, key, goals, P, single)
+        if isinstance(d_init, torch.Tensor) and d_init.numel() == P * S:
+            d_init = d_init.reshape(P, S)
+        t = occupancy_tables(self.layout, start=start, epsilon=epsilon, temperature=temperature, variant=self.variant, goals=goals,
+                             gamma=gamma, sweeps=sweeps, tol=tol, rewards=self.rewards, d_init=d_init, validate=False, **tables)
+        return _unbatch(t, key, single, ("sweeps_run", "delta"))
+
     def capture_rollout(self, actions, auto_reset=False, obs_t=None, obs_every=None):
         """rollout(actions, auto_reset) captured into ONE hipGraph (see VecEnvBase._capture); call .replay().  Recording
         observations (obs_t / obs_every) is not captured: ValueError."""
@@ -918,10 +968,10 @@ def _check_sweeps(sweeps):
         raise ValueError("sweeps must be an int >= 1")
 
 
-def _check_v_init(v_init, dev, P, S):
+def _check_v_init(v_init, dev, P, S, name="v_init"):
     if v_init is not None and not (isinstance(v_init, torch.Tensor) and v_init.dtype == torch.float32 and v_init.device == dev
                                    and v_init.is_contiguous() and tuple(v_init.shape) == (P, S)):
-        raise ValueError("v_init must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
+        raise ValueError("%s must be a contiguous float32[%d, %d] tensor on layouts' device" % (name, P, S))
 
 
 def _alloc_outputs(shapes, outputs, dev):
@@ -1022,6 +1072,41 @@ def score_tables(layouts, policy=None, q=None, variant="v0", goals=None, rewards
     return ScoredTables(**out)
 
 
+def _policy_table(m, kind, goals, policy, q, epsilon, probs, logits, temperature, thresholds):
+    """The one table of an evaluate_tables() / occupancy_tables() call on the mazes m, checked; kind is what _tables.exactly_one
+    named.  Returns (kind, table, epsilon_u32, P): kind "policy", "q" or "thresholds" -- probs= and logits= converted as
+    rollout_sample() converts them -- and P from the goals, the layouts or the table (_Mazes.problems)."""
+    S, dev = m.S, m.dev
+    eps = _abi.epsilon_u32(epsilon)
+    if kind in ("probs", "logits", "thresholds") and eps != 0:
+        raise ValueError("epsilon belongs to policy= and q=: a categorical table already says how it explores")
+    if kind in ("probs", "logits"):
+        src = probs if kind == "probs" else logits
+        if not (isinstance(src, torch.Tensor) and src.dim() == 3 and tuple(src.shape[1:]) == (S, 4)):
+            raise ValueError("%s must be a float tensor [P, %d, 4] on layouts' device" % (kind, S))
+        P = int(src.shape[0])                       # the source's: one shared v0 layout leaves P to the table
+        rows = src.reshape(P * S, 4)
+        thresholds = _tables.threshold_table(rows if kind == "probs" else None, rows if kind == "logits" else None, None,
+                                             temperature, P * S, 4, dev, "P=%d, G=%d" % (P, m.G)).view(P, S, 4)
+    if kind == "policy":
+        table, ok = policy, (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.dim() == 2
+                             and tuple(policy.shape[1:]) == (S,))
+    elif kind == "q":
+        table, ok = q, (isinstance(q, torch.Tensor) and q.dtype == torch.float32 and q.dim() == 3 and tuple(q.shape[1:]) == (S, 4)
+                        and q.data_ptr() % 16 == 0)
+    else:
+        table, ok = thresholds, (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
+                                 and thresholds.dim() == 3 and tuple(thresholds.shape[1:]) == (S, 4)
+                                 and thresholds.data_ptr() % 16 == 0)
+    if not (ok and table.device == dev and table.is_contiguous()):
+        raise ValueError("policy must be a contiguous uint8[P, %d], q a contiguous float32[P, %d, 4] and thresholds a contiguous, "
+                         "16-byte aligned uint32[P, %d, 4] tensor on layouts' device" % (S, S, S))
+    P = m.problems(goals, table)
+    if int(table.shape[0]) != P:
+        raise ValueError("the table has %d problems, the mazes %d" % (int(table.shape[0]), P))
+    return ("thresholds" if kind in ("probs", "logits") else kind), table, eps, P
+
+
 class EvaluatedTables(collections.namedtuple("EvaluatedTables", "q v sweeps_run delta")):
     """What evaluate_tables() returns: q float32[P, S, 4] (Q^pi), v float32[P, S] (V^pi), sweeps_run int32[P], delta
     float32[P]; an output that was not asked for is None."""
@@ -1061,33 +1146,7 @@ def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logit
     m = _Mazes.of(layouts, variant, validate)
     S, dev = m.S, m.dev
     kind = _tables.exactly_one("evaluate_tables()", policy=policy, q=q, probs=probs, logits=logits, thresholds=thresholds)
-    eps = _abi.epsilon_u32(epsilon)
-    if kind in ("probs", "logits", "thresholds") and eps != 0:
-        raise ValueError("epsilon belongs to policy= and q=: a categorical table already says how it explores")
-    if kind in ("probs", "logits"):
-        src = probs if kind == "probs" else logits
-        if not (isinstance(src, torch.Tensor) and src.dim() == 3 and tuple(src.shape[1:]) == (S, 4)):
-            raise ValueError("%s must be a float tensor [P, %d, 4] on layouts' device" % (kind, S))
-        P = int(src.shape[0])                       # the source's: one shared v0 layout leaves P to the table
-        rows = src.reshape(P * S, 4)
-        thresholds = _tables.threshold_table(rows if kind == "probs" else None, rows if kind == "logits" else None, None,
-                                             temperature, P * S, 4, dev, "P=%d, G=%d" % (P, m.G)).view(P, S, 4)
-    if kind == "policy":
-        table, ok = policy, (isinstance(policy, torch.Tensor) and policy.dtype == torch.uint8 and policy.dim() == 2
-                             and tuple(policy.shape[1:]) == (S,))
-    elif kind == "q":
-        table, ok = q, (isinstance(q, torch.Tensor) and q.dtype == torch.float32 and q.dim() == 3 and tuple(q.shape[1:]) == (S, 4)
-                        and q.data_ptr() % 16 == 0)
-    else:
-        table, ok = thresholds, (isinstance(thresholds, torch.Tensor) and thresholds.dtype in (torch.uint32, torch.int32)
-                                 and thresholds.dim() == 3 and tuple(thresholds.shape[1:]) == (S, 4)
-                                 and thresholds.data_ptr() % 16 == 0)
-    if not (ok and table.device == dev and table.is_contiguous()):
-        raise ValueError("policy must be a contiguous uint8[P, %d], q a contiguous float32[P, %d, 4] and thresholds a contiguous, "
-                         "16-byte aligned uint32[P, %d, 4] tensor on layouts' device" % (S, S, S))
-    P = m.problems(goals, table)
-    if int(table.shape[0]) != P:
-        raise ValueError("the table has %d problems, the mazes %d" % (int(table.shape[0]), P))
+    kind, table, eps, P = _policy_table(m, kind, goals, policy, q, epsilon, probs, logits, temperature, thresholds)
     _check_sweeps(sweeps)
     rewards = m.rewards(rewards)
     outputs = tuple(outputs)
@@ -1101,6 +1160,97 @@ def evaluate_tables(layouts, policy=None, q=None, epsilon=0.0, probs=None, logit
               table.data_ptr() if kind not in ("policy", "q") else None, float(gamma), int(sweeps), float(tol),
               None if v_init is None else v_init.data_ptr()), out)
     return EvaluatedTables(**out)
+
+
+class OccupancyTables(collections.namedtuple("OccupancyTables", "d d_sa sweeps_run delta")):
+    """What occupancy_tables() returns: d float32[P, S] (the discounted state occupancy), d_sa float32[P, S, 4] (d(s) * p_a(s)),
+    sweeps_run int32[P], delta float32[P]; an output that was not asked for is None."""
+    __slots__ = ()
+
+
+OCCUPANCY_OUTPUTS = ("d", "d_sa", "sweeps_run", "delta")
+
+
+def reset_distribution(layouts, variant="v0", goals=None):
+    """The law of the ball cell reset() draws, float32[P, G*G]: uniform over the cells include/lmaze.h lmaze_reset accepts --
+    v0: interior, not 'W', not 'X'; v3: interior, not 'W', not the problem's goal (goals int [P, 2]; with a [G, G] layout P
+    is goals' length, for v0 it is 1).  A problem without an accepted cell gets a row of zeros.  Plain torch, on layouts'
+    device, which need not be a GPU."""
+    if variant not in ("v0", "v3"):
+        raise ValueError("reset_distribution() knows the grid variants 'v0' and 'v3'")
+    if not (isinstance(layouts, torch.Tensor) and layouts.dtype == torch.uint8 and layouts.dim() in (2, 3)
+            and layouts.shape[-1] == layouts.shape[-2] and layouts.shape[-1] >= 3):
+        raise ValueError("layouts must be a uint8 tensor [G,G] or [P,G,G]")
+    G = int(layouts.shape[-1])
+    lay = layouts.reshape(-1, G, G)
+    ok = lay != ord("W")
+    ok[:, 0, :] = ok[:, -1, :] = ok[:, :, 0] = ok[:, :, -1] = False
+    if variant == "v3":
+        if not (isinstance(goals, torch.Tensor) and goals.dim() == 2 and goals.shape[1] == 2 and goals.device == layouts.device
+                and (layouts.dim() == 2 or goals.shape[0] == lay.shape[0])):
+            raise ValueError("goals must be an int tensor [P,2] on layouts' device (v3)")
+        g = goals.long()
+        ok = ok.reshape(-1, G * G).expand(g.shape[0], G * G).clone()
+        rows = torch.nonzero((g[:, 0] >= 0) & (g[:, 0] < G) & (g[:, 1] >= 0) & (g[:, 1] < G)).reshape(-1)
+        ok[rows, g[rows, 0] * G + g[rows, 1]] = False
+    else:
+        if goals is not None:
+            raise ValueError("goals= belongs to v3: v0's goal is the layout's 'X'")
+        ok = (ok & (lay != ord("X"))).reshape(-1, G * G)
+    n = ok.sum(1, keepdim=True).clamp(min=1)
+    return (ok.to(torch.float32) / n.to(torch.float32)).contiguous()
+
+
+def _check_start(start, dev, P, S, validate):
+    _check_v_init(start, dev, P, S, "start")
+    if start is None:
+        raise ValueError("start must be a contiguous float32[%d, %d] tensor on layouts' device" % (P, S))
+    if validate and not bool(((start >= 0) & torch.isfinite(start)).all()):
+        raise ValueError("start holds a negative or non-finite entry")
+
+
+def occupancy_tables(layouts, start=None, policy=None, q=None, epsilon=0.0, probs=None, logits=None, temperature=1.0, thresholds=None,
+                     variant="v0", goals=None, gamma=0.99, sweeps=4096, tol=0.0, rewards=None, d_init=None,
+                     outputs=OCCUPANCY_OUTPUTS, validate=True):
+    """Exact discounted occupancy on the GPU: where the stochastic table a closed-loop rollout would run spends its discounted
+    time, d = start + gamma * P_pi^T d, for every maze, in ONE launch (include/lmaze.h lmaze_occupancy) -- evaluate_tables()'s
+    adjoint, over the same model and the same probabilities.
+    layouts, the five table inputs, epsilon, temperature, variant, goals, rewards, gamma, sweeps, tol   as evaluate_tables().
+    start    float32 [P, G*G] on layouts' device: the mass every sweep adds; need not sum to 1.  None: reset_distribution(),
+             the law of the cell reset() places the ball on.
+    d_init   float32 [P, G*G] warm start; default 0, from which a non-negative start makes every sweep monotone and the exact
+             stop certain.
+    outputs  some of "d", "d_sa", "sweeps_run", "delta"; at least one of the first two.
+    With evaluate_tables() of the same table: J = (start * v).sum(-1) = (d_sa * r).sum() is the expected return per maze, and
+    d[..., None] * p * (q - v[..., None]) / temperature the exact gradient of J in the logits, where no pair of the state is
+    excluded.  What it is and is not: as evaluate_tables() -- the grid variants only; the infinite-horizon discounted problem;
+    mass on v0's sticky pairs is renormalised over the usable ones; mass on a terminal pair is absorbed; float32 Jacobi with
+    every operation rounded on its own, so a float32 numpy loop reproduces every bit.  validate=False skips the layouts' check
+    and the check that start has no negative or non-finite entry.
+    Returns OccupancyTables(d, d_sa, sweeps_run, delta)."""
+    kind = _tables.exactly_one("occupancy_tables()", policy=policy, q=q, probs=probs, logits=logits, thresholds=thresholds)
+    m = _Mazes.of(layouts, variant, validate)
+    S, dev = m.S, m.dev
+    kind, table, eps, P = _policy_table(m, kind, goals, policy, q, epsilon, probs, logits, temperature, thresholds)
+    _check_sweeps(sweeps)
+    rewards = m.rewards(rewards)
+    outputs = tuple(outputs)
+    if not set(outputs) <= set(OCCUPANCY_OUTPUTS) or not set(outputs) & {"d", "d_sa"}:
+        raise ValueError("outputs must name some of %s, at least one of d, d_sa" % (OCCUPANCY_OUTPUTS,))
+    if start is None:
+        start = reset_distribution(m.layouts, variant, goals)
+        if start.shape[0] != P:                     # one shared v0 layout under P tables
+            start = start.expand(P, S).contiguous()
+    else:
+        _check_start(start, dev, P, S, validate)
+    _check_v_init(d_init, dev, P, S, "d_init")
+    out = _alloc_outputs({"d": ((P, S), torch.float32), "d_sa": ((P, S, 4), torch.float32), "sweeps_run": ((P,), torch.int32),
+                          "delta": ((P,), torch.float32)}, outputs, dev)
+    m.launch("lmaze_occupancy", rewards, goals, P,
+             (table.data_ptr() if kind == "policy" else None, table.data_ptr() if kind == "q" else None, eps,
+              table.data_ptr() if kind == "thresholds" else None, start.data_ptr(), float(gamma), int(sweeps), float(tol),
+              None if d_init is None else d_init.data_ptr()), out)
+    return OccupancyTables(**out)
 
 
 def _validate_on_device(lay, need_goal=True):

@@ -829,6 +829,60 @@ int lmaze_evaluate(const LmazeParams* params, const uint8_t* layouts, const int3
 int lmaze_describe_evaluate(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
 
 /*
+ * EXACT DISCOUNTED OCCUPANCY on the grid mazes: where the stochastic table lmaze_evaluate values spends its discounted time,
+ * given where episodes start, in ONE launch; no reference counterpart.  lmaze_evaluate's adjoint: that propagates values
+ * backward, V = r + gamma P V; this propagates mass forward, d = start + gamma P^T d.  With it the expected return of a table
+ * is one dot product, <start, V> = <d_sa, r>, and the exact policy gradient of a softmax table is d(s) p_a(s) (Q(s,a) - V(s)).
+ * The problems, the model, the layout modes, the goals, the rewards and the three policy inputs are lmaze_evaluate's,
+ * unchanged: exactly one of policy or q (with epsilon_u32) or thresholds is given, and the probabilities are
+ * p_a = fl(fl(w'_a) / fl(W)) with the weight on excluded pairs renormalised over the usable ones, computed once per state.
+ * In the model a usable pair (s, a) that is not terminal leads to next(s, a): s + step(a) when the ball moves (the step leaves
+ * it on another cell), else s; step(a) = -G, +G, -1, +1 for a = 0, 1, 2, 3.  A terminal pair absorbs its mass; an excluded
+ * pair carries none.
+ * For a cell c that is not 'W', computed once before the first sweep:
+ *   win[a]  = p_a(c - step(a)) if that cell is on the grid -- judged by coordinates: for a = 2, 3 it lies in c's row -- and the
+ *             pair (c - step(a), a) is usable, not terminal and moves the ball; else 0.  Each (c, a) has at most one source.
+ *   wself   = the sum over a = 0, 1, 2, 3, in that order and from the first term itself, of p_a(c) over the pairs (c, a) that
+ *             are usable, not terminal and leave the ball in place (wall bumps and clamped targets); 0 if there is none
+ * The sweep is Jacobi, in float32, every product and sum rounded on its own (round to nearest even, never a fused multiply-add):
+ *   D_0 = d_init (problem p: d_init + p*S) or 0 when d_init is NULL
+ *   acc = 0
+ *   for a = 0, 1, 2, 3:  if win[a] != 0:  acc = fl(acc + fl(win[a] * D_(k-1)(c - step(a))))
+ *   if wself != 0:       acc = fl(acc + fl(wself * D_(k-1)(c)))
+ *   D_k(c) = fl(start(c) + fl(gamma * acc));  on a 'W' cell D_k = 0 and its start is not read
+ * The stops, sweeps_run and delta are lmaze_evaluate's: a problem stops at the first sweep that leaves the bit pattern of every
+ * D(s) unchanged -- that sweep counts --, or, when tol > 0, at the first sweep whose delta is <= tol, compared as bit patterns,
+ * or after `sweeps` sweeps.  From d_init = NULL and a start without a negative entry the sequence D_k is monotone
+ * non-decreasing in every cell, because every rounded operation above is monotone on non-negative inputs (gamma >= 0); float32 has finitely
+ * many values, so such a sequence becomes stationary and the exact stop is always reached.
+ *   start       float[problems, S], required: the mass every sweep adds.  Not validated: it need not sum to 1
+ * Outputs, each nullable, one of d_out / dsa_out required:
+ *   d_out       float[problems, S]     D_k of the last executed sweep
+ *   dsa_out     float[problems, S, 4]  fl(D_k(s) * p_a(s)); 16-byte aligned
+ *   sweeps_run  int32[problems]        sweeps executed
+ *   delta       float[problems]        max_s |D_k(s) - D_(k-1)(s)| of the last executed sweep, as lmaze_solve's
+ * One launch of occupancy_kernel, shaped as evaluate_kernel and with lmaze_solve's plan: two D buffers in LDS; the model, the
+ * four incoming weights, wself and start of a cell in registers.  The probabilities of the neighbours are exchanged once,
+ * through the second buffer, before the first sweep.  params->launch_hint, step_limit are not read.
+ * Refused, in this order: LMAZE_E_NULL params or layouts; LMAZE_E_GRID; LMAZE_E_VARIANT neither v0 nor v3; LMAZE_E_LAYOUT;
+ * LMAZE_E_NULL goal_xy for v3; LMAZE_E_NULL both d_out and dsa_out NULL; LMAZE_E_NULL unless exactly one of policy, q and
+ * thresholds is given; LMAZE_E_NULL start; LMAZE_E_COUNT problems outside [0, LMAZE_MAX_ENVS] or sweeps < 1; LMAZE_E_ALIGN
+ * thresholds, q or dsa_out off 16 bytes, goal_xy (v3) off 8, a float or int32 pointer off 4.  problems == 0 then returns 0 with
+ * nothing read.  gamma is not validated.  A grid beyond 2^24 - 1 workgroups: hipErrorInvalidConfiguration.
+ */
+int lmaze_occupancy(const LmazeParams* params, const uint8_t* layouts, const int32_t* goal_xy, int64_t problems, const uint8_t* policy,
+                    const float* q, uint32_t epsilon_u32, const uint32_t* thresholds, const float* start, float gamma, int32_t sweeps,
+                    float tol, const float* d_init, float* d_out, float* dsa_out, int32_t* sweeps_run, float* delta, void* stream);
+
+/*
+ * The launch lmaze_occupancy would queue, one line in text_host (HOST, len bytes), written by the code that launches, e.g.
+ * "occupancy_kernel<v0, wave, 4> grid=65 block=256 lds=8208 problems_per_workgroup=4" (the third argument: cells per lane; the
+ * plan is lmaze_solve's).  Nothing is queued or dereferenced.  LMAZE_E_NULL params or text_host NULL or len < 1, then
+ * lmaze_occupancy's refusals of the params and of `problems`; an empty line for problems == 0.
+ */
+int lmaze_describe_occupancy(const LmazeParams* params, int64_t problems, char* text_host, int32_t len);
+
+/*
  * MAZE GENERATION: `mazes` spanning-tree mazes of G x G cells, every one different, every free cell connected to its goal,
  * in ONE launch; no reference counterpart (the reference only has literal layouts).  The result is what LAYOUT_PER_ENV
  * entries and lmaze_solve read: layouts uint8[mazes, G, G] of the reference's cell characters.  Maze p of the call is the
