@@ -184,13 +184,22 @@ def renormalised(w, sticky, wall):
     return ~wall & ((w != wp).any(-1)) & (W > 0)
 
 
+def exact_probabilities(w, sticky, wall):
+    """float64[..., 4]: w' / W, 0 where W == 0"""
+    wp, W = usable(w, sticky, wall)
+    return np.where((W == 0)[..., None], 0.0, wp / np.where(W == 0, 1, W)[..., None].astype(np.float64))
+
+
 def exact_values(model, gamma, w):
     """float64[S]: (I - gamma P_pi) v = r_pi over the non-wall states, with the exact probabilities w' / W; a terminal pair
     pays its reward and cuts the chain.  gamma and the rewards are the float32 numbers the sweep works with."""
+    return exact_values_of(model, gamma, exact_probabilities(w, model.sticky, model.wall))
+
+
+def exact_values_of(model, gamma, prob):
+    """exact_values() with the probabilities float64[S,4] given directly (0 on every excluded pair and wall state)"""
     S = model.G * model.G
     gamma = float(np.float32(gamma))
-    wp, W = usable(w, model.sticky, model.wall)
-    prob = np.where((W == 0)[:, None], 0.0, wp / np.where(W == 0, 1, W)[:, None].astype(np.float64))
     A = np.eye(S)
     b = np.zeros(S)
     for s in np.flatnonzero(~model.wall):
@@ -201,3 +210,12 @@ def exact_values(model, gamma, w):
             if not model.terminal[s, a]:
                 A[s, model.nxt[s, a]] -= gamma * prob[s, a]
     return np.linalg.solve(A, b)
+
+
+def exact_action_values(model, gamma, v):
+    """float64[S,4]: Q = r on a terminal pair, else r + gamma v[next]; 0 on wall states; an excluded pair keeps r + gamma v[s]
+    (finite: it carries no probability)"""
+    gamma = float(np.float32(gamma))
+    q = np.where(model.terminal, model.r.astype(np.float64), model.r.astype(np.float64) + gamma * np.asarray(v, np.float64)[model.nxt])
+    q[model.wall] = 0.0
+    return q

@@ -21,20 +21,27 @@ def gather(model, p):
     """(win float32[S,4], src int64[S,4], wself float32[S]) of one problem from its probabilities p float32[S,4]: win[c,a] is
     the probability of the one pair (src[c,a], a) that moves the ball onto c, wself the ordered sum of the pairs that flow
     and leave it in place"""
-    G = model.G
+    return gather_successors(model.G, model.nxt, flows(model), model.wall, p)
+
+
+def gather_successors(G, nxt, fl, wall, p):
+    """gather() from a successor table alone, wherever it comes from -- the model's, or the one the rows of a rollout show
+    (nxt int[S,4]: the cell a pair leads to; fl bool[S,4]: the pairs whose mass moves on, i.e. usable, of a non-wall cell and
+    never seen with done set).  The geometry is asserted, not assumed: a pair that moves arrives one step(a) away, in the same
+    row for a = 2, 3, on a cell that is not a wall, and no two sources share a (cell, action)."""
     S = G * G
     cells = np.arange(S)
-    fl = flows(model)
-    moved = model.nxt != cells[:, None]
+    nxt = np.asarray(nxt).reshape(S, 4)
+    moved = nxt != cells[:, None]
     win = np.zeros((S, 4), np.float32)
     src = np.repeat(cells[:, None], 4, axis=1).astype(np.int64)
     for a, step in enumerate((-G, G, -1, 1)):
         s = np.flatnonzero(fl[:, a] & moved[:, a])
-        c = model.nxt[s, a].astype(np.int64)
+        c = nxt[s, a].astype(np.int64)
         assert (c - s == step).all() and len(np.unique(c)) == len(c)          # next = s + step(a): one source per (c, a)
         if a >= 2:
             assert (c // G == s // G).all()                                    # in the same row
-        assert not model.wall[c].any()
+        assert not wall[c].any()
         win[c, a] = p[s, a]
         src[c, a] = s
     wself = np.zeros(S, np.float32)
@@ -135,18 +142,41 @@ def occupancy_many(models, gamma, sweeps, start, tol=0.0, d_init=None, **table):
 def exact_occupancy(model, gamma, w, start):
     """float64[S]: (I - gamma P_pi^T) d = start over the non-wall states, with the exact probabilities w' / W; a terminal pair
     absorbs its mass.  gamma is the float32 number the sweep works with; d = 0 on walls."""
+    prob = E.exact_probabilities(w, model.sticky, model.wall)
+    return exact_occupancy_of(model, gamma, prob, start), prob
+
+
+def transition(model, prob):
+    """float64[S,S]: P[s, c], the probability that a step from s leaves the ball on c and the episode running -- prob
+    float64[S,4] over the pairs that flow; a terminal pair, an excluded one and a wall state carry nothing"""
+    S = model.G * model.G
+    fl = flows(model)
+    P = np.zeros((S, S))
+    for a in range(4):
+        s = np.flatnonzero(fl[:, a] & (prob[:, a] != 0))
+        np.add.at(P, (s, model.nxt[s, a]), prob[s, a])
+    return P
+
+
+def exact_occupancy_of(model, gamma, prob, start):
+    """exact_occupancy() with the probabilities float64[S,4] given directly (they are used as they are: 0 on an excluded pair
+    is the caller's to see to)"""
     S = model.G * model.G
     gamma = float(np.float32(gamma))
-    wp, W = E.usable(w, model.sticky, model.wall)
-    prob = np.where((W == 0)[:, None], 0.0, wp / np.where(W == 0, 1, W)[:, None].astype(np.float64))
-    fl = flows(model)
-    A = np.eye(S)
-    for s in np.flatnonzero(~model.wall):
-        for a in range(4):
-            if prob[s, a] != 0 and fl[s, a]:
-                A[model.nxt[s, a], s] -= gamma * prob[s, a]
     b = np.where(model.wall, 0.0, np.asarray(start, np.float64).reshape(S))
-    return np.linalg.solve(A, b), prob
+    return np.linalg.solve(np.eye(S) - gamma * transition(model, prob).T, b)
+
+
+def step_marginals(model, prob, start, T):
+    """float64[T,S]: mu_t = (P_pi^T)^t start, the law of the cell an env stands on before its step t with no done row before
+    it (a terminal pair absorbs: mu_t sums to the chance that the episode still runs); mu_0 = start off the walls"""
+    S = model.G * model.G
+    Pt = transition(model, np.asarray(prob, np.float64)).T
+    mu = np.zeros((T, S))
+    mu[0] = np.where(model.wall, 0.0, np.asarray(start, np.float64).reshape(S))
+    for t in range(1, T):
+        mu[t] = Pt @ mu[t - 1]
+    return mu
 
 
 def pad_walls(layouts):
