@@ -92,6 +92,7 @@ def _signatures():
         "lmaze_observe": [P] + [vp] * 4 + [i64, vp],
         "lmaze_observe_u8": [P] + [vp] * 5 + [i64, vp],
         "lmaze_reset": [P, vp, vp] + draw + [vp] * 6 + [i64, vp],
+        "lmaze_reset_start": [P, vp, vp, vp, i32, i32] + draw + [vp] * 6 + [i64, vp],
         "lmaze_episode_stats": [vp] * 4 + [f32, i64, vp, vp],
         "lmaze_bandwidth_probe": [vp, vp, i64, vp],
         "lmaze_render_expanded": [vp, i32, i32, C.POINTER(i32), i32, vp, i64, vp],
@@ -131,6 +132,7 @@ def _signatures():
         "lmaze_generate": [i32, i64, u64, i64, u32, vp, vp, vp],
         # what a call would launch, as a line of text
         "lmaze_describe_step": describe([P], 2),
+        "lmaze_describe_reset_start": describe([P], 1),
         **same("lmaze_describe_rollout lmaze_describe_env_rollout_qlearn", describe([P], 4)),
         **same("lmaze_describe_rollout_policy lmaze_describe_rollout_sample lmaze_describe_env_rollout", describe([P], 5)),
         **same("lmaze_describe_solve lmaze_describe_score lmaze_describe_evaluate lmaze_describe_occupancy", describe([P], 0)),
@@ -228,6 +230,13 @@ def describe_foveal_step(params, n, auto_reset=False):
 
 
 KEY_MODES = {"ball": 0, "goal": 1}
+ROW_MODES = {"ball": 0, "env": 1, "goal": 2}                  # lmaze_reset_start's row_mode of reset(key=)
+
+
+def describe_reset_start(params, n, key="ball"):
+    """The kernel / grid / LDS lmaze_reset_start would queue for n envs with these LmazeParams (lmaze_describe_reset_start):
+    "reset_start_kernel<v3, rows=goal, table=global> grid=... lds=..."; key "ball" (rows=one), "env" or "goal"; "" for n == 0."""
+    return _describe("lmaze_describe_reset_start", C.byref(params), int(n), ROW_MODES[key] if key in ROW_MODES else int(key))
 
 
 def epsilon_u32(epsilon):

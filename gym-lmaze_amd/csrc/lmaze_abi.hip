@@ -903,6 +903,69 @@ int lmaze_reset(const LmazeParams* params, const uint8_t* layout, const uint8_t*
                      nullptr, n, stream);
 }
 
+// What lmaze_reset_start and its describe refuse of the row mode: LMAZE_E_COUNT outside {0, 1, 2}, then LMAZE_E_VARIANT for
+// what v0 has no goal for
+static int check_row_mode(const LmazeParams* p, int32_t row_mode, int32_t keep_goal) {
+    if (row_mode < 0 || row_mode > 2) return LMAZE_E_COUNT;
+    if (p->variant == LMAZE_VARIANT_V0 && (row_mode == 2 || keep_goal)) return LMAZE_E_VARIANT;
+    return 0;
+}
+
+int lmaze_reset_start(const LmazeParams* params, const uint8_t* layout, const uint8_t* mask, const uint32_t* thresholds,
+                      int32_t row_mode, int32_t keep_goal, uint64_t seed, uint64_t epoch, int64_t env_base, int32_t* ball_xy,
+                      int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* obs, int64_t n, void* stream) {
+    int rc = check_grid_params(params, n, TAKES_BOTH, false);
+    if (rc) return rc;
+    rc = check_buffers(params, false, layout, ball_xy, goal_xy, obs, step_count && reward && done);
+    if (rc) return rc;
+    rc = check_row_mode(params, row_mode, keep_goal);
+    if (rc) return rc;
+    if (!thresholds) return LMAZE_E_NULL;
+    if (misaligned(thresholds, 4)) return LMAZE_E_ALIGN;
+    if (n == 0) return 0;
+    ResetStartArgs a;
+    a.r.layout = layout;
+    a.r.mask = mask;
+    a.r.ball = reinterpret_cast<int2*>(ball_xy);
+    a.r.goal = reinterpret_cast<int2*>(goal_xy);
+    a.r.step_count = step_count;
+    a.r.reward = reward;
+    a.r.done = done;
+    a.r.n = n;
+    a.r.seed = seed;
+    a.r.epoch = epoch;
+    a.r.env_base = env_base;
+    a.r.grid = params->grid;
+    a.thresholds = thresholds;
+    a.row_mode = row_mode;
+    a.keep_goal = keep_goal ? 1 : 0;
+    a.per_env = a.top = 0;                                 // the launcher's
+    hipError_t e = launch_reset_start(params->variant, a, params->layout_mode, (hipStream_t)stream, nullptr);
+    if (e != hipSuccess || !obs) return (int)e;
+    // only the envs that were reset are re-rendered, as lmaze_reset's
+    return grid_step(params, TAKES_BOTH, false, false, layout, nullptr, ball_xy, goal_xy, nullptr, nullptr, nullptr, nullptr, obs, mask,
+                     nullptr, n, stream);
+}
+
+int lmaze_describe_reset_start(const LmazeParams* params, int64_t n, int32_t row_mode, char* text_host, int32_t len) {
+    int rc = check_grid_params(params, n, TAKES_BOTH, false);
+    if (!rc) rc = check_row_mode(params, row_mode, 0);
+    if (rc) return rc;
+    if (!text_host || len < 1) return LMAZE_E_NULL;
+    text_host[0] = 0;
+    if (n == 0) return 0;
+    LaunchInfo info;
+    memset(&info, 0, sizeof(info));
+    ResetStartArgs a;
+    memset(&a, 0, sizeof(a));
+    a.r.n = n;
+    a.r.grid = params->grid;
+    a.row_mode = row_mode;
+    rc = (int)launch_reset_start(params->variant, a, params->layout_mode, nullptr, &info);
+    if (rc) return rc;
+    return format_launch(info, text_host, len);
+}
+
 int lmaze_episode_stats(const uint8_t* done, const float* reward, const int32_t* step_count,
                         const int32_t* goal_count, float reward_goal, int64_t n, int64_t* out4, void* stream) {
     if (!done || !reward || !step_count || !out4) return LMAZE_E_NULL;

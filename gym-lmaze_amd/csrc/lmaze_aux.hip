@@ -1,6 +1,8 @@
 // lmaze_aux.hip -- the kernels either side of the step path: masked on-device reset
 // (reference reset(): lmaze_env.py:64-110, lmaze_env_v3.py:134-167) and the
 // reference-layout x E nearest-neighbour render (lmaze_env.py:217-234).
+#include <stdio.h>
+
 #include "lmaze_common.h"
 #include "lmaze_learn.h"
 
@@ -104,6 +106,135 @@ hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStr
         if (wave) return hipGetLastError();
         if (v3) hipLaunchKernelGGL(reset_perenv_kernel<LMAZE_VARIANT_V3>, dim3(blocks), dim3(LMAZE_BLOCK), 0, s, a);
         else hipLaunchKernelGGL(reset_perenv_kernel<LMAZE_VARIANT_V0>, dim3(blocks), dim3(LMAZE_BLOCK), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// Reset from a start law (lmaze_reset_start): the ball cell is k = #{ j : row[j] <= u }, u the upper 31 bits of the reset
+// draw's y, over a row of S cumulative words in units of 2^-31; k == S leaves the ball.  The v3 goal is lmaze_reset's own
+// draw (or kept), and the row may be the goal's.  Nothing is read to validate a row: every index below is in [0, S).
+// ------------------------------------------------------------------------------------
+
+// the row of a v3 env under row_mode 2: its goal clamped onto the grid, as the closed-loop keys clamp it
+__device__ __forceinline__ int goal_row(int2 g, int G) { return clampi(g.x, 0, G - 1) * G + clampi(g.y, 0, G - 1); }
+
+// k for a non-decreasing row, without a branch: the largest k in [0, S] with row[k - 1] <= u, ceil(log2(S + 1)) probes
+// from `top`, the power of two above S halved.  Any other row gives some k in [0, S].
+__device__ __forceinline__ int row_search(const uint32_t* row, int S, int top, uint32_t u) {
+    int k = 0;
+    for (int b = top; b > 0; b >>= 1) {
+        const int t = k + b;
+        const uint32_t w = row[min(t, S) - 1];
+        k = (t <= S && w <= u) ? t : k;
+    }
+    return k;
+}
+
+__device__ __forceinline__ void write_start(const ResetStartArgs& a, int64_t e, int k, int goal_cell) {
+    const int G = a.r.grid;
+    if (goal_cell >= 0) a.r.goal[e] = make_int2(goal_cell / G, goal_cell % G);
+    if (k < G * G) a.r.ball[e] = make_int2(k / G, k % G);
+    write_reset(a.r, e);
+}
+
+// Shared layout, one row (ROWS 0: staged in LDS once per workgroup) or the goal's row (ROWS 2: v3, read from global memory):
+// one lane per env, as reset_shared_kernel.  LDS: the row's S words (ROWS 0), then, v3, the spawn list.
+template <int VARIANT, int ROWS>
+__global__ __launch_bounds__(LMAZE_BLOCK) void reset_start_kernel(const ResetStartArgs a) {
+    extern __shared__ int4 lds4[];
+    __shared__ int count_s;
+    const int G = a.r.grid, S = G * G;
+    const int tid = threadIdx.x;
+    uint32_t* row_s = reinterpret_cast<uint32_t*>(lds4);
+    uint16_t* list = reinterpret_cast<uint16_t*>(lds4 + (ROWS == 0 ? (S * 4 + 15) / 16 : 0));
+    if (ROWS == 0)
+        for (int j = tid; j < S; j += LMAZE_BLOCK) row_s[j] = a.thresholds[j];
+    const bool draw_goal = VARIANT == LMAZE_VARIANT_V3 && !a.keep_goal;
+    if (draw_goal && tid < 64) {
+        const int count = wave_build_spawn_list<VARIANT>(a.r.layout, G, S, list, tid);
+        if (tid == 0) count_s = count;
+    }
+    __syncthreads();
+    const int64_t e = (int64_t)blockIdx.x * LMAZE_BLOCK + tid;
+    if (e >= a.r.n) return;
+    if (a.r.mask && !a.r.mask[e]) return;
+    const uint4 r = env_draw(a.r.seed, a.r.epoch, a.r.env_base + e);
+    int goal_cell = -1;
+    if (draw_goal && count_s > 0) goal_cell = list[__umulhi(r.x, (uint32_t)count_s)];
+    const uint32_t* row = row_s;
+    if (ROWS == 2) row = a.thresholds + (size_t)(goal_cell >= 0 ? goal_cell : goal_row(a.r.goal[e], G)) * S;
+    write_start(a, e, row_search(row, S, a.top, r.y >> 1), goal_cell);
+}
+
+// A row per env (row_mode 1), and every row mode on per-env layouts: one wave per env, as reset_perenv_kernel.  The wave
+// reads the env's S words coalesced, compares them with u and sums the ballots' popcounts -- the count itself, whatever
+// the row holds.  The v3 goal is ranked on the env's own layout.  Only lane 0 writes.
+template <int VARIANT>
+__global__ __launch_bounds__(LMAZE_BLOCK) void reset_start_wave_kernel(const ResetStartArgs a) {
+    const int G = a.r.grid, S = G * G;
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * (LMAZE_BLOCK / 64) + (threadIdx.x >> 6);
+    if (e >= a.r.n) return;
+    if (a.r.mask && !a.r.mask[e]) return;
+    const uint4 r = env_draw(a.r.seed, a.r.epoch, a.r.env_base + e);
+    int goal_cell = -1;
+    if (VARIANT == LMAZE_VARIANT_V3 && !a.keep_goal) {
+        const uint8_t* lay = a.r.layout + (a.per_env ? (size_t)e * S : (size_t)0);
+        const int count = wave_count_cells<VARIANT>(lay, G, S, lane);
+        if (count > 0) goal_cell = wave_kth_cell<VARIANT>(lay, G, S, (int)__umulhi(r.x, (uint32_t)count), lane);
+    }
+    size_t at = 0;
+    if (a.row_mode == 1) at = (size_t)e;
+    if (a.row_mode == 2) at = (size_t)(goal_cell >= 0 ? goal_cell : goal_row(a.r.goal[e], G));
+    const uint32_t* row = a.thresholds + at * S;
+    const uint32_t u = r.y >> 1;
+    int k = 0;
+    for (int base = 0; base < S; base += 256) {              // four loads in flight per lane; past the row: word 0, not counted
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = base + q * 64 + lane;
+            w[q] = row[j < S ? j : 0];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) k += __popcll(__ballot(base + q * 64 + lane < S && w[q] <= u));
+    }
+    if (lane == 0) write_start(a, e, k, goal_cell);
+}
+
+// What lmaze_reset_start queues and lmaze_describe_reset_start prints: the lane-per-env kernel on a shared layout with one
+// row (in LDS) or the goal's row (global), the wave-per-env kernel otherwise.
+hipError_t launch_reset_start(int variant, const ResetStartArgs& args, int layout_mode, hipStream_t s, LaunchInfo* info) {
+    if (args.r.n == 0) return hipSuccess;
+    ResetStartArgs a = args;
+    const bool v3 = variant == LMAZE_VARIANT_V3;
+    const int S = a.r.grid * a.r.grid;
+    a.per_env = layout_mode == LMAZE_LAYOUT_PER_ENV ? 1 : 0;
+    a.top = 1;
+    while (a.top * 2 <= S) a.top *= 2;                       // the largest power of two <= S: the first probe
+    const bool lanes = !a.per_env && a.row_mode != 1;
+    const int epb = lanes ? LMAZE_BLOCK : LMAZE_BLOCK / 64;
+    const int64_t blocks = (a.r.n + epb - 1) / epb;
+    if (!grid_ok(blocks)) return hipErrorInvalidConfiguration;
+    const bool in_lds = lanes && a.row_mode == 0;
+    const size_t lds = !lanes ? 0 : (in_lds ? ((size_t)S * 4 + 15) & ~(size_t)15 : 0) + (v3 ? ((size_t)S * 2 + 15) & ~(size_t)15 : 0);
+    if (info) {
+        char name[96];
+        snprintf(name, sizeof(name), "reset_start_kernel<%s, rows=%s, table=%s>", v3 ? "v3" : "v0",
+                 a.row_mode == 0 ? "one" : (a.row_mode == 1 ? "env" : "goal"), in_lds ? "lds" : "global");
+        describe_launch(info, name, epb, 0, 1, false, blocks, LMAZE_BLOCK, lds);
+        return hipSuccess;
+    }
+    const dim3 grid((unsigned)blocks), block(LMAZE_BLOCK);
+    if (!lanes) {
+        if (v3) hipLaunchKernelGGL(reset_start_wave_kernel<LMAZE_VARIANT_V3>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(reset_start_wave_kernel<LMAZE_VARIANT_V0>, grid, block, 0, s, a);
+    } else if (a.row_mode == 0) {
+        if (v3) hipLaunchKernelGGL((reset_start_kernel<LMAZE_VARIANT_V3, 0>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((reset_start_kernel<LMAZE_VARIANT_V0, 0>), grid, block, lds, s, a);
+    } else {
+        hipLaunchKernelGGL((reset_start_kernel<LMAZE_VARIANT_V3, 2>), grid, block, lds, s, a);   // the goal's row: v3 only
     }
     return hipGetLastError();
 }

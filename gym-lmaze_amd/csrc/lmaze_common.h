@@ -84,6 +84,15 @@ struct ResetArgs {
     int32_t grid;
 };
 
+// reset from a start law (lmaze_reset_start, lmaze_aux.hip): the reset's own arguments and the cumulative rows
+struct ResetStartArgs {
+    ResetArgs r;
+    const uint32_t* thresholds;  // [S] (row_mode 0), [N, S] (1) or [S, S] (2): cumulative words in units of 2^-31
+    int32_t row_mode;            // 0 one row, 1 the env's local index, 2 the v3 goal's cell
+    int32_t keep_goal;           // v3: leave goal_xy as it is
+    int32_t per_env, top;        // set by the launcher: per-env layouts; the binary search's first probe
+};
+
 // reference-layout xE render (lmaze_aux.hip)
 struct ExpandArgs {
     const int32_t* obs;
@@ -331,6 +340,8 @@ GeneratePlan plan_generate(int32_t G, int64_t mazes);
 int describe_generate(const GeneratePlan& p, char* text, int32_t len);
 hipError_t launch_generate(const GenerateArgs& a, hipStream_t s);
 hipError_t launch_reset(int variant, const ResetArgs& a, int layout_mode, hipStream_t s);
+// info != null: describe the launch instead of queueing it
+hipError_t launch_reset_start(int variant, const ResetStartArgs& a, int layout_mode, hipStream_t s, LaunchInfo* info);
 hipError_t launch_expand(const ExpandArgs& a, hipStream_t s);
 hipError_t launch_probe(const void* src, void* dst, int64_t bytes, hipStream_t s);
 hipError_t launch_episode_stats(const uint8_t* done, const float* reward, const int32_t* step_count,

@@ -492,18 +492,79 @@ class LmazeVecEnv(VecEnvBase):
         _abi.check("lmaze_observe", rc)
         return self.obs
 
-    def reset(self, mask=None, seed=None):
-        """Masked on-device reset (mask: bool/uint8[N], None = all).  Returns the compact obs."""
+    def _start_table(self, start, thresholds, key, keep_goal, validate):
+        """reset()'s law as the table lmaze_reset_start reads, uint32[rows, G*G].  The refusals stand in this order: both of
+        start / thresholds, the shape key asks for, key="goal" on v0 (and on per-env layouts), keep_goal on v0, and with
+        validate a row of the caller's thresholds that decreases or neither ends in 2**31 nor is all zero."""
+        name = _tables.exactly_one("reset()", start=start, thresholds=thresholds)
+        if key not in _abi.ROW_MODES:
+            raise ValueError("key must be 'ball', 'goal' or 'env'")
+        S, N = self.grid ** 2, self.num_envs
+        shapes = {"ball": ((1, S), (S,)), "goal": ((S, S),), "env": ((N, S),)}[key]
+        table = start if name == "start" else thresholds
+        kinds = "a float" if name == "start" else "a contiguous uint32 (or int32)"
+        ok = isinstance(table, torch.Tensor) and table.device == self.device and tuple(table.shape) in shapes
+        if ok and name == "start":
+            ok = table.is_floating_point()
+        elif ok:
+            ok = table.dtype in (torch.uint32, torch.int32) and table.is_contiguous()
+        if not ok:
+            raise ValueError("%s must be %s tensor %s on %s (key=%r)" % (name, kinds, " or ".join(str(list(s)) for s in shapes),
+                                                                        self.device, key))
+        if key == "goal" and not self._is_v3:
+            raise ValueError("key='goal' needs the v3 variant: v0 keeps no per-env goal")
+        if key == "goal" and self.layout_mode != _abi.LAYOUT_SHARED:
+            raise ValueError("key='goal' draws from one table of goal rows on a shared layout; per-env layouts take key='env'")
+        if keep_goal and not self._is_v3:
+            raise ValueError("keep_goal needs the v3 variant: v0 keeps no per-env goal")
+        if name == "start":
+            return start_thresholds(table.reshape(-1, S))
+        if validate:
+            w = table.reshape(-1, S).view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+            if bool((w[:, 1:] < w[:, :-1]).any()):
+                raise ValueError("a row of thresholds decreases")
+            if not bool(((w[:, -1] == 2 ** 31) | (w == 0).all(1)).all()):
+                raise ValueError("a row of thresholds neither ends in 2**31 nor is all zero")
+        return table
+
+    def reset(self, mask=None, seed=None, *, start=None, thresholds=None, key="ball", keep_goal=False, validate=True):
+        """Masked on-device reset (mask: bool/uint8[N], None = all).  Returns the compact obs.
+        With neither start nor thresholds: lmaze_reset's uniform law (reset_distribution()).  With exactly one of them the
+        ball is drawn from a law the caller gives, in one placement launch (include/lmaze.h lmaze_reset_start), from the
+        same draw of (seed, epoch, env_base + i) -- the v3 goal is lmaze_reset's own, or kept with keep_goal=True:
+        start       float weights, non-negative, a row need not sum to 1: what occupancy(start=...) takes and
+                    distance_band() makes; turned into thresholds by start_thresholds().  A row of zeros: the ball stays.
+        thresholds  the table itself, uint32 (or int32, the same bits): the caller's memory, never copied.  validate=False
+                    skips the check of its rows (a device synchronisation).
+        key         "ball": one row for every env, [1, G*G] or [G*G]; "goal": v3 on a shared layout, [G*G, G*G], the row of
+                    the env's goal cell; "env": [N, G*G], row i for env i of this object, on shared or per-env layouts.
+        The cell is not excluded for being a wall or the goal.  The fused resets of step(auto_reset=True) and of the
+        rollouts keep the uniform law: a curriculum runs auto_reset=False and resets the done envs between launches.  Not
+        for captured graphs."""
+        table = None
+        if start is not None or thresholds is not None:
+            table = self._start_table(start, thresholds, key, keep_goal, validate)
+        elif keep_goal:
+            raise ValueError("keep_goal belongs to a reset from start= or thresholds=")
         if seed is not None:
             self.seed = int(seed)
             self._epoch = 0
         m, m_ptr = self._mask_ptr(mask)
-        with self._guard():
-            rc = _abi.lib.lmaze_reset(self._pp, self._p_layout, m_ptr, self.seed & (2 ** 64 - 1), self._epoch,
-                                      self.env_base, self._p_ball, self._p_goal if self._is_v3 else None,
-                                      self._p_step, self._p_reward, self._p_done, None if self._u8 else self._p_obs,
-                                      self.num_envs, self._stream())
-        _abi.check("lmaze_reset", rc)
+        if table is not None:
+            with self._guard():
+                rc = _abi.lib.lmaze_reset_start(self._pp, self._p_layout, m_ptr, table.data_ptr(), _abi.ROW_MODES[key],
+                                                1 if keep_goal else 0, self.seed & (2 ** 64 - 1), self._epoch, self.env_base,
+                                                self._p_ball, self._p_goal if self._is_v3 else None, self._p_step,
+                                                self._p_reward, self._p_done, None if self._u8 else self._p_obs,
+                                                self.num_envs, self._stream())
+            _abi.check("lmaze_reset_start", rc)
+        else:
+            with self._guard():
+                rc = _abi.lib.lmaze_reset(self._pp, self._p_layout, m_ptr, self.seed & (2 ** 64 - 1), self._epoch,
+                                          self.env_base, self._p_ball, self._p_goal if self._is_v3 else None,
+                                          self._p_step, self._p_reward, self._p_done, None if self._u8 else self._p_obs,
+                                          self.num_envs, self._stream())
+            _abi.check("lmaze_reset", rc)
         self._epoch += 1
         if self._u8:
             self.observe(mask_ptr=m_ptr)       # the narrow planes of the envs that were reset
@@ -1199,6 +1260,69 @@ def reset_distribution(layouts, variant="v0", goals=None):
         ok = (ok & (lay != ord("X"))).reshape(-1, G * G)
     n = ok.sum(1, keepdim=True).clamp(min=1)
     return (ok.to(torch.float32) / n.to(torch.float32)).contiguous()
+
+
+def start_thresholds(start):
+    """The table reset(thresholds=...) and lmaze_reset_start take, uint32[P, S] on start's device, of a float tensor
+    start[P, S] (or [S]: one row) of non-negative weights; a row need not sum to 1.  In float64:
+        a_j = start_0 + ... + start_j (running sums), s = a_(S-1);   c_j = floor(a_j / s * 2**31 + 0.5)
+    over the cells that have mass, then a running maximum: a zero-mass cell gets c_j = c_(j-1), c_(-1) = 0; the word of the
+    last massive cell and every word behind it is exactly 2**31.  Cell j is then drawn with probability
+    (c_j - c_(j-1)) / 2**31, within 2**-30 of start_j / s, and a cell without mass is never drawn.  A row of zero total mass
+    becomes a row of zeros, lmaze_reset_start's "the ball stays" row.  Refuses negative or non-finite entries."""
+    if not (isinstance(start, torch.Tensor) and start.is_floating_point() and start.dim() in (1, 2) and start.shape[-1] >= 1):
+        raise ValueError("start must be a float tensor [P, S] or [S]")
+    p = start.detach().to(torch.float64).reshape(-1, start.shape[-1])
+    if not bool(torch.isfinite(p).all()) or bool((p < 0).any()):
+        raise ValueError("start holds a negative or non-finite entry")
+    S = p.shape[1]
+    a = torch.cumsum(p, dim=1)
+    s = a[:, -1:]
+    if not bool(torch.isfinite(s).all()):
+        raise ValueError("a row of start has no finite sum")
+    massive = p > 0
+    c = torch.floor(a / torch.where(s > 0, s, torch.ones_like(s)) * 2147483648.0 + 0.5).clamp_(max=2147483648.0).to(torch.int64)
+    c = torch.cummax(torch.where(massive, c, torch.zeros_like(c)), dim=1).values
+    # from the last massive cell on: exactly 2**31 (a row without mass has no such cell and stays 0)
+    cells = torch.arange(S, device=p.device)
+    last = torch.where(massive, cells, torch.full_like(cells, -1)).max(dim=1, keepdim=True).values
+    c = torch.where((last >= 0) & (cells >= last), torch.full_like(c, 2147483648), c)
+    return torch.where(c >= 2147483648, c - 4294967296, c).to(torch.int32).view(torch.uint32).contiguous()   # the same 32 bits
+
+
+def distance_band(optimal, lo, hi, layouts, variant="v0", goals=None, empty="reset"):
+    """A curriculum stage over the distance field, float32[P, G*G]: uniform over the cells reset_distribution() gives mass AND
+    whose optimal -- score()'s fewest steps to done, int [P, G*G] or [G*G] -- lies in [lo, hi].  lo / hi: ints, or int tensors
+    [P] for a stage per maze.  A problem whose band is empty gets reset_distribution()'s row (empty="reset") or a row of zeros
+    (empty="zero": reset(start=...) then leaves that ball where it is).  layouts, variant, goals: as reset_distribution(); one
+    shared row serves every problem of optimal.  Plain torch: the law occupancy(start=...) and reset(start=...) take as it is.
+    ("Mazes by difficulty" needs no helper: sort score()'s summary column, e.g. summary[:, 0].argsort().)"""
+    if empty not in ("reset", "zero"):
+        raise ValueError("empty must be 'reset' or 'zero'")
+    base = reset_distribution(layouts, variant, goals)
+    S = base.shape[1]
+    if not (isinstance(optimal, torch.Tensor) and not optimal.is_floating_point() and optimal.device == base.device
+            and optimal.numel() % S == 0 and optimal.numel() > 0):
+        raise ValueError("optimal must be an int tensor [P, %d] on layouts' device" % S)
+    opt = optimal.reshape(-1, S).long()
+    P = opt.shape[0]
+    if base.shape[0] not in (1, P):
+        raise ValueError("optimal holds %d problems, the layouts and goals %d" % (P, base.shape[0]))
+    base = base.expand(P, S)
+
+    def bound(x, name):
+        if isinstance(x, torch.Tensor):
+            if x.is_floating_point() or x.numel() != P or x.device != base.device:
+                raise ValueError("%s must be an int or an int tensor [%d] on layouts' device" % (name, P))
+            return x.reshape(P, 1).long()
+        return int(x)
+
+    band = (base > 0) & (opt >= bound(lo, "lo")) & (opt <= bound(hi, "hi"))
+    n = band.sum(1, keepdim=True)
+    law = band.to(torch.float32) / n.clamp(min=1).to(torch.float32)
+    if empty == "reset":
+        law = torch.where(n > 0, law, base)
+    return law.contiguous()
 
 
 def _check_start(start, dev, P, S, validate):

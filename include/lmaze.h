@@ -207,6 +207,53 @@ int lmaze_reset(const LmazeParams* params, const uint8_t* layout, const uint8_t*
                 void* stream);
 
 /*
+ * lmaze_reset with the ball drawn from a start law the caller gives -- curricula over the distance field (start lo..hi
+ * steps from the goal: lmaze_score's `optimal`), prioritised starts -- per problem, from the env's own reset draw, in one
+ * placement launch.  No reference counterpart.  Below S = G*G and r = the reset draw of env i, Philox4x32-10 with
+ * lmaze_reset's counter (env_base + i, epoch) and key (seed).  For every env with mask[i] != 0 (mask NULL = all):
+ *   1. goal (v3 only)   keep_goal == 0: re-drawn exactly as lmaze_reset draws it, the ((r.x * count) >> 32)-th accepted cell
+ *                       in row-major order, and with count == 0 it stays; keep_goal != 0: goal_xy[i] is left as it is.
+ *                       v0 has no per-env goal.
+ *   2. row              row_mode 0: row 0 of thresholds uint32[S], one law for every env;
+ *                       row_mode 1: row i, the env's LOCAL index (not env_base + i), of uint32[n, S];
+ *                       row_mode 2: v3 only, row clamp(goal_x) * G + clamp(goal_y) of uint32[S, S], the goal read AFTER 1.
+ *   3. ball             u = r.y >> 1, a 31-bit draw, and k = #{ j in [0, S) : row[j] <= u }.  k < S: ball_xy[i] =
+ *                       (k / G, k % G); k == S: the ball stays where it is, lmaze_reset's "no accepted cell" case.
+ *   4. bookkeeping      step_count = 0, reward = -0.0, done = 0; obs (nullable): the masked re-render lmaze_reset queues.
+ * A row is a cumulative law in units of 2^-31: cell j is drawn with probability (row[j] - row[j-1]) / 2^31, row[-1] = 0, and
+ * a complete row ends in exactly 2^31.  (31 bits and not the sampling rollouts' 32 because 2^31 fits the word: zero-mass
+ * cells behind the last massive one are never reached, where a 32-bit table would let one draw in 2^32 through to cell
+ * S - 1, a border wall.)  A row of zeros is the "ball stays" row; a row of 2^31 everywhere puts the ball on cell 0.
+ * Rows are expected non-decreasing; for those the binary search some forms run gives k.  The table is NOT read to validate
+ * it: for any other row the result is some k in [0, S], and nothing is read or written out of bounds.  A cell is not
+ * excluded for being a wall, an 'X' or the goal: what a step does with such a state is LOADED STATE above.
+ *   thresholds  4-byte aligned device memory, read only; never written.
+ * Refused before anything is queued, in this order: lmaze_reset's own refusals (the params, the variant, then LMAZE_E_NULL /
+ * LMAZE_E_ALIGN for its buffers); LMAZE_E_COUNT row_mode outside {0, 1, 2}; LMAZE_E_VARIANT row_mode 2 or keep_goal != 0
+ * on v0; LMAZE_E_NULL thresholds; LMAZE_E_ALIGN thresholds not 4-byte aligned.  n == 0 then returns 0 with nothing read.
+ * Kernels: a shared layout with row_mode 0 or 2 -- one lane per env; the workgroup stages the one row in LDS (<= 16 KiB) or
+ * reads the goal's row from global memory, a branch-free binary search of ceil(log2(S + 1)) probes; the v3 goal from the
+ * workgroup's spawn list.  row_mode 1, and every row mode on per-env layouts -- one wave per env reads the S words
+ * coalesced and sums the ballots of the compares; the v3 goal is ranked on the env's own layout.
+ * Out of scope: the fused resets inside the *_autoreset steps and the one-launch rollouts keep lmaze_reset's uniform law (a
+ * curriculum runs them without auto-reset and resets done envs between launches); the foveal envs; captured graphs (no
+ * device-resident epoch here); compact threshold formats.
+ */
+int lmaze_reset_start(const LmazeParams* params, const uint8_t* layout, const uint8_t* mask, const uint32_t* thresholds,
+                      int32_t row_mode, int32_t keep_goal, uint64_t seed, uint64_t epoch, int64_t env_base,
+                      int32_t* ball_xy, int32_t* goal_xy, int32_t* step_count, float* reward, uint8_t* done, int32_t* obs,
+                      int64_t n, void* stream);
+
+/*
+ * What lmaze_reset_start would queue for n envs, as lmaze_describe_step: "reset_start_kernel<v3, rows=goal, table=global>
+ * grid=... block=256 lds=... envs_per_workgroup=256 workgroups_per_cu=0 chunks=1"; rows=one with table=lds on a shared
+ * layout; rows=env, and every form on per-env layouts, table=global with envs_per_workgroup=4 (a wave per env).  Refusals:
+ * the params and the variant, LMAZE_E_COUNT / LMAZE_E_VARIANT for row_mode as above, LMAZE_E_NULL for the text; n == 0
+ * gives an empty line.
+ */
+int lmaze_describe_reset_start(const LmazeParams* params, int64_t n, int32_t row_mode, char* text_host, int32_t len);
+
+/*
  * step() with the reset fused in front of it, for rollouts longer than one episode: an env
  * whose done[i] is set ON ENTRY (by the previous step) is first reset exactly as
  * lmaze_reset(mask = done, seed, epoch, env_base) would -- new placement, step_count = 0,
