@@ -65,6 +65,7 @@ def _signatures():
     epochs = draw + [vp, vp, vp]                              # ... epoch_in_dev, epoch_out_dev, stream
     batch = [i64, i32] + draw                                 # n, auto_reset, seed, epoch, env_base
     slots = [vp, i32, vp]                                     # obs_t, obs_every, stream
+    law = [vp, vp, u32, vp]                                   # policy, q, epsilon_u32, thresholds: one table, one form
 
     def same(names, args):
         return dict.fromkeys(names.split(), args)
@@ -125,6 +126,9 @@ def _signatures():
         "lmaze_advantages": [vp] * 4 + [f32, f32, vp, vp, i32, i64, vp],
         "lmaze_advantages_table": [vp] * 5 + [i64, f32, f32, vp, vp, i32, i64, vp],
         "lmaze_table_stats": [vp, vp, vp, i64, i64, i32, vp, vp, vp],
+        "lmaze_action_probs": [vp, vp, i64] + law + [i64, vp, vp],
+        "lmaze_vtrace": [vp] * 5 + [f32] * 4 + [vp, vp, i32, i64, vp],
+        "lmaze_vtrace_table": [vp] * 6 + [i64] + law + law + [f32] * 4 + [vp, vp, vp, i32, i64, vp],
         "lmaze_solve": [P, vp, vp, i64, f32, i32] + [vp] * 7,
         "lmaze_score": [P, vp, vp, i64] + [vp] * 6,
         "lmaze_evaluate": [P, vp, vp, i64, vp, vp, u32, vp, f32, i32, f32] + [vp] * 6,

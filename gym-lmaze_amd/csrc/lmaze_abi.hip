@@ -6,6 +6,7 @@
 
 #include "lmaze_common.h"
 #include "lmaze_foveal_defs.h"
+#include "lmaze_offpolicy.h"
 
 
 using namespace lmaze;
@@ -651,6 +652,94 @@ int lmaze_advantages_table(const float* reward_t, const uint8_t* done_t, const i
     const uint32_t ku = keys > ((int64_t)1 << 31) ? (uint32_t)1 << 31 : (uint32_t)(keys < 0 ? 0 : keys);
     const AdvantageArgs a{reward_t, done_t, nullptr, nullptr, key_t, key_tail, values, ku, gamma, gamma * lambda, adv_t, target_t, T, n};
     return advantages(a, reward_t && done_t && key_t && values && adv_t, keys, stream);
+}
+
+// One table of the off-policy entries, in exactly one of lmaze_evaluate's three forms; *law is filled when it is.
+static bool action_law(const uint8_t* policy, const float* q, uint32_t epsilon_u32, const uint32_t* thresholds, ActionLaw* law) {
+    if ((policy != nullptr) + (q != nullptr) + (thresholds != nullptr) != 1) return false;
+    law->policy = policy;
+    law->rows = q ? reinterpret_cast<const uint4*>(q) : reinterpret_cast<const uint4*>(thresholds);
+    law->form = policy ? LMAZE_LAW_POLICY : (q ? LMAZE_LAW_Q : LMAZE_LAW_THRESHOLDS);
+    law->epsilon = epsilon_u32;
+    return true;
+}
+
+// an int32 key is compared unsigned: a table beyond 2^31 entries has no key that could reach past it (keys >= 1)
+static uint32_t key_count(int64_t keys) { return keys > ((int64_t)1 << 31) ? (uint32_t)1 << 31 : (uint32_t)keys; }
+
+int lmaze_action_probs(const int32_t* key_t, const int32_t* actions_t, int64_t m, const uint8_t* policy, const float* q,
+                       uint32_t epsilon_u32, const uint32_t* thresholds, int64_t keys, float* prob_t, void* stream) {
+    if (!key_t || !actions_t || !prob_t) return LMAZE_E_NULL;
+    ActionProbsArgs a{};
+    if (!action_law(policy, q, epsilon_u32, thresholds, &a.law)) return LMAZE_E_NULL;
+    if (m < 0 || keys < 1) return LMAZE_E_COUNT;
+    if (misaligned(a.law.rows, 16) || misaligned(key_t, 4) || misaligned(actions_t, 4) || misaligned(prob_t, 4)) return LMAZE_E_ALIGN;
+    if (m == 0) return 0;
+    a.key_t = key_t;
+    a.actions_t = actions_t;
+    a.keys = key_count(keys);
+    a.prob_t = prob_t;
+    a.m = m;
+    return (int)launch_action_probs(a, (hipStream_t)stream);
+}
+
+// what lmaze_vtrace and lmaze_vtrace_table judge alike, behind their own pointers and tables
+static int vtrace(const VtraceArgs& a, int64_t keys, void* stream) {
+    if (a.T < 0 || a.n < 0 || a.n > LMAZE_MAX_ENVS || keys < 1) return LMAZE_E_COUNT;
+    if (misaligned(a.behaviour.rows, 16) || misaligned(a.target.rows, 16) || misaligned(a.reward_t, 4) || misaligned(a.value_t, 4) ||
+        misaligned(a.tail, 4) || misaligned(a.rho_t, 4) || misaligned(a.key_t, 4) || misaligned(a.actions_t, 4) ||
+        misaligned(a.key_tail, 4) || misaligned(a.values, 4) || misaligned(a.vs_t, 4) || misaligned(a.pg_t, 4) ||
+        misaligned(a.rho_out_t, 4))
+        return LMAZE_E_ALIGN;
+    return (int)launch_vtrace(a, (hipStream_t)stream);
+}
+
+int lmaze_vtrace(const float* reward_t, const uint8_t* done_t, const float* value_t, const float* tail, const float* rho_t,
+                 float gamma, float lambda, float rho_bar, float c_bar, float* vs_t, float* pg_adv_t, int32_t T, int64_t n, void* stream) {
+    if (!reward_t || !done_t || !value_t || (!vs_t && !pg_adv_t)) return LMAZE_E_NULL;
+    VtraceArgs a{};
+    a.reward_t = reward_t;
+    a.done_t = done_t;
+    a.value_t = value_t;
+    a.tail = tail;
+    a.rho_t = rho_t;
+    a.gamma = gamma;
+    a.lambda = lambda;
+    a.rho_bar = rho_bar;
+    a.c_bar = c_bar;
+    a.vs_t = vs_t;
+    a.pg_t = pg_adv_t;
+    a.T = T;
+    a.n = n;
+    return vtrace(a, 1, stream);
+}
+
+int lmaze_vtrace_table(const float* reward_t, const uint8_t* done_t, const int32_t* key_t, const int32_t* actions_t,
+                       const int32_t* key_tail, const float* values, int64_t keys, const uint8_t* b_policy, const float* b_q,
+                       uint32_t b_epsilon_u32, const uint32_t* b_thresholds, const uint8_t* t_policy, const float* t_q,
+                       uint32_t t_epsilon_u32, const uint32_t* t_thresholds, float gamma, float lambda, float rho_bar, float c_bar,
+                       float* vs_t, float* pg_adv_t, float* rho_out_t, int32_t T, int64_t n, void* stream) {
+    if (!reward_t || !done_t || !key_t || !actions_t || !values || (!vs_t && !pg_adv_t)) return LMAZE_E_NULL;
+    VtraceArgs a{};
+    if (!action_law(b_policy, b_q, b_epsilon_u32, b_thresholds, &a.behaviour)) return LMAZE_E_NULL;
+    if (!action_law(t_policy, t_q, t_epsilon_u32, t_thresholds, &a.target)) return LMAZE_E_NULL;
+    a.reward_t = reward_t;
+    a.done_t = done_t;
+    a.key_t = key_t;
+    a.actions_t = actions_t;
+    a.key_tail = key_tail;
+    a.values = values;
+    a.keys = keys < 1 ? 0 : key_count(keys);
+    a.gamma = gamma;
+    a.lambda = lambda;
+    a.rho_bar = rho_bar;
+    a.c_bar = c_bar;
+    a.vs_t = vs_t;
+    a.pg_t = pg_adv_t;
+    a.rho_out_t = rho_out_t;
+    a.T = T;
+    a.n = n;
+    return vtrace(a, keys, stream);
 }
 
 static int check_table_stats(const void* key_t, const void* actions_t, const void* weight_t, int64_t m, int64_t keys, int32_t actions,

@@ -459,11 +459,6 @@ hipError_t launch_returns(const float* reward_t, const uint8_t* done_t, const fl
 // before it stores them and touches no other column: adv_t may be reward_t and target_t may be value_t.
 // ------------------------------------------------------------------------------------
 #define ADV_ROWS 8
-__device__ __forceinline__ float table_value(const float* values, uint32_t keys, int32_t key) {
-    const bool in = (uint32_t)key < keys;
-    const float v = values[in ? key : 0];
-    return in ? v : 0.0f;
-}
 template <bool TABLE>
 __global__ __launch_bounds__(LMAZE_BLOCK) void advantages_kernel(const AdvantageArgs a) {
     const int64_t i = (int64_t)blockIdx.x * LMAZE_BLOCK + threadIdx.x;

@@ -206,6 +206,52 @@ struct AdvantageArgs {
     int64_t n;
 };
 hipError_t launch_advantages(const AdvantageArgs& a, hipStream_t s);
+// the value of a key, for advantages_kernel and vtrace_kernel: values[key] for 0 <= key < keys and 0 otherwise -- one unsigned
+// compare, and the gather itself unconditional on an index that is 0 for a key out of range (keys >= 1)
+__device__ __forceinline__ float table_value(const float* values, uint32_t keys, int32_t key) {
+    const bool in = (uint32_t)key < keys;
+    const float v = values[in ? key : 0];
+    return in ? v : 0.0f;
+}
+// Off-policy learning from the same rows (lmaze_action_probs / lmaze_vtrace / lmaze_vtrace_table, lmaze_offpolicy.hip).
+// One table in one of lmaze_evaluate's three forms, as the kernels read it: a byte per key, or a 16-byte row per key.
+struct ActionLaw {
+    const uint8_t* policy;    // form LMAZE_LAW_POLICY: uint8[keys]
+    const uint4* rows;        // LMAZE_LAW_THRESHOLDS: uint32[keys, 4]; LMAZE_LAW_Q: float[keys, 4] -- 16-byte aligned
+    int32_t form;             // lmaze_offpolicy.h
+    uint32_t epsilon;         // policy and q: as PolicyTable's
+};
+struct ActionProbsArgs {
+    const int32_t* key_t;     // [m]
+    const int32_t* actions_t; // [m]
+    ActionLaw law;
+    uint32_t keys;            // min(keys, 2^31)
+    float* prob_t;            // [m]
+    int64_t m;
+};
+hipError_t launch_action_probs(const ActionProbsArgs& a, hipStream_t s);
+// The rows form reads value_t / tail / rho_t; the table form (values != null) gathers values[key_t] / values[key_tail] as
+// AdvantageArgs' and computes the ratio from the two tables at (key_t, actions_t).
+struct VtraceArgs {
+    const float* reward_t;    // [T, N]
+    const uint8_t* done_t;    // [T, N]
+    const float* value_t;     // rows form: [T, N]
+    const float* tail;        // rows form: [N] or null (0)
+    const float* rho_t;       // rows form: [T, N] unclipped ratios, or null (1)
+    const int32_t* key_t;     // table form: [T, N]
+    const int32_t* actions_t; // table form: [T, N]
+    const int32_t* key_tail;  // table form: [N] or null (0)
+    const float* values;      // table form: [keys]
+    uint32_t keys;            // table form: min(keys, 2^31), the rows of values and of both tables
+    ActionLaw behaviour, target;   // table form
+    float gamma, lambda, rho_bar, c_bar;
+    float* vs_t;              // [T, N] or null
+    float* pg_t;              // [T, N] or null
+    float* rho_out_t;         // table form: [T, N] or null, the unclipped ratio
+    int32_t T;
+    int64_t n;
+};
+hipError_t launch_vtrace(const VtraceArgs& a, hipStream_t s);
 // Counts and Q24 sums per (key, action) over m samples (lmaze_table_stats, lmaze_aux.hip).  The plan is what the launcher
 // decides from the counts alone -- where the table lives, the grid -- and what lmaze_describe_table_stats prints.
 struct TableStatsArgs {

@@ -843,35 +843,7 @@ def gae(reward_t, done_t, gamma, lam, value_t=None, tail=None, values=None, key_
     reward_t float32[T,N], done_t bool / uint8[T,N], contiguous on one GPU.  out: float32[T,N] to fill with the advantages
     (it may be reward_t); default a new tensor.  targets: True allocates the value targets adv + v, a float32[T,N] tensor
     fills it (rows form: it may be value_t), False skips them.  Returns (adv_t, target_t or None)."""
-    if not (isinstance(reward_t, torch.Tensor) and _rows_like(reward_t, reward_t, (torch.float32,))):
-        raise ValueError("reward_t must be a contiguous float32[T,N] tensor on a GPU")
-    if not _rows_like(reward_t, done_t, (torch.bool, torch.uint8)):
-        raise ValueError("done_t must be a contiguous bool or uint8 tensor of reward_t's shape, on its device")
-    T, N = reward_t.shape
-    dev = reward_t.device
-    table = values is not None or key_t is not None
-    if table == (value_t is not None):
-        raise ValueError("gae() wants exactly one value source: value_t=, or values= with key_t=")
-
-    def per_env(t, dtype):
-        return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous() and tuple(t.shape) == (N,))
-    if table:
-        if tail is not None:
-            raise ValueError("tail= belongs to the rows form; the table form takes key_tail=")
-        if not (isinstance(values, torch.Tensor) and values.dtype == torch.float32 and values.dim() == 1 and values.numel() >= 1
-                and values.device == dev and values.is_contiguous()):
-            raise ValueError("values must be a contiguous float32[S] tensor, S >= 1, on reward_t's device")
-        if not _rows_like(reward_t, key_t, (torch.int32,)):
-            raise ValueError("key_t must be a contiguous int32 tensor of reward_t's shape, on its device")
-        if key_tail is not None and not per_env(key_tail, torch.int32):
-            raise ValueError("key_tail must be a contiguous int32[N] tensor on reward_t's device")
-    else:
-        if key_tail is not None:
-            raise ValueError("key_tail= belongs to the table form; the rows form takes tail=")
-        if not _rows_like(reward_t, value_t, (torch.float32,)):
-            raise ValueError("value_t must be a contiguous float32 tensor of reward_t's shape, on its device")
-        if tail is not None and not per_env(tail, torch.float32):
-            raise ValueError("tail must be a contiguous float32[N] tensor on reward_t's device")
+    T, N, dev, table = _value_source("gae()", reward_t, done_t, value_t, tail, values, key_t, key_tail)
     if out is None:
         out = torch.empty_like(reward_t)
     elif not _rows_like(reward_t, out, (torch.float32,)):
@@ -900,6 +872,41 @@ def gae(reward_t, done_t, gamma, lam, value_t=None, tail=None, values=None, key_
                                            float(lam), out.data_ptr(), ptr(targets), T, N, stream)
     _abi.check(name, rc)
     return out, targets
+
+
+def _value_source(who, reward_t, done_t, value_t, tail, values, key_t, key_tail):
+    """What gae() and vtrace() check of their rows and of their one value source -- value_t= with tail=, or values= with key_t=
+    and key_tail= -- before anything of their own.  Returns (T, N, device, whether it is the table form)."""
+    if not (isinstance(reward_t, torch.Tensor) and _rows_like(reward_t, reward_t, (torch.float32,))):
+        raise ValueError("reward_t must be a contiguous float32[T,N] tensor on a GPU")
+    if not _rows_like(reward_t, done_t, (torch.bool, torch.uint8)):
+        raise ValueError("done_t must be a contiguous bool or uint8 tensor of reward_t's shape, on its device")
+    T, N = reward_t.shape
+    dev = reward_t.device
+    table = values is not None or key_t is not None
+    if table == (value_t is not None):
+        raise ValueError("%s wants exactly one value source: value_t=, or values= with key_t=" % who)
+
+    def per_env(t, dtype):
+        return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous() and tuple(t.shape) == (N,))
+    if table:
+        if tail is not None:
+            raise ValueError("tail= belongs to the rows form; the table form takes key_tail=")
+        if not (isinstance(values, torch.Tensor) and values.dtype == torch.float32 and values.dim() == 1 and values.numel() >= 1
+                and values.device == dev and values.is_contiguous()):
+            raise ValueError("values must be a contiguous float32[S] tensor, S >= 1, on reward_t's device")
+        if not _rows_like(reward_t, key_t, (torch.int32,)):
+            raise ValueError("key_t must be a contiguous int32 tensor of reward_t's shape, on its device")
+        if key_tail is not None and not per_env(key_tail, torch.int32):
+            raise ValueError("key_tail must be a contiguous int32[N] tensor on reward_t's device")
+    else:
+        if key_tail is not None:
+            raise ValueError("key_tail= belongs to the table form; the rows form takes tail=")
+        if not _rows_like(reward_t, value_t, (torch.float32,)):
+            raise ValueError("value_t must be a contiguous float32 tensor of reward_t's shape, on its device")
+        if tail is not None and not per_env(tail, torch.float32):
+            raise ValueError("tail must be a contiguous float32[N] tensor on reward_t's device")
+    return T, N, dev, table
 
 
 def table_stats(key_t, actions_t=None, weight_t=None, *, keys, actions=4, count=None, total=None):

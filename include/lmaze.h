@@ -689,6 +689,64 @@ int lmaze_table_stats(const int32_t* key_t, const int32_t* actions_t, const floa
 int lmaze_describe_table_stats(int64_t m, int64_t keys, int32_t actions, char* text_host, int32_t len);
 
 /*
+ * The probability with which a table rule RECORDS the action of a row, for m samples -- the flattened [T, N] key_t and
+ * actions_t rows of a closed-loop rollout -- in one launch, one lane per sample; no reference counterpart.  The table is
+ * given in exactly one of lmaze_evaluate's three forms, `keys` rows of it, and a (key, action) pair weighs, in units of 2^-34:
+ *   thresholds uint32[keys, 4]   the three words of row `key` in ascending order s0 <= s1 <= s2, s(-1) = 0, s3 = 2^32:
+ *                                w = 4 (s_a - s_(a-1)) for a in 0..3 and 0 for any other id; word 3 is ignored;
+ *   policy uint8[keys]           w = (0 <= a <= 3 ? epsilon_u32 : 0) + (a == policy[key] ? 4 (2^32 - epsilon_u32) : 0): a byte
+ *                                above 3, recorded as the action, carries its greedy share;
+ *   q float[keys, 4]             the same, the greedy action being the first maximum by a strict '>' (a NaN never wins,
+ *                                nothing beats a NaN in word 0).
+ * A key outside [0, keys) weighs 0 (one unsigned compare, never a read outside the table).  prob_t[j] = fl(w) * 2^-34: the
+ * conversion rounds to nearest even and is the only rounding.  This is the law of the action the rollout records, with no
+ * exclusion and no renormalisation -- not lmaze_evaluate's law, which is conditioned on the usable pairs.
+ * key_t, actions_t int32[m], prob_t float[m].
+ * Refused, in this order: LMAZE_E_NULL key_t, actions_t or prob_t missing; LMAZE_E_NULL unless exactly one of policy, q and
+ * thresholds is given; LMAZE_E_COUNT m < 0 or keys < 1; LMAZE_E_ALIGN q or thresholds off 16 bytes, a row off 4.  m == 0 then
+ * returns 0 with nothing read.
+ */
+int lmaze_action_probs(const int32_t* key_t, const int32_t* actions_t, int64_t m, const uint8_t* policy, const float* q,
+                       uint32_t epsilon_u32, const uint32_t* thresholds, int64_t keys, float* prob_t, void* stream);
+
+/*
+ * V-trace (Espeholt et al. 2018: Retrace's lambda-return clipped at rho_bar and c_bar) over the [T, N] rows a rollout wrote
+ * under a table that is no longer the one being learnt, in ONE launch, one lane per env; no reference counterpart.  With
+ * v(t, i) the value of row t, v(T, i) the value behind the last row and ratio(t, i) the UNCLIPPED importance ratio of the row:
+ *   v_next = vs_next = v(T, i);  acc_next = 0;  for t = T-1 .. 0, with r = reward_t[t, i], v = v(t, i), ratio = ratio(t, i):
+ *     rho = ratio < rho_bar ? ratio : rho_bar;   cc = ratio < c_bar ? ratio : c_bar;   c = lambda * cc
+ *     done_t[t, i] != 0:  td = r - v;                          acc = rho * td;                                  qv = r
+ *     otherwise:          td = (r + gamma * v_next) - v;       acc = rho * td + (gamma * c) * acc_next;         qv = r + gamma * vs_next
+ *     vs_t[t, i] = vs = acc + v;   pg_adv_t[t, i] = rho * (qv - v);   v_next = v;  vs_next = vs;  acc_next = acc
+ * in float32, every operation rounded on its own in the order written (round to nearest even, never a fused multiply-add), so
+ * a float32 loop on the host reproduces every bit.  A done row cuts the bootstrap and the trace, and the done of a step limit
+ * is terminal like any other, as in lmaze_advantages.  A NaN ratio is clipped to the bars; gamma, lambda and the bars are not
+ * validated.  On-policy (ratio 1, both bars >= 1) acc is lmaze_advantages' adv_t and vs its target_t in every bit.
+ *   lmaze_vtrace        v(t, i) = value_t[t, i];  v(T, i) = tail[i], tail float[N] or NULL (0);  ratio(t, i) = rho_t[t, i],
+ *                       rho_t float[T,N] or NULL (1).
+ *   lmaze_vtrace_table  v by lmaze_advantages_table's rule from values float[keys], key_t int32[T,N] and key_tail int32[N] or
+ *                       NULL (0);  ratio(t, i) = fl(fl(wt) / fl(wb)), wt and wb lmaze_action_probs' weights of
+ *                       (key_t[t, i], actions_t[t, i]) under the target (t_*) and the behaviour (b_*) table, one correctly
+ *                       rounded division, and 0 where wb == 0: a row the behaviour table cannot have produced carries no
+ *                       weight.  Each table in exactly one of the three forms, `keys` rows; the forms need not match.  Equal
+ *                       tables give exactly 1.  rho_out_t float[T,N] or NULL receives the unclipped ratio.
+ * vs_t and pg_adv_t float[T,N], each may be NULL but not both.  Any output may be a float input row of the same call (a lane
+ * reads the rows of its own column before it stores them and touches no other column); the outputs are distinct.
+ * Refused, in this order: LMAZE_E_NULL reward_t, done_t, value_t (rows form) or key_t / actions_t / values (table form)
+ * missing, or neither vs_t nor pg_adv_t given; LMAZE_E_NULL unless exactly one of policy, q and thresholds is given, for the
+ * behaviour table, then for the target table; LMAZE_E_COUNT T < 0, n outside [0, LMAZE_MAX_ENVS] or keys < 1; LMAZE_E_ALIGN a q
+ * or thresholds table off 16 bytes, a float or int32 pointer off 4.  T == 0 or n == 0 then returns 0 with nothing read.
+ */
+int lmaze_vtrace(const float* reward_t, const uint8_t* done_t, const float* value_t, const float* tail, const float* rho_t,
+                 float gamma, float lambda, float rho_bar, float c_bar, float* vs_t, float* pg_adv_t, int32_t T, int64_t n,
+                 void* stream);
+int lmaze_vtrace_table(const float* reward_t, const uint8_t* done_t, const int32_t* key_t, const int32_t* actions_t,
+                       const int32_t* key_tail, const float* values, int64_t keys, const uint8_t* b_policy, const float* b_q,
+                       uint32_t b_epsilon_u32, const uint32_t* b_thresholds, const uint8_t* t_policy, const float* t_q,
+                       uint32_t t_epsilon_u32, const uint32_t* t_thresholds, float gamma, float lambda, float rho_bar,
+                       float c_bar, float* vs_t, float* pg_adv_t, float* rho_out_t, int32_t T, int64_t n, void* stream);
+
+/*
  * VALUE ITERATION over the grid mazes: the optimal Q table of every maze, in ONE launch; no reference counterpart (the
  * reference has no planner).  It is the table lmaze_rollout_policy, lmaze_rollout_sample and lmaze_advantages_table take.
  * Problem p is one maze of S = G*G states, state s = x * G + y (the ball-cell key of the closed-loop rollouts), and the four
